@@ -7,8 +7,11 @@ head), inputs already resident in HBM, bf16, seeded random weights of the real a
 synthetic pixels/ids of the BASELINE config-2 shape.  With N GPUs each rank scores its own 32 crops (weak scaling) and
 the fixed-size result records are all-gathered over RCCL every step, as the search loop needs them.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the bf16 MFMA GEMM,
-timed live with HIP events on the engine's stream) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+Prints ONE JSON line on rank 0: the headline `value` (crops/s) and `ms_per_step` of the `--steps` timed steps.  A plain run does
+nothing else.  `--full` adds the auxiliary legs, each of which takes runs of its own: `roofline` (dominant kernel = the bf16 MFMA
+GEMM, timed live with HIP events on the engine's stream) with the board power under load, the search / stream / latency legs,
+the per-rank shape table, the config-5 line and `cpu_baseline` (the oracle on the host cores, bounded sample); in a plain run
+those keys are null.  `--dump-outputs DIR` writes the records of the last timed step (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -401,6 +404,27 @@ def fake_engine_run(args, world, rank, dist):
         _print_last(fake_line)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(rec: torch.Tensor, n_verify: int, outdir: str) -> None:
+    """--dump-outputs: the result records of the last timed step (all ranks' crops at N > 1), split into the arrays a caller of the
+    scoring path receives (VstarEngine.unpack), one float32 DIR/<field>.npy each; tf_argmax holds token ids, exact in float32.
+    A 32-crop step writes 6 MB.  Past 64 MB a fixed seeded sample of the crops is written, their record rows in crop_rows.npy."""
+    host = rec.cpu().numpy()
+    rows = np.arange(host.shape[0])
+    if host.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // host[0].nbytes - 1            # one row's bytes left over for crop_rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(host.shape[0], keep, replace=False))
+        host = host[rows]
+    os.makedirs(outdir, exist_ok=True)
+    arrays = VstarEngine.unpack(host, n_verify)
+    if len(rows) < rec.shape[0]:
+        arrays["crop_rows"] = rows
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -440,6 +464,10 @@ def main():
                     "torch.distributed passes on every rank, else torch.distributed; off = torch.distributed")
     ap.add_argument("--fp8", action="store_true", help="BASELINE config 5 precision: LLaMA linears W8A8 on the fp8 MFMA "
                     "(separate line; the headline metric is the default bf16 run)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the auxiliary legs (power sample, GEMM "
+                    "roofline, search / stream / latency legs, per-rank shape table, config-5 line, CPU baseline; the --no-* options "
+                    "above still drop single legs); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the records of the last timed step to DIR/<field>.npy (float32)")
     args = ap.parse_args()
 
     if args.config5:
@@ -516,7 +544,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     fence()
     dt = time.perf_counter() - t0
     if use_group:
@@ -525,93 +553,97 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     crops_per_s = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, nv, args.dump_outputs)      # before --full's legs reuse the record buffer
 
     # board power and shader clock WHILE the step runs (rank 0, untimed extra steps; rocm-smi in a side thread).  Round 5 found the
     # GEMM family pinned at the board's power cap on random operands: ~1400 W with the shader clock throttled to ~1.73 GHz of its
     # 2.4 GHz (profiles/r05_power_probe.txt) — the context in which `roofline.frac` (against the 2.4-GHz peak) has to be read.
     power = None
-    if rank == 0 and not args.tiny and not args.no_power_sample:
+    if args.full and rank == 0 and not args.tiny and not args.no_power_sample:
         try:
             power = _sample_power(step_local, seconds=2.5)      # rank 0 only: must not enter a collective the other ranks skip
         except Exception as exc:            # noqa: BLE001 — context only, never fatal
             power = {"error": f"{type(exc).__name__}: {exc}"}
-    # roofline of the dominant kernel family (bf16 MFMA GEMM): HIP events around every GEMM launch on the engine stream
-    eng.profile(True)
-    for _ in range(2):
-        step()
-    gemm_ms, gemm_n, gemm_flops = eng.profile_read()
-    f8_ms_m, f8_n_m, f8_flops_m = eng.profile_read_fp8() if args.fp8 else (0.0, 0, 0.0)
-    eng.profile(False)
-    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     fl = cfg.flops_per_crop(T, full=not args.skip_owl)
     per_crop = fl["core"] if args.skip_owl else fl["full"]
-    # last LLaMA block on the needed rows only (engine.hip::llm_forward): o_proj + gate/up/down of (S - 4) rows are never executed
-    skipped = 2.0 * (S - 4) * cfg.llm_hidden * (cfg.llm_hidden + 3 * cfg.llm_mlp)
-    # HBM-side traffic of the GEMM family per launch, from the committed rocprofv3 PMC passes of this same command
-    # (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE; profiles/r01_pmc_v7.json) — not re-measured live
-    traffic, traffic_src, traffic_stale = None, None, None
-    # round 6: the stamp is the hash COMPILED INTO the loaded libvstar_hip.so (build.sh -> vstar_build_source_hash), not
-    # a hash of whatever sources lie in the tree when this line runs; a tree that differs from the binary is reported, not hidden
-    from vstar_amd.provenance import kernel_source_hash as _tree_hash, library_source_hash as kernel_source_hash
-    import glob
-    # newest committed PMC summary first: rNN_pmc_final.json of the latest round, then its numbered passes (round 2 read a stale
-    # file here because "_final" did not match the pattern)
-    def _pmc_key(path):
-        b = os.path.basename(path)
-        tag = b.split("_pmc_")[-1].replace(".json", "")
-        return (b[:3], 10 ** 6 if tag == "final" else int("".join(c for c in tag if c.isdigit()) or 0))
-    for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_pmc_*.json")), key=_pmc_key, reverse=True):
-        if "hbm" in os.path.basename(cand):
-            continue
-        try:
-            pmc = json.load(open(cand))
-            # round 5: a PMC summary is stamped with the hash of the kernel sources it was measured on; only a file of THIS build's
-            # kernels is quoted (an unstamped pre-round-5 file, or another build's, leaves `traffic` null with the reason stated)
-            if not isinstance(pmc, dict) or pmc.get("kernel_source_hash") != kernel_source_hash():
-                traffic_stale = os.path.relpath(cand, ROOT) if traffic_stale is None else traffic_stale
+    # roofline of the dominant kernel family (bf16 MFMA GEMM): HIP events around every GEMM launch on the engine stream
+    roofline = None
+    if args.full:
+        eng.profile(True)
+        for _ in range(2):
+            step()
+        gemm_ms, gemm_n, gemm_flops = eng.profile_read()
+        f8_ms_m, f8_n_m, f8_flops_m = eng.profile_read_fp8() if args.fp8 else (0.0, 0, 0.0)
+        eng.profile(False)
+        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # last LLaMA block on the needed rows only (engine.hip::llm_forward): o_proj + gate/up/down of (S - 4) rows are never executed
+        skipped = 2.0 * (S - 4) * cfg.llm_hidden * (cfg.llm_hidden + 3 * cfg.llm_mlp)
+        # HBM-side traffic of the GEMM family per launch, from the committed rocprofv3 PMC passes of this same command
+        # (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE; profiles/r01_pmc_v7.json) — not re-measured live
+        traffic, traffic_src, traffic_stale = None, None, None
+        # round 6: the stamp is the hash COMPILED INTO the loaded libvstar_hip.so (build.sh -> vstar_build_source_hash), not
+        # a hash of whatever sources lie in the tree when this line runs; a tree that differs from the binary is reported, not hidden
+        from vstar_amd.provenance import kernel_source_hash as _tree_hash, library_source_hash as kernel_source_hash
+        import glob
+        # newest committed PMC summary first: rNN_pmc_final.json of the latest round, then its numbered passes (round 2 read a stale
+        # file here because "_final" did not match the pattern)
+        def _pmc_key(path):
+            b = os.path.basename(path)
+            tag = b.split("_pmc_")[-1].replace(".json", "")
+            return (b[:3], 10 ** 6 if tag == "final" else int("".join(c for c in tag if c.isdigit()) or 0))
+        for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_pmc_*.json")), key=_pmc_key, reverse=True):
+            if "hbm" in os.path.basename(cand):
                 continue
-            gem = [k for k in pmc["kernels"] if "gemm" in k["kernel"]]
-            traffic = round(sum(k["fetch_GB_corrected"] + k["write_GB"] for k in gem) * 1e9 / sum(k["launches"] for k in gem))
-            traffic_src = os.path.relpath(cand, ROOT)
-            break
-        except Exception:
-            continue
-    peak = 5000.0 if args.fp8 else PEAK_BF16_TFLOPS      # --fp8: 93 % of the GEMM FLOPs run on the fp8 MFMA (dense peak ~5 PF)
-    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": None if args.fp8 else traffic,
-                "traffic_note": (f"bytes per GEMM launch at the L2<->fabric boundary (FETCHx2+WRITE) from the committed rocprofv3 --pmc "
-                                 f"passes of this command ({traffic_src}, stamped with this build's kernel_source_hash "
-                                 f"{kernel_source_hash()}; counters cannot be read inside an un-profiled run); includes "
-                                 "Infinity-Cache hits; algorithmic operand+output bytes per launch ~0.3 GB") if traffic is not None else
-                                (f"null: no committed PMC summary carries this build's kernel_source_hash {kernel_source_hash()} "
-                                 f"(newest candidate: {traffic_stale}) — re-run tools/collect_r06.sh on the GPU box"),
-                "kernel_source_hash": kernel_source_hash(),
-                "kernel_source_hash_matches_tree": kernel_source_hash() == _tree_hash(),
-                "under_load": None if not power or "error" in power else dict(
-                    power, peak_at_sclk=round(peak * power["sclk_mhz"] / 2400.0, 1) if power.get("sclk_mhz") else None,
-                    frac_of_peak_at_sclk=round(achieved / (peak * power["sclk_mhz"] / 2400.0), 4) if power.get("sclk_mhz") else None,
-                    note="board power / shader clock sampled with rocm-smi while the step runs; `peak` is the 2.4-GHz figure, "
-                         "peak_at_sclk scales it to the clock the power cap allows on these operands"),
-                "fp8_linears": None if not args.fp8 or f8_ms_m <= 0 else {
-                    "achieved": round(f8_flops_m / (f8_ms_m * 1e-3) / 1e12, 1), "peak": 5000.0,
-                    "frac": round(f8_flops_m / (f8_ms_m * 1e-3) / 1e12 / 5000.0, 4), "launches_per_step": int(f8_n_m) // 2},
-                "kernel": "gemm4w_kernel + gemm256_kernel + gemm128_kernel (bf16 MFMA GEMM family, all epilogues; gemm4w = the LLaMA linears, 76 % of the step)", "launches_per_step": gemm_n // 2,
-                "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
-                "gemm_share_of_step": round(gemm_ms / 2 / ms_per_step, 3),
-                # whole step / peak.  ALGORITHMIC FLOPs count the last LLaMA block on every row like the reference computes it;
-                # the engine runs that block on the ~4 rows per crop the heads read, so the EXECUTED figure is lower
-                "end_to_end_tflops_per_gpu_algorithmic": round(crops_per_s / world * per_crop / 1e12, 1),
-                "end_to_end_frac_algorithmic": round(crops_per_s / world * per_crop / 1e12 / PEAK_BF16_TFLOPS, 4),
-                "skipped_flops_per_crop": round(skipped, 1),
-                "end_to_end_tflops_per_gpu": round(crops_per_s / world * (per_crop - skipped) / 1e12, 1),
-                "end_to_end_frac": round(crops_per_s / world * (per_crop - skipped) / 1e12 / PEAK_BF16_TFLOPS, 4)}
+            try:
+                pmc = json.load(open(cand))
+                # round 5: a PMC summary is stamped with the hash of the kernel sources it was measured on; only a file of THIS build's
+                # kernels is quoted (an unstamped pre-round-5 file, or another build's, leaves `traffic` null with the reason stated)
+                if not isinstance(pmc, dict) or pmc.get("kernel_source_hash") != kernel_source_hash():
+                    traffic_stale = os.path.relpath(cand, ROOT) if traffic_stale is None else traffic_stale
+                    continue
+                gem = [k for k in pmc["kernels"] if "gemm" in k["kernel"]]
+                traffic = round(sum(k["fetch_GB_corrected"] + k["write_GB"] for k in gem) * 1e9 / sum(k["launches"] for k in gem))
+                traffic_src = os.path.relpath(cand, ROOT)
+                break
+            except Exception:
+                continue
+        peak = 5000.0 if args.fp8 else PEAK_BF16_TFLOPS      # --fp8: 93 % of the GEMM FLOPs run on the fp8 MFMA (dense peak ~5 PF)
+        roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": None if args.fp8 else traffic,
+                    "traffic_note": (f"bytes per GEMM launch at the L2<->fabric boundary (FETCHx2+WRITE) from the committed rocprofv3 --pmc "
+                                     f"passes of this command ({traffic_src}, stamped with this build's kernel_source_hash "
+                                     f"{kernel_source_hash()}; counters cannot be read inside an un-profiled run); includes "
+                                     "Infinity-Cache hits; algorithmic operand+output bytes per launch ~0.3 GB") if traffic is not None else
+                                    (f"null: no committed PMC summary carries this build's kernel_source_hash {kernel_source_hash()} "
+                                     f"(newest candidate: {traffic_stale}) — re-run tools/collect_r06.sh on the GPU box"),
+                    "kernel_source_hash": kernel_source_hash(),
+                    "kernel_source_hash_matches_tree": kernel_source_hash() == _tree_hash(),
+                    "under_load": None if not power or "error" in power else dict(
+                        power, peak_at_sclk=round(peak * power["sclk_mhz"] / 2400.0, 1) if power.get("sclk_mhz") else None,
+                        frac_of_peak_at_sclk=round(achieved / (peak * power["sclk_mhz"] / 2400.0), 4) if power.get("sclk_mhz") else None,
+                        note="board power / shader clock sampled with rocm-smi while the step runs; `peak` is the 2.4-GHz figure, "
+                             "peak_at_sclk scales it to the clock the power cap allows on these operands"),
+                    "fp8_linears": None if not args.fp8 or f8_ms_m <= 0 else {
+                        "achieved": round(f8_flops_m / (f8_ms_m * 1e-3) / 1e12, 1), "peak": 5000.0,
+                        "frac": round(f8_flops_m / (f8_ms_m * 1e-3) / 1e12 / 5000.0, 4), "launches_per_step": int(f8_n_m) // 2},
+                    "kernel": "gemm4w_kernel + gemm256_kernel + gemm128_kernel (bf16 MFMA GEMM family, all epilogues; gemm4w = the LLaMA linears, 76 % of the step)", "launches_per_step": gemm_n // 2,
+                    "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
+                    "gemm_share_of_step": round(gemm_ms / 2 / ms_per_step, 3),
+                    # whole step / peak.  ALGORITHMIC FLOPs count the last LLaMA block on every row like the reference computes it;
+                    # the engine runs that block on the ~4 rows per crop the heads read, so the EXECUTED figure is lower
+                    "end_to_end_tflops_per_gpu_algorithmic": round(crops_per_s / world * per_crop / 1e12, 1),
+                    "end_to_end_frac_algorithmic": round(crops_per_s / world * per_crop / 1e12 / PEAK_BF16_TFLOPS, 4),
+                    "skipped_flops_per_crop": round(skipped, 1),
+                    "end_to_end_tflops_per_gpu": round(crops_per_s / world * (per_crop - skipped) / 1e12, 1),
+                    "end_to_end_frac": round(crops_per_s / world * (per_crop - skipped) / 1e12 / PEAK_BF16_TFLOPS, 4)}
 
     # end-to-end search legs.  `search` / `search_grouped`: BASELINE config 2 literally (exhaustive depth-3 trees, 16 targets of one
     # image) — single-GPU runs.  `search_stream`: best-first searches that stop, 64 (image, target) samples in a cross-image window —
     # ALSO at N > 1, as a STRONG-scaling job in both shard modes (the weak-scaling step above stays the headline `value`).
     search = search_grouped = stream = stream_samples = None
     small = None
-    if world == 1 and not args.no_search_leg and not args.skip_owl:
+    if args.full and world == 1 and not args.no_search_leg and not args.skip_owl:
         try:
             search = search_leg(eng, cfg, args, rank, group=False)
         except Exception as exc:            # the headline line must survive a failure of the auxiliary leg
@@ -622,14 +654,14 @@ def main():
             search_grouped = search_leg(eng, cfg, args, rank, group=True)
         except Exception as exc:
             search_grouped = {"error": f"{type(exc).__name__}: {exc}"}
-    if not args.no_stream_leg and not args.no_search_leg and not args.skip_owl and (not args.tiny or args.rccl_selfcheck):
+    if args.full and not args.no_stream_leg and not args.no_search_leg and not args.skip_owl and (not args.tiny or args.rccl_selfcheck):
         try:
             stream = stream_leg(eng, cfg, args, world, rank, "crops")
             if world > 1:
                 stream_samples = stream_leg(eng, cfg, args, world, rank, "samples")
         except Exception as exc:
             stream = {"error": f"{type(exc).__name__}: {exc}"}
-    if world == 1 and not args.no_small_batch and not args.skip_owl and not args.tiny and B >= 8:
+    if args.full and world == 1 and not args.no_small_batch and not args.skip_owl and not args.tiny and B >= 8:
         try:
             small = small_batch_table(eng, cfg, args, dev, T)
         except Exception as exc:
@@ -657,11 +689,11 @@ def main():
             latency = lat
         except Exception as exc:
             latency = {"error": f"{type(exc).__name__}: {exc}"}
-    # BASELINE config 5 (fp8 W8A8 LLaMA linears, 64-crop batches, 8K image, depth-5 tree), bounded to a few seconds inside the default
-    # command: the batch path at 64 crops with its own roofline (fp8 MFMA GEMMs timed by HIP events, peak 5 PF), the literal search
+    # BASELINE config 5 (fp8 W8A8 LLaMA linears, 64-crop batches, 8K image, depth-5 tree), bounded to a few seconds inside a --full
+    # run: the batch path at 64 crops with its own roofline (fp8 MFMA GEMMs timed by HIP events, peak 5 PF), the literal search
     # leg on ONE target (341 crops), and the same search on the bf16 engine as the decision yardstick (visit order, final node)
     config5 = None
-    if world == 1 and not args.fp8 and not args.no_config5_line and not args.skip_owl and not args.tiny:
+    if args.full and world == 1 and not args.fp8 and not args.no_config5_line and not args.skip_owl and not args.tiny:
         try:
             B8 = 64
             cfg8 = VSMConfig.seal_7b(args.image_size, max_batch=B8, max_text_len=L, llm_w8a8=1)
@@ -737,7 +769,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and not args.tiny:
+        if args.full and not args.no_cpu_baseline and not args.tiny:
             # rank 0 times the CPU port at every N (the other ranks wait in the closing barrier, outside every timed region): a
             # SCALE line without it would count as unmeasured
             cpu = cpu_baseline(cfg, T)
@@ -746,7 +778,7 @@ def main():
         line = {
             "metric": "searched crops/sec (336x336 tiles, 7B VSM " + ("W8A8 fp8" if args.fp8 else "bf16") + ")",
             "value": round(crops_per_s, 3), "unit": "crops/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "fp8 e4m3 W8A8 for the LLaMA linears (per-token / per-channel scales), bf16 elsewhere" if args.fp8 else "bf16",
             "data": "synthetic (seeded " + ("trained-like" if args.weights == "trained_like" else "random") +

@@ -19,7 +19,7 @@ def test_bench_under_torchrun_one_rank_nccl(cuda):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny",
-           "--batch", "4", "--search-targets", "3", "--no-cpu-baseline", "--rccl-selfcheck", "--stream-samples", "8"]
+           "--batch", "4", "--search-targets", "3", "--no-cpu-baseline", "--rccl-selfcheck", "--stream-samples", "8", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

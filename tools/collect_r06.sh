@@ -3,7 +3,7 @@
 # Every summary is stamped with the hash compiled into the library the profiled command loaded (vstar_amd/provenance.py::checked_hash).
 R=$(pwd); OUT=$R/gpurun_out/r06f; RAW=/tmp/prof_r06f
 mkdir -p $OUT $RAW
-B="python $R/bench.py --no-cpu-baseline --no-search-leg --no-small-batch --no-config5-line --no-stream-leg --no-power-sample"
+B="python $R/bench.py --full --no-cpu-baseline --no-search-leg --no-small-batch --no-config5-line --no-stream-leg --no-power-sample"
 cd /tmp && export TMPDIR=/tmp
 if [ "$1" = "fp8" ]; then      # config 5 (W8A8, 64-crop batches): kernel statistics + the bench line
   rocprofv3 --kernel-trace --stats -d $RAW/stats8 -o k -- $B --fp8 --batch 64 --steps 3 --warmup 1 > /dev/null 2>&1
@@ -33,7 +33,7 @@ if [ "$1" != "stats" ]; then
   f() { ls $RAW/pmc_$1/*/pmc_results.db $RAW/pmc_$1/pmc_results.db 2>/dev/null | head -1; }
   python tools/pmc_summary.py $(f f) $(f w) $(f m) > $OUT/pmc.json
   cp $OUT/pmc.json profiles/r06_pmc_final.json      # (on the box: so that the bench line below quotes THIS build's traffic figure)
-  python bench.py --steps 20 --warmup 5 2> $OUT/bench.err | tail -1 > $OUT/bench.json
+  python bench.py --full --steps 20 --warmup 5 2> $OUT/bench.err | tail -1 > $OUT/bench.json
   python -c "
 import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']
 print('bench', d['value'], d['ms_per_step'], r['frac'], r.get('under_load'), 'traffic', r['traffic'], r['kernel_source_hash'])"

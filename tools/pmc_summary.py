@@ -4,7 +4,7 @@ in KiB; GRBM_GUI_ACTIVE is summed over the 8 XCDs, SQ_VALU_MFMA_BUSY_CYCLES over
 
   python tools/pmc_summary.py <fetch.db> <write.db> <mfma.db> > profiles/rNN_pmc.json
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out/f -o pmc -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out/f -o pmc -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
   rocprofv3 --pmc WRITE_SIZE --kernel-trace -d out/w -o pmc -- ...
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-trace -d out/m -o pmc -- ...
 """
