@@ -92,6 +92,34 @@ int vstar_vqa_forward(vstar_vqa_handle* h, int nseq, const int32_t* row_off, con
                       const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                       uint16_t* logits_f16, int32_t* argmax);
 
+/* Sampled decoding: HF 4.31 generate(do_sample=True) for one logits row.  Scores s = lp(float(x) / temperature)
+ * rounded to the logits' storage type; top-k keeps every score >= the k-th largest (ties included); top-p keeps a token iff
+ * the softmax mass of the kept tokens with a strictly greater score is < top_p (the maximal score is always kept); the token
+ * is the smallest kept index, in vocabulary order, whose inclusive prefix mass exceeds u * Z (Z = the kept mass), with
+ * u = (x0 >> 8) * 2^-24 and x0 the first word of Philox4x32-10 at key (seed lo, seed hi), counter (step, stream lo,
+ * stream hi, 0).  Masses are exp(s - max s) in unsigned 64-bit fixed point (2^-40 units), summed exactly: the draw is
+ * deterministic and a row's token depends on that row and its record only. */
+typedef struct vstar_vqa_sampling {   /* 32 bytes */
+  float    temperature;   /* > 0 */
+  int32_t  top_k;         /* 0 = off */
+  float    top_p;         /* [0,1]; >= 1 = off */
+  uint32_t step;          /* Philox counter word 0 */
+  uint64_t seed;          /* Philox key */
+  uint64_t stream;        /* Philox counter words 1-2 */
+} vstar_vqa_sampling;
+
+/* vstar_vqa_forward with the arg-max replaced by the sampling tail: params[n_want], tokens[n_want] (host).  Only the tokens
+ * cross to the host (no logits copy). */
+int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src,
+                             const int32_t* kv_slot, const int32_t* prefix_slot, const int32_t* past_len,
+                             int n_want, const int32_t* want, const vstar_vqa_sampling* params, int32_t* tokens);
+
+/* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22, rows <= 65535); host
+ * params / outputs; u_out[rows] and n_kept[rows] nullable diagnostics (the uniform drawn, the size of the kept set).  Null
+ * stream, synchronises. */
+int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld,
+                        const vstar_vqa_sampling* params, int32_t* tokens, float* u_out, int32_t* n_kept);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

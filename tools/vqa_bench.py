@@ -1,7 +1,9 @@
 """Micro-benchmark of the VQA-LLM engine at the 7B geometry (seeded random fp16 weights): image encoding, prefill,
 KV-cached decode steps at several batch sizes, forked option scoring.  Prints one JSON object.
 
-  python tools/vqa_bench.py [--out profiles/r01_vqa_bench.json] [--layers 32]
+  python tools/vqa_bench.py [--out profiles/r01_vqa_bench.json] [--layers 32] [--sample]
+--sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
+sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio.
 Decode steps are bound by the weight sweep (13.5 GB fp16 per step at 7B): `weights_GBps` = bytes of all LLaMA + lm_head
 weights / device time of one step (HIP events inside the engine), against the ~8 TB/s HBM3E peak.
 """
@@ -16,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vstar_amd.config import VQAConfig  # noqa: E402
+from vstar_amd.vqa import sampling_params  # noqa: E402
 from vstar_amd.vqa_engine import Seq, VqaEngine  # noqa: E402
 from vstar_amd.weights import random_state_dict  # noqa: E402
 
@@ -26,6 +29,8 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--batches", default="1,4,16,32")
     ap.add_argument("--steps", type=int, default=16)
+    ap.add_argument("--sample", action="store_true", help="add the sampled-decode leg next to greedy")
+    ap.add_argument("--rounds", type=int, default=3, help="--sample: greedy / sampled blocks alternated this many times")
     a = ap.parse_args()
     cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=40, max_ctx=1024, max_rows=16384, max_images=8)
     t0 = time.time()
@@ -78,6 +83,8 @@ def main():
         dec[f"B{B}"] = {"device_ms_per_step": round(d, 3), "wall_ms_per_step": round(wall, 3),
                         "tokens_per_s": round(B / wall * 1e3, 1), "weights_GBps": round(wbytes / d / 1e6, 0)}
     out["decode"] = dec
+    if a.sample:
+        out["decode_sample"] = decode_sample(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)
     # option scoring: 4 options x 12 tokens forked from one question prefix
     eng.forward([Seq(short_rows, kv_slot=0)], [(0, -1)])
     P = len(short_rows)
@@ -92,6 +99,40 @@ def main():
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         json.dump(out, open(a.out, "w"), indent=1)
+
+
+def decode_sample(eng, rows, batches, steps, rounds):
+    """Greedy vs sampled decode steps of B sequences, alternated in blocks of `steps` (same KV positions advance)."""
+    res = {}
+    for B in batches:
+        seqs = [Seq(rows, kv_slot=i) for i in range(B)]
+        _, nxt = eng.forward(seqs, [(i, -1) for i in range(B)], logits=False)
+        pos = len(rows)
+        want = [(i, 0) for i in range(B)]
+        dev = {"greedy": [], "sample": []}
+        wall = {"greedy": 0.0, "sample": 0.0}
+        for r in range(rounds):
+            for mode in ("greedy", "sample"):
+                t0 = time.time()
+                for s in range(steps):
+                    step = [Seq([int(nxt[i])], kv_slot=i, past_len=pos) for i in range(B)]
+                    if mode == "greedy":
+                        _, nxt = eng.forward(step, want, logits=False)
+                    else:
+                        nxt = eng.forward_sample(step, want, [sampling_params(0.7, 50, 0.9, seed=i, step=r * steps + s)
+                                                              for i in range(B)])
+                    dev[mode].append(eng.last_forward_ms())
+                    pos += 1
+                wall[mode] += time.time() - t0
+        leg = {}
+        for mode in ("greedy", "sample"):
+            w = wall[mode] / (rounds * steps) * 1e3
+            leg[mode] = {"device_ms_per_step": round(float(np.median(dev[mode])), 3), "wall_ms_per_step": round(w, 3),
+                         "tokens_per_s": round(B / w * 1e3, 1)}
+        leg["sample_over_greedy_tokens_per_s"] = round(leg["sample"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
+        leg["sample_minus_greedy_device_ms"] = round(leg["sample"]["device_ms_per_step"] - leg["greedy"]["device_ms_per_step"], 4)
+        res[f"B{B}"] = leg
+    return res
 
 
 if __name__ == "__main__":

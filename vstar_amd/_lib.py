@@ -29,6 +29,7 @@ EXPORTS = [
 EXPORTS_VQA = [
     "vstar_vqa_create", "vstar_vqa_destroy", "vstar_vqa_last_error", "vstar_vqa_load_tensor", "vstar_vqa_finalize_weights",
     "vstar_vqa_encode_images", "vstar_vqa_forward", "vstar_vqa_debug_read", "vstar_vqa_last_forward_ms", "vstar_vqa_op_gemm",
+    "vstar_vqa_forward_sample", "vstar_vqa_op_sample",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -49,6 +50,18 @@ class VstarResult(ctypes.Structure):
 
 
 RESULT_FLOATS = ctypes.sizeof(VstarResult) // 4
+
+
+class VqaSampling(ctypes.Structure):
+    """vstar_vqa_sampling (include/vstar_vqa.h): one row's sampling parameters and Philox coordinates, 32 bytes."""
+    _fields_ = [
+        ("temperature", c_float),
+        ("top_k", c_int32),
+        ("top_p", c_float),
+        ("step", ctypes.c_uint32),
+        ("seed", ctypes.c_uint64),
+        ("stream", ctypes.c_uint64),
+    ]
 
 
 class VstarError(RuntimeError):
@@ -183,6 +196,11 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_forward.argtypes = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p]
     lib.vstar_vqa_forward.restype = c_int
+    lib.vstar_vqa_forward_sample.argtypes = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                             c_void_p, c_void_p]
+    lib.vstar_vqa_forward_sample.restype = c_int
+    lib.vstar_vqa_op_sample.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_sample.restype = c_int
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int

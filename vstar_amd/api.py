@@ -242,12 +242,21 @@ class LlavaSearchModel:
     @torch.inference_mode()
     def generate(self, input_ids, images=None, object_features=None, images_long=None, objects_long=None, do_sample: bool = False,
                  num_beams: int = 1, temperature: float = 0, top_p=None, max_new_tokens: int = 200, use_cache: bool = True,
-                 stopping_criteria=None, **unused):
+                 stopping_criteria=None, top_k=50, seed=None, **unused):
+        """do_sample=False: greedy.  do_sample=True: HF 4.31 sampling (temperature > 0, top_k, top_p) on the device, keyed by
+        `seed` (None: drawn from torch's default CPU generator) — the same draws as VQA_LLM.free_form_inference(seed=seed)."""
+        from .vqa import resolve_seed, sampling_params
         from .vqa_engine import Seq
-        if do_sample or num_beams != 1:
-            raise NotImplementedError("the evaluation decodes greedily (temperature 0, one beam)")
+        if num_beams != 1:
+            raise NotImplementedError("beam search (num_beams > 1) is not implemented")
+        if do_sample and not temperature > 0:
+            raise ValueError(f"do_sample=True needs temperature > 0, got {temperature}")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
-        new = self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens)[0]
+        if do_sample:
+            p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
+            new = self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p])[0]
+        else:
+            new = self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens)[0]
         return torch.tensor([ids + new], dtype=torch.long)
 
 

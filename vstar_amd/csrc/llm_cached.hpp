@@ -10,6 +10,7 @@
 //     straight out of the KV cache with an optional shared prefix slot.
 #pragma once
 #include "engine_base.hpp"
+#include "sample.hpp"
 
 namespace VS_NS {
 
@@ -39,6 +40,7 @@ struct LlmCached {
   lp_t *wsel = nullptr, *wnorm = nullptr, *logits = nullptr;
   int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_seq = nullptr, *d_want = nullptr,
           *d_argmax = nullptr;
+  vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of forward(..., sample_params)
   int max_want = 256;
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
@@ -81,7 +83,8 @@ struct LlmCached {
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows);
   int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
-              const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out);
+              const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out,
+              const vstar_vqa_sampling* sample_params = nullptr);
 };
 
 inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t* embed_, const std::vector<LlmBlock>* blocks_,
@@ -122,6 +125,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&d_seq, (size_t)3 * c.max_slots * 4));
   RC(e->dalloc(&d_want, (size_t)max_want));
   RC(e->dalloc(&d_argmax, (size_t)max_want));
+  RC(e->dalloc(&d_sparams, (size_t)max_want));
   {  // split-KV decode attention (decode.hip): scores / partials / tickets for steps of up to SPLIT_ROWS sequences, zeroed once
     const size_t wb = cached_attention_split_ws_bytes(SPLIT_ROWS, c.heads, c.max_ctx);
     RC(e->dalloc(&split_ws, wb));
@@ -256,7 +260,7 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
 
 inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
-                              uint16_t* logits_out, int32_t* argmax_out) {
+                              uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
   if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
@@ -283,6 +287,12 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   }
   for (int j = 0; j < n_want; ++j)
     if (want[j] < 0 || want[j] >= R) { e->set_error("want row out of range"); return VSTAR_ERR_INVALID; }
+  if (sample_params)
+    for (int j = 0; j < n_want; ++j)
+      if (!vstar_sample_params_valid(sample_params[j])) {
+        e->set_error("sampling parameters: temperature must be > 0 and finite, top_k >= 0, top_p >= 0");
+        return VSTAR_ERR_INVALID;
+      }
   const bool prefill = all_fresh && R > 64;
   const int rows = prefill ? nseq * maxT : R;
   if (rows > c.max_rows) { e->set_error("too many rows for one forward call (max_rows)"); return VSTAR_ERR_INVALID; }
@@ -313,6 +323,8 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   LCHK(hipMemcpyAsync(d_row_seq, h_seq.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_seq, h_seqmeta.data(), h_seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
   if (n_want) LCHK(hipMemcpyAsync(d_want, h_want.data(), (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+  if (n_want && sample_params)
+    LCHK(hipMemcpyAsync(d_sparams, sample_params, (size_t)n_want * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
@@ -324,7 +336,15 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   if (n_want) {
     LCHK(gather_rows(lx, d_want, wsel, n_want, H, e->stream));
     RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, n_want, VSTAR_EPI_NONE));
-    LCHK(argmax_rows_lp(logits, n_want, c.vocab, (int64_t)vpad, d_argmax, e->stream));
+    if (sample_params) {   // the sampling tail (sample.hip) in place of the arg-max: d_argmax receives the drawn tokens
+#ifdef VSTAR_LP_F16
+      LCHK(vstar_sample_rows_f16(logits, n_want, c.vocab, (int64_t)vpad, d_sparams, d_argmax, nullptr, nullptr, e->stream));
+#else
+      LCHK(vstar_sample_rows_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_sparams, d_argmax, nullptr, nullptr, e->stream));
+#endif
+    } else {
+      LCHK(argmax_rows_lp(logits, n_want, c.vocab, (int64_t)vpad, d_argmax, e->stream));
+    }
   }
   LCHK(hipEventRecord(ev1, e->stream));
   if (n_want && logits_out)

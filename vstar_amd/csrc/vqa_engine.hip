@@ -273,6 +273,50 @@ int vstar_vqa_forward(vstar_vqa_handle* h, int nseq, const int32_t* row_off, con
   return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, argmax);
 }
 
+int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             const vstar_vqa_sampling* params, int32_t* tokens) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
+  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, tokens, params);
+}
+
+int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
+                        int32_t* tokens, float* u_out, int32_t* n_kept) {
+  if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||
+      (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_sample: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  for (int r = 0; r < rows; ++r)
+    if (!vstar_sample_params_valid(params[r])) {
+      tls_error() = "vstar_vqa_op_sample: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
+      return VSTAR_ERR_INVALID;
+    }
+  vstar_vqa_sampling* d_p = nullptr;
+  int32_t *d_tok = nullptr, *d_kept = nullptr;
+  float* d_u = nullptr;
+  hipError_t e = hipMalloc(&d_p, (size_t)rows * sizeof(vstar_vqa_sampling));
+  if (e == hipSuccess) e = hipMalloc(&d_tok, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_u, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_kept, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_p, params, (size_t)rows * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = dtype == VSTAR_F16 ? vstar_sample_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr)
+                           : vstar_sample_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tokens, d_tok, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && u_out) e = hipMemcpy(u_out, d_u, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_kept) e = hipMemcpy(n_kept, d_kept, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  hipFree(d_p);
+  hipFree(d_tok);
+  hipFree(d_u);
+  hipFree(d_kept);
+  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_sample: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
+  return VSTAR_OK;
+}
+
 int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,
                       int epilogue, int kernel, const void* norm_w, float norm_eps) {
   if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || K % 64) { tls_error() = "bad argument"; return VSTAR_ERR_INVALID; }

@@ -2,7 +2,7 @@
 
 Same constructor role, same methods and return conventions:
     get_patch / get_object_crop ............ vstar_bench_eval.py:49-77
-    free_form_inference(image, question, ...) -> str ................ :78-113   (temperature 0: greedy, KV cache)
+    free_form_inference(image, question, ...) -> str ................ :78-113   (temperature 0: greedy; > 0: sampled on the device)
     multiple_choices_inference(image, question, options, ...) -> int  :115-165  (shared-prefix option scoring)
 plus a batched form (`free_form_batch`) that decodes many samples in one engine call per step — the reference runs batch 1; on an MI355X a decode step is bound by the 13.5 GB weight sweep, so sequences are
 advanced together.
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from ._lib import VqaSampling
 from .config import IMAGE_TOKEN_INDEX, OBJECT_TOKEN_INDEX, VQAConfig
 from .preprocess import CLIP_MEAN, CLIP_STD, SyntheticTokenizer, _normalise
 from .vqa_engine import Seq, VqaEngine
@@ -59,6 +60,35 @@ def tokenizer_image_object_token(prompt: str, tokenizer) -> List[int]:
             ids.append(marks[i - 1])
         ids.extend(t[1:] if has_bos else t)
     return ids
+
+
+def resolve_seed(seed: Optional[int]) -> int:
+    """The Philox key of a sampled decode: `seed` itself, or (None) one drawn from torch's default CPU generator."""
+    if seed is None:
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    return int(seed)
+
+
+def sampling_params(temperature: float, top_k: Optional[int] = 50, top_p: Optional[float] = None, seed: int = 0,
+                    stream: int = 0, step: int = 0) -> VqaSampling:
+    """One row's vstar_vqa_sampling record with HF 4.31's conventions: temperature > 0; top_k None / 0 = off (HF default 50);
+    top_p None or >= 1 = off."""
+    if not temperature > 0:
+        raise ValueError(f"sampling needs temperature > 0, got {temperature}")
+    top_k = 0 if top_k is None else int(top_k)
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0 (0 / None = off), got {top_k}")
+    top_p = 1.0 if top_p is None else float(top_p)
+    if not top_p >= 0:
+        raise ValueError(f"top_p must be in [0, 1], got {top_p}")
+    mask = (1 << 64) - 1
+    return VqaSampling(temperature=float(temperature), top_k=min(top_k, 2 ** 31 - 1), top_p=min(top_p, 1.0),
+                       step=step & 0xffffffff, seed=int(seed) & mask, stream=int(stream) & mask)
+
+
+def _with_step(p: VqaSampling, step: int) -> VqaSampling:
+    return VqaSampling(temperature=p.temperature, top_k=p.top_k, top_p=p.top_p, step=step & 0xffffffff, seed=p.seed,
+                       stream=p.stream)
 
 
 class _ImageProcessor:
@@ -155,18 +185,30 @@ class VQA_LLM:
 
     # ---- free-form answer (vstar_bench_eval.py:78-113) ----
     def free_form_inference(self, image, question, temperature=0, top_p=None, num_beams=1, max_new_tokens=200,
-                            object_crops=None, images_long=None, objects_long=None) -> str:
-        if temperature != 0 or num_beams != 1:
-            raise NotImplementedError("the evaluation decodes greedily (temperature 0, one beam)")
+                            object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None) -> str:
+        """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
+        top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
+        so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws."""
+        if num_beams != 1:
+            raise NotImplementedError("beam search (num_beams > 1) is not implemented")
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
-                                          objects_long=objects_long)], max_new_tokens)[0]
+                                          objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
+                                    top_k=top_k, seed=seed)[0]
 
-    def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200) -> List[str]:
-        """Greedy decode of several samples at once: one prefill call, then one engine call per generated position."""
+    def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
+                        seed=None) -> List[str]:
+        """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
+        greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
+        single free_form_inference call with that seed."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if n > cfg.max_slots:
             raise ValueError("more samples than KV slots")
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0 (0 = greedy), got {temperature}")
+        if temperature > 0:
+            base = resolve_seed(seed)
+            params = [sampling_params(temperature, top_k, top_p, s.get("seed", base + i)) for i, s in enumerate(samples)]
         seqs, lens = [], []
         fslot = 0
         for i, s in enumerate(samples):
@@ -176,7 +218,10 @@ class VQA_LLM:
             _, rows = self._question_rows(s["question"], img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))
             seqs.append(Seq(rows, kv_slot=i))
             lens.append(len(rows))
-        self.generated_ids = self.greedy_decode(seqs, lens, max_new_tokens)
+        if temperature > 0:
+            self.generated_ids = self.sample_decode(seqs, lens, max_new_tokens, params)
+        else:
+            self.generated_ids = self.greedy_decode(seqs, lens, max_new_tokens)
         texts = []
         for ids in self.generated_ids:
             out = self.tokenizer.batch_decode([ids], skip_special_tokens=True)[0].strip()
@@ -186,11 +231,22 @@ class VQA_LLM:
         return texts
 
     def greedy_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int) -> List[List[int]]:
-        """model.generate(do_sample=False, use_cache=True) for every sequence; a sequence stops at EOS (the reference's
-        keyword criterion stops on '</s>', the decoded EOS) or when the context is full."""
-        eng, cfg = self.engine, self.cfg
+        """model.generate(do_sample=False, use_cache=True) for every sequence."""
+        return self._decode(seqs, lens, max_new_tokens, lambda step, want, idx, t: self.engine.forward(step, want, logits=False)[1])
+
+    def sample_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, params) -> List[List[int]]:
+        """model.generate(do_sample=True, use_cache=True): params[i] (`_lib.VqaSampling`) drives sequence i; the Philox step
+        of a draw is the index of the token it generates (0 = the token drawn from the prefill's last row)."""
+        def choose(step, want, idx, t):
+            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx])
+        return self._decode(seqs, lens, max_new_tokens, choose)
+
+    def _decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, choose) -> List[List[int]]:
+        """The generate() loop over a token chooser choose(step_seqs, want, sequence indices, token index) -> tokens; a
+        sequence stops at EOS (the reference's keyword criterion stops on '</s>', the decoded EOS) or when the context is full."""
+        cfg = self.cfg
         n = len(seqs)
-        _, nxt = eng.forward(seqs, [(i, -1) for i in range(n)], logits=False)
+        nxt = choose(seqs, [(i, -1) for i in range(n)], list(range(n)), 0)
         out: List[List[int]] = [[] for _ in range(n)]
         pos = list(lens)
         live = list(range(n))
@@ -205,7 +261,7 @@ class VQA_LLM:
             if not live or len(out[live[0]]) >= max_new_tokens:
                 break
             step = [Seq([cur[i]], kv_slot=seqs[i].kv_slot, past_len=pos[i]) for i in live]
-            _, nxt = eng.forward(step, [(j, 0) for j in range(len(live))], logits=False)
+            nxt = choose(step, [(j, 0) for j in range(len(live))], live, len(out[live[0]]))
             for j, i in enumerate(live):
                 cur[i] = int(nxt[j])
                 pos[i] += 1

@@ -17,6 +17,10 @@ from .weights import vqa_state_dict_spec
 _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
+def _ptr(a: Optional[np.ndarray]):
+    return ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
 @dataclass
 class Seq:
     """New rows of one sequence for `VqaEngine.forward`."""
@@ -97,9 +101,10 @@ class VqaEngine:
         return out
 
     # ---- LlavaSearchLlamaForCausalLM.forward over new rows (llava_search_llama.py:56-113) ----
-    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True):
-        """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
-        Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want])."""
+    @staticmethod
+    def _rows_args(seqs: Sequence[Seq], want: Sequence[Tuple[int, int]]):
+        """The row arguments (nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want) of the C-ABI forward calls, and the
+        arrays behind them (keep them alive while the call runs)."""
         n = len(seqs)
         row_off = np.zeros(n + 1, np.int32)
         for i, s in enumerate(seqs):
@@ -109,13 +114,33 @@ class VqaEngine:
         pre = np.asarray([s.kv_slot if s.prefix_slot is None else s.prefix_slot for s in seqs], np.int32)
         past = np.asarray([s.past_len for s in seqs], np.int32)
         w = np.asarray([row_off[i] + (r if r >= 0 else len(seqs[i].rows) + r) for i, r in want], np.int32)
-        nw = len(w)
+        return (n, _ptr(row_off), _ptr(src), _ptr(kv), _ptr(pre), _ptr(past), len(w), _ptr(w)), (row_off, src, kv, pre, past, w)
+
+    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True):
+        """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
+        Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want])."""
+        args, _keep = self._rows_args(seqs, want)
+        nw = args[6]
         out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if (logits and nw) else None
         out_arg = np.empty((max(nw, 1),), np.int32)
-        P = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None
-        _lib.check_vqa(self.lib.vstar_vqa_forward(self.handle, n, P(row_off), P(src), P(kv), P(pre), P(past), nw, P(w),
-                                                  P(out_logits), P(out_arg)), self.handle)
+        _lib.check_vqa(self.lib.vstar_vqa_forward(self.handle, *args, _ptr(out_logits), _ptr(out_arg)), self.handle)
         return out_logits, out_arg[:nw]
+
+    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params) -> np.ndarray:
+        """`forward` with the arg-max replaced by the on-device sampling tail (csrc/sample.hip): `params` holds one
+        `_lib.VqaSampling` per wanted row (or one record for all of them).  Returns the drawn tokens, int32 [n_want]; the
+        logits never leave the device."""
+        args, _keep = self._rows_args(seqs, want)
+        nw = args[6]
+        if isinstance(params, _lib.VqaSampling):
+            params = [params] * nw
+        if len(params) != nw:
+            raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
+        prm = (_lib.VqaSampling * max(nw, 1))(*params)
+        out = np.empty((max(nw, 1),), np.int32)
+        _lib.check_vqa(self.lib.vstar_vqa_forward_sample(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out)),
+                       self.handle)
+        return out[:nw]
 
     def last_forward_ms(self) -> float:
         return float(self.lib.vstar_vqa_last_forward_ms(self.handle))
