@@ -120,6 +120,35 @@ int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_o
 int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld,
                         const vstar_vqa_sampling* params, int32_t* tokens, float* u_out, int32_t* n_kept);
 
+/* Beam search: HF 4.31 generate(num_beams=k).  vstar_vqa_forward with the arg-max replaced by the beam-select
+ * tail: wanted row j carries the fp32 beam score beam_scores[j]; rows group_off[g] .. group_off[g+1]-1 of `want` form group g
+ * (the k beams of one sample, 1 .. 16 rows).  Per row lp = log_softmax(logits) (log-sum-exp in double, rounded to fp16) and
+ * s = beam score + lp (one fp32 add); per group the n_cand (<= 32, <= rows x vocab) largest s, sorted by (s descending,
+ * row_in_group * vocab + token ascending), come back as cand_scores / cand_tokens / cand_rows [n_groups, n_cand] (host).
+ * logits_f16 (nullable): the raw logits rows as in vstar_vqa_forward. */
+int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                           const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                           const float* beam_scores, int n_groups, const int32_t* group_off, int n_cand, float* cand_scores,
+                           int32_t* cand_tokens, int32_t* cand_rows, uint16_t* logits_f16);
+/* Beam reorder without moving K/V: every slot has an ancestry row (position p of its sequence lives in slot anc[slot][p]);
+ * entries [lo, hi) of dst_slot[i] become those of src_slot[i] for i < n, as if every source were read before any destination is
+ * written (swaps, one source feeding several destinations).  The destinations become "ancestral": their continued sequences
+ * (prefix_slot == kv_slot) attend through the table; a fresh sequence (past_len 0) in the slot, or a fork INTO it (prefix_slot
+ * another slot, whose [0, past_len) it then reads) makes it an ordinary slot again; forking FROM an ancestral slot is an error
+ * (kv_copy it into a slot of its own first).  The rows a
+ * forward call writes always land in the sequence's own slot, so a physical row is written once and never overwritten while a
+ * descendant can read it — as long as every beam of a search advances by the same positions. */
+int vstar_vqa_kv_reorder(vstar_vqa_handle* h, int n, const int32_t* dst_slot, const int32_t* src_slot, int lo, int hi);
+/* Physical copy of the K/V rows [lo, hi) of every layer into dst's own rows, read through src's ancestry (dst != src); dst's
+ * ancestry becomes the identity.  Detaches a beam; the yardstick of the reorder's bit-identity tests. */
+int vstar_vqa_kv_copy(vstar_vqa_handle* h, int dst, int src, int lo, int hi);
+/* Op-level beam select (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22); host
+ * beam_scores[rows], group_off[n_groups+1], outputs [n_groups, n_cand]; lp_out (nullable, host, [rows, vocab]) the rounded
+ * log-probabilities as float.  Null stream, synchronises. */
+int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const float* beam_scores,
+                             int n_groups, const int32_t* group_off, int n_cand, float* cand_scores, int32_t* cand_tokens,
+                             int32_t* cand_rows, float* lp_out);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

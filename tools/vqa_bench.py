@@ -4,6 +4,8 @@ KV-cached decode steps at several batch sizes, forked option scoring.  Prints on
   python tools/vqa_bench.py [--out profiles/r01_vqa_bench.json] [--layers 32] [--sample]
 --sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
 sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio.
+--beams 1,2,4,8 adds `decode_beams`: beam-search steps of one prompt with k beams (forward_beam's select tail, the host scorer,
+the KV ancestry reorder) alternated with greedy steps of k copies of the same prompt, and the beam / greedy step-time ratio.
 Decode steps are bound by the weight sweep (13.5 GB fp16 per step at 7B): `weights_GBps` = bytes of all LLaMA + lm_head
 weights / device time of one step (HIP events inside the engine), against the ~8 TB/s HBM3E peak.
 """
@@ -30,7 +32,8 @@ def main():
     ap.add_argument("--batches", default="1,4,16,32")
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--sample", action="store_true", help="add the sampled-decode leg next to greedy")
-    ap.add_argument("--rounds", type=int, default=3, help="--sample: greedy / sampled blocks alternated this many times")
+    ap.add_argument("--rounds", type=int, default=3, help="--sample / --beams: blocks alternated this many times")
+    ap.add_argument("--beams", default="", help="comma-separated beam counts: add the beam-search leg next to greedy")
     a = ap.parse_args()
     cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=40, max_ctx=1024, max_rows=16384, max_images=8)
     t0 = time.time()
@@ -85,6 +88,8 @@ def main():
     out["decode"] = dec
     if a.sample:
         out["decode_sample"] = decode_sample(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)
+    if a.beams:
+        out["decode_beams"] = decode_beams(eng, plain_rows, [int(x) for x in a.beams.split(",")], a.steps, a.rounds)
     # option scoring: 4 options x 12 tokens forked from one question prefix
     eng.forward([Seq(short_rows, kv_slot=0)], [(0, -1)])
     P = len(short_rows)
@@ -132,6 +137,49 @@ def decode_sample(eng, rows, batches, steps, rounds):
         leg["sample_over_greedy_tokens_per_s"] = round(leg["sample"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
         leg["sample_minus_greedy_device_ms"] = round(leg["sample"]["device_ms_per_step"] - leg["greedy"]["device_ms_per_step"], 4)
         res[f"B{B}"] = leg
+    return res
+
+
+def decode_beams(eng, rows, beams, steps, rounds):
+    """Beam-search steps (k beams of one prompt, slots k .. 2k-1: select tail + host scorer + ancestry reorder) vs greedy steps
+    of k copies of the prompt (slots 0 .. k-1), alternated in blocks of `steps`.  EOS is disabled (id -1) so that every step
+    runs all k beams."""
+    from vstar_amd.beam import BeamSearch
+    res = {}
+    P = len(rows)
+    for k in beams:
+        g_slots, b_slots = list(range(k)), list(range(k, 2 * k))
+        _, nxt = eng.forward([Seq(rows, kv_slot=s) for s in g_slots], [(i, -1) for i in range(k)], logits=False)
+        bs = BeamSearch(k, P, -1, 10 ** 9)
+        cs, ct, cr, _ = eng.forward_beam([Seq(rows, kv_slot=b_slots[0])], [(0, -1)] * k, bs.scores, [0, k], 2 * k)
+        gpos = bpos = P
+        goff = [0, k]
+        dev = {"greedy": [], "beam": []}
+        wall = {"greedy": 0.0, "beam": 0.0}
+        for r in range(rounds):
+            for mode in ("greedy", "beam"):
+                t0 = time.time()
+                for s in range(steps):
+                    if mode == "greedy":
+                        _, nxt = eng.forward([Seq([int(nxt[i])], kv_slot=g_slots[i], past_len=gpos) for i in range(k)],
+                                             [(i, 0) for i in range(k)], logits=False)
+                        gpos += 1
+                    else:
+                        par = bs.process(cs[0], ct[0], cr[0])
+                        eng.kv_reorder(b_slots, [b_slots[p] for p in par], 0, bpos)
+                        cs, ct, cr, _ = eng.forward_beam([Seq([bs.tokens[b][-1]], kv_slot=b_slots[b], past_len=bpos) for b in range(k)],
+                                                         [(b, 0) for b in range(k)], bs.scores, goff, 2 * k)
+                        bpos += 1
+                    dev[mode].append(eng.last_forward_ms())
+                wall[mode] += time.time() - t0
+        leg = {}
+        for mode in ("greedy", "beam"):
+            w = wall[mode] / (rounds * steps) * 1e3
+            leg[mode] = {"device_ms_per_step": round(float(np.median(dev[mode])), 3), "wall_ms_per_step": round(w, 3),
+                         "tokens_per_s": round(k / w * 1e3, 1)}
+        leg["beam_over_greedy_step_time"] = round(leg["beam"]["wall_ms_per_step"] / leg["greedy"]["wall_ms_per_step"], 4)
+        leg["beam_minus_greedy_device_ms"] = round(leg["beam"]["device_ms_per_step"] - leg["greedy"]["device_ms_per_step"], 4)
+        res[f"k{k}"] = leg
     return res
 
 

@@ -242,16 +242,29 @@ class LlavaSearchModel:
     @torch.inference_mode()
     def generate(self, input_ids, images=None, object_features=None, images_long=None, objects_long=None, do_sample: bool = False,
                  num_beams: int = 1, temperature: float = 0, top_p=None, max_new_tokens: int = 200, use_cache: bool = True,
-                 stopping_criteria=None, top_k=50, seed=None, **unused):
-        """do_sample=False: greedy.  do_sample=True: HF 4.31 sampling (temperature > 0, top_k, top_p) on the device, keyed by
-        `seed` (None: drawn from torch's default CPU generator) — the same draws as VQA_LLM.free_form_inference(seed=seed)."""
+                 stopping_criteria=None, top_k=50, seed=None, length_penalty: float = 1.0, early_stopping=False,
+                 num_return_sequences: int = 1, **unused):
+        """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
+        early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
+        sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
+        — the same draws as VQA_LLM.free_form_inference(seed=seed).  Beam sampling is not implemented."""
         from .vqa import resolve_seed, sampling_params
         from .vqa_engine import Seq
-        if num_beams != 1:
-            raise NotImplementedError("beam search (num_beams > 1) is not implemented")
+        if num_beams != 1 and do_sample:
+            raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not implemented")
+        if num_beams < 1:
+            raise ValueError(f"num_beams must be >= 1, got {num_beams}")
+        if not 1 <= num_return_sequences <= num_beams:
+            raise ValueError(f"num_return_sequences must be in [1, num_beams], got {num_return_sequences}")
+        if num_beams > self.cfg.max_slots:
+            raise ValueError(f"num_beams={num_beams} needs {num_beams} KV slots; the engine has max_slots={self.cfg.max_slots}")
         if do_sample and not temperature > 0:
             raise ValueError(f"do_sample=True needs temperature > 0, got {temperature}")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
+        if num_beams > 1:
+            outs = self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
+                                         early_stopping, num_return_sequences)[0]
+            return torch.tensor([ids + o for o in outs], dtype=torch.long)
         if do_sample:
             p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
             new = self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p])[0]

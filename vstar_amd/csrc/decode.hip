@@ -462,13 +462,23 @@ __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __rest
 // ------------------------------------------------ attention over the KV cache ------------------------------------------------
 // FUSED (decode steps: every sequence contributes exactly one new row): the workgroup also applies RoPE to its row's q and
 // k, appends k and v to the cache and attends to them from LDS — rope_kv_append's work without its launch.
-template <bool FUSED>
+// ANC (beam search): key / value row j of a sequence lives in slot anc[kv_slot * ctx + j] (the KV ancestry
+// table) instead of `j < past ? prefix : own`; the caller has set the entries of the rows it writes to kv_slot.
+template <bool ANC>
+__device__ __forceinline__ const lp_t* kv_row(const lp_t* head0, const lp_t* pre, const lp_t* own, const int32_t* arow, int j, int past,
+                                              int64_t slot_stride) {
+  constexpr int D = 128;
+  if constexpr (ANC) return head0 + (int64_t)arow[j] * slot_stride + (int64_t)j * D;
+  else return (j < past ? pre : own) + (int64_t)j * D;
+}
+
+template <bool FUSED, bool ANC>
 __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc,
                                                           const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_pos,
                                                           const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix,
                                                           const int32_t* __restrict__ seq_past, const lp_t* __restrict__ cos_sin,
                                                           lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride,
-                                                          float inv_scale) {
+                                                          float inv_scale, const int32_t* __restrict__ anc) {
   constexpr int D = 128;
   extern __shared__ float dyn[];            // [D] q | [nk] scores/probabilities
   __shared__ float redbuf[8];
@@ -484,6 +494,9 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   const lp_t* kpre = kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
   lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
   const lp_t* vpre = vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  const lp_t* kh0 = kc + (int64_t)h * ctx * D;
+  const lp_t* vh0 = vc + (int64_t)h * ctx * D;
+  const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   float* qs = dyn;
   float* sc = dyn + D;
   const lp_t* rowp = qkv + (int64_t)r * (3 * H * D) + h * D;
@@ -525,7 +538,7 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
       kv8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (j < nkc) kv8[u] = *(const lpx8*)((j < past ? kpre : kown) + (int64_t)j * D + l16 * 8);
+      if (j < nkc) kv8[u] = *(const lpx8*)(kv_row<ANC>(kh0, kpre, kown, arow, j, past, slot_stride) + l16 * 8);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -584,7 +597,7 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
       v8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
       pr[u] = 0.f;
       if (j < nkc) {
-        v8[u] = *(const lpx8*)((j < past ? vpre : vown) + (int64_t)j * D + l16 * 8);
+        v8[u] = *(const lpx8*)(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride) + l16 * 8);
         pr[u] = rlp(sc[j] * inv);
       }
     }
@@ -628,11 +641,12 @@ __device__ __forceinline__ void split_range(int nkc, int p, int* lo, int* hi) {
   *hi = *lo + span < nkc ? *lo + span : nkc;
 }
 
+template <bool ANC>
 __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
     const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc, const int32_t* __restrict__ row_seq,
     const int32_t* __restrict__ row_pos, const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix,
     const int32_t* __restrict__ seq_past, const lp_t* __restrict__ cos_sin, float* __restrict__ ws_scores, float* __restrict__ ws_stats,
-    int H, int ctx, int64_t slot_stride, float inv_scale) {
+    int H, int ctx, int64_t slot_stride, float inv_scale, const int32_t* __restrict__ anc) {
   constexpr int D = 128;
   extern __shared__ float dyn[];            // this partition's scores (span + 1)
   __shared__ float qs[D], own_k[D], redbuf[8];
@@ -644,6 +658,8 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   lp_t* kown = kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
   const lp_t* kpre = kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
   lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const lp_t* kh0 = kc + (int64_t)h * ctx * D;
+  const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const lp_t* rowp = qkv + (int64_t)r * (3 * H * D) + h * D;
   const bool last = p == SPLIT_P - 1;
   if (tid < 128) {                           // rotate-half RoPE with HF's rounding points: tid 0-63 q pairs, 64-127 k pairs
@@ -682,7 +698,7 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
       kv8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (j < j_hi) kv8[u] = *(const lpx8*)((j < past ? kpre : kown) + (int64_t)j * D + l16 * 8);
+      if (j < j_hi) kv8[u] = *(const lpx8*)(kv_row<ANC>(kh0, kpre, kown, arow, j, past, slot_stride) + l16 * 8);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -733,11 +749,12 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   }
 }
 
+template <bool ANC>
 __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
     const lp_t* __restrict__ vc, const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_pos,
     const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix, const int32_t* __restrict__ seq_past,
     const float* __restrict__ ws_scores, const float* __restrict__ ws_stats, float* __restrict__ ws_opart, int* __restrict__ ws_cnt,
-    lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride) {
+    lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride, const int32_t* __restrict__ anc) {
   constexpr int D = 128;
   __shared__ float part[16][D];
   __shared__ int ticket;
@@ -748,6 +765,8 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
   const int past = seq_past[seq], nkc = pos;
   const lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
   const lp_t* vpre = vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  const lp_t* vh0 = vc + (int64_t)h * ctx * D;
+  const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const float* st = ws_stats + ((int64_t)r * H + h) * SPLIT_P * 2;
   float M = -3.0e38f;
 #pragma unroll
@@ -773,7 +792,7 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
       v8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
       pr[u] = 0.f;
       if (j < j_hi) {
-        v8[u] = *(const lpx8*)((j < past ? vpre : vown) + (int64_t)j * D + l16 * 8);
+        v8[u] = *(const lpx8*)(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride) + l16 * 8);
         pr[u] = rlp(__expf(gsc[j] - M) * inv);     // probabilities rounded to the storage type (HF .to(query.dtype))
       }
     }
@@ -883,6 +902,53 @@ __global__ __launch_bounds__(256) void perceiver_attn_kernel(const lp_t* __restr
   }
 }
 
+// ------------------------------------------------ KV ancestry table ------------------------------------------------
+// the rows a forward call writes live in their own slot
+__global__ void kv_anc_mark_kernel(const int32_t* __restrict__ row_slot, const int32_t* __restrict__ row_pos, int R,
+                                   int32_t* __restrict__ anc, int ctx) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int pos = row_pos[r];
+  if (pos < 0) return;                                   // padding row
+  anc[(int64_t)row_slot[r] * ctx + pos] = row_slot[r];
+}
+
+__global__ void kv_anc_fill_kernel(int32_t* __restrict__ row, int value, int lo, int hi) {
+  const int p = lo + blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < hi) row[p] = value;
+}
+
+__global__ void kv_anc_gather_kernel(const int32_t* __restrict__ anc, int32_t* __restrict__ tmp, const int32_t* __restrict__ src,
+                                     int lo, int w, int ctx) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (p < w) tmp[(int64_t)i * w + p] = anc[(int64_t)src[i] * ctx + lo + p];
+}
+
+__global__ void kv_anc_scatter_kernel(int32_t* __restrict__ anc, const int32_t* __restrict__ tmp, const int32_t* __restrict__ dst,
+                                      int lo, int w, int ctx) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (p < w) anc[(int64_t)dst[i] * ctx + lo + p] = tmp[(int64_t)i * w + p];
+}
+
+// K / V rows [lo, lo + w) of every layer and head: dst's own rows <- the rows src's ancestry points at (16 B per thread)
+__global__ void kv_copy_rows_kernel(lp_t* __restrict__ kc, lp_t* __restrict__ vc, const int32_t* __restrict__ anc, int dst, int src,
+                                    int lo, int w, int H, int ctx, int64_t slot_stride, int64_t layer_stride, int64_t n) {
+  constexpr int D = 128;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const int v8 = (int)(idx & 15);
+  int64_t rest = idx >> 4;
+  const int p = lo + (int)(rest % w);
+  rest /= w;
+  const int h = (int)(rest % H);
+  rest /= H;
+  const int which = (int)(rest & 1);
+  const int64_t layer = rest >> 1;
+  lp_t* base = (which ? vc : kc) + layer * layer_stride + (int64_t)h * ctx * D + (int64_t)p * D + v8 * 8;
+  const int from = anc[(int64_t)src * ctx + p];
+  *(lpx8*)(base + (int64_t)dst * slot_stride) = *(const lpx8*)(base + (int64_t)from * slot_stride);
+}
+
 __global__ void argmax_rows_lp_kernel(const lp_t* __restrict__ x, int cols, int64_t ld, int32_t* __restrict__ out) {
   __shared__ float bv[4];
   __shared__ int bi[4];
@@ -961,11 +1027,11 @@ size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx) {
   return rh * ((size_t)ctx * 4 + SPLIT_P * 2 * 4 + SPLIT_P * 128 * 4 + 4) + 256;
 }
 
-hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
-                            const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
-                            lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
-                            int split_max_rows) {
-  if (R <= 0) return hipSuccess;
+template <bool ANC>
+static hipError_t cached_attention_t(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
+                                     const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
+                                     lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
+                                     int split_max_rows, const int32_t* anc) {
   static const bool split_on = [] { const char* v = getenv("VSTAR_DECODE_SPLIT_KV"); return !v || atoi(v) != 0; }();
   // decode steps of few sequences: P partitions per (row, head) so that the K / V streams of a head run on 8 CUs instead of one
   if (split_on && fused_cos_sin && split_ws && R <= split_max_rows && R * H <= 128 && max_keys >= 256) {
@@ -975,21 +1041,67 @@ hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* 
     float* ws_opart = ws_stats + rh * SPLIT_P * 2;
     int* ws_cnt = (int*)(ws_opart + rh * SPLIT_P * 128);
     const int span = ((((max_keys + SPLIT_P - 1) / SPLIT_P) + 63) & ~63) + 1;
-    hipLaunchKernelGGL(cached_attn_split_scores_kernel, dim3(R, H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s, qkv, kc, vc,
-                       row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, ws_scores, ws_stats, H, ctx, slot_stride,
-                       sqrtf(128.0f));
-    hipLaunchKernelGGL(cached_attn_split_pv_kernel, dim3(R, H, SPLIT_P), dim3(256), 0, s, vc, row_seq, row_pos, seq_kv, seq_prefix,
-                       seq_past, ws_scores, ws_stats, ws_opart, ws_cnt, out, H, ctx, slot_stride);
+    hipLaunchKernelGGL(cached_attn_split_scores_kernel<ANC>, dim3(R, H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s, qkv, kc,
+                       vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, ws_scores, ws_stats, H, ctx, slot_stride,
+                       sqrtf(128.0f), anc);
+    hipLaunchKernelGGL(cached_attn_split_pv_kernel<ANC>, dim3(R, H, SPLIT_P), dim3(256), 0, s, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, ws_scores, ws_stats, ws_opart, ws_cnt, out, H, ctx, slot_stride, anc);
     return hipGetLastError();
   }
   const size_t lds = (size_t)(128 + max_keys) * sizeof(float);
   if (lds > 40 * 1024) return hipErrorInvalidValue;
   if (fused_cos_sin)
-    hipLaunchKernelGGL(cached_attn_kernel<true>, dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix,
-                       seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f));
+    hipLaunchKernelGGL((cached_attn_kernel<true, ANC>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc);
   else
-    hipLaunchKernelGGL(cached_attn_kernel<false>, dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix,
-                       seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f));
+    hipLaunchKernelGGL((cached_attn_kernel<false, ANC>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc);
+  return hipGetLastError();
+}
+
+hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
+                            const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
+                            lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
+                            int split_max_rows, const int32_t* anc) {
+  if (R <= 0) return hipSuccess;
+  if (anc)
+    return cached_attention_t<true>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, out, R, H, ctx,
+                                    slot_stride, max_keys, s, split_ws, split_max_rows, anc);
+  return cached_attention_t<false>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, out, R, H, ctx,
+                                   slot_stride, max_keys, s, split_ws, split_max_rows, nullptr);
+}
+
+// ---- KV ancestry table (beam search): anc[slot * ctx + p] = the slot whose cache holds position p ----
+hipError_t kv_anc_mark(const int32_t* row_slot, const int32_t* row_pos, int R, int32_t* anc, int ctx, hipStream_t s) {
+  if (R <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kv_anc_mark_kernel, dim3((R + 255) / 256), dim3(256), 0, s, row_slot, row_pos, R, anc, ctx);
+  return hipGetLastError();
+}
+
+hipError_t kv_anc_fill(int32_t* anc, int slot, int value, int lo, int hi, int ctx, hipStream_t s) {
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > ctx ? ctx : hi;
+  if (hi <= lo) return hipSuccess;
+  hipLaunchKernelGGL(kv_anc_fill_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, s, anc + (int64_t)slot * ctx, value, lo, hi);
+  return hipGetLastError();
+}
+
+hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, const int32_t* d_src, int n, int lo, int hi, int ctx,
+                          hipStream_t s) {
+  const int w = hi - lo;
+  if (n <= 0 || w <= 0) return hipSuccess;
+  const dim3 grid((w + 255) / 256, n);
+  hipLaunchKernelGGL(kv_anc_gather_kernel, grid, dim3(256), 0, s, anc, tmp, d_src, lo, w, ctx);     // every source read ...
+  hipLaunchKernelGGL(kv_anc_scatter_kernel, grid, dim3(256), 0, s, anc, tmp, d_dst, lo, w, ctx);    // ... before any destination
+  return hipGetLastError();
+}
+
+hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
+                        int64_t slot_stride, int64_t layer_stride, hipStream_t s) {
+  if (hi <= lo) return hipSuccess;
+  const int64_t n = (int64_t)2 * layers * H * (hi - lo) * 16;
+  hipLaunchKernelGGL(kv_copy_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kc, vc, anc, dst, src, lo, hi - lo, H, ctx,
+                     slot_stride, layer_stride, n);
   return hipGetLastError();
 }
 

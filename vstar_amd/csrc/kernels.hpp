@@ -109,7 +109,18 @@ hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const int32_t* row_pos
 hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
                             const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
                             lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s,
-                            void* split_ws = nullptr, int split_max_rows = 0);
+                            void* split_ws = nullptr, int split_max_rows = 0, const int32_t* anc = nullptr);
+// KV ancestry table of beam search (anc: [slots, ctx] int32, entry (slot, p) = the slot whose cache holds position p of the
+// sequence in `slot`; cached_attention reads K/V through it when `anc` is given).  mark: entry (row_slot[r], row_pos[r]) =
+// row_slot[r] for every row; fill: slot's entries [lo, hi) = value; reorder: entries [lo, hi) of dst[i] = those of src[i], every
+// source read before any destination is written (tmp: n * (hi - lo) ints); copy_rows: K/V rows [lo, hi) of every layer of
+// `dst` = the rows src's entries point at (a physical copy).
+hipError_t kv_anc_mark(const int32_t* row_slot, const int32_t* row_pos, int R, int32_t* anc, int ctx, hipStream_t s);
+hipError_t kv_anc_fill(int32_t* anc, int slot, int value, int lo, int hi, int ctx, hipStream_t s);
+hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, const int32_t* d_src, int n, int lo, int hi, int ctx,
+                          hipStream_t s);
+hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
+                        int64_t slot_stride, int64_t layer_stride, hipStream_t s);
 // workspace of the split-KV decode path (scores, partial statistics / outputs, tickets) for up to max_rows new rows per step;
 // must be zero-filled once
 size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx);

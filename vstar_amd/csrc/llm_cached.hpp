@@ -11,8 +11,21 @@
 #pragma once
 #include "engine_base.hpp"
 #include "sample.hpp"
+#include "beam.hpp"
 
 namespace VS_NS {
+
+// The beam-search tail of forward() (beam.hip): host arrays.  The wanted rows carry scores[n_want] and form
+// n_groups groups (rows goff[g] .. goff[g+1]-1 of `want`); each group's n_cand best (score, token, row in group) come back.
+struct LlmBeamArgs {
+  const float* scores = nullptr;
+  int n_groups = 0;
+  const int32_t* goff = nullptr;
+  int n_cand = 0;
+  float* cand_s = nullptr;
+  int32_t* cand_tok = nullptr;
+  int32_t* cand_row = nullptr;
+};
 
 struct LlmCachedCfg {
   int hidden = 0, heads = 0, mlp = 0, layers = 0, vocab = 0;
@@ -44,6 +57,17 @@ struct LlmCached {
   int max_want = 256;
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
+  // ---- beam search ----
+  // KV ancestry table [max_slots, max_ctx]: position p of the sequence in slot s lives in slot d_anc[s * max_ctx + p].  A slot is
+  // "ancestral" (anc_flag) once kv_reorder has written its entries; its continued sequences then attend through the table (the
+  // ANC attention kernels).  A fresh sequence (past_len 0) in the slot resets it to identity, and so does a fork into it (prefix
+  // another slot) — unless the same call runs ANC, where the fork's entries are written as [0, past) -> prefix instead.  Forking
+  // FROM an ancestral slot is an error.
+  int32_t *d_anc = nullptr, *d_anc_tmp = nullptr, *d_reo = nullptr;
+  std::vector<char> anc_flag;
+  float *d_bscore = nullptr, *d_cand_s = nullptr;
+  int32_t *d_goff = nullptr, *d_cand_t = nullptr, *d_cand_r = nullptr;
+  char* beam_ws = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_ms = 0;
   // ---- greedy decode of ONE sequence as a replayed hipGraph (decode_greedy_graph) ----
@@ -81,10 +105,12 @@ struct LlmCached {
   int lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M, int epi,
                const lp_t* Wt = nullptr);
   int llm_layers_prefill(int nseq, int S);
-  int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows);
+  int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
               const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out,
-              const vstar_vqa_sampling* sample_params = nullptr);
+              const vstar_vqa_sampling* sample_params = nullptr, const LlmBeamArgs* beam = nullptr);
+  int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
+  int kv_copy(int dst, int src, int lo, int hi);
 };
 
 inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t* embed_, const std::vector<LlmBlock>* blocks_,
@@ -130,6 +156,22 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
     const size_t wb = cached_attention_split_ws_bytes(SPLIT_ROWS, c.heads, c.max_ctx);
     RC(e->dalloc(&split_ws, wb));
     if (hipMemset(split_ws, 0, wb) != hipSuccess) { set_error("split-KV workspace memset failed"); return VSTAR_ERR_HIP; }
+  }
+  {  // beam search: the ancestry table (identity), its reorder scratch, the select tail's buffers
+    const size_t na = (size_t)c.max_slots * c.max_ctx;
+    RC(e->dalloc(&d_anc, na));
+    RC(e->dalloc(&d_anc_tmp, na));
+    RC(e->dalloc(&d_reo, (size_t)2 * c.max_slots));
+    std::vector<int32_t> ident(na);
+    for (size_t i = 0; i < na; ++i) ident[i] = (int32_t)(i / c.max_ctx);
+    if (hipMemcpy(d_anc, ident.data(), na * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("ancestry table upload failed"); return VSTAR_ERR_HIP; }
+    anc_flag.assign((size_t)c.max_slots, 0);
+    RC(e->dalloc(&d_bscore, (size_t)max_want));
+    RC(e->dalloc(&d_goff, (size_t)max_want + 1));
+    RC(e->dalloc(&d_cand_s, (size_t)max_want * VSTAR_BEAM_MAX_CAND));
+    RC(e->dalloc(&d_cand_t, (size_t)max_want * VSTAR_BEAM_MAX_CAND));
+    RC(e->dalloc(&d_cand_r, (size_t)max_want * VSTAR_BEAM_MAX_CAND));
+    RC(e->dalloc(&beam_ws, vstar_beam_ws_bytes(max_want, VSTAR_BEAM_MAX_CAND)));
   }
   if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { set_error("hipEventCreate failed"); return VSTAR_ERR_HIP; }
   {  // tile-major copies of q|k|v, gate|up and down for the decode GEMV (o_proj's 33 MB live in the Infinity Cache either way).
@@ -237,7 +279,7 @@ inline int LlmCached::llm_layers_prefill(int nseq, int S) {
   return 0;
 }
 
-inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool single_rows) {
+inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc) {
   const LlmCachedCfg& c = cfg;
   const int H = c.hidden;
   const int32_t *d_kv = d_seq, *d_prefix = d_seq + c.max_slots * 4, *d_past = d_seq + 2 * c.max_slots * 4;
@@ -250,7 +292,7 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
     if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream));
     LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
-                          c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS));
+                          c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc));
     RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H));
     RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i]));
     RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i]));
@@ -260,7 +302,8 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
 
 inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
-                              uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params) {
+                              uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params,
+                              const LlmBeamArgs* beam) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
   if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
@@ -293,9 +336,44 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
         e->set_error("sampling parameters: temperature must be > 0 and finite, top_k >= 0, top_p >= 0");
         return VSTAR_ERR_INVALID;
       }
+  if (beam) {
+    if (n_want < 1 || !beam->cand_s || !beam->cand_tok || !beam->cand_row) { e->set_error("forward_beam: no wanted rows / outputs"); return VSTAR_ERR_INVALID; }
+    if (const char* m = vstar_beam_check(n_want, c.vocab, beam->scores, beam->n_groups, beam->goff, beam->n_cand)) {
+      e->set_error(std::string("forward_beam: ") + m);
+      return VSTAR_ERR_INVALID;
+    }
+  }
+  // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
+  bool use_anc = false;
+  for (int i = 0; i < nseq; ++i) {
+    const bool fork = past_len[i] > 0 && prefix_slot[i] != kv_slot[i];
+    if (fork && anc_flag[prefix_slot[i]]) {      // its [0, past) is scattered over other slots: not one prefix slot
+      e->set_error("forking from a beam-reordered KV slot is not supported (kv_copy it into a slot of its own first)");
+      return VSTAR_ERR_INVALID;
+    }
+    use_anc = use_anc || (!fork && past_len[i] > 0 && anc_flag[kv_slot[i]]);
+  }
   const bool prefill = all_fresh && R > 64;
   const int rows = prefill ? nseq * maxT : R;
   if (rows > c.max_rows) { e->set_error("too many rows for one forward call (max_rows)"); return VSTAR_ERR_INVALID; }
+  for (int i = 0; i < nseq; ++i) {
+    const int s = kv_slot[i];
+    if (past_len[i] > 0 && prefix_slot[i] != s) {
+      // a fork into slot s: its [0, past) lives in the (non-ancestral) prefix slot, the rest in s itself.  In an ANC call the
+      // table must say so (s becomes ancestral); otherwise the plain kernels read the prefix and s goes back to identity.
+      if (use_anc) {
+        LCHK(kv_anc_fill(d_anc, s, prefix_slot[i], 0, past_len[i], c.max_ctx, e->stream));
+        LCHK(kv_anc_fill(d_anc, s, s, past_len[i], c.max_ctx, c.max_ctx, e->stream));
+        anc_flag[s] = 1;
+      } else if (anc_flag[s]) {
+        LCHK(kv_anc_fill(d_anc, s, s, 0, c.max_ctx, c.max_ctx, e->stream));
+        anc_flag[s] = 0;
+      }
+    } else if (past_len[i] == 0 && anc_flag[s]) {      // a fresh sequence in a reordered slot: the slot owns its rows again
+      LCHK(kv_anc_fill(d_anc, s, s, 0, c.max_ctx, c.max_ctx, e->stream));
+      anc_flag[s] = 0;
+    }
+  }
   // ---- row metadata ----
   std::vector<int32_t> h_src((size_t)rows, INT32_MIN), h_pos((size_t)rows, -1), h_slot((size_t)rows, 0), h_seq((size_t)rows, 0);
   std::vector<int32_t> h_want((size_t)(n_want ? n_want : 1), 0), remap((size_t)R);
@@ -325,18 +403,31 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   if (n_want) LCHK(hipMemcpyAsync(d_want, h_want.data(), (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
   if (n_want && sample_params)
     LCHK(hipMemcpyAsync(d_sparams, sample_params, (size_t)n_want * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice, e->stream));
+  if (beam) {
+    LCHK(hipMemcpyAsync(d_bscore, beam->scores, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+    LCHK(hipMemcpyAsync(d_goff, beam->goff, (size_t)(beam->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  }
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, rows, H, e->stream));
+  if (use_anc) LCHK(kv_anc_mark(d_row_slot, d_row_pos, rows, d_anc, c.max_ctx, e->stream));   // the new rows live in their own slot
   if (prefill) RC(llm_layers_prefill(nseq, maxT));
-  else RC(llm_layers_cached(rows, nseq, max_keys, maxT == 1));
+  else RC(llm_layers_cached(rows, nseq, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
   // ---- model.norm + lm_head on the wanted rows (llava_search_llama.py:92-93) ----
   const size_t vpad = (size_t)(c.vocab + 255) / 256 * 256;
   if (n_want) {
     LCHK(gather_rows(lx, d_want, wsel, n_want, H, e->stream));
     RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, n_want, VSTAR_EPI_NONE));
-    if (sample_params) {   // the sampling tail (sample.hip) in place of the arg-max: d_argmax receives the drawn tokens
+    if (beam) {            // the beam-search tail (beam.hip) in place of the arg-max: each group's n_cand best candidates
+#ifdef VSTAR_LP_F16
+      LCHK(vstar_beam_select_f16(logits, n_want, c.vocab, (int64_t)vpad, d_bscore, beam->n_groups, d_goff, beam->n_cand, beam_ws,
+                                 d_cand_s, d_cand_t, d_cand_r, nullptr, e->stream));
+#else
+      LCHK(vstar_beam_select_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_bscore, beam->n_groups, d_goff, beam->n_cand, beam_ws,
+                                  d_cand_s, d_cand_t, d_cand_r, nullptr, e->stream));
+#endif
+    } else if (sample_params) {   // the sampling tail (sample.hip) in place of the arg-max: d_argmax receives the drawn tokens
 #ifdef VSTAR_LP_F16
       LCHK(vstar_sample_rows_f16(logits, n_want, c.vocab, (int64_t)vpad, d_sparams, d_argmax, nullptr, nullptr, e->stream));
 #else
@@ -350,11 +441,60 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   if (n_want && logits_out)
     LCHK(hipMemcpy2DAsync(logits_out, (size_t)c.vocab * 2, logits, vpad * 2, (size_t)c.vocab * 2, n_want,
                             hipMemcpyDeviceToHost, e->stream));
-  if (n_want && argmax_out) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  if (n_want && argmax_out && !beam) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  if (beam) {
+    const size_t nc = (size_t)beam->n_groups * beam->n_cand;
+    LCHK(hipMemcpyAsync(beam->cand_s, d_cand_s, nc * 4, hipMemcpyDeviceToHost, e->stream));
+    LCHK(hipMemcpyAsync(beam->cand_tok, d_cand_t, nc * 4, hipMemcpyDeviceToHost, e->stream));
+    LCHK(hipMemcpyAsync(beam->cand_row, d_cand_r, nc * 4, hipMemcpyDeviceToHost, e->stream));
+  }
   LCHK(hipStreamSynchronize(e->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) last_ms = ms;
   e->collect_profile();
+  return 0;
+}
+
+// Beam reorder without moving K/V: entries [lo, hi) of dst[i]'s ancestry = those of src[i], all sources read first (swaps and
+// repeated sources are fine); the destinations become ancestral slots.
+inline int LlmCached::kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi) {
+  if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
+  const LlmCachedCfg& c = cfg;
+  if (n <= 0 || n > c.max_slots || !dst || !src || lo < 0 || hi < lo || hi > c.max_ctx) {
+    e->set_error("kv_reorder: bad argument (1 <= n <= max_slots, 0 <= lo <= hi <= max_ctx)");
+    return VSTAR_ERR_INVALID;
+  }
+  std::vector<char> seen((size_t)c.max_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (dst[i] < 0 || dst[i] >= c.max_slots || src[i] < 0 || src[i] >= c.max_slots) { e->set_error("kv_reorder: KV slot out of range"); return VSTAR_ERR_INVALID; }
+    if (seen[dst[i]]) { e->set_error("kv_reorder: a destination slot appears twice"); return VSTAR_ERR_INVALID; }
+    seen[dst[i]] = 1;
+  }
+  if (hi == lo) return 0;
+  LCHK(hipSetDevice(e->device));
+  std::vector<int32_t> ds((size_t)2 * n);
+  for (int i = 0; i < n; ++i) { ds[i] = dst[i]; ds[(size_t)n + i] = src[i]; }
+  LCHK(hipMemcpyAsync(d_reo, ds.data(), ds.size() * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(kv_anc_reorder(d_anc, d_anc_tmp, d_reo, d_reo + n, n, lo, hi, c.max_ctx, e->stream));
+  LCHK(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < n; ++i) anc_flag[dst[i]] = 1;
+  return 0;
+}
+
+// Physical copy of K/V rows [lo, hi) of every layer into dst's own rows, read through src's ancestry; dst's ancestry becomes the
+// identity (dst is no longer ancestral).
+inline int LlmCached::kv_copy(int dst, int src, int lo, int hi) {
+  if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
+  const LlmCachedCfg& c = cfg;
+  if (dst < 0 || dst >= c.max_slots || src < 0 || src >= c.max_slots || dst == src || lo < 0 || hi < lo || hi > c.max_ctx) {
+    e->set_error("kv_copy: bad argument (distinct slots in range, 0 <= lo <= hi <= max_ctx)");
+    return VSTAR_ERR_INVALID;
+  }
+  LCHK(hipSetDevice(e->device));
+  LCHK(kv_copy_rows(kcache, vcache, d_anc, dst, src, lo, hi, c.layers, c.heads, c.max_ctx, slot_stride, layer_stride, e->stream));
+  LCHK(kv_anc_fill(d_anc, dst, dst, 0, c.max_ctx, c.max_ctx, e->stream));
+  LCHK(hipStreamSynchronize(e->stream));
+  anc_flag[dst] = 0;
   return 0;
 }
 
@@ -405,6 +545,7 @@ inline int LlmCached::decode_greedy_graph(int32_t first_token, int past, int slo
   const LlmCachedCfg& c = cfg;
   static const bool disabled = [] { const char* v = getenv("VSTAR_DECODE_GRAPH"); return v && atoi(v) == 0; }();
   if (disabled || e->profile || max_new < 1) return 0;
+  if (slot < 0 || slot >= c.max_slots || anc_flag[slot]) return 0;     // a beam-reordered slot: the graph's attention reads no ancestry
   if (first_token == eos_id || max_new < 2) {          // the answer is the prefill's arg-max alone: no decode step at all
     out_ids[0] = first_token;
     *n_out = 1;

@@ -282,6 +282,80 @@ int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_o
   return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, tokens, params);
 }
 
+int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                           const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                           const float* beam_scores, int n_groups, const int32_t* group_off, int n_cand, float* cand_scores,
+                           int32_t* cand_tokens, int32_t* cand_rows, uint16_t* logits_f16) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (!beam_scores || !group_off || !cand_scores || !cand_tokens || !cand_rows) {
+    h->set_error("forward_beam: beam_scores, group_off and the candidate outputs are required");
+    return VSTAR_ERR_INVALID;
+  }
+  LlmBeamArgs b;
+  b.scores = beam_scores; b.n_groups = n_groups; b.goff = group_off; b.n_cand = n_cand;
+  b.cand_s = cand_scores; b.cand_tok = cand_tokens; b.cand_row = cand_rows;
+  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, nullptr, nullptr, &b);
+}
+
+int vstar_vqa_kv_reorder(vstar_vqa_handle* h, int n, const int32_t* dst_slot, const int32_t* src_slot, int lo, int hi) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  return h->run.kv_reorder(n, dst_slot, src_slot, lo, hi);
+}
+
+int vstar_vqa_kv_copy(vstar_vqa_handle* h, int dst, int src, int lo, int hi) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  return h->run.kv_copy(dst, src, lo, hi);
+}
+
+int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const float* beam_scores, int n_groups,
+                             const int32_t* group_off, int n_cand, float* cand_scores, int32_t* cand_tokens, int32_t* cand_rows,
+                             float* lp_out) {
+  if (!dev_logits || !cand_scores || !cand_tokens || !cand_rows || rows > 65535 || ld < vocab ||
+      (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_beam_select: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_beam_check(rows, vocab, beam_scores, n_groups, group_off, n_cand)) {
+    tls_error() = std::string("vstar_vqa_op_beam_select: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
+  const size_t nc = (size_t)n_groups * n_cand;
+  float *d_sc = nullptr, *d_cs = nullptr, *d_lp = nullptr;
+  int32_t *d_go = nullptr, *d_ct = nullptr, *d_cr = nullptr;
+  void* d_ws = nullptr;
+  hipError_t e = hipMalloc(&d_sc, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_go, (size_t)(n_groups + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_cs, nc * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_ct, nc * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_cr, nc * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_ws, vstar_beam_ws_bytes(rows, n_cand));
+  if (e == hipSuccess && lp_out) e = hipMalloc(&d_lp, (size_t)rows * vocab * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_sc, beam_scores, (size_t)rows * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_go, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = dtype == VSTAR_F16 ? vstar_beam_select_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_sc, n_groups, d_go, n_cand, d_ws, d_cs,
+                                                   d_ct, d_cr, d_lp, nullptr)
+                           : vstar_beam_select_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_sc, n_groups, d_go, n_cand, d_ws,
+                                                    d_cs, d_ct, d_cr, d_lp, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(cand_scores, d_cs, nc * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cand_tokens, d_ct, nc * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cand_rows, d_cr, nc * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && lp_out) e = hipMemcpy(lp_out, d_lp, (size_t)rows * vocab * 4, hipMemcpyDeviceToHost);
+  hipFree(d_sc);
+  hipFree(d_go);
+  hipFree(d_cs);
+  hipFree(d_ct);
+  hipFree(d_cr);
+  hipFree(d_ws);
+  if (d_lp) hipFree(d_lp);
+  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_beam_select: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
+  return VSTAR_OK;
+}
+
 int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
                         int32_t* tokens, float* u_out, int32_t* n_kept) {
   if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||

@@ -188,37 +188,46 @@ class VQA_LLM:
                             object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
-        so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws."""
-        if num_beams != 1:
-            raise NotImplementedError("beam search (num_beams > 1) is not implemented")
+        so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
+        4.31 beam search; beam sampling (num_beams > 1 with temperature > 0) is not implemented."""
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
                                           objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
-                                    top_k=top_k, seed=seed)[0]
+                                    top_k=top_k, seed=seed, num_beams=num_beams)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
-                        seed=None) -> List[str]:
+                        seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
-        single free_form_inference call with that seed."""
+        single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
+        i*k .. i*k+k-1 (n*k <= max_slots), one group per sample in every step's forward."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
-        if n > cfg.max_slots:
-            raise ValueError("more samples than KV slots")
+        if num_beams < 1:
+            raise ValueError(f"num_beams must be >= 1, got {num_beams}")
+        if num_beams > 1 and temperature > 0:
+            raise NotImplementedError("beam sampling (num_beams > 1 with temperature > 0) is not implemented")
+        if n * num_beams > cfg.max_slots:
+            raise ValueError(f"{n} samples x {num_beams} beams need {n * num_beams} KV slots; the engine has max_slots="
+                             f"{cfg.max_slots} (build it with a larger VQAConfig.max_slots)")
         if temperature < 0:
             raise ValueError(f"temperature must be >= 0 (0 = greedy), got {temperature}")
         if temperature > 0:
             base = resolve_seed(seed)
             params = [sampling_params(temperature, top_k, top_p, s.get("seed", base + i)) for i, s in enumerate(samples)]
-        seqs, lens = [], []
+        seqs, lens, id_lens = [], [], []
         fslot = 0
         for i, s in enumerate(samples):
             crops = s.get("object_crops")
             img_slots, obj_slots = self._encode(s["image"], crops, fslot)
             fslot += 1 + len(obj_slots)
-            _, rows = self._question_rows(s["question"], img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))
-            seqs.append(Seq(rows, kv_slot=i))
+            ids, rows = self._question_rows(s["question"], img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))
+            seqs.append(Seq(rows, kv_slot=i * num_beams))
             lens.append(len(rows))
-        if temperature > 0:
+            id_lens.append(len(ids))
+        if num_beams > 1:
+            outs = self.beam_decode(seqs, lens, id_lens, max_new_tokens, num_beams, length_penalty, early_stopping)
+            self.generated_ids = [o[0] for o in outs]
+        elif temperature > 0:
             self.generated_ids = self.sample_decode(seqs, lens, max_new_tokens, params)
         else:
             self.generated_ids = self.greedy_decode(seqs, lens, max_new_tokens)
@@ -240,6 +249,47 @@ class VQA_LLM:
         def choose(step, want, idx, t):
             return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx])
         return self._decode(seqs, lens, max_new_tokens, choose)
+
+    def beam_decode(self, seqs: Sequence[Seq], lens: Sequence[int], id_lens: Sequence[int], max_new_tokens: int, num_beams: int,
+                    length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1) -> List[List[List[int]]]:
+        """model.generate(num_beams=k, do_sample=False) (HF 4.31 beam_search) for every sequence: seqs[i] (the
+        prompt rows, prefilled into slot seqs[i].kv_slot = beam 0) owns slots kv_slot .. kv_slot+k-1; lens[i] = its KV rows,
+        id_lens[i] = its un-expanded input_ids length (the lengths of the contract).  One forward per step advances the k beams of
+        every unfinished sequence, the device returns each sequence's 2k candidates, the host scorer (vstar_amd/beam.py) picks
+        the next beams and the KV ancestry is reordered — K/V never move.  Returns, per sequence, the num_return_sequences best
+        generated id lists (EOS-terminated / EOS-padded as 4.31's finalize)."""
+        from .beam import BeamSearch
+        cfg, eng, k = self.cfg, self.engine, num_beams
+        n = len(seqs)
+        slots = [[s.kv_slot + b for b in range(k)] for s in seqs]
+        if any(sl[-1] >= cfg.max_slots for sl in slots) or len({x for sl in slots for x in sl}) != n * k:
+            raise ValueError(f"{n} sequences x {k} beams need {n * k} distinct KV slots below max_slots={cfg.max_slots}")
+        if 2 * k > k * cfg.llm_vocab:
+            raise ValueError("2 * num_beams candidates exceed num_beams x vocabulary")
+        bs = [BeamSearch(k, id_lens[i], self.eos_token_id, id_lens[i] + max_new_tokens, length_penalty, early_stopping)
+              for i in range(n)]
+        goff = lambda m: np.arange(m + 1, dtype=np.int32) * k       # noqa: E731
+        # start: the prompt's last row k times, scores [0, -1e9, ...] (4.31's beam_scores initialisation)
+        cs, ct, cr, _ = eng.forward_beam([Seq(list(s.rows), kv_slot=s.kv_slot) for s in seqs], [(i, -1) for i in range(n) for _ in range(k)],
+                                         np.concatenate([b.scores for b in bs]), goff(n), 2 * k)
+        pos = list(lens)
+        live = list(range(n))
+        while live:
+            dst, src = [], []
+            for j, i in enumerate(live):
+                parents = bs[i].process(cs[j], ct[j], cr[j])
+                dst += slots[i]
+                src += [slots[i][p] for p in parents]
+            eng.kv_reorder(dst, src, 0, max(pos[i] for i in live))
+            live = [i for i in live if not bs[i].done and len(bs[i].tokens[0]) < max_new_tokens and pos[i] + 1 < cfg.max_ctx]
+            if not live:
+                break
+            step = [Seq([bs[i].tokens[b][-1]], kv_slot=slots[i][b], past_len=pos[i]) for i in live for b in range(k)]
+            cs, ct, cr, _ = eng.forward_beam(step, [(j, 0) for j in range(len(step))], np.concatenate([bs[i].scores for i in live]),
+                                             goff(len(live)), 2 * k)
+            for i in live:
+                pos[i] += 1
+        return [b.finalize(num_return_sequences) for b in bs]
 
     def _decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, choose) -> List[List[int]]:
         """The generate() loop over a token chooser choose(step_seqs, want, sequence indices, token index) -> tokens; a

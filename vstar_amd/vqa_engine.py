@@ -142,6 +142,40 @@ class VqaEngine:
                        self.handle)
         return out[:nw]
 
+    def forward_beam(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], beam_scores, group_off, n_cand: int,
+                     logits: bool = False):
+        """`forward` with the arg-max replaced by the on-device beam select (csrc/beam.hip): wanted row j carries
+        the fp32 beam score beam_scores[j]; wanted rows group_off[g] .. group_off[g+1]-1 form group g.  Returns (scores float32
+        [n_groups, n_cand], tokens int32 [n_groups, n_cand], rows-in-group int32 [n_groups, n_cand], logits float16 [n_want,
+        vocab] or None), the candidates of each group sorted by (score descending, row * vocab + token ascending)."""
+        args, _keep = self._rows_args(seqs, want)
+        nw = args[6]
+        sc = np.ascontiguousarray(beam_scores, np.float32)
+        go = np.ascontiguousarray(group_off, np.int32)
+        if sc.shape != (nw,):
+            raise ValueError(f"{sc.size} beam scores for {nw} wanted rows")
+        ng = max(len(go) - 1, 0)
+        cs = np.empty((max(ng, 1), max(n_cand, 1)), np.float32)
+        ct = np.empty_like(cs, dtype=np.int32)
+        cr = np.empty_like(cs, dtype=np.int32)
+        out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if (logits and nw) else None
+        _lib.check_vqa(self.lib.vstar_vqa_forward_beam(self.handle, *args, _ptr(sc), ng, _ptr(go), int(n_cand), _ptr(cs), _ptr(ct),
+                                                       _ptr(cr), _ptr(out_logits)), self.handle)
+        return cs[:ng, :n_cand], ct[:ng, :n_cand], cr[:ng, :n_cand], out_logits
+
+    def kv_reorder(self, dst_slots: Sequence[int], src_slots: Sequence[int], lo: int, hi: int) -> None:
+        """Beam reorder without moving K/V: ancestry entries [lo, hi) of dst_slots[i] = those of src_slots[i], all sources read
+        before any destination is written (include/vstar_vqa.h)."""
+        d = np.ascontiguousarray(dst_slots, np.int32)
+        s = np.ascontiguousarray(src_slots, np.int32)
+        if d.shape != s.shape:
+            raise ValueError("kv_reorder: dst_slots and src_slots differ in length")
+        _lib.check_vqa(self.lib.vstar_vqa_kv_reorder(self.handle, int(d.size), _ptr(d), _ptr(s), int(lo), int(hi)), self.handle)
+
+    def kv_copy(self, dst: int, src: int, lo: int, hi: int) -> None:
+        """Physical copy of K/V rows [lo, hi) into dst's own rows, read through src's ancestry; dst's ancestry -> identity."""
+        _lib.check_vqa(self.lib.vstar_vqa_kv_copy(self.handle, int(dst), int(src), int(lo), int(hi)), self.handle)
+
     def last_forward_ms(self) -> float:
         return float(self.lib.vstar_vqa_last_forward_ms(self.handle))
 
