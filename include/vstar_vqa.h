@@ -149,6 +149,21 @@ int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vo
                              int n_groups, const int32_t* group_off, int n_cand, float* cand_scores, int32_t* cand_tokens,
                              int32_t* cand_rows, float* lp_out);
 
+/* Scoring: vstar_vqa_forward with the arg-max replaced by the scoring tail: targets[n_want] (host), nll[n_want]
+ * fp32 (host), target_rank[n_want] nullable.  Per wanted row j: lse = max + log(sum exp(x_i - max)) in double (fixed summation
+ * order), nll[j] = (float)(lse - x[targets[j]]) — the token's negative log-likelihood, one rounding; x[target] = -inf gives
+ * +inf, NaN logits give NaN; target_rank[j] = #{i : x_i > x[targets[j]]} (0: the arg-max is the target).  A target outside
+ * [0, llm_vocab) is an error.  A row may appear in `want` several times with different targets.  n_want <= max_rows: the
+ * wanted rows are processed in consecutive chunks of 256 (the last one shorter), each through norm -> lm_head -> score, so rows
+ * [256 c, 256 (c + 1)) see the lm_head of a vstar_vqa_forward call that wants exactly those rows.  No logits cross to the host. */
+int vstar_vqa_forward_score(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                            const int32_t* targets, float* nll, int32_t* target_rank);
+/* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld], F16/BF16 (1 <= vocab <= 2^22, rows <= 65535), host targets /
+ * outputs; target_rank and lse_out (double [rows], the log-sum-exp) nullable.  Null stream, synchronises. */
+int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* targets, float* nll,
+                       int32_t* target_rank, double* lse_out);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

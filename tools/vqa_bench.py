@@ -6,6 +6,13 @@ KV-cached decode steps at several batch sizes, forked option scoring.  Prints on
 sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio.
 --beams 1,2,4,8 adds `decode_beams`: beam-search steps of one prompt with k beams (forward_beam's select tail, the host scorer,
 the KV ancestry reorder) alternated with greedy steps of k copies of the same prompt, and the beam / greedy step-time ratio.
+--score 1,4,8,16 adds `score`: multiple-choice scoring of B questions (~300 cached rows, 4 options x 12 tokens) through
+`VQA_LLM.multiple_choices_batch` (two engine calls, the losses reduced by the on-device scoring tail) alternated
+in blocks with a loop of `VQA_LLM.option_losses` (one question at a time, logits to the host), questions/s of both and the
+spread of the alternated blocks.  --only-score skips every other leg.
+--score-kernels N (use with --layers 2 under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py ...`): 20 forward
+calls with the arg-max tail and 20 with the scoring tail on N wanted rows, so that the trace's per-kernel statistics compare
+score_rows_kernel with argmax_rows at that row count.
 Decode steps are bound by the weight sweep (13.5 GB fp16 per step at 7B): `weights_GBps` = bytes of all LLaMA + lm_head
 weights / device time of one step (HIP events inside the engine), against the ~8 TB/s HBM3E peak.
 """
@@ -34,8 +41,15 @@ def main():
     ap.add_argument("--sample", action="store_true", help="add the sampled-decode leg next to greedy")
     ap.add_argument("--rounds", type=int, default=3, help="--sample / --beams: blocks alternated this many times")
     ap.add_argument("--beams", default="", help="comma-separated beam counts: add the beam-search leg next to greedy")
+    ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
+    ap.add_argument("--only-score", action="store_true", help="run the --score leg alone")
+    ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
-    cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=40, max_ctx=1024, max_rows=16384, max_images=8)
+    score_b = [int(x) for x in a.score.split(",")] if a.score else []
+    if a.only_score and not score_b:
+        ap.error("--only-score needs --score B[,B...]")
+    n_q = max(score_b + [1])                     # the scoring leg needs 5 KV slots and one feature slot per question
+    cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=max(40, 5 * n_q), max_ctx=1024, max_rows=16384, max_images=max(8, n_q))
     t0 = time.time()
     eng = VqaEngine(cfg, 0)
     eng.load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
@@ -43,6 +57,13 @@ def main():
     H, M, V, L = cfg.llm_hidden, cfg.llm_mlp, cfg.llm_vocab, cfg.llm_layers
     wbytes = 2.0 * (L * (4 * H * H + 3 * H * M) + V * H)
     out = {"config": {"layers": L, "hidden": H, "vocab": V, "weights_GB": round(wbytes / 1e9, 2)}, "weights_load_s": round(load_s, 1)}
+    if a.score_kernels:
+        out["score_kernels"] = score_kernels(eng, cfg, a.score_kernels)
+        print(json.dumps(out))
+        return
+    if a.only_score:
+        out["score"] = score_leg(eng, cfg, score_b, a.rounds)
+        return finish(out, a)
     g = torch.Generator().manual_seed(0)
     pix = torch.randn(3, 3, 224, 224, generator=g)
     eng.encode_images(pix, 0)
@@ -100,10 +121,79 @@ def main():
                     [(j, t) for j in range(4) for t in range(11)])
         ms.append(eng.last_forward_ms())
     out["option_scoring_4x12_ms"] = round(min(ms), 3)
+    if score_b:
+        out["score"] = score_leg(eng, cfg, score_b, a.rounds)
+    finish(out, a)
+
+
+def finish(out, a):
     print(json.dumps(out))
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         json.dump(out, open(a.out, "w"), indent=1)
+
+
+_FWD_MS = [0.0]
+
+
+def score_leg(eng, cfg, batches, rounds):
+    """Questions/s of multiple-choice scoring: `multiple_choices_batch` (device tail, B questions per call pair) vs a loop of
+    today's `option_losses` (host logits), alternated `rounds` times; both include the same image encoding and tokenisation."""
+    from PIL import Image
+    from vstar_amd.vqa import VQA_LLM
+    llm = VQA_LLM(cfg=cfg, engine=eng)
+    for name in ("forward", "forward_score"):     # sum the engine's own forward time per block (wall time also holds CLIP + host work)
+        def timed(*a, _f=getattr(eng, name), **kw):
+            r = _f(*a, **kw)
+            _FWD_MS[0] += eng.last_forward_ms()
+            return r
+        setattr(eng, name, timed)
+    rng = np.random.default_rng(0)
+    words = ["red", "blue", "green", "mug", "table", "left", "right", "small", "large", "near", "behind", "cup"]
+    samples = []
+    for i in range(max(batches)):
+        opts = [" ".join(words[(i + 3 * j + t) % len(words)] for t in range(8)) for j in range(4)]      # 8 words + ': ' / '</s>' pieces
+        samples.append(dict(image=Image.fromarray(rng.integers(0, 256, (336, 336, 3), dtype=np.uint8)),
+                            question=f"What is the colour of the mug number {i} on the table", options=opts))
+    res = {}
+    for B in batches:
+        sub = samples[:B]
+        plan = llm.score_continuations_batch(sub[:1])
+        run = {"device": lambda: llm.multiple_choices_batch(sub),
+               "host": lambda: [int(torch.stack(llm.option_losses(s["image"], s["question"], s["options"])).argmin()) for s in sub]}
+        picks = {m: f() for m, f in run.items()}            # warm-up, and the two paths' choices
+        t = {"device": [], "host": []}
+        fwd = {"device": [], "host": []}         # the LLM side alone: device time of the forward calls of a block (HIP events)
+        for _ in range(rounds):
+            for m in ("device", "host"):
+                _FWD_MS[0] = 0.0
+                t0 = time.time()
+                run[m]()
+                t[m].append(time.time() - t0)
+                fwd[m].append(_FWD_MS[0])
+        leg = {"option_tokens": [len(v) for v in plan[0]], "same_choices": picks["device"] == picks["host"]}
+        for m in ("device", "host"):
+            med = float(np.median(t[m]))
+            leg[m] = {"questions_per_s": round(B / med, 2), "block_ms": [round(x * 1e3, 1) for x in t[m]],
+                      "spread": round((max(t[m]) - min(t[m])) / med, 3),
+                      "forward_device_ms_per_block": [round(x, 2) for x in fwd[m]]}
+        leg["device_over_host_questions_per_s"] = round(leg["device"]["questions_per_s"] / leg["host"]["questions_per_s"], 3)
+        res[f"B{B}"] = leg
+    return res
+
+
+def score_kernels(eng, cfg, n):
+    """The arg-max tail and the scoring tail on n wanted rows of one 300-row prompt, 20 calls each (for a kernel trace)."""
+    g = torch.Generator().manual_seed(0)
+    eng.encode_images(torch.randn(1, 3, 224, 224, generator=g), 0)
+    rows = torch.randint(3, 30000, (44,), generator=g).tolist() + eng.feature_rows(0, True)
+    seqs, want = [Seq(rows, kv_slot=0)], [(0, t % len(rows)) for t in range(n)]
+    tg = torch.randint(0, cfg.llm_vocab, (n,), generator=g).numpy()
+    for _ in range(20):
+        if n <= 256:
+            eng.forward(seqs, want, logits=False)
+        eng.forward_score(seqs, want, tg, rank=True)
+    return {"rows": n, "calls": 20}
 
 
 def decode_sample(eng, rows, batches, steps, rounds):

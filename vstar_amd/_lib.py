@@ -30,7 +30,7 @@ EXPORTS_VQA = [
     "vstar_vqa_create", "vstar_vqa_destroy", "vstar_vqa_last_error", "vstar_vqa_load_tensor", "vstar_vqa_finalize_weights",
     "vstar_vqa_encode_images", "vstar_vqa_forward", "vstar_vqa_debug_read", "vstar_vqa_last_forward_ms", "vstar_vqa_op_gemm",
     "vstar_vqa_forward_sample", "vstar_vqa_op_sample", "vstar_vqa_forward_beam", "vstar_vqa_kv_reorder", "vstar_vqa_kv_copy",
-    "vstar_vqa_op_beam_select",
+    "vstar_vqa_op_beam_select", "vstar_vqa_forward_score", "vstar_vqa_op_score",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -212,6 +212,11 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_beam_select.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p]
     lib.vstar_vqa_op_beam_select.restype = c_int
+    lib.vstar_vqa_forward_score.argtypes = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_score.restype = c_int
+    lib.vstar_vqa_op_score.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_score.restype = c_int
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int

@@ -105,6 +105,18 @@ def focus_question(question, found, image, pad_left, pad_top):
     return FOCUS_MSG + "; ".join(parts) + ".\n" + question
 
 
+def _choice_sample(vqa_llm, e, mean_color):
+    """The arguments of one question's option ranking (vstar_bench_eval.py:224-256) as a `multiple_choices_batch` sample."""
+    image = Image.open(e["path"]).convert("RGB")
+    found = e.get("found", [])
+    if not e["missing"]:
+        return dict(image=image, question=e["question"], options=e["options"])
+    crops = torch.stack([vqa_llm.get_object_crop(image, deepcopy(f["bbox"]), patch_scale=1.2) for f in found], 0)
+    square, left, top = expand2square_centered(image, mean_color)
+    return dict(image=square, question=focus_question(e["question"], found, square, left, top), options=e["options"],
+                object_crops=crops, images_long=[False], objects_long=[len(found) <= 2] * len(found))
+
+
 def make_vsm(args, device: int = 0):
     """The VSM of the evaluation loop (vstar_bench_eval.py:171-177).  `--vision-tower` must name a LOCAL
     openai/clip-vit-large-patch14 directory: the CLIP tower is not part of the VSM checkpoint and there is no hub access."""
@@ -129,7 +141,9 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     # Three passes over independent questions instead of the reference's one pass (vstar_bench_eval.py:190-262): (1) the VQA-LLM's
     # free-form answers -> missing objects, (2) ALL visual searches in one cross-image lock-step stream (`--search-window`
     # concurrent searches per engine batch; 1 = one image at a time like the reference), (3) option ranking.  Per question the
-    # values are the same; the engine sees full batches.
+    # values are the same; the engine sees full batches.  `--vqa-batch N` > 1 also batches passes 1 and 3: N questions per
+    # free_form_batch / multiple_choices_batch call (the option losses reduced on the device); 1 = per question.
+    vqa_batch = max(1, int(getattr(args, "vqa_batch", 1) or 1))
     window = int(getattr(args, "search_window", 0) or 0)
     max_found = getattr(args, "max_found_objects", None)        # (tests: tiny engines hold few object crops)
     entries = []
@@ -138,10 +152,20 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
         for image_file in sorted(f for f in os.listdir(folder) if ".json" not in f):
             path = os.path.join(folder, image_file)
             ann = json.load(open(path.split(".")[0] + ".json"))
-            square, _, _ = expand2square_centered(Image.open(path).convert("RGB"), mean_color)
-            prediction = vqa_llm.free_form_inference(square, ann["question"])
+            prediction = None
+            if vqa_batch == 1:
+                square, _, _ = expand2square_centered(Image.open(path).convert("RGB"), mean_color)
+                prediction = vqa_llm.free_form_inference(square, ann["question"])
             entries.append({"split": split, "image_file": image_file, "path": path, "question": ann["question"], "options": ann["options"],
-                            "prediction": prediction, "missing": parse_missing_objects(prediction)})
+                            "prediction": prediction, "missing": parse_missing_objects(prediction) if vqa_batch == 1 else None})
+    # pass 1, batched: free_form_batch takes one KV slot and one feature slot per question, so its chunks are capped by the engine
+    cfg = getattr(vqa_llm, "cfg", None)
+    ff_batch = min(vqa_batch, getattr(cfg, "max_slots", vqa_batch), getattr(cfg, "max_images", vqa_batch))
+    for k in range(0, len(entries) if vqa_batch > 1 else 0, ff_batch):
+        chunk = entries[k:k + ff_batch]
+        squares = [expand2square_centered(Image.open(e["path"]).convert("RGB"), mean_color)[0] for e in chunk]
+        for e, prediction in zip(chunk, vqa_llm.free_form_batch([dict(image=im, question=e["question"]) for im, e in zip(squares, chunk)])):
+            e["prediction"], e["missing"] = prediction, parse_missing_objects(prediction)
     todo = [e for e in entries if e["missing"]]
     if window == 1:
         founds = [search_objects(vsm, e["path"], e["missing"], args) for e in todo]
@@ -149,18 +173,25 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
         founds = search_objects_stream(vsm, [(e["path"], e["missing"]) for e in todo], args, window=window or None)
     for e, f in zip(todo, founds):
         e["found"] = f[:max_found] if max_found else f
+    for k in range(0, len(entries) if vqa_batch > 1 else 0, vqa_batch):      # pass 3, batched: the same per-question arguments
+        chunk = entries[k:k + vqa_batch]
+        for e, chosen in zip(chunk, vqa_llm.multiple_choices_batch([_choice_sample(vqa_llm, e, mean_color) for e in chunk])):
+            e["chosen"] = chosen
     for split in ("direct_attributes", "relative_position"):
         results[split] = []
         for e in (x for x in entries if x["split"] == split):
             question, options, missing, found = e["question"], e["options"], e["missing"], e.get("found", [])
-            image = Image.open(e["path"]).convert("RGB")
-            if missing:
+            if vqa_batch > 1:
+                chosen = e["chosen"]
+            elif missing:
+                image = Image.open(e["path"]).convert("RGB")
                 crops = torch.stack([vqa_llm.get_object_crop(image, deepcopy(f["bbox"]), patch_scale=1.2) for f in found], 0)
                 square, left, top = expand2square_centered(image, mean_color)
                 long_objects = [len(found) <= 2] * len(found)
                 chosen = vqa_llm.multiple_choices_inference(square, focus_question(question, found, square, left, top), options,
                                                             crops, images_long=[False], objects_long=long_objects)
             else:
+                image = Image.open(e["path"]).convert("RGB")
                 chosen = vqa_llm.multiple_choices_inference(image, question, options)
             correct = 1 if chosen == 0 else 0
             per_type[split].append(correct)

@@ -18,12 +18,14 @@
 #include <stdint.h>
 #include <cmath>
 #include "beam.hpp"
+#include "row_lse.hpp"
 
 namespace {
 
-constexpr int THREADS = 1024;
-constexpr int WAVES = THREADS / 64;
-constexpr int CACHE = 32768;           // rows up to this length stay in LDS (64 KiB)
+using rowlse::bits2f;
+using rowlse::CACHE;                   // rows up to this length stay in LDS (64 KiB)
+using rowlse::THREADS;
+using rowlse::WAVES;
 constexpr int MAX_VOCAB = 1 << 22;
 constexpr int MERGE_THREADS = VSTAR_BEAM_MAX_K * VSTAR_BEAM_MAX_CAND;
 
@@ -38,10 +40,6 @@ struct BeamSmem {
   uint32_t sel_above;
 };
 
-template <bool BF16> __device__ __forceinline__ float bits2f(uint32_t b) {
-  if constexpr (BF16) return __uint_as_float(b << 16);
-  else return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-}
 template <bool BF16> __device__ __forceinline__ uint32_t f2bits(float f) {     // round to nearest even (torch's cast)
   if constexpr (BF16) return __builtin_bit_cast(uint16_t, (__bf16)f);
   else return __builtin_bit_cast(uint16_t, (_Float16)f);
@@ -66,29 +64,6 @@ template <bool BF16> __device__ __forceinline__ uint32_t lp_key(uint32_t x, doub
 }
 template <bool BF16> __device__ __forceinline__ float key_lp(uint32_t key) {
   return bits2f<BF16>((key & 0x8000u) ? (key & 0x7fffu) : (~key & 0xffffu));
-}
-
-template <typename Sm> __device__ __forceinline__ float block_max(Sm& sm, float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) sm.wf[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float m = sm.wf[0];
-  for (int w = 1; w < WAVES; ++w) m = fmaxf(m, sm.wf[w]);
-  __syncthreads();
-  return m;
-}
-
-// sum in a fixed order: lane 0's butterfly result per wave, then the waves in index order (every thread gets the same bits)
-template <typename Sm> __device__ __forceinline__ double block_sum(Sm& sm, double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm.wd[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < WAVES; ++w) s += sm.wd[w];
-  __syncthreads();
-  return s;
 }
 
 // exclusive prefix of v in thread order, and the block total
@@ -148,23 +123,12 @@ __global__ __launch_bounds__(THREADS) void beam_rows_kernel(const uint16_t* __re
   const float bs = scores[row];
   const uint32_t n_row = (uint32_t)(n_cand < vocab ? n_cand : vocab);
   if (tid < 256) sm.hist[tid] = 0;
-  // ---- max (and the row into LDS) ----
-  float mx = -INFINITY;
-  for (int i = tid; i < vocab; i += THREADS) {
-    const uint16_t b = xr[i];
-    if constexpr (CACHED) sm.bits[i] = b;
-    mx = fmaxf(mx, bits2f<BF16>(b));
-  }
-  mx = block_max(sm, mx);                            // (synchronises: the cached bits are visible from here on)
+  // ---- max (and the row into LDS), log-sum-exp in double: row_lse.hpp, shared with the scoring tail ----
+  const double lse = rowlse::row_lse<BF16, CACHED>(sm, xr, vocab);
   auto raw = [&](int i) -> uint32_t {
     if constexpr (CACHED) return sm.bits[i];
     else return xr[i];
   };
-  // ---- log-sum-exp in double ----
-  double se = 0.0;
-  const double dmx = (double)mx;
-  for (int i = tid; i < vocab; i += THREADS) se += exp((double)bits2f<BF16>(raw(i)) - dmx);
-  const double lse = dmx + log(block_sum(sm, se));
   // ---- lp keys (in place in LDS: each thread rewrites the elements it read), the high-byte histogram ----
   for (int i = tid; i < vocab; i += THREADS) {
     const uint32_t key = lp_key<BF16>(raw(i), lse);

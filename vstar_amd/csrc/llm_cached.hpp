@@ -12,6 +12,7 @@
 #include "engine_base.hpp"
 #include "sample.hpp"
 #include "beam.hpp"
+#include "score.hpp"
 
 namespace VS_NS {
 
@@ -25,6 +26,18 @@ struct LlmBeamArgs {
   float* cand_s = nullptr;
   int32_t* cand_tok = nullptr;
   int32_t* cand_row = nullptr;
+};
+
+// The scoring tail of forward() (score.hip): host arrays.  Wanted row j is scored against targets[j]; nll[j]
+// (and rank[j], nullable) come back.  A row may be wanted several times with different targets.
+// CHUNKING RULE (part of the contract — lm_head's row count selects its GEMM kernel): this tail alone accepts n_want up to
+// max_rows; the wanted rows are processed in consecutive chunks of max_want (256) rows, the last one shorter, each chunk
+// gather -> final norm -> lm_head -> score through the one [max_want, vpad] logits buffer.  So wanted rows [256 c, 256 (c + 1))
+// see the lm_head a plain forward() with exactly those wanted rows runs.
+struct LlmScoreArgs {
+  const int32_t* targets = nullptr;
+  float* nll = nullptr;
+  int32_t* rank = nullptr;
 };
 
 struct LlmCachedCfg {
@@ -54,7 +67,9 @@ struct LlmCached {
   int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_seq = nullptr, *d_want = nullptr,
           *d_argmax = nullptr;
   vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of forward(..., sample_params)
-  int max_want = 256;
+  int max_want = 256;                            // wanted rows of one lm_head call (the scoring tail chunks by it, up to max_rows)
+  int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
+  float* d_nll = nullptr;                        // [max_rows]
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
   // ---- beam search ----
@@ -108,7 +123,8 @@ struct LlmCached {
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
               const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out,
-              const vstar_vqa_sampling* sample_params = nullptr, const LlmBeamArgs* beam = nullptr);
+              const vstar_vqa_sampling* sample_params = nullptr, const LlmBeamArgs* beam = nullptr,
+              const LlmScoreArgs* score = nullptr);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
   int kv_copy(int dst, int src, int lo, int hi);
 };
@@ -149,7 +165,10 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&d_row_slot, R));
   RC(e->dalloc(&d_row_seq, R));
   RC(e->dalloc(&d_seq, (size_t)3 * c.max_slots * 4));
-  RC(e->dalloc(&d_want, (size_t)max_want));
+  RC(e->dalloc(&d_want, std::max(R, (size_t)max_want)));     // (the scoring tail wants up to max_rows rows)
+  RC(e->dalloc(&d_starget, R));
+  RC(e->dalloc(&d_srank, R));
+  RC(e->dalloc(&d_nll, R));
   RC(e->dalloc(&d_argmax, (size_t)max_want));
   RC(e->dalloc(&d_sparams, (size_t)max_want));
   {  // split-KV decode attention (decode.hip): scores / partials / tickets for steps of up to SPLIT_ROWS sequences, zeroed once
@@ -303,11 +322,16 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
 inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                               uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params,
-                              const LlmBeamArgs* beam) {
+                              const LlmBeamArgs* beam, const LlmScoreArgs* score) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
+  if (score) {             // the scoring tail chunks its wanted rows (LlmScoreArgs): its limit is max_rows, not max_want
+    if (sample_params || beam || logits_out || argmax_out) { e->set_error("forward_score: the scoring tail excludes the other outputs"); return VSTAR_ERR_INVALID; }
+    if (n_want < 1 || !score->targets || !score->nll) { e->set_error("forward_score: no wanted rows / targets / outputs"); return VSTAR_ERR_INVALID; }
+    if (n_want > c.max_rows) { e->set_error("forward_score: more wanted rows than max_rows"); return VSTAR_ERR_INVALID; }
+  }
   if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
-      n_want > max_want || (n_want && !want)) {
+      (!score && n_want > max_want) || (n_want && !want)) {
     e->set_error("llm forward: bad argument");
     return VSTAR_ERR_INVALID;
   }
@@ -343,6 +367,11 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
       return VSTAR_ERR_INVALID;
     }
   }
+  if (score)
+    if (const char* m = vstar_score_check(n_want, c.vocab, score->targets)) {
+      e->set_error(std::string("forward_score: ") + m);
+      return VSTAR_ERR_INVALID;
+    }
   // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
   bool use_anc = false;
   for (int i = 0; i < nseq; ++i) {
@@ -407,6 +436,7 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
     LCHK(hipMemcpyAsync(d_bscore, beam->scores, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
     LCHK(hipMemcpyAsync(d_goff, beam->goff, (size_t)(beam->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
   }
+  if (score) LCHK(hipMemcpyAsync(d_starget, score->targets, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
@@ -416,7 +446,20 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   else RC(llm_layers_cached(rows, nseq, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
   // ---- model.norm + lm_head on the wanted rows (llava_search_llama.py:92-93) ----
   const size_t vpad = (size_t)(c.vocab + 255) / 256 * 256;
-  if (n_want) {
+  if (score) {             // the scoring tail (score.hip), chunked by max_want wanted rows (LlmScoreArgs): only nll / rank leave
+    for (int c0 = 0; c0 < n_want; c0 += max_want) {
+      const int m = n_want - c0 < max_want ? n_want - c0 : max_want;
+      LCHK(gather_rows(lx, d_want + c0, wsel, m, H, e->stream));
+      RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, m, VSTAR_EPI_NONE));
+#ifdef VSTAR_LP_F16
+      LCHK(vstar_score_rows_f16(logits, m, c.vocab, (int64_t)vpad, d_starget + c0, d_nll + c0, score->rank ? d_srank + c0 : nullptr,
+                                nullptr, e->stream));
+#else
+      LCHK(vstar_score_rows_bf16(logits, m, c.vocab, (int64_t)vpad, d_starget + c0, d_nll + c0, score->rank ? d_srank + c0 : nullptr,
+                                 nullptr, e->stream));
+#endif
+    }
+  } else if (n_want) {
     LCHK(gather_rows(lx, d_want, wsel, n_want, H, e->stream));
     RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, n_want, VSTAR_EPI_NONE));
     if (beam) {            // the beam-search tail (beam.hip) in place of the arg-max: each group's n_cand best candidates
@@ -441,7 +484,11 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   if (n_want && logits_out)
     LCHK(hipMemcpy2DAsync(logits_out, (size_t)c.vocab * 2, logits, vpad * 2, (size_t)c.vocab * 2, n_want,
                             hipMemcpyDeviceToHost, e->stream));
-  if (n_want && argmax_out && !beam) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  if (n_want && argmax_out && !beam && !score) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  if (score) {
+    LCHK(hipMemcpyAsync(score->nll, d_nll, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+    if (score->rank) LCHK(hipMemcpyAsync(score->rank, d_srank, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  }
   if (beam) {
     const size_t nc = (size_t)beam->n_groups * beam->n_cand;
     LCHK(hipMemcpyAsync(beam->cand_s, d_cand_s, nc * 4, hipMemcpyDeviceToHost, e->stream));

@@ -356,6 +356,50 @@ int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vo
   return VSTAR_OK;
 }
 
+int vstar_vqa_forward_score(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                            const int32_t* targets, float* nll, int32_t* target_rank) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (!targets || !nll) { h->set_error("forward_score: targets and nll are required"); return VSTAR_ERR_INVALID; }
+  LlmScoreArgs sc;
+  sc.targets = targets; sc.nll = nll; sc.rank = target_rank;
+  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, nullptr, nullptr, nullptr, &sc);
+}
+
+int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* targets, float* nll,
+                       int32_t* target_rank, double* lse_out) {
+  if (!dev_logits || !nll || rows > 65535 || ld < vocab || (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_score: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_score_check(rows, vocab, targets)) {
+    tls_error() = std::string("vstar_vqa_op_score: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
+  int32_t *d_t = nullptr, *d_r = nullptr;
+  float* d_n = nullptr;
+  double* d_l = nullptr;
+  hipError_t e = hipMalloc(&d_t, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_n, (size_t)rows * 4);
+  if (e == hipSuccess && target_rank) e = hipMalloc(&d_r, (size_t)rows * 4);
+  if (e == hipSuccess && lse_out) e = hipMalloc(&d_l, (size_t)rows * 8);
+  if (e == hipSuccess) e = hipMemcpy(d_t, targets, (size_t)rows * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = dtype == VSTAR_F16 ? vstar_score_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_t, d_n, d_r, d_l, nullptr)
+                           : vstar_score_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_t, d_n, d_r, d_l, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(nll, d_n, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && target_rank) e = hipMemcpy(target_rank, d_r, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && lse_out) e = hipMemcpy(lse_out, d_l, (size_t)rows * 8, hipMemcpyDeviceToHost);
+  hipFree(d_t);
+  hipFree(d_n);
+  if (d_r) hipFree(d_r);
+  if (d_l) hipFree(d_l);
+  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_score: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
+  return VSTAR_OK;
+}
+
 int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
                         int32_t* tokens, float* u_out, int32_t* n_kept) {
   if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||

@@ -4,7 +4,8 @@ Same constructor role, same methods and return conventions:
     get_patch / get_object_crop ............ vstar_bench_eval.py:49-77
     free_form_inference(image, question, ...) -> str ................ :78-113   (temperature 0: greedy; > 0: sampled on the device)
     multiple_choices_inference(image, question, options, ...) -> int  :115-165  (shared-prefix option scoring)
-plus a batched form (`free_form_batch`) that decodes many samples in one engine call per step — the reference runs batch 1; on an MI355X a decode step is bound by the 13.5 GB weight sweep, so sequences are
+plus `score_continuations` / `option_losses_batch` / `multiple_choices_batch`, the same scoring for many questions per engine call
+with the log-likelihoods reduced on the device, and a batched form (`free_form_batch`) that decodes many samples in one engine call per step — the reference runs batch 1; on an MI355X a decode step is bound by the 13.5 GB weight sweep, so sequences are
 advanced together.
 
 MI355X-first differences that do not change results: the question prefix of the multiple-choice scoring is prefilled
@@ -350,3 +351,105 @@ class VQA_LLM:
             loss = torch.nn.functional.cross_entropy(lg.float(), torch.tensor(ids, dtype=torch.long)).to(torch.float16)
             losses.append(loss)
         return losses
+
+    # ---- batched scoring with the on-device loss tail (csrc/score.hip) ----
+    def score_continuations(self, image, question, continuations, object_crops=None, images_long=None,
+                            objects_long=None) -> List[np.ndarray]:
+        """Per-token negative log-likelihoods (float32 [n_tokens]) of each continuation as the assistant's answer to `question`
+        — the tokens `option_losses` scores — computed on the device: no logits cross to the host."""
+        return self.score_continuations_batch([dict(image=image, question=question, options=continuations,
+                                                    object_crops=object_crops, images_long=images_long,
+                                                    objects_long=objects_long)])[0]
+
+    def score_continuations_batch(self, samples: Sequence[dict]) -> List[List[np.ndarray]]:
+        """`score_continuations` for many samples (dicts with image, question, options and optionally object_crops, images_long,
+        objects_long), two engine calls per chunk of samples: call 1 prefills every question of the chunk in one ragged batch
+        and scores its last row once per option against that option's first token; call 2 advances every option as a fork of
+        its question's KV slot and scores rows 0 .. len-2 against tokens 1 .. len-1.  Question i of a chunk and its options sit
+        in consecutive KV slots.  A chunk is closed before the sample that would exceed max_images (1 + object crops per
+        sample), max_slots (1 + options), max_rows (call 1: the questions' rows, padded to the longest when they are
+        prefilled together; call 2: the options' rows) — values do not depend on how the samples fall into chunks beyond the
+        GEMM kernels the row counts select."""
+        cfg, eng = self.cfg, self.engine
+        plans = []
+        for s in samples:
+            crops = s.get("object_crops")
+            n_obj = len(crops) if crops is not None else 0
+            if 1 + len(s["options"]) > cfg.max_slots:
+                raise ValueError("more options than KV slots")
+            if 1 + n_obj > cfg.max_images:
+                raise ValueError(f"{1 + n_obj} images/object crops exceed the engine's feature table (max_images="
+                                 f"{cfg.max_images}); build the engine with a larger VQAConfig.max_images")
+            dummy = ([0], list(range(1, 1 + n_obj)), s.get("images_long"), s.get("objects_long"))
+            q_ids, q_rows = self._question_rows(s["question"], *dummy)
+            opt_ids = [self._question_rows(s["question"], *dummy, answer=o)[0][len(q_ids):] for o in s["options"]]   # (:145-146)
+            # (the ids do not depend on the feature slots; the rows do, and are expanded again once the chunk's slots are known.
+            # A one-token option is scored by call 1 alone but still rides through call 2 with no wanted row, as in option_losses:
+            # call 2 of a batch of one then has exactly option_losses' rows, and with them the GEMM kernels its row count selects)
+            plans.append(dict(s=s, n_img=1 + n_obj, n_slots=1 + len(opt_ids), P=len(q_rows), q_ids=q_ids, opt_ids=opt_ids,
+                              n_opt_rows=sum(len(i) for i in opt_ids)))
+
+        def call1_rows(ps):        # the engine right-pads fresh sequences of more than 64 rows in all to the longest
+            tot = sum(p["P"] for p in ps)
+            return len(ps) * max(p["P"] for p in ps) if tot > 64 else tot
+
+        chunks, cur = [], []
+        for p in plans:
+            t = cur + [p]
+            if cur and (sum(x["n_img"] for x in t) > cfg.max_images or sum(x["n_slots"] for x in t) > cfg.max_slots or
+                        call1_rows(t) > cfg.max_rows or sum(x["n_opt_rows"] for x in t) > cfg.max_rows):
+                chunks.append(cur)
+                t = [p]
+            cur = t
+        if cur:
+            chunks.append(cur)
+        out: List[List[np.ndarray]] = []
+        for ch in chunks:
+            out += self._score_chunk(ch)
+        return out
+
+    def _score_chunk(self, plans) -> List[List[np.ndarray]]:
+        eng = self.engine
+        fslot = kslot = 0
+        q_seqs, want1, tgt1, o_seqs, want2, tgt2 = [], [], [], [], [], []
+        for i, p in enumerate(plans):
+            s = p["s"]
+            img_slots, obj_slots = self._encode(s["image"], s.get("object_crops"), fslot)
+            fslot += p["n_img"]
+            q_rows = eng.expand_ids(p["q_ids"], img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))
+            q_seqs.append(Seq(q_rows, kv_slot=kslot))
+            for j, ids in enumerate(p["opt_ids"]):
+                want1.append((i, -1))
+                tgt1.append(ids[0])
+                want2 += [(len(o_seqs), t) for t in range(len(ids) - 1)]
+                tgt2 += ids[1:]
+                o_seqs.append(Seq(ids, kv_slot=kslot + 1 + j, past_len=len(q_rows), prefix_slot=kslot))
+            kslot += p["n_slots"]
+        first = eng.forward_score(q_seqs, want1, tgt1) if want1 else np.zeros(0, np.float32)
+        rest = eng.forward_score(o_seqs, want2, tgt2) if want2 else np.zeros(0, np.float32)
+        out, a, b = [], 0, 0
+        for p in plans:
+            per = []
+            for ids in p["opt_ids"]:
+                per.append(np.concatenate([first[a:a + 1], rest[b:b + len(ids) - 1]]).astype(np.float32))
+                a += 1
+                b += len(ids) - 1
+            out.append(per)
+        return out
+
+    @staticmethod
+    def nll_loss(nll: np.ndarray) -> torch.Tensor:
+        """The loss of one continuation from its per-token values, in token order: fp16(fp32(sum_double(nll) / n)) — what
+        CrossEntropyLoss(mean) on the fp16 logits followed by .to(float16) gives, up to fp32 rounding."""
+        acc = 0.0
+        for v in np.asarray(nll, np.float32):
+            acc += float(v)
+        return torch.tensor(np.float16(np.float32(acc / len(nll))))
+
+    def option_losses_batch(self, samples: Sequence[dict]) -> List[List[torch.Tensor]]:
+        """`option_losses` of every sample (fp16 0-d tensors), through `score_continuations_batch`."""
+        return [[self.nll_loss(v) for v in per] for per in self.score_continuations_batch(samples)]
+
+    def multiple_choices_batch(self, samples: Sequence[dict]) -> List[int]:
+        """`multiple_choices_inference` of every sample: the arg-min of its fp16 option losses, first index on ties."""
+        return [int(torch.stack(losses).argmin().item()) for losses in self.option_losses_batch(samples)]

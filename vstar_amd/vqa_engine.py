@@ -163,6 +163,22 @@ class VqaEngine:
                                                        _ptr(cr), _ptr(out_logits)), self.handle)
         return cs[:ng, :n_cand], ct[:ng, :n_cand], cr[:ng, :n_cand], out_logits
 
+    def forward_score(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], targets, rank: bool = False):
+        """`forward` with the arg-max replaced by the on-device scoring tail (csrc/score.hip): wanted row j is
+        scored against the token id targets[j].  Returns nll float32 [n_want] — the tokens' negative log-likelihoods — and, with
+        rank=True, (nll, target_rank int32 [n_want]) where rank 0 means the arg-max is the target.  A row may be wanted several
+        times with different targets; n_want may be as large as max_rows (the engine chunks by 256 rows); the logits never leave
+        the device."""
+        args, _keep = self._rows_args(seqs, want)
+        nw = args[6]
+        tg = np.ascontiguousarray(targets, np.int32)
+        if tg.shape != (nw,):
+            raise ValueError(f"{tg.size} targets for {nw} wanted rows")
+        nll = np.empty((max(nw, 1),), np.float32)
+        rk = np.empty((max(nw, 1),), np.int32) if rank else None
+        _lib.check_vqa(self.lib.vstar_vqa_forward_score(self.handle, *args, _ptr(tg), _ptr(nll), _ptr(rk)), self.handle)
+        return (nll[:nw], rk[:nw]) if rank else nll[:nw]
+
     def kv_reorder(self, dst_slots: Sequence[int], src_slots: Sequence[int], lo: int, hi: int) -> None:
         """Beam reorder without moving K/V: ancestry entries [lo, hi) of dst_slots[i] = those of src_slots[i], all sources read
         before any destination is written (include/vstar_vqa.h)."""

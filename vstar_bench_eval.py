@@ -27,6 +27,10 @@ def parse_args(argv):
     p.add_argument("--device", default=0, type=int)
     p.add_argument("--search-window", dest="search_window", default=0, type=int, help="concurrent visual searches per engine batch "
                    "(cross-image lock step); 0 = one engine batch, 1 = one image at a time like the reference")
+    p.add_argument("--vqa-batch", dest="vqa_batch", default=1, type=int, help="questions per VQA-LLM engine call in the free-form and "
+                   "option-ranking passes (free_form_batch / multiple_choices_batch, option losses reduced on the device); 1 = one "
+                   "question at a time like the reference.  The free-form pass sends at most min(N, max_slots, max_images) questions per call; the "
+                   "option-ranking pass splits a batch by itself when it exceeds max_slots / max_images / max_rows")
     p.add_argument("--engine-comm", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="world > 1 on GPUs: gather the per-step records with the C-ABI's own RCCL communicator on the engine stream "
                    "(vstar_allgather_results) instead of torch.distributed.  auto (default, round 6): used when the communicator comes up "
