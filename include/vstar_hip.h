@@ -355,6 +355,67 @@ int vstar_op_attention(void* stream, uint16_t* dev_qkv, uint16_t* dev_out, void*
                        int B, int S, int H, int D, int causal, float rope_theta);
 size_t vstar_op_attention_workspace(int B, int S, int H, int D);
 
+/* ---- Doors of the small kernels (tests/test_small_ops_gpu.py).  Each launches ONE kernel on `stream` and synchronises.
+ * 16-bit tensors are bf16 bits; `cols` / `C` of the 16-byte-vector kernels must be a multiple of 8 (VSTAR_ERR_HIP otherwise). ---- */
+/* OWL-ViT class head: emb [crops * rows_per_crop, ld] fp32 = dense0 (Q) | shift | scale, query [B, Q] -> out[b * out_stride_crop + p]
+ * = (e^ . q^ + shift) * (elu(scale) + 1) with the bf16 rounding points of the bf16 model; record b reads crop b / img_div. */
+int vstar_op_owl_class_logits(void* stream, const float* dev_emb, int ld, int Q, const uint16_t* dev_query, float* dev_out,
+                              int out_stride_crop, int B, int rows_per_crop, int img_div);
+/* OWL-ViT box head: out[b * out_stride_crop + p * 4 + c] = sigmoid(bf16(raw[(b / img_div) * grid^2 + p, c]) + box_bias(p, c)), bf16-rounded fp32. */
+int vstar_op_owl_box_finish(void* stream, const float* dev_raw, int ld, float* dev_out, int out_stride_crop, int B, int grid, int img_div);
+/* src [B, h, w, C] channels-last -> bilinear x2 (align_corners = False, fp32, rounded to bf16) -> 3x3 im2col with zero padding:
+ * A [B * 2h * 2w, 9 C], k = (ky * 3 + kx) * C + c. */
+int vstar_op_upsample2x_im2col3x3(void* stream, const uint16_t* dev_src, uint16_t* dev_A, int B, int h, int w, int C);
+/* out[b * out_stride_crop + pix] = bf16(sum_c hyper[b, c] * up[b, pix, c]) as fp32; C == 32 only. */
+int vstar_op_hyper_mask(void* stream, const uint16_t* dev_hyper, const uint16_t* dev_up, float* dev_out, int out_stride_crop, int B,
+                        int npix, int C);
+/* pix [B, 3, I, I] -> A [B * (I / ps)^2, Kpad], k = c * ps^2 + ky * ps + kx, columns >= 3 ps^2 zero. */
+int vstar_op_im2col_patch(void* stream, const uint16_t* dev_pix, uint16_t* dev_A, int B, int I, int ps, int Kpad);
+/* tokens [B, P + 1, C]: row 0 = cls + pos[0], row 1 + p = patch[b, p] + pos[1 + p] (fp32 add, one rounding). */
+int vstar_op_vit_assemble_tokens(void* stream, const uint16_t* dev_patch, const uint16_t* dev_cls, const uint16_t* dev_pos,
+                                 uint16_t* dev_tokens, int B, int P, int C);
+/* x [B, L - 1 + P, C]: spliced position s < img_col = table[ids[b, s]], s >= img_col + P = table[ids[b, s - P + 1]]; the P rows
+ * from img_col on are not written; ids are clamped to [0, vocab). */
+int vstar_op_llm_embed_text(void* stream, const int32_t* dev_ids, int L, int img_col, int P, const uint16_t* dev_table, int vocab,
+                            uint16_t* dev_x, int B, int C);
+/* out[r] = a[r] + b[r % b_rows] over [rows, cols]. */
+int vstar_op_add_bcast(void* stream, const uint16_t* dev_a, const uint16_t* dev_b, uint16_t* dev_out, int64_t rows, int cols,
+                       int64_t b_rows);
+/* out[n * rows_per + p] = a[(n / rep) * rows_per + p] + b[0] for n < n_out. */
+int vstar_op_add_bcast_repeat(void* stream, const uint16_t* dev_a, const uint16_t* dev_b, uint16_t* dev_out, int n_out, int rep,
+                              int rows_per, int cols);
+/* dst[(r * rep_stride + i) * ld + c] = src[i * ld + c] for r < nrep, i < nrows, c < cols. */
+int vstar_op_bcast_rows(void* stream, const uint16_t* dev_src, uint16_t* dev_dst, int nrep, int64_t rep_stride, int nrows, int cols,
+                        int64_t ld);
+/* y[b, p] = x[b, 1 + p] * x[b, 0] over x [B, N, C] -> y [B, N - 1, C]. */
+int vstar_op_owl_cls_mul(void* stream, const uint16_t* dev_x, uint16_t* dev_y, int B, int N, int C);
+/* y[r] = x[idx[r]] over rows of `cols` elements. */
+int vstar_op_gather_rows(void* stream, const uint16_t* dev_x, const int32_t* dev_idx, uint16_t* dev_y, int rows, int cols);
+/* out[r * out_stride] = argmax of the fp32 row x[r * ld .. + cols): first occurrence of the maximum, NaN counts as the maximum (torch.argmax). */
+int vstar_op_argmax_rows(void* stream, const float* dev_x, int rows, int cols, int ld, int32_t* dev_out, int out_stride);
+/* vstar_op_layernorm / vstar_op_rmsnorm with y[r] = norm(x[row_index[r]]) (row_index null: r) and, for LayerNorm, act 1 = exact GELU
+ * of the bf16-rounded affine result (LayerNorm2d + GELU); beta may be null. */
+int vstar_op_layernorm_ex(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, const uint16_t* dev_beta, uint16_t* dev_y,
+                          int rows, int cols, float eps, const int32_t* dev_row_index, int act);
+int vstar_op_rmsnorm_ex(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, uint16_t* dev_y, int rows, int cols, float eps,
+                        const int32_t* dev_row_index);
+/* r[m] = 1 / sqrt(E[x^2] - E[x]^2 + eps) from x [rows, cols] (x != null) or from partials [rows, ld] = cols / 64 sums of squares |
+ * cols / 64 sums per row (x == null); cols % 64 == 0. */
+int vstar_op_ln_rstd(void* stream, const uint16_t* dev_x, const float* dev_partials, int ld, int rows, int cols, float eps,
+                     float* dev_r);
+/* In place W[n, k] = bf16(W[n, k] * w[k]) for n < rows;  vstar_op_fill: v[i] = bf16(value) for i < n. */
+int vstar_op_scale_cols(void* stream, uint16_t* dev_W, const uint16_t* dev_w, int64_t rows, int K);
+int vstar_op_fill(void* stream, uint16_t* dev_v, int64_t n, float value);
+/* Per-row symmetric fp8 e4m3: scale[r] = absmax / 448 (1 for a zero row), q[r * ldq + c] = e4m3(x[r * ldx + c] * (1 / scale[r])). */
+int vstar_op_quantize_rows_fp8(void* stream, const uint16_t* dev_x, int64_t ldx, uint8_t* dev_q, int64_t ldq, float* dev_scale, int rows,
+                               int cols);
+/* The same bytes and scales as vstar_op_rmsnorm followed by vstar_op_quantize_rows_fp8 (dense, ld = cols); cols <= 4096. */
+int vstar_op_rmsnorm_quant_fp8(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, uint8_t* dev_q, float* dev_scale, int rows,
+                               int cols, float eps);
+/* SAM-head attention: q [B, Nq, H * D], k / v [B, Nk, H * D] -> out [B, Nq, H * D], scale 1 / sqrt(D); D in {16, 32}, Nk <= 2560. */
+int vstar_op_small_attention(void* stream, const uint16_t* dev_q, const uint16_t* dev_k, const uint16_t* dev_v, uint16_t* dev_out, int B,
+                             int Nq, int Nk, int H, int D);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ EXPORTS = [
     "vstar_image_set_slot", "vstar_image_set_slot_async", "vstar_preprocess_crops_slots", "vstar_comm_unique_id", "vstar_comm_init", "vstar_allgather_results",
     "vstar_comm_destroy", "vstar_build_source_hash", "vstar_op_mx_scale_bytes", "vstar_op_mx_scale_offset", "vstar_op_quantize_mx",
     "vstar_op_gemm_mx", "vstar_op_gemm_fp8_mxout", "vstar_op_attention_mx", "vstar_w8a8_mx_active",
+    # doors of the small kernels (tests/test_small_ops_gpu.py)
+    "vstar_op_owl_class_logits", "vstar_op_owl_box_finish", "vstar_op_upsample2x_im2col3x3", "vstar_op_hyper_mask",
+    "vstar_op_im2col_patch", "vstar_op_vit_assemble_tokens", "vstar_op_llm_embed_text", "vstar_op_add_bcast",
+    "vstar_op_add_bcast_repeat", "vstar_op_bcast_rows", "vstar_op_owl_cls_mul", "vstar_op_gather_rows", "vstar_op_argmax_rows",
+    "vstar_op_layernorm_ex", "vstar_op_rmsnorm_ex", "vstar_op_ln_rstd", "vstar_op_scale_cols", "vstar_op_fill",
+    "vstar_op_quantize_rows_fp8", "vstar_op_rmsnorm_quant_fp8", "vstar_op_small_attention",
 ]
 
 # every symbol include/vstar_vqa.h declares
@@ -181,6 +187,22 @@ def load() -> ctypes.CDLL:
     lib.vstar_op_attention.restype = c_int
     lib.vstar_op_attention_workspace.argtypes = [c_int, c_int, c_int, c_int]
     lib.vstar_op_attention_workspace.restype = c_size_t
+    # doors of the small kernels: (stream, ...) -> int
+    V, I, L, F = c_void_p, c_int, c_int64, c_float
+    for name, args in {
+        "owl_class_logits": [V, I, I, V, V, I, I, I, I], "owl_box_finish": [V, I, V, I, I, I, I],
+        "upsample2x_im2col3x3": [V, V, I, I, I, I], "hyper_mask": [V, V, V, I, I, I, I],
+        "im2col_patch": [V, V, I, I, I, I], "vit_assemble_tokens": [V, V, V, V, I, I, I],
+        "llm_embed_text": [V, I, I, I, V, I, V, I, I], "add_bcast": [V, V, V, L, I, L],
+        "add_bcast_repeat": [V, V, V, I, I, I, I], "bcast_rows": [V, V, I, L, I, I, L], "owl_cls_mul": [V, V, I, I, I],
+        "gather_rows": [V, V, V, I, I], "argmax_rows": [V, I, I, I, V, I],
+        "layernorm_ex": [V, V, V, V, I, I, F, V, I], "rmsnorm_ex": [V, V, V, I, I, F, V], "ln_rstd": [V, V, I, I, I, F, V],
+        "scale_cols": [V, V, L, I], "fill": [V, L, F], "quantize_rows_fp8": [V, L, V, L, V, I, I],
+        "rmsnorm_quant_fp8": [V, V, V, V, I, I, F], "small_attention": [V, V, V, V, I, I, I, I, I],
+    }.items():
+        fn = getattr(lib, "vstar_op_" + name)
+        fn.argtypes = [c_void_p] + args
+        fn.restype = c_int
     # ---- VQA-LLM engine (include/vstar_vqa.h) ----
     lib.vstar_vqa_create.argtypes = [POINTER(CVqaConfig), c_int, POINTER(H)]
     lib.vstar_vqa_create.restype = c_int

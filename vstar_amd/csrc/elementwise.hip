@@ -136,6 +136,14 @@ __global__ void gather_rows_kernel(const lp_t* __restrict__ x, const int32_t* __
   *(lpx8*)(y + (int64_t)r * cols + v * 8) = *(const lpx8*)(x + (int64_t)idx_[r] * cols + v * 8);
 }
 
+// whether candidate (v, c) replaces (best, bi): larger value, or the same value at a smaller column; NaN ranks above every number
+// (torch.argmax), so a row holding NaN returns the column of its first NaN — never the "nothing seen yet" marker
+__device__ __forceinline__ bool argmax_takes(float v, int c, float best, int bi) {
+  const bool vn = v != v, bn = best != best;
+  if (vn != bn) return vn;
+  return (vn || v == best) ? c < bi : v > best;
+}
+
 // one block per row; first maximal index wins (torch.argmax tie rule on CPU/GPU is "first occurrence")
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int cols, int ld, int32_t* out,
                                                           int out_stride) {
@@ -147,19 +155,19 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   int bi = 0x7fffffff;
   for (int c = threadIdx.x; c < cols; c += 256) {
     const float v = xr[c];
-    if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+    if (argmax_takes(v, c, best, bi)) { best = v; bi = c; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    if (argmax_takes(ov, oi, best, bi)) { best = ov; bi = oi; }
   }
   if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w)
-      if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+      if (argmax_takes(sv[w], si[w], best, bi)) { best = sv[w]; bi = si[w]; }
     out[(int64_t)row * out_stride] = bi;
   }
 }

@@ -1739,6 +1739,88 @@ int vstar_op_attention(void* stream, uint16_t* qkv, uint16_t* out, void* ws, siz
   return op_rc(e);
 }
 
+// ---- doors of the small kernels (heads / layout / norm / fp8 rows / SAM attention): ONE launcher each, then synchronise ----
+static int op_done(hipError_t e, void* stream) {
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  return op_rc(e);
+}
+int vstar_op_owl_class_logits(void* stream, const float* emb, int ld, int Q, const uint16_t* query, float* out, int out_stride_crop,
+                              int B, int rows_per_crop, int img_div) {
+  return op_done(owl_class_logits(emb, ld, Q, query, out, out_stride_crop, B, rows_per_crop, (hipStream_t)stream, img_div), stream);
+}
+int vstar_op_owl_box_finish(void* stream, const float* raw, int ld, float* out, int out_stride_crop, int B, int grid, int img_div) {
+  return op_done(owl_box_finish(raw, ld, out, out_stride_crop, B, grid, (hipStream_t)stream, img_div), stream);
+}
+int vstar_op_upsample2x_im2col3x3(void* stream, const uint16_t* src, uint16_t* A, int B, int h, int w, int C) {
+  return op_done(upsample2x_im2col3x3(src, A, B, h, w, C, (hipStream_t)stream), stream);
+}
+int vstar_op_hyper_mask(void* stream, const uint16_t* hyper, const uint16_t* up, float* out, int out_stride_crop, int B, int npix,
+                        int C) {
+  return op_done(hyper_mask(hyper, up, out, out_stride_crop, B, npix, C, (hipStream_t)stream), stream);
+}
+int vstar_op_im2col_patch(void* stream, const uint16_t* pix, uint16_t* A, int B, int I, int ps, int Kpad) {
+  return op_done(im2col_patch(pix, A, B, I, ps, Kpad, (hipStream_t)stream), stream);
+}
+int vstar_op_vit_assemble_tokens(void* stream, const uint16_t* patch, const uint16_t* cls, const uint16_t* pos, uint16_t* tokens,
+                                 int B, int P, int C) {
+  return op_done(vit_assemble_tokens(patch, cls, pos, tokens, B, P, C, (hipStream_t)stream), stream);
+}
+int vstar_op_llm_embed_text(void* stream, const int32_t* ids, int L, int img_col, int P, const uint16_t* table, int vocab,
+                            uint16_t* x, int B, int C) {
+  return op_done(llm_embed_text(ids, L, img_col, P, table, vocab, x, B, C, (hipStream_t)stream), stream);
+}
+int vstar_op_add_bcast(void* stream, const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t rows, int cols, int64_t b_rows) {
+  return op_done(add_bcast(a, b, out, rows, cols, b_rows, (hipStream_t)stream), stream);
+}
+int vstar_op_add_bcast_repeat(void* stream, const uint16_t* a, const uint16_t* b, uint16_t* out, int n_out, int rep, int rows_per,
+                              int cols) {
+  return op_done(add_bcast_repeat(a, b, out, n_out, rep, rows_per, cols, (hipStream_t)stream), stream);
+}
+int vstar_op_bcast_rows(void* stream, const uint16_t* src, uint16_t* dst, int nrep, int64_t rep_stride, int nrows, int cols,
+                        int64_t ld) {
+  return op_done(bcast_rows(src, dst, nrep, rep_stride, nrows, cols, ld, (hipStream_t)stream), stream);
+}
+int vstar_op_owl_cls_mul(void* stream, const uint16_t* x, uint16_t* y, int B, int N, int C) {
+  return op_done(owl_cls_mul(x, y, B, N, C, (hipStream_t)stream), stream);
+}
+int vstar_op_gather_rows(void* stream, const uint16_t* x, const int32_t* idx, uint16_t* y, int rows, int cols) {
+  return op_done(gather_rows(x, idx, y, rows, cols, (hipStream_t)stream), stream);
+}
+int vstar_op_argmax_rows(void* stream, const float* x, int rows, int cols, int ld, int32_t* out, int out_stride) {
+  return op_done(argmax_rows(x, rows, cols, ld, out, out_stride, (hipStream_t)stream), stream);
+}
+int vstar_op_layernorm_ex(void* stream, const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y, int rows, int cols,
+                          float eps, const int32_t* row_index, int act) {
+  return op_done(layernorm_lp(x, g, b, y, rows, cols, eps, row_index, act, (hipStream_t)stream), stream);
+}
+int vstar_op_rmsnorm_ex(void* stream, const uint16_t* x, const uint16_t* g, uint16_t* y, int rows, int cols, float eps,
+                        const int32_t* row_index) {
+  return op_done(rmsnorm_lp(x, g, y, rows, cols, eps, row_index, (hipStream_t)stream), stream);
+}
+int vstar_op_ln_rstd(void* stream, const uint16_t* x, const float* partials, int ld, int rows, int cols, float eps, float* r) {
+  if (!x && !partials) { tls_error() = "vstar_op_ln_rstd: x and partials are both NULL"; return VSTAR_ERR_INVALID; }
+  return op_done(x ? ln_rstd_rows(x, rows, cols, eps, r, (hipStream_t)stream)
+                   : ln_rstd_partials(partials, ld, rows, cols, eps, r, (hipStream_t)stream), stream);
+}
+int vstar_op_scale_cols(void* stream, uint16_t* W, const uint16_t* w, int64_t rows, int K) {
+  return op_done(scale_cols_lp(W, w, rows, K, (hipStream_t)stream), stream);
+}
+int vstar_op_fill(void* stream, uint16_t* v, int64_t n, float value) {
+  return op_done(fill_lp(v, n, value, (hipStream_t)stream), stream);
+}
+int vstar_op_quantize_rows_fp8(void* stream, const uint16_t* x, int64_t ldx, uint8_t* q, int64_t ldq, float* scale, int rows,
+                               int cols) {
+  return op_done(quantize_rows_fp8(x, ldx, q, ldq, scale, rows, cols, (hipStream_t)stream), stream);
+}
+int vstar_op_rmsnorm_quant_fp8(void* stream, const uint16_t* x, const uint16_t* gamma, uint8_t* q, float* scale, int rows, int cols,
+                               float eps) {
+  return op_done(rmsnorm_quant_fp8(x, gamma, q, scale, rows, cols, eps, (hipStream_t)stream), stream);
+}
+int vstar_op_small_attention(void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int Nq,
+                             int Nk, int H, int D) {
+  return op_done(small_attention(q, k, v, out, B, Nq, Nk, H, D, (hipStream_t)stream), stream);
+}
+
 }  // extern "C"
 
 // accessors for comm.hip (the handle's layout is private to this file)

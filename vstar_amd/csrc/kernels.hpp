@@ -126,6 +126,8 @@ hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src
 size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx);
 // q [n*L, H*DH], kv [n*NK, 2*H*DH] (k | v) -> out [n*L, H*DH]
 hipError_t perceiver_attention(const lp_t* q, const lp_t* kv, lp_t* out, int n, int L, int NK, int H, int DH, hipStream_t s);
+// argmax over 16-bit logits rows: the first column holding the largest NUMBER. Unlike argmax_rows (below) it does not rank NaN: a NaN
+// never wins, and a row of only NaN and / or values <= -3e38 (-inf) returns 0 — always an index in [0, cols)
 hipError_t argmax_rows_lp(const lp_t* x, int rows, int cols, int64_t ld, int32_t* out, hipStream_t s);
 
 // ---- W8A8 (quant.hip): per-row symmetric fp8 e4m3 quantisation, scale = absmax / 448 ----
@@ -196,7 +198,8 @@ hipError_t bcast_rows(const lp_t* src, lp_t* dst, int nrep, int64_t rep_stride, 
 hipError_t owl_cls_mul(const lp_t* x, lp_t* y, int B, int N, int C, hipStream_t s);
 // gather rows: y[r,:] = x[idx[r],:]
 hipError_t gather_rows(const lp_t* x, const int32_t* idx, lp_t* y, int rows, int cols, hipStream_t s);
-// argmax over fp32 logits rows
+// argmax over fp32 logits rows (cols >= 1): the FIRST column holding the maximum, where NaN ranks above every number — torch.argmax's
+// rule, so a row with NaN returns the column of its first NaN and every row returns an index in [0, cols)
 hipError_t argmax_rows(const float* x, int rows, int cols, int ld, int32_t* out, int out_stride, hipStream_t s);
 
 // ---- heads (heads.hip) ----
