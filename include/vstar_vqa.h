@@ -56,7 +56,9 @@ typedef struct vstar_vqa_config {
   int32_t max_ctx;            /* positions per slot */
   int32_t max_rows;           /* new rows per forward call (after padding a ragged prefill batch) */
   int32_t max_images;         /* feature-table slots; each holds P long rows then pcv_latents short rows */
-  int32_t reserved[8];
+  int32_t decode_weight_bits; /* 0 (default) = fp16 weights everywhere; 8 = int8 weight-only decode of the LLaMA block linears
+                               * (q|k|v, o_proj, gate|up, down_proj), see vstar_vqa_decode_weight_bits; anything else fails at create */
+  int32_t reserved[7];
 } vstar_vqa_config;
 
 typedef struct vstar_vqa_engine vstar_vqa_handle;
@@ -174,6 +176,27 @@ int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, i
  * does for input_layernorm -> q/k/v and post_attention_layernorm -> gate/up.  Runs on the null stream and synchronises. */
 int vstar_vqa_op_gemm(const void* dev_A, const void* dev_W, const void* dev_bias, const void* dev_residual, void* dev_C,
                       int M, int N, int K, int epilogue, int kernel, const void* dev_norm_w, float norm_eps);
+
+/* int8 weight-only decode (W8A16), opt-in through vstar_vqa_config.decode_weight_bits = 8.  finalize_weights then
+ * quantises the LLaMA block linears once, on the device, per output row n of W[N, K]: a = max_k |W[n,k]|, s = float(a) / 127.0f
+ * (one correctly rounded fp32 divide; s = 1 when a == 0), q[n,k] = clamp(rint(float(W[n,k]) / s), -127, 127) as int8 (-128 never
+ * occurs).  Calls of up to 64 rows (decode steps) stream the int8 weights through the weight-streaming kernels — every MFMA sees
+ * fp16(q), exact, and the reduced fp32 accumulator is multiplied once by s — while the fp16 weights are REPLACED by
+ * fp16(float(q) * s), so prefill and larger calls run the same quantised model on the tile kernels.  lm_head, the embedding, the
+ * CLIP tower, the projectors and the Perceiver stay fp16.  A failed allocation fails finalize_weights (no fp16 fallback).
+ * Returns 8 when the mode is active on a finalized engine, else 0. */
+int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h);
+/* Op-level quantiser (tests): DEVICE W [rows, K] fp16 (K % 8 == 0) -> q int8 [rows, K], scale fp32 [rows], and (nullable, may
+ * alias W) What fp16 [rows, K] = fp16(float(q) * s).  Null stream, synchronises. */
+int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q_i8, float* dev_scale_f32, void* dev_What_f16);
+/* Op-level W8A16 GEMV (tests, micro-benchmarks): vstar_vqa_op_gemm with the weight given as int8 rows dev_Wq [ceil(N/256)*256, K]
+ * and fp32 scales dev_scale [ceil(N/256)*256]: C = epilogue((A · fp16(q)^T) * s + bias) (+ residual), operand rules as
+ * vstar_vqa_op_gemm.  kernel: 1 = dispatch (the LDS-ring variant where eligible), 3 = force the register-streaming kernel.
+ * layout: 0 = the ring reads the row-major int8, 1 = the op packs a temporary tile-major image and the ring reads that (needs
+ * N % 16 == 0, SiLU-mul N % 32 == 0).  Outside the weight-streaming domain (M > 64) it is an error. */
+int vstar_vqa_op_gemm_w8(const void* dev_A, const void* dev_Wq, const float* dev_scale, const void* dev_bias,
+                         const void* dev_residual, void* dev_C, int M, int N, int K, int epilogue, int kernel,
+                         const void* dev_norm_w, float norm_eps, int layout);
 
 /* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float. Returns elements written. */
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t capacity);

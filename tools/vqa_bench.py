@@ -13,6 +13,10 @@ spread of the alternated blocks.  --only-score skips every other leg.
 --score-kernels N (use with --layers 2 under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py ...`): 20 forward
 calls with the arg-max tail and 20 with the scoring tail on N wanted rows, so that the trace's per-kernel statistics compare
 score_rows_kernel with argmax_rows at that row count.
+--decode-bits 0,8 runs `decode_bits` ALONE: two engines in one process on the same weights, fp16 and the int8 weight-only
+decode mode, greedy decode blocks of --steps alternated --rounds times at every batch size; tokens/s and the
+effective weight stream of both (bytes a step actually reads: int8 block linears + fp16 lm_head in the 8-bit mode), their ratio
+and the spread over the rounds.
 Decode steps are bound by the weight sweep (13.5 GB fp16 per step at 7B): `weights_GBps` = bytes of all LLaMA + lm_head
 weights / device time of one step (HIP events inside the engine), against the ~8 TB/s HBM3E peak.
 """
@@ -43,11 +47,18 @@ def main():
     ap.add_argument("--beams", default="", help="comma-separated beam counts: add the beam-search leg next to greedy")
     ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
     ap.add_argument("--only-score", action="store_true", help="run the --score leg alone")
+    ap.add_argument("--decode-bits", default="", help="'0,8': fp16 against the int8 weight-only decode mode, alternated blocks (runs alone)")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
     score_b = [int(x) for x in a.score.split(",")] if a.score else []
     if a.only_score and not score_b:
         ap.error("--only-score needs --score B[,B...]")
+    if a.decode_bits:
+        bits = [int(x) for x in a.decode_bits.split(",")]
+        if sorted(bits) != [0, 8]:
+            ap.error("--decode-bits takes 0,8")
+        out = {"decode_bits": decode_bits(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)}
+        return finish(out, a)
     n_q = max(score_b + [1])                     # the scoring leg needs 5 KV slots and one feature slot per question
     cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=max(40, 5 * n_q), max_ctx=1024, max_rows=16384, max_images=max(8, n_q))
     t0 = time.time()
@@ -178,6 +189,54 @@ def score_leg(eng, cfg, batches, rounds):
                       "spread": round((max(t[m]) - min(t[m])) / med, 3),
                       "forward_device_ms_per_block": [round(x, 2) for x in fwd[m]]}
         leg["device_over_host_questions_per_s"] = round(leg["device"]["questions_per_s"] / leg["host"]["questions_per_s"], 3)
+        res[f"B{B}"] = leg
+    return res
+
+
+def decode_bits(layers, batches, steps, rounds):
+    """fp16 engine against the int8 weight-only decode engine (same seeded weights), greedy steps of B sequences with ~300 cached
+    positions, blocks of `steps` alternated `rounds` times in one process."""
+    engs = {}
+    for bits in (0, 8):
+        cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=max(batches + [1]), max_ctx=1024, max_rows=16384, max_images=1,
+                                decode_weight_bits=bits)
+        engs[bits] = VqaEngine(cfg, 0)
+        engs[bits].load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
+        assert engs[bits].decode_weight_bits() == bits
+    H, M, V, L = cfg.llm_hidden, cfg.llm_mlp, cfg.llm_vocab, cfg.llm_layers
+    blk = L * (4 * H * H + 3 * H * M)
+    wbytes = {0: 2.0 * (blk + V * H), 8: 1.0 * blk + 4.0 * L * (5 * H + 2 * M) + 2.0 * V * H}
+    g = torch.Generator().manual_seed(0)
+    rows = torch.randint(3, 30000, (296,), generator=g).tolist()
+    res = {"config": {"layers": L, "hidden": H, "weights_GB_per_step": {str(b): round(w / 1e9, 2) for b, w in wbytes.items()}}}
+    for B in batches:
+        nxt, pos = {}, {}
+        for bits, eng in engs.items():
+            _, nxt[bits] = eng.forward([Seq(rows, kv_slot=i) for i in range(B)], [(i, -1) for i in range(B)], logits=False)
+            pos[bits] = len(rows)
+        want = [(i, 0) for i in range(B)]
+        dev = {0: [], 8: []}
+        blocks = {0: [], 8: []}
+        for r in range(rounds + 1):                  # round 0 warms both engines up and is dropped
+            for bits, eng in engs.items():
+                t0 = time.time()
+                d = []
+                for s in range(steps):
+                    _, nxt[bits] = eng.forward([Seq([int(nxt[bits][i])], kv_slot=i, past_len=pos[bits]) for i in range(B)], want, logits=False)
+                    d.append(eng.last_forward_ms())
+                    pos[bits] += 1
+                if r:
+                    blocks[bits].append((time.time() - t0) / steps * 1e3)
+                    dev[bits] += d
+        leg = {}
+        for bits in (0, 8):
+            w, d = float(np.median(blocks[bits])), float(np.median(dev[bits]))
+            leg[f"bits{bits}"] = {"device_ms_per_step": round(d, 3), "wall_ms_per_step": round(w, 3), "tokens_per_s": round(B / w * 1e3, 1),
+                                  "wall_ms_per_step_blocks": [round(x, 3) for x in blocks[bits]],
+                                  "spread": round((max(blocks[bits]) - min(blocks[bits])) / w, 3),
+                                  "weights_GBps": round(wbytes[bits] / d / 1e6, 0)}
+        leg["bits8_over_bits0_tokens_per_s"] = round(leg["bits8"]["tokens_per_s"] / leg["bits0"]["tokens_per_s"], 3)
+        leg["bits8_over_bits0_device_time"] = round(leg["bits8"]["device_ms_per_step"] / leg["bits0"]["device_ms_per_step"], 3)
         res[f"B{B}"] = leg
     return res
 

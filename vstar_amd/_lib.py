@@ -37,6 +37,7 @@ EXPORTS_VQA = [
     "vstar_vqa_encode_images", "vstar_vqa_forward", "vstar_vqa_debug_read", "vstar_vqa_last_forward_ms", "vstar_vqa_op_gemm",
     "vstar_vqa_forward_sample", "vstar_vqa_op_sample", "vstar_vqa_forward_beam", "vstar_vqa_kv_reorder", "vstar_vqa_kv_copy",
     "vstar_vqa_op_beam_select", "vstar_vqa_forward_score", "vstar_vqa_op_score",
+    "vstar_vqa_decode_weight_bits", "vstar_vqa_op_quantize_w8", "vstar_vqa_op_gemm_w8",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -242,6 +243,13 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int
+    lib.vstar_vqa_decode_weight_bits.argtypes = [H]
+    lib.vstar_vqa_decode_weight_bits.restype = c_int
+    lib.vstar_vqa_op_quantize_w8.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_quantize_w8.restype = c_int
+    lib.vstar_vqa_op_gemm_w8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_float, c_int]
+    lib.vstar_vqa_op_gemm_w8.restype = c_int
     lib.vstar_vqa_debug_read.argtypes = [H, c_char_p, c_void_p, c_int64]
     lib.vstar_vqa_debug_read.restype = c_int64
     lib.vstar_vqa_last_forward_ms.argtypes = [H]

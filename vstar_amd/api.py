@@ -274,18 +274,22 @@ class LlavaSearchModel:
 
 
 def load_pretrained_model(model_path, model_base=None, model_name: str = "", load_8bit: bool = False, load_4bit: bool = False,
-                          device_map="auto", device="cuda", *, cfg=None, state_dict=None, tokenizer=None, vision_tower=None):
+                          device_map="auto", device="cuda", *, cfg=None, state_dict=None, tokenizer=None, vision_tower=None,
+                          decode_weight_bits=0):
     """Same signature and return tuple as LLaVA/llava/model/builder.py:26-151: (tokenizer, model, image_processor, context_len).
-    `model_path`: LOCAL checkpoint directory of craigwu/seal_vqa_7b (offline: `cfg` + `state_dict` [+ `tokenizer`])."""
+    `model_path`: LOCAL checkpoint directory of craigwu/seal_vqa_7b (offline: `cfg` + `state_dict` [+ `tokenizer`]).
+    decode_weight_bits=8: the engine's own int8 weight-only decode mode, not bitsandbytes' LLM.int8."""
     if load_8bit or load_4bit:
-        raise NotImplementedError("bitsandbytes 8-bit / 4-bit loading is out of scope: the engine runs fp16 (builder.py:43)")
+        raise NotImplementedError("bitsandbytes 8-bit / 4-bit loading is out of scope: the engine runs fp16 (builder.py:43); "
+                                  "its own int8 weight-only decode mode is decode_weight_bits=8")
     if model_base is not None:
         raise NotImplementedError("LoRA / model_base merging is out of scope (the evaluation passes model_base=None)")
     if "mpt" in model_name.lower():
         raise NotImplementedError("the MPT variant is out of scope")
     from .vqa import VQA_LLM
     llm = VQA_LLM(SimpleNamespace(vqa_model_path=model_path, conv_type="v1", vision_tower=vision_tower), cfg=cfg,
-                  state_dict=state_dict, tokenizer=tokenizer, device=_device_index(device))
+                  state_dict=state_dict, tokenizer=tokenizer, device=_device_index(device),
+                  decode_weight_bits=decode_weight_bits or None)
     return llm.tokenizer, LlavaSearchModel(llm), llm.image_processor, llm.context_len
 
 

@@ -161,7 +161,8 @@ class CVqaConfig(ctypes.Structure):
         ("pcv_latents", ctypes.c_int32), ("pcv_ff_mult", ctypes.c_int32),
         ("max_slots", ctypes.c_int32), ("max_ctx", ctypes.c_int32), ("max_rows", ctypes.c_int32),
         ("max_images", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 8),
+        ("decode_weight_bits", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 7),
     ]
 
 
@@ -191,6 +192,7 @@ class VQAConfig:
     max_ctx: int = 2048
     max_rows: int = 8192
     max_images: int = 16
+    decode_weight_bits: int = 0     # 8: int8 weight-only decode of the LLaMA block linears; 0: fp16 everywhere
 
     @property
     def n_img_tokens(self) -> int:

@@ -30,7 +30,33 @@ namespace {
 constexpr int SK_WAVES = 8;
 constexpr int SKR_WAVE_BYTES = 10240;      // gemm_skinny_ring_kernel: LDS ring per wave
 
-template <int EPI, bool OUT_F32, int MT>
+// W8 forms (GemmParams::Wq): the lane's 8 k-elements of a W row are 8 bytes of int8.  Eight int8 -> eight fp16,
+// exact and without a cvt chain: q ^ 0x80 = q + 128 as an unsigned byte u; the 16-bit pattern 0x6400 | u is the fp16 number
+// 1024 + u (the ulp of [1024, 2048) is 1); one packed subtraction of 1152 leaves q.  Two bytes per v_perm_b32, two halves per v_pk_add_f16.
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;      // 8 int8 weights: what a lane loads per MFMA k-step
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;      // 16 bytes: the converted fragment, a chunk of the int8 tile image
+__device__ __forceinline__ lpx8 w8_to_f16x8(u32x2 raw) {
+  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+  const h2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+  u32x4 o;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const unsigned x = raw[w] ^ 0x80808080u;
+    const unsigned lo = __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u);   // bytes [x0, 0x64, x1, 0x64]
+    const unsigned hi = __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u);   // bytes [x2, 0x64, x3, 0x64]
+    o[2 * w] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, lo) - off);
+    o[2 * w + 1] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, hi) - off);
+  }
+  return __builtin_bit_cast(lpx8, o);
+}
+// the one fp32 multiply per output column of the W8 forms: the lane's four columns start at packed row n
+__device__ __forceinline__ f32x4 w8_scale_cols(f32x4 acc, const float* __restrict__ scale, int n) {
+#pragma clang fp contract(off)      // a multiply of its own: never fused into the epilogue's bias / residual add
+  const f32x4 sc = *(const f32x4*)(scale + n);
+  return acc * sc;
+}
+
+template <int EPI, bool OUT_F32, int MT, bool W8 = false>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmParams p) {
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
   __shared__ float red[SK_WAVES][MT][64][4];
@@ -39,8 +65,12 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
   const int n0 = blockIdx.x * 16 * NT;
 
   const lp_t* wp[NT];
+  const int8_t* wq[NT];            // W8: the same row and k offset, one byte per element
 #pragma unroll
-  for (int t = 0; t < NT; ++t) wp[t] = p.W + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8;
+  for (int t = 0; t < NT; ++t) {
+    wp[t] = W8 ? nullptr : p.W + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8;
+    wq[t] = W8 ? p.Wq + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8 : nullptr;
+  }
   const lp_t* ap[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
@@ -100,7 +130,10 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
     for (int u = 0; u < 2 * UH; ++u) {
       const int k = (ds + (u >> 1) * SK_WAVES) * 64 + (u & 1) * 32;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) wf[u][t] = __builtin_nontemporal_load((const lpx8*)(wp[t] + k));   // streamed once
+      for (int t = 0; t < NT; ++t) {
+        if constexpr (W8) wf[u][t] = w8_to_f16x8(__builtin_nontemporal_load((const u32x2*)(wq[t] + k)));
+        else wf[u][t] = __builtin_nontemporal_load((const lpx8*)(wp[t] + k));   // streamed once
+      }
 #pragma unroll
       for (int m = 0; m < MT; ++m) af[u][m] = *(const lpx8*)(ap[m] + k);
     }
@@ -125,7 +158,9 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
       const int k = ds * 64 + h * 32;
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const lpx8 wf = *(const lpx8*)(wp[t] + k);
+        lpx8 wf;
+        if constexpr (W8) wf = w8_to_f16x8(*(const u32x2*)(wq[t] + k));
+        else wf = *(const lpx8*)(wp[t] + k);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           lpx8 a = *(const lpx8*)(ap[m] + k);
@@ -153,6 +188,10 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
   const int n_out = (EPI == VSTAR_EPI_SILU_MUL) ? p.N / 2 : p.N;
   const int row = wave * 16 + fr;
   if (row >= p.M) return;
+  if constexpr (W8) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) s[t] = w8_scale_cols(s[t], p.wq_scale, n0 + t * 16 + g * 4);
+  }
   if (EPI == VSTAR_EPI_SILU_MUL) gemm_epilogue_store<EPI, OUT_F32>(p, row, n0 / 2 + g * 4, n_out, s[0], s[NT - 1]);
   else gemm_epilogue_store<EPI, OUT_F32>(p, row, n0 + g * 4, n_out, s[0], s[0]);
 }
@@ -169,14 +208,25 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
 // what 6 TB/s x ~2 us of latency needs.  No barrier in the K loop (private rings, counted vmcnt).  Everything in the queue is an
 // LDS-DMA request on purpose: register loads mixed into the counted waits returned out of order with the DMA requests
 // (wrong results under load), requests of one kind retire in order.
-template <int EPI, bool OUT_F32, bool NORM>
+// W8 form (GemmParams::Wq): a 16-row weight tile of one double step is 16 x 64 B = 1 KiB = ONE request (lane ->
+// row lane/4, LDS slot lane%4 <- global chunk slot ^ ((row>>2)&3)), the activation piece is unchanged.  A stage is NT + 1 KiB, so
+// the 10 KiB of a wave hold 5 stages (NT = 1: 10 KiB in flight, fp16: 9) or 3 (NT = 2: 9 KiB, fp16: 10 — a fourth stage would
+// need 12 KiB per wave and two workgroups of 80 KiB are all the LDS a CU has).  In WEIGHT bytes, which are what HBM has to
+// deliver (the activation pieces come from L2), that is 5 KiB per wave against fp16's 6 (NT = 1) and 6 against 8 (NT = 2): the
+// activation piece of a double step stays 1 KiB while its weight tile halves, so a W8 ring of the same LDS holds FEWER weight
+// bytes in flight than the fp16 ring, not more.  The counted queue still holds DMA requests only; the scales
+// are read with ordinary loads after the last vmcnt(0), behind the reduction.
+template <int EPI, bool OUT_F32, bool NORM, bool W8 = false>
 __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(const GemmParams p) {
   typedef const __attribute__((address_space(1))) void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
-  constexpr int RD = NT == 1 ? 3 : 2;                 // ring depth (stages)
-  constexpr int STAGE = NT * 2048 + 1024;             // bytes per stage: W tiles | activation piece
-  constexpr int SOPS = 2 * NT + 1;                    // DMA requests per stage and wave
+  constexpr int WREQ = W8 ? 1 : 2;                    // DMA requests (1 KiB each) per 16-row weight tile and stage
+  constexpr int WTILE = WREQ * 1024;                  // bytes of one 16-row weight tile of a stage
+  constexpr int RD = W8 ? (NT == 1 ? 5 : 3) : (NT == 1 ? 3 : 2);     // ring depth (stages)
+  constexpr int STAGE = NT * WTILE + 1024;            // bytes per stage: W tiles | activation piece
+  constexpr int SOPS = WREQ * NT + 1;                 // DMA requests per stage and wave
+  static_assert(RD * STAGE <= SKR_WAVE_BYTES && (RD + 1) * STAGE > SKR_WAVE_BYTES, "the ring fills the wave's LDS share");
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [8 waves][10 KiB]; reused for the reduction
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, g = lane >> 4;
@@ -186,13 +236,17 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
   // DMA sources of this lane: a request moves 8 rows x 128 B, lane -> row lane/8, LDS slot lane%8 <- global chunk slot ^ ((row>>1)&7)
   const int st_r = lane >> 3, st_c = lane & 7;
   const lp_t* wsrc[NT][2];
+  const int8_t* wsrc8[NT];         // W8: one request per tile, 16 rows x 64 B
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int t = 0; t < NT; ++t) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int row = h * 8 + st_r;
-      wsrc[t][h] = p.W + (int64_t)(n0 + t * 16 + row) * p.K + (st_c ^ ((row >> 1) & 7)) * 8;
+      wsrc[t][h] = W8 ? nullptr : p.W + (int64_t)(n0 + t * 16 + row) * p.K + (st_c ^ ((row >> 1) & 7)) * 8;
     }
+    const int row8 = lane >> 2;
+    wsrc8[t] = W8 ? p.Wq + (int64_t)(n0 + t * 16 + row8) * p.K + ((lane & 3) ^ ((row8 >> 2) & 3)) * 16 : nullptr;
+  }
   const lp_t* asrc;
   {
     const int cg = (st_c ^ ((st_r >> 1) & 7)) * 8;
@@ -204,9 +258,11 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
   int w_rd[2], a_rd[2], n_rd[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    w_rd[u] = fr * 128 + (((u * 4 + g) ^ ((fr >> 1) & 7)) * 16);
-    a_rd[u] = NT * 2048 + arow * 128 + (((u * 4 + g) ^ ((arow >> 1) & 7)) * 16);
-    n_rd[u] = NT * 2048 + 7 * 128 + (((u * 4 + g) ^ 3) * 16);
+    // W8: row fr at fr * 64, the 8 bytes of k = u*32 + g*8 are half g&1 of chunk u*2 + g/2, stored at slot chunk ^ ((fr>>2)&3)
+    w_rd[u] = W8 ? fr * 64 + (((u * 2 + (g >> 1)) ^ ((fr >> 2) & 3)) * 16) + (g & 1) * 8
+                 : fr * 128 + (((u * 4 + g) ^ ((fr >> 1) & 7)) * 16);
+    a_rd[u] = NT * WTILE + arow * 128 + (((u * 4 + g) ^ ((arow >> 1) & 7)) * 16);
+    n_rd[u] = NT * WTILE + 7 * 128 + (((u * 4 + g) ^ 3) * 16);
   }
 
   f32x4 acc[NT];
@@ -216,20 +272,28 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
   const int nd = p.K >> 6;
   const int n = (nd - wave + SK_WAVES - 1) / SK_WAVES;          // this wave's double steps: ds = wave + 8 i
   // tile-major weights (GemmParams::W_tiled): this workgroup's pieces lie back to back, [k-step][t][h] x 1 KiB, already in request order
-  const bool tiled = p.W_tiled != nullptr;
-  const lp_t* wt = tiled ? p.W_tiled + ((int64_t)blockIdx.x * nd * (2 * NT)) * 512 + lane * 8 : nullptr;
+  const bool tiled = W8 ? p.Wq_tiled != nullptr : p.W_tiled != nullptr;
+  const lp_t* wt = (!W8 && tiled) ? p.W_tiled + ((int64_t)blockIdx.x * nd * (2 * NT)) * 512 + lane * 8 : nullptr;
+  // (W8, GemmParams::Wq_tiled: [k-step][t] x 1 KiB)
+  const int8_t* wt8 = (W8 && tiled) ? p.Wq_tiled + ((int64_t)blockIdx.x * nd * NT) * 1024 + lane * 16 : nullptr;
   auto issue = [&](int slot, int i) {
     const int ks = wave + i * SK_WAVES;
     const int k = ks * 64;
     char* st = ring + slot * STAGE;
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < NT; ++t) {
+      if constexpr (W8) {
+        const int8_t* src = tiled ? wt8 + ((int64_t)ks * NT + t) * 1024 : wsrc8[t] + k;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + t * WTILE), 16, 0, 0);
+      } else {
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const lp_t* src = tiled ? wt + ((int64_t)ks * (2 * NT) + t * 2 + h) * 512 : wsrc[t][h] + k;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + t * 2048 + h * 1024), 16, 0, 0);
+        for (int h = 0; h < 2; ++h) {
+          const lp_t* src = tiled ? wt + ((int64_t)ks * (2 * NT) + t * 2 + h) * 512 : wsrc[t][h] + k;
+          __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + t * 2048 + h * 1024), 16, 0, 0);
+        }
       }
-    __builtin_amdgcn_global_load_lds((gptr_t)(asrc + k), (lptr_t)(st + NT * 2048), 16, 0, 0);
+    }
+    __builtin_amdgcn_global_load_lds((gptr_t)(asrc + k), (lptr_t)(st + NT * WTILE), 16, 0, 0);
   };
   // the first RD stages go out before anything else: neither the weights nor the raw activation rows depend on the statistics
   // (with the fused norm the last wave's last slot carries the row statistics first and is filled after them: two workgroups
@@ -289,7 +353,10 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
 #pragma unroll
-      for (int t = 0; t < NT; ++t) wf[u][t] = *(const lpx8*)(st + t * 2048 + w_rd[u]);
+      for (int t = 0; t < NT; ++t) {
+        if constexpr (W8) wf[u][t] = w8_to_f16x8(*(const u32x2*)(st + t * WTILE + w_rd[u]));
+        else wf[u][t] = *(const lpx8*)(st + t * WTILE + w_rd[u]);
+      }
       a[u] = *(const lpx8*)(st + a_rd[u]);
       if (NORM) a[u] = normed(a[u], *(const lpx8*)(st + n_rd[u]), rstd);
     }
@@ -304,8 +371,9 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
     // stages i0 .. i0+RD-1 are in flight; stage i0 + j has landed once at most the RD - 1 younger stages are outstanding
 #pragma unroll
     for (int j = 0; j < RD; ++j) {
-      static_assert(SOPS * (RD - 1) == 6 || SOPS * (RD - 1) == 5, "add the literal below");
-      if constexpr (SOPS * (RD - 1) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      static_assert(SOPS * (RD - 1) == 8 || SOPS * (RD - 1) == 6 || SOPS * (RD - 1) == 5, "add the literal below");
+      if constexpr (SOPS * (RD - 1) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");        // W8, NT = 1: 2 x 4
+      else if constexpr (SOPS * (RD - 1) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // fp16 NT = 1: 3 x 2; W8 NT = 2: 3 x 2
       else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       consume(j);
       issue(j, i0 + RD + j);
@@ -342,6 +410,10 @@ __global__ __launch_bounds__(SK_WAVES * 64, 2) void gemm_skinny_ring_kernel(cons
   if (wave != 0) return;
   const int n_out = (EPI == VSTAR_EPI_SILU_MUL) ? p.N / 2 : p.N;
   if (fr >= p.M) return;
+  if constexpr (W8) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) s[t] = w8_scale_cols(s[t], p.wq_scale, n0 + t * 16 + g * 4);
+  }
   if (EPI == VSTAR_EPI_SILU_MUL) gemm_epilogue_store<EPI, OUT_F32>(p, fr, n0 / 2 + g * 4, n_out, s[0], s[NT - 1]);
   else gemm_epilogue_store<EPI, OUT_F32>(p, fr, n0 + g * 4, n_out, s[0], s[0]);
 }
@@ -364,27 +436,85 @@ __global__ void skinny_tile_pack_kernel(const lp_t* __restrict__ W, lp_t* __rest
   *(lpx8*)(Wt + idx * 8) = *(const lpx8*)(W + row * K + ks * 64 + chunk * 8);
 }
 
-template <int EPI, bool OUT_F32>
+#ifdef VSTAR_LP_F16
+// ------------------------------------------------ int8 weight-only decode: quantiser, tile-major image ------------------------
+// One workgroup per row of W [rows, K]: pass 1 the row's absolute maximum, pass 2 q = clamp(rint(w / s), +-127) with
+// s = amax / 127 (both divides correctly rounded; s = 1 for an all-zero row, so padding rows give q = 0, s = 1).  What (nullable,
+// may alias W, hence no __restrict__ on either: a thread reads its 8 elements before it writes them) = fp16(float(q) * s), the
+// value the tile kernels then see.
+__global__ __launch_bounds__(256) void quantize_rows_w8_kernel(const lp_t* W, int K, int8_t* __restrict__ q,
+                                                               float* __restrict__ scale, lp_t* What) {
+  __shared__ float part[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const lp_t* wr = W + (int64_t)row * K;
+  float a = 0.f;
+  for (int v = tid; v * 8 < K; v += 256) {
+    const lpx8 t = *(const lpx8*)(wr + v * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a = fmaxf(a, fabsf(lp2f((lp_t)t[e])));
+  }
+  a = wave_max(a);
+  if ((tid & 63) == 0) part[tid >> 6] = a;
+  __syncthreads();
+  a = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+  const float sc = a == 0.f ? 1.0f : __fdiv_rn(a, 127.0f);
+  if (tid == 0) scale[row] = sc;
+  for (int v = tid; v * 8 < K; v += 256) {
+    const lpx8 t = *(const lpx8*)(wr + v * 8);
+    u32x2 packed = {0u, 0u};
+    lpx8 back;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float r = rintf(__fdiv_rn(lp2f((lp_t)t[e]), sc));
+      r = fminf(fmaxf(r, -127.f), 127.f);
+      const int qi = (int)r;
+      packed[e >> 2] |= (unsigned)(qi & 0xff) << ((e & 3) * 8);
+      back[e] = (short)f2lp((float)qi * sc);
+    }
+    *(u32x2*)(q + (int64_t)row * K + v * 8) = packed;
+    if (What) *(lpx8*)(What + (int64_t)row * K + v * 8) = back;
+  }
+}
+
+// one thread per 16-byte chunk of the tile-major int8 image (see GemmParams::Wq_tiled)
+__global__ void skinny_tile_pack_w8_kernel(const int8_t* __restrict__ Wq, int8_t* __restrict__ Wt, int K, int nt, int64_t n_chunks) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_chunks) return;
+  const int lane = (int)(idx & 63);
+  const int64_t piece = idx >> 6;
+  const int nd = K >> 6;
+  const int t = (int)(piece % nt);
+  const int64_t r2 = piece / nt;
+  const int ks = (int)(r2 % nd);
+  const int64_t wg = r2 / nd;
+  const int row16 = lane >> 2;
+  const int64_t row = wg * 16 * nt + t * 16 + row16;
+  const int chunk = (lane & 3) ^ ((row16 >> 2) & 3);          // the source-side swizzle of the W8 ring kernel's requests
+  *(u32x4*)(Wt + idx * 16) = *(const u32x4*)(Wq + row * K + ks * 64 + chunk * 16);
+}
+#endif
+
+template <int EPI, bool OUT_F32, bool W8 = false>
 hipError_t launch_skinny_ring(const GemmParams& p0, hipStream_t s) {
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
   constexpr int lds = SK_WAVES * SKR_WAVE_BYTES;
   GemmParams p = p0;
-  if (p.N % (16 * NT)) p.W_tiled = nullptr;                     // whole 16 NT-row tiles only
+  if (p.N % (16 * NT)) p.W_tiled = nullptr, p.Wq_tiled = nullptr;    // whole 16 NT-row tiles only
   const int blocks = (p.N + 16 * NT - 1) / (16 * NT);
-  static bool attr_done[2] = {false, false};
+  static bool attr_done[2] = {false, false};                   // (per instantiation: the W8 forms keep their own)
   const int nm = p.norm_w ? 1 : 0;
   if (!attr_done[nm]) {
-    const void* k = nm ? (const void*)gemm_skinny_ring_kernel<EPI, OUT_F32, true> : (const void*)gemm_skinny_ring_kernel<EPI, OUT_F32, false>;
+    const void* k = nm ? (const void*)gemm_skinny_ring_kernel<EPI, OUT_F32, true, W8> : (const void*)gemm_skinny_ring_kernel<EPI, OUT_F32, false, W8>;
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     attr_done[nm] = true;
   }
-  if (nm) hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, true>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
-  else hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, false>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
+  if (nm) hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, true, W8>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
+  else hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, false, W8>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
   return hipGetLastError();
 }
 
-template <int EPI, bool OUT_F32>
+template <int EPI, bool OUT_F32, bool W8 = false>
 hipError_t launch_skinny(const GemmParams& p, hipStream_t s) {
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
   const int blocks = (p.N + 16 * NT - 1) / (16 * NT);
@@ -392,12 +522,12 @@ hipError_t launch_skinny(const GemmParams& p, hipStream_t s) {
   // M <= 8 (decode steps of up to 8 sequences; 7 with the fused norm): the LDS-ring variant, bit-identical (VSTAR_SKINNY_RING=0: the register-streaming kernel, A/B and tests);
   // the W rows it reads are padded to 256, so whole 16-row tiles exist for every workgroup
   static const bool ring = [] { const char* e = getenv("VSTAR_SKINNY_RING"); return !e || atoi(e) != 0; }();
-  if (ring && p.M <= (p.norm_w ? 7 : 8) && p.K >= 512 && p.tile_force != -1) return launch_skinny_ring<EPI, OUT_F32>(p, s);   // tile_force -1: tests
+  if (ring && p.M <= (p.norm_w ? 7 : 8) && p.K >= 512 && p.tile_force != -1) return launch_skinny_ring<EPI, OUT_F32, W8>(p, s);   // tile_force -1: tests
   switch (mt) {
-    case 1: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 1>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 2: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 2>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 3: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 3>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 4: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 4>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 1: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 1, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 2: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 2, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 3: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 3, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 4: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 4, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -988,8 +1118,36 @@ hipError_t skinny_pack_tiles(const lp_t* W, lp_t* Wt, int n_rows, int K, int nt,
   return hipGetLastError();
 }
 
+#ifdef VSTAR_LP_F16
+hipError_t quantize_rows_w8(const lp_t* W, int rows, int K, int8_t* q, float* scale, lp_t* What, hipStream_t s) {
+  if (!W || !q || !scale || rows <= 0 || K <= 0 || K % 8) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(quantize_rows_w8_kernel, dim3(rows), dim3(256), 0, s, W, K, q, scale, What);
+  return hipGetLastError();
+}
+
+hipError_t skinny_pack_tiles_w8(const int8_t* Wq, int8_t* Wt, int n_rows, int K, int nt, hipStream_t s) {
+  if (n_rows <= 0 || K <= 0 || K % 64 || (nt != 1 && nt != 2) || n_rows % (16 * nt)) return hipErrorInvalidValue;
+  const int64_t n_chunks = (int64_t)n_rows * K / 16;
+  hipLaunchKernelGGL(skinny_tile_pack_w8_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, Wq, Wt, K, nt, n_chunks);
+  return hipGetLastError();
+}
+#endif
+
 hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
   if (!gemm_skinny_eligible(p)) return hipErrorInvalidValue;
+  if (p.Wq) {              // int8 weights (GemmParams::Wq): fp16 build, 16-bit output
+#ifdef VSTAR_LP_F16
+    if (!p.wq_scale || out_f32) return hipErrorInvalidValue;
+    switch (epilogue) {
+      case VSTAR_EPI_NONE: return launch_skinny<VSTAR_EPI_NONE, false, true>(p, s);
+      case VSTAR_EPI_QUICK_GELU: return launch_skinny<VSTAR_EPI_QUICK_GELU, false, true>(p, s);
+      case VSTAR_EPI_GELU: return launch_skinny<VSTAR_EPI_GELU, false, true>(p, s);
+      case VSTAR_EPI_RELU: return launch_skinny<VSTAR_EPI_RELU, false, true>(p, s);
+      case VSTAR_EPI_SILU_MUL: return launch_skinny<VSTAR_EPI_SILU_MUL, false, true>(p, s);
+    }
+#endif
+    return hipErrorInvalidValue;
+  }
 #define SK_CASE(E)                                                                   \
   case E:                                                                            \
     return out_f32 ? launch_skinny<E, true>(p, s) : launch_skinny<E, false>(p, s);

@@ -54,6 +54,15 @@ struct GemmParams {
   // 1 KiB, each in the lane order of the LDS-DMA request that fetches it (skinny_pack_tiles): a workgroup then streams ONE sequential
   // region of HBM instead of 16 / 32 row streams 2 K bytes apart (tools/probes/stream_layout_probe.hip: gate|up 5.4 -> 7.0 TB/s)
   const lp_t* W_tiled;
+  // gemm_skinny_kernel / gemm_skinny_ring_kernel only, fp16 build: int8 weights with fp16 activations (W8A16).
+  // Wq != null => the weight operand is Wq [ceil(N/256)*256, K] int8, K-contiguous like W, and wq_scale [ceil(N/256)*256] fp32 one
+  // scale per packed row: every MFMA sees fp16(q) (exact: |q| <= 127) in place of W, and the reduced accumulator of column n is
+  // multiplied once by wq_scale[n] before gemm_epilogue_store.  W is then not read.
+  // Wq_tiled (ring kernel, or null): the TILE-MAJOR int8 image, [N / (16 NT)][K / 64][NT] pieces of 1 KiB.  A piece is ONE LDS-DMA
+  // request (16 rows x 64 B, where fp16 needs two of 8 rows x 128 B): lane l carries 16 bytes of row l / 4, namely chunk
+  // (l % 4) ^ ((row / 4) % 4) of that row's 64 bytes, so that LDS holds row r at r * 64 with its 16-byte chunks swizzled by
+  // (r / 4) % 4 and the 8-byte fragment reads of rows r, r + 4, r + 8, r + 12 fall into different banks (skinny_pack_tiles_w8).
+  const int8_t* Wq; const float* wq_scale; const int8_t* Wq_tiled;
   // gemm4w only, W8A8 with block-scaled activations (mx.hpp; round 6).  a_mx != null: A holds fp8 bytes whose E8M0
   // block scales (one per row and 32 k, tile-major: mx_scale_offset with m128 = M / 128) are applied inside the MFMA; w_scale as above.
   // c_mx != null (VSTAR_EPI_SILU_MUL): the epilogue writes SiLU(gate) * up as fp8 bytes to (uint8_t*)C (ldc in bytes) and the block
@@ -94,6 +103,14 @@ hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipSt
 // Wt <- tile-major image of the packed row-major W [n_rows][K] for gemm_skinny_ring_kernel (nt = 2 for SiLU(gate)*up weights whose
 // rows interleave gate / up in blocks of 16, else 1); n_rows % (16 nt) == 0, K % 64 == 0; Wt holds n_rows * K elements
 hipError_t skinny_pack_tiles(const lp_t* W, lp_t* Wt, int n_rows, int K, int nt, hipStream_t s);
+#ifdef VSTAR_LP_F16
+// ---- int8 weight-only decode (W8A16; fp16 build only: the in-register int8 -> fp16 conversion is exact there) ----
+// Per row n of W [rows, K] (fp16): a = max|W[n,:]|, s = a / 127 (one correctly rounded fp32 divide; 1 when a == 0),
+// q = clamp(rint(float(W) / s), -127, 127).  What (nullable, may alias W): fp16(float(q) * s).  One workgroup per row.
+hipError_t quantize_rows_w8(const lp_t* W, int rows, int K, int8_t* q, float* scale, lp_t* What, hipStream_t s);
+// the tile-major int8 image (GemmParams::Wq_tiled) of the row-major Wq [n_rows][K]; n_rows % (16 nt) == 0, K % 64 == 0
+hipError_t skinny_pack_tiles_w8(const int8_t* Wq, int8_t* Wt, int n_rows, int K, int nt, hipStream_t s);
+#endif
 
 // ---- KV-cached language model + Perceiver resampler (decode.hip) ----
 // x[r,:] = src[r] >= 0 ? table[src[r]] : (src[r] == INT32_MIN ? 0 : feats[-(src[r]+1)])

@@ -44,7 +44,12 @@ struct LlmCachedCfg {
   int hidden = 0, heads = 0, mlp = 0, layers = 0, vocab = 0;
   float rms_eps = 1e-6f, rope_theta = 10000.f;
   int max_slots = 1, max_ctx = 1024, max_rows = 1024;
+  int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only)
 };
+
+// int8 decode copies of one block linear: row-major q [Npad, K] + per-row scales [Npad] for the register kernel
+// and the row-major ring, and the tile-major image for the ring (null where the fp16 path would have none either)
+struct LinW8 { int8_t* q = nullptr; float* s = nullptr; int8_t* qt = nullptr; };
 
 struct LlmCached {
   EngineBase* e = nullptr;
@@ -100,6 +105,12 @@ struct LlmCached {
   // built when the runner is initialised, VSTAR_DECODE_TILED=0 keeps the row-major streams (A/B, tests: bit-identical).
   std::vector<lp_t*> wt_qkv, wt_gate_up, wt_down;
   bool tiled_fallback = false;      // the tile-major copies were wanted but did not fit / pack: decode runs on the row-major weights
+  // ---- int8 weight-only decode (cfg.weight_bits == 8) ----
+  // Per layer the int8 copies of q|k|v, o, gate|up and down; the fp16 masters then hold the DEQUANTISED weights (prefill and every
+  // call of more than 64 rows run the same quantised model on the tile kernels) and the fp16 tile-major copies above are not built.
+  std::vector<LinW8> w8_qkv, w8_o, w8_gate_up, w8_down;
+  int build_w8();
+  const LinW8* w8(const std::vector<LinW8>& v, int i) const { return v.empty() ? nullptr : &v[(size_t)i]; }
 
   void set_error(const std::string& m) { e->set_error(m); }
   int init(EngineBase* owner, const LlmCachedCfg& c, const lp_t* embed_, const std::vector<LlmBlock>* blocks_,
@@ -116,9 +127,9 @@ struct LlmCached {
   int decode_step_body(int keys_bound);
   int decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids, int* n_out, bool* used);
   int lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
-               const lp_t* res = nullptr, int64_t ldr = 0, const lp_t* Wt = nullptr);
+               const lp_t* res = nullptr, int64_t ldr = 0, const lp_t* Wt = nullptr, const LinW8* q8 = nullptr);
   int lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M, int epi,
-               const lp_t* Wt = nullptr);
+               const lp_t* Wt = nullptr, const LinW8* q8 = nullptr);
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
@@ -197,7 +208,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
      // OPTIONAL: the row-major weights serve the same GEMV (W_tiled == nullptr), so a failed allocation or pack — ~11.8 GB more at
      // 7B — drops the copies, clears the error and continues row-major instead of failing generate().
     const char* env = getenv("VSTAR_DECODE_TILED");
-    const bool on = !(env && atoi(env) == 0);
+    const bool on = !(env && atoi(env) == 0) && c.weight_bits != 8;      // (the int8 mode builds its own images: build_w8)
     wt_qkv.clear(); wt_gate_up.clear(); wt_down.clear();      // a retried init starts from empty lists: wt_*[i] is layer i or nothing
     std::vector<void*> mine;                                  // this block's allocations, freed together if any step fails
     bool ok = true;
@@ -234,8 +245,80 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
       }
     }
   }
+  if (c.weight_bits == 8) RC(build_w8());
+  else if (c.weight_bits != 0) { set_error("decode_weight_bits must be 0 or 8"); return VSTAR_ERR_INVALID; }
   ready = true;
   return 0;
+}
+
+// The int8 decode mode, once, on the device, from the packed fp16 weights: every int8 buffer is allocated and filled FIRST (a
+// failed allocation or launch is an error with the fp16 masters untouched: there is no fp16 fallback behind the caller's back),
+// then the masters are overwritten with the dequantised weights.  A launch or the synchronise failing DURING that overwrite leaves
+// some masters dequantised and others not: the error is returned, `ready` stays false, every forward of the engine then fails
+// with VSTAR_ERR_STATE, and the weights have to be loaded again.  VSTAR_DECODE_TILED=0 and the fp16 path's eligibility rules
+// (whole 16 NT-row tiles, hidden >= 512; o_proj has no tile-major copy) decide which linears get a tile-major image.
+inline int LlmCached::build_w8() {
+#ifdef VSTAR_LP_F16
+  const LlmCachedCfg& c = cfg;
+  const char* env = getenv("VSTAR_DECODE_TILED");
+  const bool tiled_on = !(env && atoi(env) == 0) && c.hidden >= 512;
+  std::vector<void*> mine;
+  auto fail = [&](const std::string& m, int rc) {
+    for (void* q : mine) hipFree(q);
+    (void)hipGetLastError();
+    w8_qkv.clear(); w8_o.clear(); w8_gate_up.clear(); w8_down.clear();
+    set_error(m);
+    return rc;
+  };
+  auto take = [&](size_t bytes) -> void* {
+    void* t = nullptr;
+    if (hipMalloc(&t, bytes) != hipSuccess) return nullptr;
+    mine.push_back(t);
+    return t;
+  };
+  auto quant = [&](const Lin& L, int nt, bool want_tiles, LinW8* out) -> int {
+    const int npad = (L.N + 255) / 256 * 256;
+    if (L.K % 64) return VSTAR_ERR_INVALID;
+    out->q = (int8_t*)take((size_t)npad * L.K);
+    out->s = (float*)take((size_t)npad * sizeof(float));
+    if (!out->q || !out->s) return VSTAR_ERR_NOMEM;
+    if (quantize_rows_w8(L.W, npad, L.K, out->q, out->s, nullptr, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    if (want_tiles && L.N % (16 * nt) == 0) {
+      out->qt = (int8_t*)take((size_t)L.N * L.K);
+      if (!out->qt) return VSTAR_ERR_NOMEM;
+      if (skinny_pack_tiles_w8(out->q, out->qt, L.N, L.K, nt, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    }
+    return 0;
+  };
+  w8_qkv.assign((size_t)c.layers, LinW8{}); w8_o.assign((size_t)c.layers, LinW8{});
+  w8_gate_up.assign((size_t)c.layers, LinW8{}); w8_down.assign((size_t)c.layers, LinW8{});
+  for (int i = 0; i < c.layers; ++i) {
+    const LlmBlock& b = (*blocks)[i];
+    int rc = quant(b.qkv, 1, tiled_on, &w8_qkv[i]);
+    if (!rc) rc = quant(b.o, 1, false, &w8_o[i]);
+    if (!rc) rc = quant(b.gate_up, 2, tiled_on, &w8_gate_up[i]);
+    if (!rc) rc = quant(b.down, 1, tiled_on, &w8_down[i]);
+    if (rc) return fail("int8 decode weights: allocation or quantiser launch failed (layer " + std::to_string(i) + ")", rc);
+  }
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int8 decode weights: quantiser failed", VSTAR_ERR_HIP);
+  // every int8 buffer exists: now the masters become the dequantised weights (same q, same scales: deterministic)
+  for (int i = 0; i < c.layers; ++i) {
+    const LlmBlock& b = (*blocks)[i];
+    const Lin* ls[4] = {&b.qkv, &b.o, &b.gate_up, &b.down};
+    const LinW8* qs[4] = {&w8_qkv[i], &w8_o[i], &w8_gate_up[i], &w8_down[i]};
+    for (int j = 0; j < 4; ++j) {
+      const int npad = (ls[j]->N + 255) / 256 * 256;
+      if (quantize_rows_w8(ls[j]->W, npad, ls[j]->K, qs[j]->q, qs[j]->s, ls[j]->W, e->stream) != hipSuccess)
+        return fail("int8 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+    }
+  }
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int8 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+  for (void* q : mine) e->allocs.push_back(q);
+  return 0;
+#else
+  set_error("decode_weight_bits = 8 needs the fp16 engine");
+  return VSTAR_ERR_INVALID;
+#endif
 }
 
 #define LCHK(expr)                                                                           \
@@ -249,11 +332,12 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
 
 // GEMM dispatch for the language model: weight-streaming kernel for decode-sized M, MFMA tile kernels otherwise
 inline int LlmCached::lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi, const lp_t* res,
-                               int64_t ldr, const lp_t* Wt) {
+                               int64_t ldr, const lp_t* Wt, const LinW8* q8) {
   GemmParams p{};
   p.A = A; p.lda = lda; p.W = L.W; p.bias = L.b; p.res = res; p.ldr = ldr; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
   p.W_tiled = Wt;
   if (gemm_skinny_eligible(p)) {
+    if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }      // int8 decode mode: the W8 forms of the same kernels
     const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
     if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
     return 0;
@@ -264,19 +348,20 @@ inline int LlmCached::lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C
 // RMSNorm + Linear: for decode-sized M the norm is fused into the weight-streaming GEMM's operand load (bit-identical to
 // the two-kernel form), otherwise norm kernel into `scratch`, then the GEMM
 inline int LlmCached::lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M,
-                               int epi, const lp_t* Wt) {
+                               int epi, const lp_t* Wt, const LinW8* q8) {
   const int H = cfg.hidden;
   GemmParams p{};
   p.A = x; p.lda = H; p.W = L.W; p.bias = L.b; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
   p.W_tiled = Wt;
   if (M <= 16 && L.K == H && gemm_skinny_eligible(p)) {
     p.norm_w = norm_w; p.norm_eps = cfg.rms_eps;
+    if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }
     const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
     if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
     return 0;
   }
   LCHK(rmsnorm_lp(x, norm_w, scratch, M, H, cfg.rms_eps, nullptr, e->stream));
-  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, Wt);
+  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, Wt, q8);
 }
 
 inline int LlmCached::llm_layers_prefill(int nseq, int S) {
@@ -307,14 +392,15 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
     const LlmBlock& b = (*blocks)[i];
     lp_t* kc = kcache + (int64_t)i * layer_stride;
     lp_t* vc = vcache + (int64_t)i * layer_stride;
-    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i]));
+    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i], w8(w8_qkv, i)));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
     if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream));
     LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
                           c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc));
-    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H));
-    RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i]));
-    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i]));
+    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, nullptr, w8(w8_o, i)));
+    RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i],
+                w8(w8_gate_up, i)));
+    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i], w8(w8_down, i)));
   }
   return 0;
 }

@@ -192,6 +192,10 @@ class VqaEngine:
         """Physical copy of K/V rows [lo, hi) into dst's own rows, read through src's ancestry; dst's ancestry -> identity."""
         _lib.check_vqa(self.lib.vstar_vqa_kv_copy(self.handle, int(dst), int(src), int(lo), int(hi)), self.handle)
 
+    def decode_weight_bits(self) -> int:
+        """8 when the int8 weight-only decode mode is active (finalized engine built with decode_weight_bits=8), else 0."""
+        return int(self.lib.vstar_vqa_decode_weight_bits(self.handle))
+
     def last_forward_ms(self) -> float:
         return float(self.lib.vstar_vqa_last_forward_ms(self.handle))
 

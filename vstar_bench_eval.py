@@ -25,6 +25,8 @@ def parse_args(argv):
     p.add_argument("--vqa-llm", default=None, help="module:factory providing another VQA-LLM implementation")
     p.add_argument("--vsm-factory", default=None, help="module:factory(args, device) providing another VSM implementation")
     p.add_argument("--device", default=0, type=int)
+    p.add_argument("--vqa-decode-bits", dest="vqa_decode_bits", default=0, type=int, choices=[0, 8],
+                   help="8: the VQA-LLM's int8 weight-only decode mode (DESIGN.md 8.4); 0: fp16 weights everywhere")
     p.add_argument("--search-window", dest="search_window", default=0, type=int, help="concurrent visual searches per engine batch "
                    "(cross-image lock step); 0 = one engine batch, 1 = one image at a time like the reference")
     p.add_argument("--vqa-batch", dest="vqa_batch", default=1, type=int, help="questions per VQA-LLM engine call in the free-form and "
@@ -55,7 +57,7 @@ def main(argv):
             vqa_llm = getattr(importlib.import_module(mod), fn)(args)
         else:
             from vstar_amd.vqa import VQA_LLM
-            vqa_llm = VQA_LLM(args, device=local_rank if world > 1 else args.device)
+            vqa_llm = VQA_LLM(args, device=local_rank if world > 1 else args.device, decode_weight_bits=args.vqa_decode_bits or None)
         from vstar_amd.bench_eval import eval_model, make_vsm
         vsm = None
         if args.vsm_factory:
