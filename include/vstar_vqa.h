@@ -166,6 +166,32 @@ int vstar_vqa_forward_score(vstar_vqa_handle* h, int nseq, const int32_t* row_of
 int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* targets, float* nll,
                        int32_t* target_rank, double* lse_out);
 
+/* Speculative decoding: vstar_vqa_forward with the arg-max replaced by the verify tail.  A sequence is fed its
+ * current token plus d draft tokens as one multi-row continuation, all d + 1 rows wanted; rows group_off[g] .. group_off[g+1]-1 of
+ * `want` form group g — rows of ONE sequence in position order, 1 .. 16 of them — and draft[j] is the token wanted row j's choice
+ * is compared with, i.e. the token fed as the next row (-1 = not compared: always so on a group's last row).  Per group, with rows
+ * r0 .. r0+m:  n_accept_out[g] = a, the number of leading rows whose choice accepted its draft;  tokens_out[r0 .. r0+a] = the
+ * chosen tokens (the a accepted drafts and one more token), tokens_out behind them = -1.  The sequence's cache is then valid up to
+ * past_len + a + 1 positions; the rows behind are overwritten by its next call.
+ *   params == NULL (greedy): a row's choice is vstar_vqa_forward's arg-max of that row, bit for bit; it accepts iff it equals
+ *     the draft.
+ *   params[n_want] (sampled): the kept set and fixed-point masses m_i, Z = sum m_i, of vstar_vqa_forward_sample.  A row without
+ *     draft is that call's draw.  With draft x: accept iff x is kept and floor(u_a * Z) < m_x, u_a the uniform of Philox counter
+ *     (step, stream + 1); otherwise the token is drawn from the kept set without x (Z' = Z - m_x, or Z): the smallest kept index
+ *     != x whose inclusive prefix mass, skipping x, exceeds floor(u * Z'), u the uniform of (step, stream), and the group ends.
+ *     Either way P(token = y) = m_y / Z.
+ * Errors (VSTAR_ERR_INVALID, before any launch): a draft outside [0, llm_vocab) other than -1, a last row with a draft, a group of
+ * more than 16 rows, groups that do not cover the wanted rows, wanted rows of a group that are not rows of one sequence in
+ * position order.  Only n_accept_out and tokens_out cross to the host. */
+int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                             int32_t* n_accept_out, int32_t* tokens_out);
+/* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld], F16/BF16 (1 <= vocab <= 2^22, rows <= 65535); host group_off /
+ * draft / params (nullable: greedy) / outputs.  Null stream, synchronises. */
+int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
+                        const int32_t* draft, const vstar_vqa_sampling* params, int32_t* n_accept_out, int32_t* tokens_out);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

@@ -17,6 +17,14 @@ score_rows_kernel with argmax_rows at that row count.
 decode mode, greedy decode blocks of --steps alternated --rounds times at every batch size; tokens/s and the
 effective weight stream of both (bytes a step actually reads: int8 block linears + fp16 lm_head in the 8-bit mode), their ratio
 and the spread over the rounds.
+--spec 1,3,6 runs `decode_spec` ALONE: one sequence (~300 cached positions), first a plain greedy decode of
+--spec-tokens tokens, then for every draft length d and every share of corrupted draft positions in --spec-corrupt (a replay
+drafter proposing that output: 1.0 = acceptance 0, 0.0 = acceptance 1) `VQA_LLM.speculative_decode` blocks alternated --rounds
+times with `greedy_decode` blocks of the same process; tokens/s of both (median over the blocks), their ratio, the spread of the
+blocks, the acceptance counters, and the device time of a verify step against its row count (1 .. 16 rows).
+--spec-kernels R (under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py --layers 2 --spec-kernels R`): 20 one-sequence
+steps of R rows with the arg-max tail on R wanted rows and 20 with the greedy and the sampled verify tail, for the per-kernel
+statistics of the verify kernels against argmax_rows_lp.
 Decode steps are bound by the weight sweep (13.5 GB fp16 per step at 7B): `weights_GBps` = bytes of all LLaMA + lm_head
 weights / device time of one step (HIP events inside the engine), against the ~8 TB/s HBM3E peak.
 """
@@ -48,6 +56,10 @@ def main():
     ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
     ap.add_argument("--only-score", action="store_true", help="run the --score leg alone")
     ap.add_argument("--decode-bits", default="", help="'0,8': fp16 against the int8 weight-only decode mode, alternated blocks (runs alone)")
+    ap.add_argument("--spec", default="", help="comma-separated draft lengths: speculative against plain greedy decode (runs alone)")
+    ap.add_argument("--spec-tokens", type=int, default=64, help="--spec: tokens decoded per block")
+    ap.add_argument("--spec-corrupt", default="1.0,0.5,0.0", help="--spec: shares of corrupted draft positions")
+    ap.add_argument("--spec-kernels", type=int, default=0, help="rows: the arg-max and verify tails alone, for a kernel trace")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
     score_b = [int(x) for x in a.score.split(",")] if a.score else []
@@ -58,6 +70,10 @@ def main():
         if sorted(bits) != [0, 8]:
             ap.error("--decode-bits takes 0,8")
         out = {"decode_bits": decode_bits(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)}
+        return finish(out, a)
+    if a.spec or a.spec_kernels:
+        out = decode_spec(a.layers, [int(x) for x in a.spec.split(",")] if a.spec else [], a.spec_tokens,
+                          [float(x) for x in a.spec_corrupt.split(",")], a.rounds, a.spec_kernels)
         return finish(out, a)
     n_q = max(score_b + [1])                     # the scoring leg needs 5 KV slots and one feature slot per question
     cfg = VQAConfig.seal_7b(llm_layers=a.layers, max_slots=max(40, 5 * n_q), max_ctx=1024, max_rows=16384, max_images=max(8, n_q))
@@ -238,6 +254,70 @@ def decode_bits(layers, batches, steps, rounds):
         leg["bits8_over_bits0_tokens_per_s"] = round(leg["bits8"]["tokens_per_s"] / leg["bits0"]["tokens_per_s"], 3)
         leg["bits8_over_bits0_device_time"] = round(leg["bits8"]["device_ms_per_step"] / leg["bits0"]["device_ms_per_step"], 3)
         res[f"B{B}"] = leg
+    return res
+
+
+def decode_spec(layers, ds, n_tok, corrupts, rounds, kernel_rows):
+    """Speculative against plain greedy decode of one sequence in one process (see the module docstring)."""
+    from vstar_amd.spec import ReplayDrafter
+    from vstar_amd.vqa import VQA_LLM
+    cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=2, max_ctx=1024, max_rows=16384, max_images=1)
+    eng = VqaEngine(cfg, 0)
+    eng.load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
+    llm = VQA_LLM(cfg=cfg, engine=eng)
+    llm.eos_token_id = -1                        # seeded random weights: no stop token, every block decodes n_tok tokens
+    g = torch.Generator().manual_seed(0)
+    prompt = torch.randint(3, 30000, (296,), generator=g).tolist()
+    P = len(prompt)
+    res = {"config": {"layers": cfg.llm_layers, "hidden": cfg.llm_hidden, "prompt_rows": P, "tokens_per_block": n_tok}}
+    if kernel_rows:
+        R = kernel_rows
+        eng.forward([Seq(prompt, kv_slot=0)], [(0, -1)], logits=False)
+        step, want = [Seq(prompt[:R], kv_slot=0, past_len=P)], [(0, r) for r in range(R)]
+        draft = prompt[1:R] + [-1]
+        for _ in range(20):
+            eng.forward(step, want, logits=False)
+            eng.forward_verify(step, want, [0, R], draft)
+            eng.forward_verify(step, want, [0, R], draft, [sampling_params(0.7, 50, 0.9, seed=1, step=r) for r in range(R)])
+        res["spec_kernels"] = {"rows": R, "calls": 20}
+        return res
+    seq = lambda: [Seq(prompt, kv_slot=0)]       # noqa: E731
+    plain = llm.greedy_decode(seq(), [P], n_tok)
+    # device time of one verify step against its row count (the drafts are wrong: only the step's cost is measured)
+    rows_ms = {}
+    for R in (1, 2, 4, 7, 8, 9, 16):
+        step, want = [Seq(prompt[:R], kv_slot=0, past_len=P)], [(0, r) for r in range(R)]
+        ms = []
+        for _ in range(6):
+            eng.forward_verify(step, want, [0, R], prompt[1:R] + [-1])
+            ms.append(eng.last_forward_ms())
+        rows_ms[str(R)] = round(float(np.median(ms[1:])), 3)
+    res["verify_step_device_ms_by_rows"] = rows_ms
+    legs = {}
+    for d in ds:
+        for c in corrupts:
+            drafter = ReplayDrafter([prompt], plain, cfg.llm_vocab, corrupt=c, seed=d)
+            run = {"greedy": lambda: llm.greedy_decode(seq(), [P], n_tok),
+                   "spec": lambda: llm.speculative_decode(seq(), [P], [prompt], n_tok, d, None, drafter)}
+            t = {"greedy": [], "spec": []}
+            outs = {}
+            for r in range(rounds + 1):          # round 0 warms up and is dropped
+                for m in ("greedy", "spec"):
+                    t0 = time.time()
+                    outs[m] = run[m]()
+                    if r:
+                        t[m].append(time.time() - t0)
+            st = dict(llm.spec_stats)
+            leg = {"stats": st, "acceptance": round(st["accepted"] / max(st["drafted"], 1), 3),
+                   "tokens_per_call": round(st["tokens"] / st["calls"], 3),
+                   "agreement_with_greedy": round(sum(x == y for x, y in zip(outs["spec"][0], outs["greedy"][0])) / n_tok, 4)}
+            for m in ("greedy", "spec"):
+                med = float(np.median(t[m]))
+                leg[m] = {"tokens_per_s": round(len(outs[m][0]) / med, 1), "block_ms": [round(x * 1e3, 1) for x in t[m]],
+                          "spread": round((max(t[m]) - min(t[m])) / med, 3)}
+            leg["spec_over_greedy_tokens_per_s"] = round(leg["spec"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 3)
+            legs[f"d{d}_corrupt{c}"] = leg
+    res["decode_spec"] = legs
     return res
 
 

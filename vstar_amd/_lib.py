@@ -38,6 +38,7 @@ EXPORTS_VQA = [
     "vstar_vqa_forward_sample", "vstar_vqa_op_sample", "vstar_vqa_forward_beam", "vstar_vqa_kv_reorder", "vstar_vqa_kv_copy",
     "vstar_vqa_op_beam_select", "vstar_vqa_forward_score", "vstar_vqa_op_score",
     "vstar_vqa_decode_weight_bits", "vstar_vqa_op_quantize_w8", "vstar_vqa_op_gemm_w8",
+    "vstar_vqa_forward_verify", "vstar_vqa_op_verify",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -240,6 +241,12 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_forward_score.restype = c_int
     lib.vstar_vqa_op_score.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vstar_vqa_op_score.restype = c_int
+    lib.vstar_vqa_forward_verify.argtypes = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_verify.restype = c_int
+    lib.vstar_vqa_op_verify.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]
+    lib.vstar_vqa_op_verify.restype = c_int
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int

@@ -243,12 +243,15 @@ class LlavaSearchModel:
     def generate(self, input_ids, images=None, object_features=None, images_long=None, objects_long=None, do_sample: bool = False,
                  num_beams: int = 1, temperature: float = 0, top_p=None, max_new_tokens: int = 200, use_cache: bool = True,
                  stopping_criteria=None, top_k=50, seed=None, length_penalty: float = 1.0, early_stopping=False,
-                 num_return_sequences: int = 1, **unused):
+                 num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
-        — the same draws as VQA_LLM.free_form_inference(seed=seed).  Beam sampling is not implemented."""
-        from .vqa import resolve_seed, sampling_params
+        — the same draws as VQA_LLM.free_form_inference(seed=seed).  Beam sampling is not implemented.
+        prompt_lookup_num_tokens = d > 0 (<= 15; num_beams 1): speculative decoding with up to d draft tokens per step from
+        `draft_fn` (default: prompt lookup over the text ids, vstar_amd/spec.py — our matching rule, not HF's), greedy or
+        sampled; the same ids as VQA_LLM.free_form_inference(speculative=d)."""
+        from .vqa import check_spec_tokens, resolve_seed, sampling_params
         from .vqa_engine import Seq
         if num_beams != 1 and do_sample:
             raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not implemented")
@@ -260,7 +263,15 @@ class LlavaSearchModel:
             raise ValueError(f"num_beams={num_beams} needs {num_beams} KV slots; the engine has max_slots={self.cfg.max_slots}")
         if do_sample and not temperature > 0:
             raise ValueError(f"do_sample=True needs temperature > 0, got {temperature}")
+        spec = check_spec_tokens(prompt_lookup_num_tokens or 0)
+        if spec and num_beams > 1:
+            raise ValueError("prompt_lookup_num_tokens > 0 cannot be combined with beam search (num_beams > 1)")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
+        if spec:
+            p = [sampling_params(temperature, top_k, top_p, resolve_seed(seed))] if do_sample else None
+            new = self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], [[t for t in ids if t >= 0]], max_new_tokens, spec,
+                                               p, draft_fn)[0]
+            return torch.tensor([ids + new], dtype=torch.long)
         if num_beams > 1:
             outs = self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
                                          early_stopping, num_return_sequences)[0]

@@ -145,6 +145,8 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     # free_form_batch / multiple_choices_batch call (the option losses reduced on the device); 1 = per question.
     vqa_batch = max(1, int(getattr(args, "vqa_batch", 1) or 1))
     window = int(getattr(args, "search_window", 0) or 0)
+    spec_tokens = int(getattr(args, "vqa_spec_tokens", 0) or 0)     # `--vqa-spec-tokens d`: speculative free-form decode
+    spec_kw = {"speculative": spec_tokens} if spec_tokens else {}   # (0: the call other VQA-LLM implementations also take)
     max_found = getattr(args, "max_found_objects", None)        # (tests: tiny engines hold few object crops)
     entries = []
     for split in ("direct_attributes", "relative_position"):
@@ -155,7 +157,7 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
             prediction = None
             if vqa_batch == 1:
                 square, _, _ = expand2square_centered(Image.open(path).convert("RGB"), mean_color)
-                prediction = vqa_llm.free_form_inference(square, ann["question"])
+                prediction = vqa_llm.free_form_inference(square, ann["question"], **spec_kw)
             entries.append({"split": split, "image_file": image_file, "path": path, "question": ann["question"], "options": ann["options"],
                             "prediction": prediction, "missing": parse_missing_objects(prediction) if vqa_batch == 1 else None})
     # pass 1, batched: free_form_batch takes one KV slot and one feature slot per question, so its chunks are capped by the engine
@@ -164,7 +166,7 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     for k in range(0, len(entries) if vqa_batch > 1 else 0, ff_batch):
         chunk = entries[k:k + ff_batch]
         squares = [expand2square_centered(Image.open(e["path"]).convert("RGB"), mean_color)[0] for e in chunk]
-        for e, prediction in zip(chunk, vqa_llm.free_form_batch([dict(image=im, question=e["question"]) for im, e in zip(squares, chunk)])):
+        for e, prediction in zip(chunk, vqa_llm.free_form_batch([dict(image=im, question=e["question"]) for im, e in zip(squares, chunk)], **spec_kw)):
             e["prediction"], e["missing"] = prediction, parse_missing_objects(prediction)
     todo = [e for e in entries if e["missing"]]
     if window == 1:

@@ -13,6 +13,7 @@
 #include "sample.hpp"
 #include "beam.hpp"
 #include "score.hpp"
+#include "spec.hpp"
 
 namespace VS_NS {
 
@@ -38,6 +39,18 @@ struct LlmScoreArgs {
   const int32_t* targets = nullptr;
   float* nll = nullptr;
   int32_t* rank = nullptr;
+};
+
+// The verify tail of forward() (spec.hip): host arrays.  The wanted rows form n_groups groups (rows goff[g] ..
+// goff[g+1]-1 of `want`: consecutive-or-later rows of ONE sequence in position order); wanted row j's choice is compared with
+// draft[j] (-1: not compared; always -1 on a group's last row).  n_accept[n_groups] and tokens[n_want] come back.  Greedy unless
+// forward() is also given sample_params (one record per wanted row).
+struct LlmVerifyArgs {
+  int n_groups = 0;
+  const int32_t* goff = nullptr;
+  const int32_t* draft = nullptr;
+  int32_t* n_accept = nullptr;
+  int32_t* tokens = nullptr;
 };
 
 struct LlmCachedCfg {
@@ -75,6 +88,7 @@ struct LlmCached {
   int max_want = 256;                            // wanted rows of one lm_head call (the scoring tail chunks by it, up to max_rows)
   int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
   float* d_nll = nullptr;                        // [max_rows]
+  int32_t *d_vdraft = nullptr, *d_vflag = nullptr, *d_vtok = nullptr, *d_vacc = nullptr;   // [max_want] the verify tail's drafts / flags / outputs
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
   // ---- beam search ----
@@ -135,7 +149,7 @@ struct LlmCached {
   int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
               const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out,
               const vstar_vqa_sampling* sample_params = nullptr, const LlmBeamArgs* beam = nullptr,
-              const LlmScoreArgs* score = nullptr);
+              const LlmScoreArgs* score = nullptr, const LlmVerifyArgs* verify = nullptr);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
   int kv_copy(int dst, int src, int lo, int hi);
 };
@@ -182,6 +196,10 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&d_nll, R));
   RC(e->dalloc(&d_argmax, (size_t)max_want));
   RC(e->dalloc(&d_sparams, (size_t)max_want));
+  RC(e->dalloc(&d_vdraft, (size_t)max_want));
+  RC(e->dalloc(&d_vflag, (size_t)max_want));
+  RC(e->dalloc(&d_vtok, (size_t)max_want));
+  RC(e->dalloc(&d_vacc, (size_t)max_want));
   {  // split-KV decode attention (decode.hip): scores / partials / tickets for steps of up to SPLIT_ROWS sequences, zeroed once
     const size_t wb = cached_attention_split_ws_bytes(SPLIT_ROWS, c.heads, c.max_ctx);
     RC(e->dalloc(&split_ws, wb));
@@ -408,13 +426,17 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
 inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                               uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params,
-                              const LlmBeamArgs* beam, const LlmScoreArgs* score) {
+                              const LlmBeamArgs* beam, const LlmScoreArgs* score, const LlmVerifyArgs* verify) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
   if (score) {             // the scoring tail chunks its wanted rows (LlmScoreArgs): its limit is max_rows, not max_want
-    if (sample_params || beam || logits_out || argmax_out) { e->set_error("forward_score: the scoring tail excludes the other outputs"); return VSTAR_ERR_INVALID; }
+    if (sample_params || beam || verify || logits_out || argmax_out) { e->set_error("forward_score: the scoring tail excludes the other outputs"); return VSTAR_ERR_INVALID; }
     if (n_want < 1 || !score->targets || !score->nll) { e->set_error("forward_score: no wanted rows / targets / outputs"); return VSTAR_ERR_INVALID; }
     if (n_want > c.max_rows) { e->set_error("forward_score: more wanted rows than max_rows"); return VSTAR_ERR_INVALID; }
+  }
+  if (verify) {            // the verify tail: greedy, or sampled with sample_params; no other tail, no logits / arg-max outputs
+    if (beam || score || logits_out || argmax_out) { e->set_error("forward_verify: the verify tail excludes the other tails and outputs"); return VSTAR_ERR_INVALID; }
+    if (n_want < 1 || !verify->goff || !verify->draft || !verify->n_accept || !verify->tokens) { e->set_error("forward_verify: no wanted rows / groups / drafts / outputs"); return VSTAR_ERR_INVALID; }
   }
   if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
       (!score && n_want > max_want) || (n_want && !want)) {
@@ -451,6 +473,22 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
     if (const char* m = vstar_beam_check(n_want, c.vocab, beam->scores, beam->n_groups, beam->goff, beam->n_cand)) {
       e->set_error(std::string("forward_beam: ") + m);
       return VSTAR_ERR_INVALID;
+    }
+  }
+  if (verify) {
+    if (const char* m = vstar_verify_check(n_want, c.vocab, verify->n_groups, verify->goff, verify->draft)) {
+      e->set_error(std::string("forward_verify: ") + m);
+      return VSTAR_ERR_INVALID;
+    }
+    // a group is one sequence's rows in position order: the prefix rule compares row j's choice with the token fed as a LATER row
+    for (int g = 0; g < verify->n_groups; ++g) {
+      int seq = 0;
+      while (row_off[seq + 1] <= want[verify->goff[g]]) ++seq;
+      for (int j = verify->goff[g]; j < verify->goff[g + 1]; ++j)
+        if (want[j] >= row_off[seq + 1] || (j > verify->goff[g] && want[j] <= want[j - 1])) {
+          e->set_error("forward_verify: the wanted rows of a group must be rows of one sequence in position order");
+          return VSTAR_ERR_INVALID;
+        }
     }
   }
   if (score)
@@ -522,6 +560,10 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
     LCHK(hipMemcpyAsync(d_bscore, beam->scores, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
     LCHK(hipMemcpyAsync(d_goff, beam->goff, (size_t)(beam->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
   }
+  if (verify) {
+    LCHK(hipMemcpyAsync(d_goff, verify->goff, (size_t)(verify->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    LCHK(hipMemcpyAsync(d_vdraft, verify->draft, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+  }
   if (score) LCHK(hipMemcpyAsync(d_starget, score->targets, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
@@ -548,7 +590,16 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   } else if (n_want) {
     LCHK(gather_rows(lx, d_want, wsel, n_want, H, e->stream));
     RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, n_want, VSTAR_EPI_NONE));
-    if (beam) {            // the beam-search tail (beam.hip) in place of the arg-max: each group's n_cand best candidates
+    if (verify) {          // the verify tail (spec.hip) in place of the arg-max: per group the accepted count, per row the token
+      const vstar_vqa_sampling* vp = sample_params ? d_sparams : nullptr;
+#ifdef VSTAR_LP_F16
+      LCHK(vstar_verify_rows_f16(logits, n_want, c.vocab, (int64_t)vpad, d_goff, verify->n_groups, d_vdraft, vp, d_argmax, d_vflag,
+                                 d_vacc, d_vtok, e->stream));
+#else
+      LCHK(vstar_verify_rows_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_goff, verify->n_groups, d_vdraft, vp, d_argmax, d_vflag,
+                                  d_vacc, d_vtok, e->stream));
+#endif
+    } else if (beam) {     // the beam-search tail (beam.hip) in place of the arg-max: each group's n_cand best candidates
 #ifdef VSTAR_LP_F16
       LCHK(vstar_beam_select_f16(logits, n_want, c.vocab, (int64_t)vpad, d_bscore, beam->n_groups, d_goff, beam->n_cand, beam_ws,
                                  d_cand_s, d_cand_t, d_cand_r, nullptr, e->stream));
@@ -571,6 +622,10 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
     LCHK(hipMemcpy2DAsync(logits_out, (size_t)c.vocab * 2, logits, vpad * 2, (size_t)c.vocab * 2, n_want,
                             hipMemcpyDeviceToHost, e->stream));
   if (n_want && argmax_out && !beam && !score) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  if (verify) {
+    LCHK(hipMemcpyAsync(verify->n_accept, d_vacc, (size_t)verify->n_groups * 4, hipMemcpyDeviceToHost, e->stream));
+    LCHK(hipMemcpyAsync(verify->tokens, d_vtok, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+  }
   if (score) {
     LCHK(hipMemcpyAsync(score->nll, d_nll, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
     if (score->rank) LCHK(hipMemcpyAsync(score->rank, d_srank, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));

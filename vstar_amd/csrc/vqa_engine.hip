@@ -405,6 +405,68 @@ int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, i
   return VSTAR_OK;
 }
 
+int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                             int32_t* n_accept_out, int32_t* tokens_out) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (!group_off || !draft || !n_accept_out || !tokens_out) {
+    h->set_error("forward_verify: group_off, draft and the outputs are required");
+    return VSTAR_ERR_INVALID;
+  }
+  LlmVerifyArgs v;
+  v.n_groups = n_groups; v.goff = group_off; v.draft = draft; v.n_accept = n_accept_out; v.tokens = tokens_out;
+  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, nullptr, params, nullptr, nullptr, &v);
+}
+
+int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
+                        const int32_t* draft, const vstar_vqa_sampling* params, int32_t* n_accept_out, int32_t* tokens_out) {
+  if (!dev_logits || !n_accept_out || !tokens_out || rows > 65535 || ld < vocab || (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_verify: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_verify_check(rows, vocab, n_groups, group_off, draft)) {
+    tls_error() = std::string("vstar_vqa_op_verify: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
+  if (params)
+    for (int r = 0; r < rows; ++r)
+      if (!vstar_sample_params_valid(params[r])) {
+        tls_error() = "vstar_vqa_op_verify: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
+        return VSTAR_ERR_INVALID;
+      }
+  vstar_vqa_sampling* d_p = nullptr;
+  int32_t *d_go = nullptr, *d_dr = nullptr, *d_ch = nullptr, *d_fl = nullptr, *d_ac = nullptr, *d_tok = nullptr;
+  hipError_t e = hipMalloc(&d_go, (size_t)(n_groups + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_dr, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_ch, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_fl, (size_t)rows * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_ac, (size_t)n_groups * 4);
+  if (e == hipSuccess) e = hipMalloc(&d_tok, (size_t)rows * 4);
+  if (e == hipSuccess && params) e = hipMalloc(&d_p, (size_t)rows * sizeof(vstar_vqa_sampling));
+  if (e == hipSuccess) e = hipMemcpy(d_go, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_dr, draft, (size_t)rows * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && params) e = hipMemcpy(d_p, params, (size_t)rows * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = dtype == VSTAR_F16 ? vstar_verify_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p, d_ch, d_fl,
+                                                   d_ac, d_tok, nullptr)
+                           : vstar_verify_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p, d_ch,
+                                                    d_fl, d_ac, d_tok, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(n_accept_out, d_ac, (size_t)n_groups * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(tokens_out, d_tok, (size_t)rows * 4, hipMemcpyDeviceToHost);
+  hipFree(d_go);
+  hipFree(d_dr);
+  hipFree(d_ch);
+  hipFree(d_fl);
+  hipFree(d_ac);
+  hipFree(d_tok);
+  if (d_p) hipFree(d_p);
+  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_verify: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
+  return VSTAR_OK;
+}
+
 int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
                         int32_t* tokens, float* u_out, int32_t* n_kept) {
   if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||

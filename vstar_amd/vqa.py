@@ -87,6 +87,13 @@ def sampling_params(temperature: float, top_k: Optional[int] = 50, top_p: Option
                        step=step & 0xffffffff, seed=int(seed) & mask, stream=int(stream) & mask)
 
 
+def check_spec_tokens(d) -> int:
+    """The draft length of a speculative decode: an integer in [0, 15] (0 = off)."""
+    if isinstance(d, bool) or int(d) != d or not 0 <= int(d) <= 15:
+        raise ValueError(f"the number of speculative draft tokens must be an integer in [0, 15], got {d!r}")
+    return int(d)
+
+
 def _with_step(p: VqaSampling, step: int) -> VqaSampling:
     return VqaSampling(temperature=p.temperature, top_k=p.top_k, top_p=p.top_p, step=step & 0xffffffff, seed=p.seed,
                        stream=p.stream)
@@ -151,6 +158,7 @@ class VQA_LLM:
         self.engine = engine
         self.model = SimpleNamespace(config=SimpleNamespace(vocab_size=self.cfg.llm_vocab))
         self.eos_token_id = getattr(self.tokenizer, "eos_token_id", 2)
+        self.spec_stats: Dict[str, int] = {}       # counters of the last speculative_decode (empty until one has run)
 
     # ---- vstar_bench_eval.py:49-77 ----
     def get_patch(self, bbox, image_width, image_height, patch_size=224, patch_scale=None):
@@ -192,25 +200,33 @@ class VQA_LLM:
 
     # ---- free-form answer (vstar_bench_eval.py:78-113) ----
     def free_form_inference(self, image, question, temperature=0, top_p=None, num_beams=1, max_new_tokens=200,
-                            object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None) -> str:
+                            object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None, speculative=0,
+                            draft_fn=None) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
         so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
-        4.31 beam search; beam sampling (num_beams > 1 with temperature > 0) is not implemented."""
+        4.31 beam search; beam sampling (num_beams > 1 with temperature > 0) is not implemented.
+        speculative = d > 0: speculative decoding with up to d (<= 15) draft tokens per step from `draft_fn` (default: prompt
+        lookup, vstar_amd/spec.py), greedy or sampled; 0 is the plain decode."""
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
                                           objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
-                                    top_k=top_k, seed=seed, num_beams=num_beams)[0]
+                                    top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
-                        seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False) -> List[str]:
+                        seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, speculative: int = 0,
+                        draft_fn=None) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
         single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
-        i*k .. i*k+k-1 (n*k <= max_slots), one group per sample in every step's forward."""
+        i*k .. i*k+k-1 (n*k <= max_slots), one group per sample in every step's forward.  speculative = d > 0 (num_beams 1):
+        `speculative_decode` with up to d drafts per sequence and step; 0 (default) is the plain path."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if num_beams < 1:
             raise ValueError(f"num_beams must be >= 1, got {num_beams}")
+        speculative = check_spec_tokens(speculative)
+        if speculative and num_beams > 1:
+            raise ValueError("speculative decoding (speculative > 0) cannot be combined with beam search (num_beams > 1)")
         if num_beams > 1 and temperature > 0:
             raise NotImplementedError("beam sampling (num_beams > 1 with temperature > 0) is not implemented")
         if n * num_beams > cfg.max_slots:
@@ -221,7 +237,7 @@ class VQA_LLM:
         if temperature > 0:
             base = resolve_seed(seed)
             params = [sampling_params(temperature, top_k, top_p, s.get("seed", base + i)) for i, s in enumerate(samples)]
-        seqs, lens, id_lens = [], [], []
+        seqs, lens, id_lens, text_ids = [], [], [], []
         fslot = 0
         for i, s in enumerate(samples):
             crops = s.get("object_crops")
@@ -231,7 +247,11 @@ class VQA_LLM:
             seqs.append(Seq(rows, kv_slot=i * num_beams))
             lens.append(len(rows))
             id_lens.append(len(ids))
-        if num_beams > 1:
+            text_ids.append([t for t in ids if t >= 0])
+        if speculative:
+            self.generated_ids = self.speculative_decode(seqs, lens, text_ids, max_new_tokens, speculative,
+                                                         params if temperature > 0 else None, draft_fn)
+        elif num_beams > 1:
             outs = self.beam_decode(seqs, lens, id_lens, max_new_tokens, num_beams, length_penalty, early_stopping)
             self.generated_ids = [o[0] for o in outs]
         elif temperature > 0:
@@ -256,6 +276,71 @@ class VQA_LLM:
         def choose(step, want, idx, t):
             return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx])
         return self._decode(seqs, lens, max_new_tokens, choose)
+
+    def speculative_decode(self, seqs: Sequence[Seq], lens: Sequence[int], ids: Sequence[Sequence[int]], max_new_tokens: int,
+                           d: int, params=None, draft_fn=None) -> List[List[int]]:
+        """Speculative decoding: greedy (params None) or sampled (params[i] drives sequence i as in
+        `sample_decode`).  ids[i]: the un-expanded text ids of sequence i (placeholders left out) — what the drafter sees, with
+        the generated tokens appended.  Every engine call feeds each live sequence the rows [cur, draft_0 .. draft_{k-1}] at
+        past_len = pos, k <= d drafts from draft_fn (default `spec.prompt_lookup_draft`); the verify tail returns the accepted
+        count a and a + 1 tokens, and pos += a + 1.  The rows of rejected drafts stay in the cache behind pos and are overwritten
+        by the next call.  k is cut so that the sequence's context, the call's rows (max_rows, 256 wanted rows) and
+        max_new_tokens are respected.  The tokens are those of the logits of the verify forward: greedy picks their arg-max,
+        sampled draws follow their kept distribution.  self.spec_stats = calls / drafted / accepted / tokens of this run."""
+        from .spec import prompt_lookup_draft
+        cfg, eng = self.cfg, self.engine
+        d = check_spec_tokens(d)
+        draft_fn = draft_fn or prompt_lookup_draft
+        n = len(seqs)
+        want0 = [(i, -1) for i in range(n)]
+        if params is None:
+            first = eng.forward(seqs, want0, logits=False)[1]
+        else:
+            first = eng.forward_sample(seqs, want0, [_with_step(params[i], 0) for i in range(n)])
+        stats = dict(calls=1, drafted=0, accepted=0, tokens=0)
+        out: List[List[int]] = [[int(first[i])] for i in range(n)]
+        pos = list(lens)
+        row_cap = min(cfg.max_rows, 256)
+
+        def alive(i):       # the stop rule of _decode: EOS, the token budget, or a full context
+            return out[i][-1] != self.eos_token_id and len(out[i]) < max_new_tokens and pos[i] + 1 < cfg.max_ctx
+
+        live = [i for i in range(n) if alive(i)]
+        while live:
+            spare = row_cap - len(live)                 # rows left for drafts once every live sequence has its current token
+            step, wanted, groups, draft, prm = [], [], [0], [], []
+            for j, i in enumerate(live):
+                k = min(d, max_new_tokens - len(out[i]) - 1, cfg.max_ctx - pos[i] - 2, max(spare, 0))
+                guess: List[int] = []
+                if k > 0:
+                    for t in list(draft_fn(list(ids[i]) + out[i], k))[:k]:
+                        t = int(t)
+                        if not 0 <= t < cfg.llm_vocab:   # a drafter's id the model does not have: the draft ends there
+                            break
+                        guess.append(t)
+                spare -= len(guess)
+                rows = [out[i][-1]] + guess
+                step.append(Seq(rows, kv_slot=seqs[i].kv_slot, past_len=pos[i]))
+                wanted += [(j, r) for r in range(len(rows))]
+                groups.append(groups[-1] + len(rows))
+                draft += guess + [-1]
+                if params is not None:
+                    prm += [_with_step(params[i], len(out[i]) + r) for r in range(len(rows))]
+                stats["drafted"] += len(guess)
+            acc, tok = eng.forward_verify(step, wanted, groups, draft, prm if params is not None else None)
+            stats["calls"] += 1
+            for j, i in enumerate(live):
+                a = int(acc[j])
+                new = [int(t) for t in tok[groups[j]:groups[j] + a + 1]]
+                stats["accepted"] += a
+                pos[i] += a + 1
+                if self.eos_token_id in new:            # the sequence ends at its first EOS
+                    new = new[:new.index(self.eos_token_id) + 1]
+                out[i] += new
+            live = [i for i in live if alive(i)]
+        stats["tokens"] = sum(len(o) for o in out)
+        self.spec_stats = stats
+        return out
 
     def beam_decode(self, seqs: Sequence[Seq], lens: Sequence[int], id_lens: Sequence[int], max_new_tokens: int, num_beams: int,
                     length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1) -> List[List[List[int]]]:

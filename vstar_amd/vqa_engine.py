@@ -179,6 +179,32 @@ class VqaEngine:
         _lib.check_vqa(self.lib.vstar_vqa_forward_score(self.handle, *args, _ptr(tg), _ptr(nll), _ptr(rk)), self.handle)
         return (nll[:nw], rk[:nw]) if rank else nll[:nw]
 
+    def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None):
+        """`forward` with the arg-max replaced by the on-device verify tail of speculative decoding (csrc/spec.hip, DESIGN.md
+        §8.5): wanted rows groups[g] .. groups[g+1]-1 are the rows of one sequence in position order (its current token and the
+        drafts fed behind it), draft[j] the token wanted row j's choice is compared with (-1 on a group's last row).  params:
+        None = greedy, else one `_lib.VqaSampling` per wanted row (or one record for all).  Returns (n_accept int32 [n_groups],
+        tokens int32 [n_want]): per group the accepted drafts and one more token, -1 behind them."""
+        args, _keep = self._rows_args(step, wanted)
+        nw = args[6]
+        go = np.ascontiguousarray(groups, np.int32)
+        dr = np.ascontiguousarray(draft, np.int32)
+        if dr.shape != (nw,):
+            raise ValueError(f"{dr.size} draft entries for {nw} wanted rows")
+        ng = max(len(go) - 1, 0)
+        prm = None
+        if params is not None:
+            if isinstance(params, _lib.VqaSampling):
+                params = [params] * nw
+            if len(params) != nw:
+                raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
+            prm = (_lib.VqaSampling * max(nw, 1))(*params)
+        acc = np.empty((max(ng, 1),), np.int32)
+        tok = np.empty((max(nw, 1),), np.int32)
+        _lib.check_vqa(self.lib.vstar_vqa_forward_verify(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None,
+                                                         _ptr(go), ng, _ptr(dr), _ptr(acc), _ptr(tok)), self.handle)
+        return acc[:ng], tok[:nw]
+
     def kv_reorder(self, dst_slots: Sequence[int], src_slots: Sequence[int], lo: int, hi: int) -> None:
         """Beam reorder without moving K/V: ancestry entries [lo, hi) of dst_slots[i] = those of src_slots[i], all sources read
         before any destination is written (include/vstar_vqa.h)."""

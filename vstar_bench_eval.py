@@ -33,6 +33,9 @@ def parse_args(argv):
                    "option-ranking passes (free_form_batch / multiple_choices_batch, option losses reduced on the device); 1 = one "
                    "question at a time like the reference.  The free-form pass sends at most min(N, max_slots, max_images) questions per call; the "
                    "option-ranking pass splits a batch by itself when it exceeds max_slots / max_images / max_rows")
+    p.add_argument("--vqa-spec-tokens", dest="vqa_spec_tokens", default=0, type=int, help="d > 0 (<= 15): the free-form pass decodes "
+                   "speculatively with up to d prompt-lookup draft tokens per step (DESIGN.md 8.5; 3 keeps every kernel of a one-row "
+                   "step at 7B); 0 = the plain greedy decode")
     p.add_argument("--engine-comm", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="world > 1 on GPUs: gather the per-step records with the C-ABI's own RCCL communicator on the engine stream "
                    "(vstar_allgather_results) instead of torch.distributed.  auto (default, round 6): used when the communicator comes up "
