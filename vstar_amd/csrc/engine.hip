@@ -1173,7 +1173,8 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
     else rows.push_back(ids[i]);
   }
   int32_t row_off[2] = {0, (int32_t)rows.size()}, slot = 0, past = 0, want = (int32_t)rows.size() - 1, nxt = 0;
-  RC(gen.forward(1, row_off, rows.data(), &slot, &slot, &past, 1, &want, nullptr, &nxt));
+  const LlmTail greedy = LlmTail::argmax(nullptr, &nxt);
+  RC(gen.forward(LlmRows{1, row_off, rows.data(), &slot, &slot, &past, 1, &want}, greedy));
   int n = 0;
   past = (int32_t)rows.size();
   {
@@ -1187,7 +1188,7 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
     out_ids[n++] = nxt;
     if (nxt == eos_id || n >= max_new) break;
     int32_t one_off[2] = {0, 1}, w0 = 0, tok = nxt;
-    RC(gen.forward(1, one_off, &tok, &slot, &slot, &past, 1, &w0, nullptr, &nxt));
+    RC(gen.forward(LlmRows{1, one_off, &tok, &slot, &slot, &past, 1, &w0}, greedy));
     ++past;
   }
   *n_out = n;

@@ -10,12 +10,19 @@
 //     straight out of the KV cache with an optional shared prefix slot.
 #pragma once
 #include "engine_base.hpp"
-#include "sample.hpp"
-#include "beam.hpp"
-#include "score.hpp"
-#include "spec.hpp"
+#include <array>
+#include "tails_lp.hpp"
 
 namespace VS_NS {
+
+// The new rows of one forward() call: the eight row arguments of vstar_vqa_forward, documented there (include/vstar_vqa.h);
+// host arrays.
+struct LlmRows {
+  int nseq = 0;
+  const int32_t *row_off = nullptr, *src = nullptr, *kv_slot = nullptr, *prefix_slot = nullptr, *past_len = nullptr;
+  int n_want = 0;
+  const int32_t* want = nullptr;
+};
 
 // The beam-search tail of forward() (beam.hip): host arrays.  The wanted rows carry scores[n_want] and form
 // n_groups groups (rows goff[g] .. goff[g+1]-1 of `want`); each group's n_cand best (score, token, row in group) come back.
@@ -44,13 +51,35 @@ struct LlmScoreArgs {
 // The verify tail of forward() (spec.hip): host arrays.  The wanted rows form n_groups groups (rows goff[g] ..
 // goff[g+1]-1 of `want`: consecutive-or-later rows of ONE sequence in position order); wanted row j's choice is compared with
 // draft[j] (-1: not compared; always -1 on a group's last row).  n_accept[n_groups] and tokens[n_want] come back.  Greedy unless
-// forward() is also given sample_params (one record per wanted row).
+// the tail also carries sampling records (one per wanted row).
 struct LlmVerifyArgs {
   int n_groups = 0;
   const int32_t* goff = nullptr;
   const int32_t* draft = nullptr;
   int32_t* n_accept = nullptr;
   int32_t* tokens = nullptr;
+};
+
+struct LlmCached;
+
+// What forward() does with the wanted rows' logits: exactly one of the five tails, built by the function of its name — so a call
+// cannot ask for two tails, or for a tail together with an output that tail does not have.
+struct LlmTail {
+  enum Kind { ARGMAX, SAMPLE, BEAM, SCORE, VERIFY };
+  static LlmTail argmax(uint16_t* logits_out, int32_t* argmax_out) { LlmTail t; t.logits_out = logits_out; t.tokens_out = argmax_out; return t; }
+  static LlmTail sample(const vstar_vqa_sampling* params, int32_t* tokens) { LlmTail t; t.kind = SAMPLE; t.params = params; t.tokens_out = tokens; return t; }
+  static LlmTail beam_select(const LlmBeamArgs& b, uint16_t* logits_out) { LlmTail t; t.kind = BEAM; t.beam = b; t.logits_out = logits_out; return t; }
+  static LlmTail score_rows(const LlmScoreArgs& sc) { LlmTail t; t.kind = SCORE; t.score = sc; return t; }
+  static LlmTail verify_rows(const LlmVerifyArgs& v, const vstar_vqa_sampling* params) { LlmTail t; t.kind = VERIFY; t.verify = v; t.params = params; return t; }
+
+ private:      // only the five functions above fill these, only LlmCached reads them
+  friend struct LlmCached;
+  LlmTail() = default;
+  Kind kind = ARGMAX;
+  uint16_t* logits_out = nullptr;                // ARGMAX, BEAM (nullable): the wanted rows' logits [n_want, vocab]
+  int32_t* tokens_out = nullptr;                 // ARGMAX (nullable): the arg-max; SAMPLE: the drawn tokens (sample.hip)
+  const vstar_vqa_sampling* params = nullptr;    // SAMPLE; VERIFY (nullable: greedy): one record per wanted row
+  LlmBeamArgs beam; LlmScoreArgs score; LlmVerifyArgs verify;      // the kind's own host arrays
 };
 
 struct LlmCachedCfg {
@@ -84,7 +113,7 @@ struct LlmCached {
   lp_t *wsel = nullptr, *wnorm = nullptr, *logits = nullptr;
   int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_seq = nullptr, *d_want = nullptr,
           *d_argmax = nullptr;
-  vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of forward(..., sample_params)
+  vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of the SAMPLE and sampled VERIFY tails
   int max_want = 256;                            // wanted rows of one lm_head call (the scoring tail chunks by it, up to max_rows)
   int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
   float* d_nll = nullptr;                        // [max_rows]
@@ -146,10 +175,14 @@ struct LlmCached {
                const lp_t* Wt = nullptr, const LinW8* q8 = nullptr);
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
-  int forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot, const int32_t* prefix_slot,
-              const int32_t* past_len, int n_want, const int32_t* want, uint16_t* logits_out, int32_t* argmax_out,
-              const vstar_vqa_sampling* sample_params = nullptr, const LlmBeamArgs* beam = nullptr,
-              const LlmScoreArgs* score = nullptr, const LlmVerifyArgs* verify = nullptr);
+  // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
+  struct TailCopy { void* dev = nullptr; const void* in = nullptr; void* out = nullptr; size_t bytes = 0; };
+  size_t vpad() const { return (size_t)(cfg.vocab + 255) / 256 * 256; }      // row stride of the logits buffer
+  int forward(const LlmRows& rw, const LlmTail& tail);
+  int head(int w0, int m);
+  int tail_check(const LlmRows& r, const LlmTail& t);
+  std::array<TailCopy, 5> tail_copies(const LlmTail& t, int n_want);
+  int tail_launch(const LlmTail& t, int w0, int m);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
   int kv_copy(int dst, int src, int lo, int hi);
 };
@@ -181,10 +214,9 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&lqkv, R * 3 * H));
   RC(e->dalloc(&latt, R * H));
   RC(e->dalloc(&lact, R * c.mlp));
-  const size_t vpad = (size_t)(c.vocab + 255) / 256 * 256;
   RC(e->dalloc(&wsel, (size_t)max_want * H));
   RC(e->dalloc(&wnorm, (size_t)max_want * H));
-  RC(e->dalloc(&logits, (size_t)max_want * vpad));
+  RC(e->dalloc(&logits, (size_t)max_want * vpad()));
   RC(e->dalloc(&d_src, R));
   RC(e->dalloc(&d_row_pos, R));
   RC(e->dalloc(&d_row_slot, R));
@@ -423,28 +455,110 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
   return 0;
 }
 
-inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
-                              const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
-                              uint16_t* logits_out, int32_t* argmax_out, const vstar_vqa_sampling* sample_params,
-                              const LlmBeamArgs* beam, const LlmScoreArgs* score, const LlmVerifyArgs* verify) {
+// model.norm + lm_head (llava_search_llama.py:92-93) on wanted rows [w0, w0 + m), m <= max_want, into rows [0, m) of the one
+// [max_want, vpad] logits buffer; lm_head sees m rows (its row count selects the GEMM kernel)
+inline int LlmCached::head(int w0, int m) {
+  LCHK(gather_rows(lx, d_want + w0, wsel, m, cfg.hidden, e->stream));
+  return lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad(), m, VSTAR_EPI_NONE);
+}
+
+// ---- the five tails, one switch per stage: checks, host <-> device copies, launch ----
+// (forward() validates the rows first, then the tail: of two simultaneous faults the row fault is the one reported)
+inline int LlmCached::tail_check(const LlmRows& r, const LlmTail& t) {
+  const int n_want = r.n_want, V = cfg.vocab;
+  if (t.params && !vstar_sample_params_valid(t.params, n_want)) {
+    e->set_error("sampling parameters: temperature must be > 0 and finite, top_k >= 0, top_p >= 0");
+    return VSTAR_ERR_INVALID;
+  }
+  const char* m = nullptr;
+  switch (t.kind) {
+    default: break;            // ARGMAX, SAMPLE: nothing of their own
+    case LlmTail::BEAM:
+      if (n_want < 1 || !t.beam.cand_s || !t.beam.cand_tok || !t.beam.cand_row) { e->set_error("forward_beam: no wanted rows / outputs"); return VSTAR_ERR_INVALID; }
+      if ((m = vstar_beam_check(n_want, V, t.beam.scores, t.beam.n_groups, t.beam.goff, t.beam.n_cand))) { e->set_error(std::string("forward_beam: ") + m); return VSTAR_ERR_INVALID; }
+      break;
+    case LlmTail::SCORE:       // this tail chunks its wanted rows (CHUNKING RULE): its limit is max_rows, not max_want
+      if (n_want < 1 || !t.score.targets || !t.score.nll) { e->set_error("forward_score: no wanted rows / targets / outputs"); return VSTAR_ERR_INVALID; }
+      if (n_want > cfg.max_rows) { e->set_error("forward_score: more wanted rows than max_rows"); return VSTAR_ERR_INVALID; }
+      if ((m = vstar_score_check(n_want, V, t.score.targets))) { e->set_error(std::string("forward_score: ") + m); return VSTAR_ERR_INVALID; }
+      break;
+    case LlmTail::VERIFY: {
+      const LlmVerifyArgs& v = t.verify;
+      if (n_want < 1 || !v.goff || !v.draft || !v.n_accept || !v.tokens) { e->set_error("forward_verify: no wanted rows / groups / drafts / outputs"); return VSTAR_ERR_INVALID; }
+      if ((m = vstar_verify_check(n_want, V, v.n_groups, v.goff, v.draft))) { e->set_error(std::string("forward_verify: ") + m); return VSTAR_ERR_INVALID; }
+      // a group is one sequence's rows in position order: the prefix rule compares row j's choice with the token fed as a LATER row
+      for (int g = 0; g < v.n_groups; ++g) {
+        int seq = 0;
+        while (r.row_off[seq + 1] <= r.want[v.goff[g]]) ++seq;
+        for (int j = v.goff[g]; j < v.goff[g + 1]; ++j)
+          if (r.want[j] >= r.row_off[seq + 1] || (j > v.goff[g] && r.want[j] <= r.want[j - 1])) {
+            e->set_error("forward_verify: the wanted rows of a group must be rows of one sequence in position order");
+            return VSTAR_ERR_INVALID;
+          }
+      }
+      break;
+    }
+  }
+  return 0;
+}
+
+// A tail's copies, in stream order: uploads (`in`, host -> dev) go out with the row metadata before the layers, downloads (dev ->
+// `out`, host) behind the tail.  An entry whose host pointer is null (an output the caller did not ask for, greedy verify's
+// params, the unused entries of the array) or that has zero bytes is no copy.
+inline std::array<LlmCached::TailCopy, 5> LlmCached::tail_copies(const LlmTail& t, int n_want) {
+  const size_t nw4 = (size_t)n_want * 4, np = (size_t)n_want * sizeof(vstar_vqa_sampling);
+  const LlmBeamArgs& b = t.beam;
+  const LlmVerifyArgs& v = t.verify;
+  const size_t nc4 = (size_t)b.n_groups * b.n_cand * 4;
+  switch (t.kind) {
+    case LlmTail::ARGMAX: return {{{d_argmax, nullptr, t.tokens_out, nw4}}};
+    case LlmTail::SAMPLE: return {{{d_sparams, t.params, nullptr, np}, {d_argmax, nullptr, t.tokens_out, nw4}}};
+    case LlmTail::BEAM:
+      return {{{d_bscore, b.scores, nullptr, nw4}, {d_goff, b.goff, nullptr, (size_t)(b.n_groups + 1) * 4},
+               {d_cand_s, nullptr, b.cand_s, nc4}, {d_cand_t, nullptr, b.cand_tok, nc4}, {d_cand_r, nullptr, b.cand_row, nc4}}};
+    case LlmTail::SCORE: return {{{d_starget, t.score.targets, nullptr, nw4}, {d_nll, nullptr, t.score.nll, nw4}, {d_srank, nullptr, t.score.rank, nw4}}};
+    case LlmTail::VERIFY:
+      return {{{d_sparams, t.params, nullptr, np}, {d_goff, v.goff, nullptr, (size_t)(v.n_groups + 1) * 4}, {d_vdraft, v.draft, nullptr, nw4},
+               {d_vacc, nullptr, v.n_accept, (size_t)v.n_groups * 4}, {d_vtok, nullptr, v.tokens, nw4}}};
+  }
+  return {};
+}
+
+// the tail's kernel(s) on rows [0, m) of the logits buffer = wanted rows [w0, w0 + m) (w0 > 0: the scoring tail's later chunks)
+inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
+  const int V = cfg.vocab;
+  const int64_t ld = (int64_t)vpad();
+  switch (t.kind) {
+    case LlmTail::ARGMAX: LCHK(argmax_rows_lp(logits, m, V, ld, d_argmax, e->stream)); break;
+    case LlmTail::SAMPLE:      // d_argmax receives the drawn tokens
+      LCHK(vstar_sample_rows_lp(logits, m, V, ld, d_sparams, d_argmax, nullptr, nullptr, e->stream));
+      break;
+    case LlmTail::BEAM:        // each group's n_cand best candidates
+      LCHK(vstar_beam_select_lp(logits, m, V, ld, d_bscore, t.beam.n_groups, d_goff, t.beam.n_cand, beam_ws, d_cand_s, d_cand_t, d_cand_r,
+                                nullptr, e->stream));
+      break;
+    case LlmTail::SCORE:       // only nll / rank leave
+      LCHK(vstar_score_rows_lp(logits, m, V, ld, d_starget + w0, d_nll + w0, t.score.rank ? d_srank + w0 : nullptr, nullptr, e->stream));
+      break;
+    case LlmTail::VERIFY:      // per group the accepted count, per row the token; d_argmax / d_vflag are its scratch
+      LCHK(vstar_verify_rows_lp(logits, m, V, ld, d_goff, t.verify.n_groups, d_vdraft, t.params ? d_sparams : nullptr, d_argmax, d_vflag,
+                                d_vacc, d_vtok, e->stream));
+      break;
+  }
+  return 0;
+}
+
+inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
-  if (score) {             // the scoring tail chunks its wanted rows (LlmScoreArgs): its limit is max_rows, not max_want
-    if (sample_params || beam || verify || logits_out || argmax_out) { e->set_error("forward_score: the scoring tail excludes the other outputs"); return VSTAR_ERR_INVALID; }
-    if (n_want < 1 || !score->targets || !score->nll) { e->set_error("forward_score: no wanted rows / targets / outputs"); return VSTAR_ERR_INVALID; }
-    if (n_want > c.max_rows) { e->set_error("forward_score: more wanted rows than max_rows"); return VSTAR_ERR_INVALID; }
-  }
-  if (verify) {            // the verify tail: greedy, or sampled with sample_params; no other tail, no logits / arg-max outputs
-    if (beam || score || logits_out || argmax_out) { e->set_error("forward_verify: the verify tail excludes the other tails and outputs"); return VSTAR_ERR_INVALID; }
-    if (n_want < 1 || !verify->goff || !verify->draft || !verify->n_accept || !verify->tokens) { e->set_error("forward_verify: no wanted rows / groups / drafts / outputs"); return VSTAR_ERR_INVALID; }
-  }
+  const int nseq = rw.nseq, n_want = rw.n_want;
+  const int32_t *row_off = rw.row_off, *src = rw.src, *kv_slot = rw.kv_slot, *prefix_slot = rw.prefix_slot, *past_len = rw.past_len, *want = rw.want;
   if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
-      (!score && n_want > max_want) || (n_want && !want)) {
+      (tail.kind != LlmTail::SCORE && n_want > max_want) || (n_want && !want)) {
     e->set_error("llm forward: bad argument");
     return VSTAR_ERR_INVALID;
   }
   LCHK(hipSetDevice(e->device));
-  const int H = c.hidden;
   const int R = row_off[nseq];
   int maxT = 0, max_keys = 0;
   bool all_fresh = true;
@@ -462,40 +576,7 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   }
   for (int j = 0; j < n_want; ++j)
     if (want[j] < 0 || want[j] >= R) { e->set_error("want row out of range"); return VSTAR_ERR_INVALID; }
-  if (sample_params)
-    for (int j = 0; j < n_want; ++j)
-      if (!vstar_sample_params_valid(sample_params[j])) {
-        e->set_error("sampling parameters: temperature must be > 0 and finite, top_k >= 0, top_p >= 0");
-        return VSTAR_ERR_INVALID;
-      }
-  if (beam) {
-    if (n_want < 1 || !beam->cand_s || !beam->cand_tok || !beam->cand_row) { e->set_error("forward_beam: no wanted rows / outputs"); return VSTAR_ERR_INVALID; }
-    if (const char* m = vstar_beam_check(n_want, c.vocab, beam->scores, beam->n_groups, beam->goff, beam->n_cand)) {
-      e->set_error(std::string("forward_beam: ") + m);
-      return VSTAR_ERR_INVALID;
-    }
-  }
-  if (verify) {
-    if (const char* m = vstar_verify_check(n_want, c.vocab, verify->n_groups, verify->goff, verify->draft)) {
-      e->set_error(std::string("forward_verify: ") + m);
-      return VSTAR_ERR_INVALID;
-    }
-    // a group is one sequence's rows in position order: the prefix rule compares row j's choice with the token fed as a LATER row
-    for (int g = 0; g < verify->n_groups; ++g) {
-      int seq = 0;
-      while (row_off[seq + 1] <= want[verify->goff[g]]) ++seq;
-      for (int j = verify->goff[g]; j < verify->goff[g + 1]; ++j)
-        if (want[j] >= row_off[seq + 1] || (j > verify->goff[g] && want[j] <= want[j - 1])) {
-          e->set_error("forward_verify: the wanted rows of a group must be rows of one sequence in position order");
-          return VSTAR_ERR_INVALID;
-        }
-    }
-  }
-  if (score)
-    if (const char* m = vstar_score_check(n_want, c.vocab, score->targets)) {
-      e->set_error(std::string("forward_score: ") + m);
-      return VSTAR_ERR_INVALID;
-    }
+  RC(tail_check(rw, tail));
   // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
   bool use_anc = false;
   for (int i = 0; i < nseq; ++i) {
@@ -554,88 +635,28 @@ inline int LlmCached::forward(int nseq, const int32_t* row_off, const int32_t* s
   LCHK(hipMemcpyAsync(d_row_seq, h_seq.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_seq, h_seqmeta.data(), h_seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
   if (n_want) LCHK(hipMemcpyAsync(d_want, h_want.data(), (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
-  if (n_want && sample_params)
-    LCHK(hipMemcpyAsync(d_sparams, sample_params, (size_t)n_want * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice, e->stream));
-  if (beam) {
-    LCHK(hipMemcpyAsync(d_bscore, beam->scores, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
-    LCHK(hipMemcpyAsync(d_goff, beam->goff, (size_t)(beam->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  }
-  if (verify) {
-    LCHK(hipMemcpyAsync(d_goff, verify->goff, (size_t)(verify->n_groups + 1) * 4, hipMemcpyHostToDevice, e->stream));
-    LCHK(hipMemcpyAsync(d_vdraft, verify->draft, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
-  }
-  if (score) LCHK(hipMemcpyAsync(d_starget, score->targets, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+  const std::array<TailCopy, 5> copies = tail_copies(tail, n_want);
+  for (const TailCopy& x : copies)
+    if (x.in && x.bytes) LCHK(hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
-  LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, rows, H, e->stream));
+  LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, rows, c.hidden, e->stream));
   if (use_anc) LCHK(kv_anc_mark(d_row_slot, d_row_pos, rows, d_anc, c.max_ctx, e->stream));   // the new rows live in their own slot
   if (prefill) RC(llm_layers_prefill(nseq, maxT));
   else RC(llm_layers_cached(rows, nseq, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
-  // ---- model.norm + lm_head on the wanted rows (llava_search_llama.py:92-93) ----
-  const size_t vpad = (size_t)(c.vocab + 255) / 256 * 256;
-  if (score) {             // the scoring tail (score.hip), chunked by max_want wanted rows (LlmScoreArgs): only nll / rank leave
-    for (int c0 = 0; c0 < n_want; c0 += max_want) {
-      const int m = n_want - c0 < max_want ? n_want - c0 : max_want;
-      LCHK(gather_rows(lx, d_want + c0, wsel, m, H, e->stream));
-      RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, m, VSTAR_EPI_NONE));
-#ifdef VSTAR_LP_F16
-      LCHK(vstar_score_rows_f16(logits, m, c.vocab, (int64_t)vpad, d_starget + c0, d_nll + c0, score->rank ? d_srank + c0 : nullptr,
-                                nullptr, e->stream));
-#else
-      LCHK(vstar_score_rows_bf16(logits, m, c.vocab, (int64_t)vpad, d_starget + c0, d_nll + c0, score->rank ? d_srank + c0 : nullptr,
-                                 nullptr, e->stream));
-#endif
-    }
-  } else if (n_want) {
-    LCHK(gather_rows(lx, d_want, wsel, n_want, H, e->stream));
-    RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, n_want, VSTAR_EPI_NONE));
-    if (verify) {          // the verify tail (spec.hip) in place of the arg-max: per group the accepted count, per row the token
-      const vstar_vqa_sampling* vp = sample_params ? d_sparams : nullptr;
-#ifdef VSTAR_LP_F16
-      LCHK(vstar_verify_rows_f16(logits, n_want, c.vocab, (int64_t)vpad, d_goff, verify->n_groups, d_vdraft, vp, d_argmax, d_vflag,
-                                 d_vacc, d_vtok, e->stream));
-#else
-      LCHK(vstar_verify_rows_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_goff, verify->n_groups, d_vdraft, vp, d_argmax, d_vflag,
-                                  d_vacc, d_vtok, e->stream));
-#endif
-    } else if (beam) {     // the beam-search tail (beam.hip) in place of the arg-max: each group's n_cand best candidates
-#ifdef VSTAR_LP_F16
-      LCHK(vstar_beam_select_f16(logits, n_want, c.vocab, (int64_t)vpad, d_bscore, beam->n_groups, d_goff, beam->n_cand, beam_ws,
-                                 d_cand_s, d_cand_t, d_cand_r, nullptr, e->stream));
-#else
-      LCHK(vstar_beam_select_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_bscore, beam->n_groups, d_goff, beam->n_cand, beam_ws,
-                                  d_cand_s, d_cand_t, d_cand_r, nullptr, e->stream));
-#endif
-    } else if (sample_params) {   // the sampling tail (sample.hip) in place of the arg-max: d_argmax receives the drawn tokens
-#ifdef VSTAR_LP_F16
-      LCHK(vstar_sample_rows_f16(logits, n_want, c.vocab, (int64_t)vpad, d_sparams, d_argmax, nullptr, nullptr, e->stream));
-#else
-      LCHK(vstar_sample_rows_bf16(logits, n_want, c.vocab, (int64_t)vpad, d_sparams, d_argmax, nullptr, nullptr, e->stream));
-#endif
-    } else {
-      LCHK(argmax_rows_lp(logits, n_want, c.vocab, (int64_t)vpad, d_argmax, e->stream));
-    }
+  // ---- head + tail, max_want wanted rows at a time: one pass, except for the scoring tail (CHUNKING RULE, LlmScoreArgs) ----
+  for (int w0 = 0; w0 < n_want; w0 += max_want) {
+    const int m = n_want - w0 < max_want ? n_want - w0 : max_want;
+    RC(head(w0, m));
+    RC(tail_launch(tail, w0, m));
   }
   LCHK(hipEventRecord(ev1, e->stream));
-  if (n_want && logits_out)
-    LCHK(hipMemcpy2DAsync(logits_out, (size_t)c.vocab * 2, logits, vpad * 2, (size_t)c.vocab * 2, n_want,
+  if (n_want && tail.logits_out)
+    LCHK(hipMemcpy2DAsync(tail.logits_out, (size_t)c.vocab * 2, logits, vpad() * 2, (size_t)c.vocab * 2, n_want,
                             hipMemcpyDeviceToHost, e->stream));
-  if (n_want && argmax_out && !beam && !score) LCHK(hipMemcpyAsync(argmax_out, d_argmax, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
-  if (verify) {
-    LCHK(hipMemcpyAsync(verify->n_accept, d_vacc, (size_t)verify->n_groups * 4, hipMemcpyDeviceToHost, e->stream));
-    LCHK(hipMemcpyAsync(verify->tokens, d_vtok, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
-  }
-  if (score) {
-    LCHK(hipMemcpyAsync(score->nll, d_nll, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
-    if (score->rank) LCHK(hipMemcpyAsync(score->rank, d_srank, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
-  }
-  if (beam) {
-    const size_t nc = (size_t)beam->n_groups * beam->n_cand;
-    LCHK(hipMemcpyAsync(beam->cand_s, d_cand_s, nc * 4, hipMemcpyDeviceToHost, e->stream));
-    LCHK(hipMemcpyAsync(beam->cand_tok, d_cand_t, nc * 4, hipMemcpyDeviceToHost, e->stream));
-    LCHK(hipMemcpyAsync(beam->cand_row, d_cand_r, nc * 4, hipMemcpyDeviceToHost, e->stream));
-  }
+  for (const TailCopy& x : copies)
+    if (x.out && x.bytes) LCHK(hipMemcpyAsync(x.out, x.dev, x.bytes, hipMemcpyDeviceToHost, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) last_ms = ms;
@@ -710,10 +731,8 @@ inline int LlmCached::decode_step_body(int keys_bound) {
   const int H = c.hidden;
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, 1, H, e->stream));
   RC(llm_layers_cached(1, 1, keys_bound, true));
-  const size_t vpad = (size_t)(c.vocab + 255) / 256 * 256;
-  LCHK(gather_rows(lx, d_want, wsel, 1, H, e->stream));
-  RC(lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad, 1, VSTAR_EPI_NONE));
-  LCHK(argmax_rows_lp(logits, 1, c.vocab, (int64_t)vpad, d_argmax, e->stream));
+  RC(head(0, 1));
+  LCHK(argmax_rows_lp(logits, 1, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
   hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos,
                      d_seq + 2 * c.max_slots * 4, d_dec, dec_cap);
   LCHK(hipGetLastError());

@@ -15,3 +15,8 @@ hipError_t vstar_sample_rows_bf16(const uint16_t* x, int rows, int vocab, int64_
                                   int32_t* tokens, float* u_out, int32_t* n_kept, hipStream_t s);
 // host-side check of one parameter record (temperature > 0 and finite, top_k >= 0, top_p in [0, 1] or above, not NaN)
 bool vstar_sample_params_valid(const vstar_vqa_sampling& p);
+inline bool vstar_sample_params_valid(const vstar_vqa_sampling* p, int n) {      // ... of n records
+  for (int i = 0; i < n; ++i)
+    if (!vstar_sample_params_valid(p[i])) return false;
+  return true;
+}

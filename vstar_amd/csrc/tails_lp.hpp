@@ -1,0 +1,35 @@
+// tails_lp.hpp — the four decode tails (sample / beam / score / spec .hip) under `_lp` names, as argmax_rows_lp has one: each
+// forwards to the launcher of the including instantiation's storage type (VSTAR_LP_F16: fp16, else bf16).  The .hip files stay
+// compiled once, dtype-explicit; the arguments are documented at the launchers (sample.hpp, beam.hpp, score.hpp, spec.hpp).
+#pragma once
+#include "common.hpp"
+#include "sample.hpp"
+#include "beam.hpp"
+#include "score.hpp"
+#include "spec.hpp"
+
+#ifdef VSTAR_LP_F16
+#define VSTAR_TAIL_LP(name) name##_f16
+#else
+#define VSTAR_TAIL_LP(name) name##_bf16
+#endif
+namespace VS_NS {      // (one definition per instantiation: the two differ)
+inline hipError_t vstar_sample_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* d_params, int32_t* tokens,
+                                       float* u_out, int32_t* n_kept, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_sample_rows)(x, rows, vocab, ld, d_params, tokens, u_out, n_kept, s);
+}
+inline hipError_t vstar_beam_select_lp(const lp_t* x, int rows, int vocab, int64_t ld, const float* d_scores, int n_groups, const int32_t* d_goff,
+                                       int n_cand, void* ws, float* cand_s, int32_t* cand_tok, int32_t* cand_row, float* lp_out, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_beam_select)(x, rows, vocab, ld, d_scores, n_groups, d_goff, n_cand, ws, cand_s, cand_tok, cand_row, lp_out, s);
+}
+inline hipError_t vstar_score_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const int32_t* d_targets, float* nll, int32_t* rank,
+                                      double* lse_out, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_score_rows)(x, rows, vocab, ld, d_targets, nll, rank, lse_out, s);
+}
+inline hipError_t vstar_verify_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                       const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag, int32_t* n_accept, int32_t* tokens,
+                                       hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_verify_rows)(x, rows, vocab, ld, group_off, n_groups, draft, params, choice, flag, n_accept, tokens, s);
+}
+}  // namespace VS_NS
+#undef VSTAR_TAIL_LP

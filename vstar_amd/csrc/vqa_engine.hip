@@ -8,12 +8,45 @@
 #ifndef VSTAR_LP_F16
 #error "vqa_engine.hip is the fp16 instantiation: build with -DVSTAR_LP_F16"
 #endif
+#include <type_traits>
 #include "llm_cached.hpp"
 #include "../../include/vstar_vqa.h"
 
 
 namespace {
 struct PcvLayer { lp_t *nm_g, *nm_b, *nl_g, *nl_b, *ff_g, *ff_b; Lin to_q, to_kv, to_out, ff1, ff2; };
+
+// Device scratch of an op-level wrapper (vstar_vqa_op_*): n elements allocated on construction (none when !wanted), freed on scope
+// exit.  `e` is the wrapper's one error: every step is skipped once it holds a failure, so the first failure is what it reports.
+template <class T>
+struct OpBuf {
+  hipError_t& e;
+  T* p = nullptr;
+  size_t bytes;
+  OpBuf(hipError_t& err, size_t n, bool wanted = true) : e(err), bytes(n * sizeof(T)) {
+    if (wanted && e == hipSuccess) e = hipMalloc(&p, bytes);
+  }
+  OpBuf(const OpBuf&) = delete;
+  ~OpBuf() { if (p) hipFree(p); }
+  void upload(const T* host) { if (p && e == hipSuccess) e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice); }
+  void download(T* host) { if (p && host && e == hipSuccess) e = hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost); }
+  operator T*() const { return p; }
+};
+
+// the op's launcher for the logits' storage type, then hipDeviceSynchronize: both skipped after a failure.  P is deduced from the
+// launchers alone (common_type<P>::type is a non-deduced context), so the arguments convert to the launchers' parameter types: an
+// OpBuf<T> becomes its T* (OpBuf<char> a void*), nullptr the null stream
+template <class... P>
+void op_launch(hipError_t& e, int dtype, hipError_t (*f16)(P...), hipError_t (*bf16)(P...), typename std::common_type<P>::type... a) {
+  if (e == hipSuccess) e = (dtype == VSTAR_F16 ? f16 : bf16)(a...);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+}
+
+int op_result(hipError_t e, const char* op) {
+  if (e == hipSuccess) return VSTAR_OK;
+  tls_error() = std::string(op) + ": " + hipGetErrorString(e);
+  return VSTAR_ERR_HIP;
+}
 }  // namespace
 
 struct vstar_vqa_engine : EngineBase {
@@ -210,6 +243,13 @@ int vstar_vqa_engine::encode(int n, const uint16_t* pix, int first_slot) {
 }
 
 // =============================================== C ABI ===============================================
+// the preamble of the entry points that need a finalized engine
+static int vqa_ready(vstar_vqa_handle* h) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  return VSTAR_OK;
+}
+
 extern "C" {
 
 int vstar_vqa_create(const vstar_vqa_config* cfg, int device, vstar_vqa_handle** out) {
@@ -273,46 +313,85 @@ int vstar_vqa_encode_images(vstar_vqa_handle* h, int n, const uint16_t* pixels_f
 int vstar_vqa_forward(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                       const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                       uint16_t* logits_f16, int32_t* argmax) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
-  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, argmax);
+  if (int rc = vqa_ready(h)) return rc;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::argmax(logits_f16, argmax));
 }
 
 int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                              const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                              const vstar_vqa_sampling* params, int32_t* tokens) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (int rc = vqa_ready(h)) return rc;
   if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
-  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, tokens, params);
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::sample(params, tokens));
 }
 
 int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                            const float* beam_scores, int n_groups, const int32_t* group_off, int n_cand, float* cand_scores,
                            int32_t* cand_tokens, int32_t* cand_rows, uint16_t* logits_f16) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (int rc = vqa_ready(h)) return rc;
   if (!beam_scores || !group_off || !cand_scores || !cand_tokens || !cand_rows) {
     h->set_error("forward_beam: beam_scores, group_off and the candidate outputs are required");
     return VSTAR_ERR_INVALID;
   }
-  LlmBeamArgs b;
-  b.scores = beam_scores; b.n_groups = n_groups; b.goff = group_off; b.n_cand = n_cand;
-  b.cand_s = cand_scores; b.cand_tok = cand_tokens; b.cand_row = cand_rows;
-  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, nullptr, nullptr, &b);
+  const LlmBeamArgs b{beam_scores, n_groups, group_off, n_cand, cand_scores, cand_tokens, cand_rows};
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::beam_select(b, logits_f16));
+}
+
+int vstar_vqa_forward_score(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                            const int32_t* targets, float* nll, int32_t* target_rank) {
+  if (int rc = vqa_ready(h)) return rc;
+  if (!targets || !nll) { h->set_error("forward_score: targets and nll are required"); return VSTAR_ERR_INVALID; }
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
+                        LlmTail::score_rows(LlmScoreArgs{targets, nll, target_rank}));
+}
+
+int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                             int32_t* n_accept_out, int32_t* tokens_out) {
+  if (int rc = vqa_ready(h)) return rc;
+  if (!group_off || !draft || !n_accept_out || !tokens_out) {
+    h->set_error("forward_verify: group_off, draft and the outputs are required");
+    return VSTAR_ERR_INVALID;
+  }
+  const LlmVerifyArgs v{n_groups, group_off, draft, n_accept_out, tokens_out};
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::verify_rows(v, params));
 }
 
 int vstar_vqa_kv_reorder(vstar_vqa_handle* h, int n, const int32_t* dst_slot, const int32_t* src_slot, int lo, int hi) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (int rc = vqa_ready(h)) return rc;
   return h->run.kv_reorder(n, dst_slot, src_slot, lo, hi);
 }
 
 int vstar_vqa_kv_copy(vstar_vqa_handle* h, int dst, int src, int lo, int hi) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  if (int rc = vqa_ready(h)) return rc;
   return h->run.kv_copy(dst, src, lo, hi);
+}
+
+// ---- the tails at op level, on device logits the caller owns: checks, scratch (OpBuf), launch + synchronise, copies back ----
+int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
+                        int32_t* tokens, float* u_out, int32_t* n_kept) {
+  if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||
+      (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_sample: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (!vstar_sample_params_valid(params, rows)) {
+    tls_error() = "vstar_vqa_op_sample: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
+    return VSTAR_ERR_INVALID;
+  }
+  hipError_t e = hipSuccess;
+  OpBuf<vstar_vqa_sampling> d_p(e, rows);
+  OpBuf<int32_t> d_tok(e, rows), d_kept(e, rows);
+  OpBuf<float> d_u(e, rows);
+  d_p.upload(params);
+  op_launch(e, dtype, vstar_sample_rows_f16, vstar_sample_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr);
+  d_tok.download(tokens);
+  d_u.download(u_out);
+  d_kept.download(n_kept);
+  return op_result(e, "vstar_vqa_op_sample");
 }
 
 int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const float* beam_scores, int n_groups,
@@ -328,48 +407,19 @@ int vstar_vqa_op_beam_select(const void* dev_logits, int dtype, int rows, int vo
     return VSTAR_ERR_INVALID;
   }
   const size_t nc = (size_t)n_groups * n_cand;
-  float *d_sc = nullptr, *d_cs = nullptr, *d_lp = nullptr;
-  int32_t *d_go = nullptr, *d_ct = nullptr, *d_cr = nullptr;
-  void* d_ws = nullptr;
-  hipError_t e = hipMalloc(&d_sc, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_go, (size_t)(n_groups + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_cs, nc * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_ct, nc * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_cr, nc * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_ws, vstar_beam_ws_bytes(rows, n_cand));
-  if (e == hipSuccess && lp_out) e = hipMalloc(&d_lp, (size_t)rows * vocab * 4);
-  if (e == hipSuccess) e = hipMemcpy(d_sc, beam_scores, (size_t)rows * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_go, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = dtype == VSTAR_F16 ? vstar_beam_select_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_sc, n_groups, d_go, n_cand, d_ws, d_cs,
-                                                   d_ct, d_cr, d_lp, nullptr)
-                           : vstar_beam_select_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_sc, n_groups, d_go, n_cand, d_ws,
-                                                    d_cs, d_ct, d_cr, d_lp, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(cand_scores, d_cs, nc * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(cand_tokens, d_ct, nc * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(cand_rows, d_cr, nc * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && lp_out) e = hipMemcpy(lp_out, d_lp, (size_t)rows * vocab * 4, hipMemcpyDeviceToHost);
-  hipFree(d_sc);
-  hipFree(d_go);
-  hipFree(d_cs);
-  hipFree(d_ct);
-  hipFree(d_cr);
-  hipFree(d_ws);
-  if (d_lp) hipFree(d_lp);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_beam_select: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
-}
-
-int vstar_vqa_forward_score(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
-                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
-                            const int32_t* targets, float* nll, int32_t* target_rank) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
-  if (!targets || !nll) { h->set_error("forward_score: targets and nll are required"); return VSTAR_ERR_INVALID; }
-  LlmScoreArgs sc;
-  sc.targets = targets; sc.nll = nll; sc.rank = target_rank;
-  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, nullptr, nullptr, nullptr, &sc);
+  hipError_t e = hipSuccess;
+  OpBuf<float> d_sc(e, rows), d_cs(e, nc), d_lp(e, (size_t)rows * vocab, lp_out != nullptr);
+  OpBuf<int32_t> d_go(e, (size_t)n_groups + 1), d_ct(e, nc), d_cr(e, nc);
+  OpBuf<char> d_ws(e, vstar_beam_ws_bytes(rows, n_cand));
+  d_sc.upload(beam_scores);
+  d_go.upload(group_off);
+  op_launch(e, dtype, vstar_beam_select_f16, vstar_beam_select_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_sc, n_groups, d_go,
+            n_cand, d_ws, d_cs, d_ct, d_cr, d_lp, nullptr);
+  d_cs.download(cand_scores);
+  d_ct.download(cand_tokens);
+  d_cr.download(cand_rows);
+  d_lp.download(lp_out);
+  return op_result(e, "vstar_vqa_op_beam_select");
 }
 
 int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* targets, float* nll,
@@ -382,42 +432,16 @@ int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, i
     tls_error() = std::string("vstar_vqa_op_score: ") + m;
     return VSTAR_ERR_INVALID;
   }
-  int32_t *d_t = nullptr, *d_r = nullptr;
-  float* d_n = nullptr;
-  double* d_l = nullptr;
-  hipError_t e = hipMalloc(&d_t, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_n, (size_t)rows * 4);
-  if (e == hipSuccess && target_rank) e = hipMalloc(&d_r, (size_t)rows * 4);
-  if (e == hipSuccess && lse_out) e = hipMalloc(&d_l, (size_t)rows * 8);
-  if (e == hipSuccess) e = hipMemcpy(d_t, targets, (size_t)rows * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = dtype == VSTAR_F16 ? vstar_score_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_t, d_n, d_r, d_l, nullptr)
-                           : vstar_score_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_t, d_n, d_r, d_l, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(nll, d_n, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && target_rank) e = hipMemcpy(target_rank, d_r, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && lse_out) e = hipMemcpy(lse_out, d_l, (size_t)rows * 8, hipMemcpyDeviceToHost);
-  hipFree(d_t);
-  hipFree(d_n);
-  if (d_r) hipFree(d_r);
-  if (d_l) hipFree(d_l);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_score: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
-}
-
-int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
-                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
-                             const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
-                             int32_t* n_accept_out, int32_t* tokens_out) {
-  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
-  if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
-  if (!group_off || !draft || !n_accept_out || !tokens_out) {
-    h->set_error("forward_verify: group_off, draft and the outputs are required");
-    return VSTAR_ERR_INVALID;
-  }
-  LlmVerifyArgs v;
-  v.n_groups = n_groups; v.goff = group_off; v.draft = draft; v.n_accept = n_accept_out; v.tokens = tokens_out;
-  return h->run.forward(nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, nullptr, nullptr, params, nullptr, nullptr, &v);
+  hipError_t e = hipSuccess;
+  OpBuf<int32_t> d_t(e, rows), d_r(e, rows, target_rank != nullptr);
+  OpBuf<float> d_n(e, rows);
+  OpBuf<double> d_l(e, rows, lse_out != nullptr);
+  d_t.upload(targets);
+  op_launch(e, dtype, vstar_score_rows_f16, vstar_score_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_t, d_n, d_r, d_l, nullptr);
+  d_n.download(nll);
+  d_r.download(target_rank);
+  d_l.download(lse_out);
+  return op_result(e, "vstar_vqa_op_score");
 }
 
 int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
@@ -430,76 +454,21 @@ int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, 
     tls_error() = std::string("vstar_vqa_op_verify: ") + m;
     return VSTAR_ERR_INVALID;
   }
-  if (params)
-    for (int r = 0; r < rows; ++r)
-      if (!vstar_sample_params_valid(params[r])) {
-        tls_error() = "vstar_vqa_op_verify: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
-        return VSTAR_ERR_INVALID;
-      }
-  vstar_vqa_sampling* d_p = nullptr;
-  int32_t *d_go = nullptr, *d_dr = nullptr, *d_ch = nullptr, *d_fl = nullptr, *d_ac = nullptr, *d_tok = nullptr;
-  hipError_t e = hipMalloc(&d_go, (size_t)(n_groups + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_dr, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_ch, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_fl, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_ac, (size_t)n_groups * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_tok, (size_t)rows * 4);
-  if (e == hipSuccess && params) e = hipMalloc(&d_p, (size_t)rows * sizeof(vstar_vqa_sampling));
-  if (e == hipSuccess) e = hipMemcpy(d_go, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_dr, draft, (size_t)rows * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && params) e = hipMemcpy(d_p, params, (size_t)rows * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = dtype == VSTAR_F16 ? vstar_verify_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p, d_ch, d_fl,
-                                                   d_ac, d_tok, nullptr)
-                           : vstar_verify_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p, d_ch,
-                                                    d_fl, d_ac, d_tok, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(n_accept_out, d_ac, (size_t)n_groups * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(tokens_out, d_tok, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  hipFree(d_go);
-  hipFree(d_dr);
-  hipFree(d_ch);
-  hipFree(d_fl);
-  hipFree(d_ac);
-  hipFree(d_tok);
-  if (d_p) hipFree(d_p);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_verify: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
-}
-
-int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
-                        int32_t* tokens, float* u_out, int32_t* n_kept) {
-  if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||
-      (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
-    tls_error() = "vstar_vqa_op_sample: bad argument";
+  if (params && !vstar_sample_params_valid(params, rows)) {
+    tls_error() = "vstar_vqa_op_verify: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
     return VSTAR_ERR_INVALID;
   }
-  for (int r = 0; r < rows; ++r)
-    if (!vstar_sample_params_valid(params[r])) {
-      tls_error() = "vstar_vqa_op_sample: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
-      return VSTAR_ERR_INVALID;
-    }
-  vstar_vqa_sampling* d_p = nullptr;
-  int32_t *d_tok = nullptr, *d_kept = nullptr;
-  float* d_u = nullptr;
-  hipError_t e = hipMalloc(&d_p, (size_t)rows * sizeof(vstar_vqa_sampling));
-  if (e == hipSuccess) e = hipMalloc(&d_tok, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_u, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_kept, (size_t)rows * 4);
-  if (e == hipSuccess) e = hipMemcpy(d_p, params, (size_t)rows * sizeof(vstar_vqa_sampling), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = dtype == VSTAR_F16 ? vstar_sample_rows_f16((const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr)
-                           : vstar_sample_rows_bf16((const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(tokens, d_tok, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && u_out) e = hipMemcpy(u_out, d_u, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n_kept) e = hipMemcpy(n_kept, d_kept, (size_t)rows * 4, hipMemcpyDeviceToHost);
-  hipFree(d_p);
-  hipFree(d_tok);
-  hipFree(d_u);
-  hipFree(d_kept);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_sample: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
+  hipError_t e = hipSuccess;
+  OpBuf<int32_t> d_go(e, (size_t)n_groups + 1), d_dr(e, rows), d_ch(e, rows), d_fl(e, rows), d_ac(e, n_groups), d_tok(e, rows);
+  OpBuf<vstar_vqa_sampling> d_p(e, rows, params != nullptr);
+  d_go.upload(group_off);
+  d_dr.upload(draft);
+  d_p.upload(params);
+  op_launch(e, dtype, vstar_verify_rows_f16, vstar_verify_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p,
+            d_ch, d_fl, d_ac, d_tok, nullptr);
+  d_ac.download(n_accept_out);
+  d_tok.download(tokens_out);
+  return op_result(e, "vstar_vqa_op_verify");
 }
 
 int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,
@@ -517,8 +486,7 @@ int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void
   if (kernel == 1 || kernel == 3 || (kernel == 0 && gemm_skinny_eligible(p))) e = gemm_skinny_lp(p, epilogue, false, nullptr);
   else e = gemm_lp(p, epilogue, false, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_gemm: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
+  return op_result(e, "vstar_vqa_op_gemm");
 }
 
 int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h) { return (h && h->finalized && !h->run.w8_qkv.empty()) ? 8 : 0; }
@@ -530,8 +498,7 @@ int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q
   }
   hipError_t e = quantize_rows_w8((const lp_t*)dev_W_f16, rows, K, (int8_t*)dev_q_i8, dev_scale_f32, (lp_t*)dev_What_f16, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_quantize_w8: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
+  return op_result(e, "vstar_vqa_op_quantize_w8");
 }
 
 int vstar_vqa_op_gemm_w8(const void* A, const void* Wq, const float* scale, const void* bias, const void* res, void* C, int M, int N,
@@ -548,19 +515,14 @@ int vstar_vqa_op_gemm_w8(const void* A, const void* Wq, const float* scale, cons
   p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
   if (kernel == 3) p.tile_force = -1;
   if (!gemm_skinny_eligible(p)) { tls_error() = "vstar_vqa_op_gemm_w8: outside the weight-streaming kernels' domain (M <= 64)"; return VSTAR_ERR_INVALID; }
-  void* tiles = nullptr;
+  if (layout == 1 && N % (16 * nt)) { tls_error() = "vstar_vqa_op_gemm_w8: the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
   hipError_t e = hipSuccess;
-  if (layout == 1) {
-    if (N % (16 * nt)) { tls_error() = "vstar_vqa_op_gemm_w8: the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
-    e = hipMalloc(&tiles, (size_t)N * K);
-    if (e == hipSuccess) e = skinny_pack_tiles_w8((const int8_t*)Wq, (int8_t*)tiles, N, K, nt, nullptr);
-    p.Wq_tiled = (const int8_t*)tiles;
-  }
+  OpBuf<int8_t> tiles(e, (size_t)N * K, layout == 1);
+  if (layout == 1 && e == hipSuccess) e = skinny_pack_tiles_w8((const int8_t*)Wq, tiles, N, K, nt, nullptr);
+  p.Wq_tiled = tiles;
   if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, false, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (tiles) hipFree(tiles);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_vqa_op_gemm_w8: ") + hipGetErrorString(e); return VSTAR_ERR_HIP; }
-  return VSTAR_OK;
+  return op_result(e, "vstar_vqa_op_gemm_w8");
 }
 
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t cap) {

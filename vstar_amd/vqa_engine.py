@@ -116,6 +116,23 @@ class VqaEngine:
         w = np.asarray([row_off[i] + (r if r >= 0 else len(seqs[i].rows) + r) for i, r in want], np.int32)
         return (n, _ptr(row_off), _ptr(src), _ptr(kv), _ptr(pre), _ptr(past), len(w), _ptr(w)), (row_off, src, kv, pre, past, w)
 
+    @staticmethod
+    def _per_row(values, dtype, nw: int, what: str) -> np.ndarray:
+        """One value per wanted row as a contiguous array (a tail's scores / targets / drafts)."""
+        a = np.ascontiguousarray(values, dtype)
+        if a.shape != (nw,):
+            raise ValueError(f"{a.size} {what} for {nw} wanted rows")
+        return a
+
+    @staticmethod
+    def _sampling_array(params, nw: int):
+        """One `_lib.VqaSampling` for all wanted rows, or a list of one per row -> the ctypes array behind the C pointer."""
+        if isinstance(params, _lib.VqaSampling):
+            params = [params] * nw
+        if len(params) != nw:
+            raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
+        return (_lib.VqaSampling * max(nw, 1))(*params)
+
     def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True):
         """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
         Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want])."""
@@ -132,11 +149,7 @@ class VqaEngine:
         logits never leave the device."""
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
-        if isinstance(params, _lib.VqaSampling):
-            params = [params] * nw
-        if len(params) != nw:
-            raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
-        prm = (_lib.VqaSampling * max(nw, 1))(*params)
+        prm = self._sampling_array(params, nw)
         out = np.empty((max(nw, 1),), np.int32)
         _lib.check_vqa(self.lib.vstar_vqa_forward_sample(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out)),
                        self.handle)
@@ -150,10 +163,8 @@ class VqaEngine:
         vocab] or None), the candidates of each group sorted by (score descending, row * vocab + token ascending)."""
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
-        sc = np.ascontiguousarray(beam_scores, np.float32)
+        sc = self._per_row(beam_scores, np.float32, nw, "beam scores")
         go = np.ascontiguousarray(group_off, np.int32)
-        if sc.shape != (nw,):
-            raise ValueError(f"{sc.size} beam scores for {nw} wanted rows")
         ng = max(len(go) - 1, 0)
         cs = np.empty((max(ng, 1), max(n_cand, 1)), np.float32)
         ct = np.empty_like(cs, dtype=np.int32)
@@ -171,9 +182,7 @@ class VqaEngine:
         the device."""
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
-        tg = np.ascontiguousarray(targets, np.int32)
-        if tg.shape != (nw,):
-            raise ValueError(f"{tg.size} targets for {nw} wanted rows")
+        tg = self._per_row(targets, np.int32, nw, "targets")
         nll = np.empty((max(nw, 1),), np.float32)
         rk = np.empty((max(nw, 1),), np.int32) if rank else None
         _lib.check_vqa(self.lib.vstar_vqa_forward_score(self.handle, *args, _ptr(tg), _ptr(nll), _ptr(rk)), self.handle)
@@ -188,17 +197,9 @@ class VqaEngine:
         args, _keep = self._rows_args(step, wanted)
         nw = args[6]
         go = np.ascontiguousarray(groups, np.int32)
-        dr = np.ascontiguousarray(draft, np.int32)
-        if dr.shape != (nw,):
-            raise ValueError(f"{dr.size} draft entries for {nw} wanted rows")
+        dr = self._per_row(draft, np.int32, nw, "draft entries")
         ng = max(len(go) - 1, 0)
-        prm = None
-        if params is not None:
-            if isinstance(params, _lib.VqaSampling):
-                params = [params] * nw
-            if len(params) != nw:
-                raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
-            prm = (_lib.VqaSampling * max(nw, 1))(*params)
+        prm = self._sampling_array(params, nw) if params is not None else None
         acc = np.empty((max(ng, 1),), np.int32)
         tok = np.empty((max(nw, 1),), np.int32)
         _lib.check_vqa(self.lib.vstar_vqa_forward_verify(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None,
