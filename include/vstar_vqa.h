@@ -58,8 +58,13 @@ typedef struct vstar_vqa_config {
   int32_t max_images;         /* feature-table slots; each holds P long rows then pcv_latents short rows */
   int32_t decode_weight_bits; /* 0 (default) = fp16 weights everywhere; 8 = int8 weight-only decode of the LLaMA block linears
                                * (q|k|v, o_proj, gate|up, down_proj), see vstar_vqa_decode_weight_bits; anything else fails at create */
-  int32_t reserved[7];
+  int32_t decode_weight_format; /* 0 (default) = decode_weight_bits alone decides; VSTAR_VQA_WFMT_W4G128 (1) = int4 group-scaled
+                               * weight-only decode (one fp16 scale per 128 input channels): needs decode_weight_bits
+                               * == 0, llm_hidden % 128 == 0 and llm_mlp % 128 == 0; anything else fails at create */
+  int32_t reserved[6];
 } vstar_vqa_config;
+
+#define VSTAR_VQA_WFMT_W4G128 1 /* vstar_vqa_config.decode_weight_format */
 
 typedef struct vstar_vqa_engine vstar_vqa_handle;
 
@@ -210,7 +215,7 @@ int vstar_vqa_op_gemm(const void* dev_A, const void* dev_W, const void* dev_bias
  * fp16(q), exact, and the reduced fp32 accumulator is multiplied once by s — while the fp16 weights are REPLACED by
  * fp16(float(q) * s), so prefill and larger calls run the same quantised model on the tile kernels.  lm_head, the embedding, the
  * CLIP tower, the projectors and the Perceiver stay fp16.  A failed allocation fails finalize_weights (no fp16 fallback).
- * Returns 8 when the mode is active on a finalized engine, else 0. */
+ * Returns 8 when the mode is active on a finalized engine, 4 in the int4 group-scaled mode (below), else 0. */
 int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h);
 /* Op-level quantiser (tests): DEVICE W [rows, K] fp16 (K % 8 == 0) -> q int8 [rows, K], scale fp32 [rows], and (nullable, may
  * alias W) What fp16 [rows, K] = fp16(float(q) * s).  Null stream, synchronises. */
@@ -221,6 +226,32 @@ int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q
  * layout: 0 = the ring reads the row-major int8, 1 = the op packs a temporary tile-major image and the ring reads that (needs
  * N % 16 == 0, SiLU-mul N % 32 == 0).  Outside the weight-streaming domain (M > 64) it is an error. */
 int vstar_vqa_op_gemm_w8(const void* dev_A, const void* dev_Wq, const float* dev_scale, const void* dev_bias,
+                         const void* dev_residual, void* dev_C, int M, int N, int K, int epilogue, int kernel,
+                         const void* dev_norm_w, float norm_eps, int layout);
+
+/* int4 group-scaled weight-only decode (W4A16, groups of 128), opt-in through
+ * vstar_vqa_config.decode_weight_format = VSTAR_VQA_WFMT_W4G128 (decode_weight_bits stays 0: the value 4 there keeps failing at
+ * create).  finalize_weights quantises the LLaMA block linears once, on the device, per row n of W[N, K] and group j = k / 128
+ * (fp32 unless said otherwise): a = max |W[n, 128 j .. 128 j + 127]|, s = fp16(float(a) / 7.0f) (one correctly rounded divide,
+ * one round-to-nearest-even conversion), s = min(s, 9352) (7 * 9352 is finite in fp16), s = 1 if s == 0,
+ * q = clamp(rint(float(W) / float(s)), -7, 7) (-8 is never produced), What = fp16(q) * s as ONE fp16 multiply (subnormals kept).
+ * Storage: u = q + 8 in 1..15 (0 decodes to -8); eight elements per little-endian 32-bit word, element e in nibble
+ * (e >> 1) + 4 (e & 1); row-major image uint32 [Npad, K / 8], scales fp16 [Npad, K / 128], Npad = ceil(N / 256) * 256, padding
+ * rows q = 0 (u = 8), s = 1.  Calls of up to 64 rows stream the words through the W4 form of the register weight-streaming kernel,
+ * which applies the group scale to the weights in registers: every MFMA sees exactly What, so the call is BIT-IDENTICAL to the fp16
+ * kernel on What — and the fp16 weights are REPLACED by What, so prefill and larger calls run the same quantised model.  There is no
+ * LDS-ring form: decode steps of up to 8 sequences take the register kernel too, which reads a tile-major image of the words and
+ * scales (one coalesced 1-KiB load per wave and pair of its double steps) unless VSTAR_DECODE_TILED=0.  lm_head, the embedding, the CLIP tower, the
+ * projectors and the Perceiver stay fp16.  vstar_vqa_decode_weight_bits returns 4 on a finalized engine in this mode. */
+/* Op-level quantiser (tests): DEVICE W [rows, K] fp16 (K % 128 == 0) -> q uint32 [rows, K / 8], scale fp16 [rows, K / 128], and
+ * (nullable, may alias W) What fp16 [rows, K].  Null stream, synchronises. */
+int vstar_vqa_op_quantize_w4(const void* dev_W_f16, int rows, int K, void* dev_q_u32, void* dev_scale_f16, void* dev_What_f16);
+/* Op-level W4A16 GEMV (tests, micro-benchmarks): vstar_vqa_op_gemm_w8's parameter list and meanings with the weight given as words
+ * dev_Wq [ceil(N/256)*256, K / 8] and fp16 scales dev_scale [ceil(N/256)*256, K / 128] (K % 128 == 0):
+ * C = epilogue(A · (fp16(q) * s)^T + bias) (+ residual).  kernel: 1 = dispatch, 3 = force the register-streaming kernel (both run
+ * it: there is no W4 ring).  layout: 0 = the kernel reads the row-major words and scales, 1 = the op packs a temporary tile-major
+ * image and the kernel reads that (needs N % 16 == 0, SiLU-mul N % 32 == 0).  M > 64 is an error. */
+int vstar_vqa_op_gemm_w4(const void* dev_A, const void* dev_Wq, const void* dev_scale, const void* dev_bias,
                          const void* dev_residual, void* dev_C, int M, int N, int K, int epilogue, int kernel,
                          const void* dev_norm_w, float norm_eps, int layout);
 

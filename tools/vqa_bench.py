@@ -13,10 +13,11 @@ spread of the alternated blocks.  --only-score skips every other leg.
 --score-kernels N (use with --layers 2 under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py ...`): 20 forward
 calls with the arg-max tail and 20 with the scoring tail on N wanted rows, so that the trace's per-kernel statistics compare
 score_rows_kernel with argmax_rows at that row count.
---decode-bits 0,8 runs `decode_bits` ALONE: two engines in one process on the same weights, fp16 and the int8 weight-only
-decode mode, greedy decode blocks of --steps alternated --rounds times at every batch size; tokens/s and the
-effective weight stream of both (bytes a step actually reads: int8 block linears + fp16 lm_head in the 8-bit mode), their ratio
-and the spread over the rounds.
+--decode-bits 0,8 or 0,8,4 runs `decode_bits` ALONE: one engine per mode in one process on the same weights — fp16, the int8
+weight-only decode mode and the int4 group-scaled mode (§8.6) — greedy decode blocks of --steps alternated
+--rounds times at every batch size; tokens/s and the effective weight stream of each (bytes a step actually reads: the quantised
+block linears with their scales + the fp16 lm_head), the ratios against fp16 (and 4-bit against 8-bit) and the spread over the
+rounds.  The yardsticks of the 4-bit mode are the same process's fp16 and 8-bit engines.
 --spec 1,3,6 runs `decode_spec` ALONE: one sequence (~300 cached positions), first a plain greedy decode of
 --spec-tokens tokens, then for every draft length d and every share of corrupted draft positions in --spec-corrupt (a replay
 drafter proposing that output: 1.0 = acceptance 0, 0.0 = acceptance 1) `VQA_LLM.speculative_decode` blocks alternated --rounds
@@ -55,7 +56,7 @@ def main():
     ap.add_argument("--beams", default="", help="comma-separated beam counts: add the beam-search leg next to greedy")
     ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
     ap.add_argument("--only-score", action="store_true", help="run the --score leg alone")
-    ap.add_argument("--decode-bits", default="", help="'0,8': fp16 against the int8 weight-only decode mode, alternated blocks (runs alone)")
+    ap.add_argument("--decode-bits", default="", help="'0,8' or '0,8,4': fp16 against the int8 / int4 weight-only decode modes, alternated blocks (runs alone)")
     ap.add_argument("--spec", default="", help="comma-separated draft lengths: speculative against plain greedy decode (runs alone)")
     ap.add_argument("--spec-tokens", type=int, default=64, help="--spec: tokens decoded per block")
     ap.add_argument("--spec-corrupt", default="1.0,0.5,0.0", help="--spec: shares of corrupted draft positions")
@@ -67,9 +68,9 @@ def main():
         ap.error("--only-score needs --score B[,B...]")
     if a.decode_bits:
         bits = [int(x) for x in a.decode_bits.split(",")]
-        if sorted(bits) != [0, 8]:
-            ap.error("--decode-bits takes 0,8")
-        out = {"decode_bits": decode_bits(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)}
+        if bits[0] != 0 or len(set(bits)) != len(bits) or not set(bits) <= {0, 4, 8} or len(bits) < 2:
+            ap.error("--decode-bits takes 0 followed by 8, 4 or both")
+        out = {"decode_bits": decode_bits(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds, bits)}
         return finish(out, a)
     if a.spec or a.spec_kernels:
         out = decode_spec(a.layers, [int(x) for x in a.spec.split(",")] if a.spec else [], a.spec_tokens,
@@ -209,19 +210,22 @@ def score_leg(eng, cfg, batches, rounds):
     return res
 
 
-def decode_bits(layers, batches, steps, rounds):
-    """fp16 engine against the int8 weight-only decode engine (same seeded weights), greedy steps of B sequences with ~300 cached
-    positions, blocks of `steps` alternated `rounds` times in one process."""
+def decode_bits(layers, batches, steps, rounds, modes=(0, 8)):
+    """fp16 engine against the int8 / int4 weight-only decode engines (same seeded weights), greedy steps of B sequences with ~300
+    cached positions, blocks of `steps` alternated `rounds` times in one process."""
     engs = {}
-    for bits in (0, 8):
-        cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=max(batches + [1]), max_ctx=1024, max_rows=16384, max_images=1,
-                                decode_weight_bits=bits)
+    for bits in modes:
+        cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=max(batches + [1]), max_ctx=1024, max_rows=16384,
+                                max_images=1).with_decode_bits(bits)
         engs[bits] = VqaEngine(cfg, 0)
         engs[bits].load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
         assert engs[bits].decode_weight_bits() == bits
     H, M, V, L = cfg.llm_hidden, cfg.llm_mlp, cfg.llm_vocab, cfg.llm_layers
     blk = L * (4 * H * H + 3 * H * M)
-    wbytes = {0: 2.0 * (blk + V * H), 8: 1.0 * blk + 4.0 * L * (5 * H + 2 * M) + 2.0 * V * H}
+    # (8: one fp32 scale per packed row; 4: half a byte per weight + one fp16 scale per 128 of them = 4.125 bits)
+    wbytes = {0: 2.0 * (blk + V * H), 8: 1.0 * blk + 4.0 * L * (5 * H + 2 * M) + 2.0 * V * H,
+              4: (0.5 + 2.0 / 128) * blk + 2.0 * V * H}
+    wbytes = {b: wbytes[b] for b in modes}
     g = torch.Generator().manual_seed(0)
     rows = torch.randint(3, 30000, (296,), generator=g).tolist()
     res = {"config": {"layers": L, "hidden": H, "weights_GB_per_step": {str(b): round(w / 1e9, 2) for b, w in wbytes.items()}}}
@@ -231,8 +235,8 @@ def decode_bits(layers, batches, steps, rounds):
             _, nxt[bits] = eng.forward([Seq(rows, kv_slot=i) for i in range(B)], [(i, -1) for i in range(B)], logits=False)
             pos[bits] = len(rows)
         want = [(i, 0) for i in range(B)]
-        dev = {0: [], 8: []}
-        blocks = {0: [], 8: []}
+        dev = {b: [] for b in modes}
+        blocks = {b: [] for b in modes}
         for r in range(rounds + 1):                  # round 0 warms both engines up and is dropped
             for bits, eng in engs.items():
                 t0 = time.time()
@@ -245,14 +249,16 @@ def decode_bits(layers, batches, steps, rounds):
                     blocks[bits].append((time.time() - t0) / steps * 1e3)
                     dev[bits] += d
         leg = {}
-        for bits in (0, 8):
+        for bits in modes:
             w, d = float(np.median(blocks[bits])), float(np.median(dev[bits]))
             leg[f"bits{bits}"] = {"device_ms_per_step": round(d, 3), "wall_ms_per_step": round(w, 3), "tokens_per_s": round(B / w * 1e3, 1),
                                   "wall_ms_per_step_blocks": [round(x, 3) for x in blocks[bits]],
                                   "spread": round((max(blocks[bits]) - min(blocks[bits])) / w, 3),
                                   "weights_GBps": round(wbytes[bits] / d / 1e6, 0)}
-        leg["bits8_over_bits0_tokens_per_s"] = round(leg["bits8"]["tokens_per_s"] / leg["bits0"]["tokens_per_s"], 3)
-        leg["bits8_over_bits0_device_time"] = round(leg["bits8"]["device_ms_per_step"] / leg["bits0"]["device_ms_per_step"], 3)
+        for x, y in ((8, 0), (4, 0), (4, 8)):
+            if x in modes and y in modes:
+                leg[f"bits{x}_over_bits{y}_tokens_per_s"] = round(leg[f"bits{x}"]["tokens_per_s"] / leg[f"bits{y}"]["tokens_per_s"], 3)
+                leg[f"bits{x}_over_bits{y}_device_time"] = round(leg[f"bits{x}"]["device_ms_per_step"] / leg[f"bits{y}"]["device_ms_per_step"], 3)
         res[f"B{B}"] = leg
     return res
 

@@ -1,12 +1,12 @@
-"""Logits error and option rankings of the int8 weight-only decode mode against the unquantised fp16 engine on the
-inputs of tests/golden/vqa_tiny_*.npz.  Reported, not asserted: the weights are seeded random numbers, which says little about a
-trained checkpoint.  Prints one JSON object.
+"""Logits error and option rankings of the int8 weight-only decode mode, or with --bits 4 of the int4 group-scaled
+mode (§8.6), against the unquantised fp16 engine on the inputs of tests/golden/vqa_tiny_*.npz.  Reported, not asserted: the weights
+are seeded random numbers, which says little about a trained checkpoint.  Prints one JSON object.
 
   python tools/vqa_w8_accuracy.py [--out profiles/vqa_w8_accuracy.json]
+  python tools/vqa_w8_accuracy.py --bits 4 [--out profiles/vqa_w4_accuracy.json]
 """
 import argparse
 import ast
-import dataclasses
 import glob
 import json
 import os
@@ -61,20 +61,22 @@ def run(cfg, wseed, pix, ids, opts, n_obj, il, ol):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bits", type=int, default=8, choices=[4, 8], help="the quantised mode compared with fp16")
     a = ap.parse_args()
     out = {}
+    B, w = a.bits, f"w{a.bits}"
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "vqa_tiny_*.npz"))):
         z, cfg, pix, ids, opts, n_obj, il, ol = load_case(path)
-        res = {b: run(dataclasses.replace(cfg, decode_weight_bits=b), int(z["weight_seed"]), pix, ids, opts, n_obj, il, ol) for b in (0, 8)}
-        rank = {b: np.argsort(res[b][2]).tolist() for b in (0, 8)}
+        res = {b: run(cfg.with_decode_bits(b), int(z["weight_seed"]), pix, ids, opts, n_obj, il, ol) for b in (0, B)}
+        rank = {b: np.argsort(res[b][2]).tolist() for b in (0, B)}
         out[os.path.basename(path)] = {
-            "q_logits_rel_l2_w8_vs_fp16": rel_l2(res[8][0], res[0][0]), "opt_logits_rel_l2_w8_vs_fp16": rel_l2(res[8][1], res[0][1]),
+            f"q_logits_rel_l2_{w}_vs_fp16": rel_l2(res[B][0], res[0][0]), f"opt_logits_rel_l2_{w}_vs_fp16": rel_l2(res[B][1], res[0][1]),
             "q_logits_rel_l2_fp16_vs_golden": rel_l2(res[0][0][-1], z["q_logits_last"]),
-            "q_logits_rel_l2_w8_vs_golden": rel_l2(res[8][0][-1], z["q_logits_last"]),
-            "losses_fp16": [round(x, 4) for x in res[0][2]], "losses_w8": [round(x, 4) for x in res[8][2]],
+            f"q_logits_rel_l2_{w}_vs_golden": rel_l2(res[B][0][-1], z["q_logits_last"]),
+            "losses_fp16": [round(x, 4) for x in res[0][2]], f"losses_{w}": [round(x, 4) for x in res[B][2]],
             "losses_golden": np.asarray(z["losses"]).round(4).tolist(),
-            "ranking_fp16": rank[0], "ranking_w8": rank[8], "ranking_golden": np.argsort(z["losses"]).tolist(),
-            "ranking_survives": rank[8] == np.argsort(z["losses"]).tolist()}
+            "ranking_fp16": rank[0], f"ranking_{w}": rank[B], "ranking_golden": np.argsort(z["losses"]).tolist(),
+            "ranking_survives": rank[B] == np.argsort(z["losses"]).tolist()}
     print(json.dumps(out))
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -38,6 +38,7 @@ EXPORTS_VQA = [
     "vstar_vqa_forward_sample", "vstar_vqa_op_sample", "vstar_vqa_forward_beam", "vstar_vqa_kv_reorder", "vstar_vqa_kv_copy",
     "vstar_vqa_op_beam_select", "vstar_vqa_forward_score", "vstar_vqa_op_score",
     "vstar_vqa_decode_weight_bits", "vstar_vqa_op_quantize_w8", "vstar_vqa_op_gemm_w8",
+    "vstar_vqa_op_quantize_w4", "vstar_vqa_op_gemm_w4",
     "vstar_vqa_forward_verify", "vstar_vqa_op_verify",
 ]
 
@@ -257,6 +258,11 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_gemm_w8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int]
     lib.vstar_vqa_op_gemm_w8.restype = c_int
+    lib.vstar_vqa_op_quantize_w4.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_quantize_w4.restype = c_int
+    lib.vstar_vqa_op_gemm_w4.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_float, c_int]
+    lib.vstar_vqa_op_gemm_w4.restype = c_int
     lib.vstar_vqa_debug_read.argtypes = [H, c_char_p, c_void_p, c_int64]
     lib.vstar_vqa_debug_read.restype = c_int64
     lib.vstar_vqa_last_forward_ms.argtypes = [H]

@@ -289,10 +289,13 @@ def load_pretrained_model(model_path, model_base=None, model_name: str = "", loa
                           decode_weight_bits=0):
     """Same signature and return tuple as LLaVA/llava/model/builder.py:26-151: (tokenizer, model, image_processor, context_len).
     `model_path`: LOCAL checkpoint directory of craigwu/seal_vqa_7b (offline: `cfg` + `state_dict` [+ `tokenizer`]).
-    decode_weight_bits=8: the engine's own int8 weight-only decode mode, not bitsandbytes' LLM.int8."""
+    decode_weight_bits=8: the engine's own int8 weight-only decode mode (DESIGN.md §8.4), not bitsandbytes' LLM.int8;
+    decode_weight_bits=4: its int4 mode with one fp16 scale per 128 input channels (§8.6; the GPTQ / AWQ layout, quantised here by
+    round-to-nearest), not bitsandbytes' NF4 — load_4bit keeps raising."""
     if load_8bit or load_4bit:
         raise NotImplementedError("bitsandbytes 8-bit / 4-bit loading is out of scope: the engine runs fp16 (builder.py:43); "
-                                  "its own int8 weight-only decode mode is decode_weight_bits=8")
+                                  "its own weight-only decode modes are decode_weight_bits=8 (int8 per row) and "
+                                  "decode_weight_bits=4 (int4 in groups of 128, not NF4)")
     if model_base is not None:
         raise NotImplementedError("LoRA / model_base merging is out of scope (the evaluation passes model_base=None)")
     if "mpt" in model_name.lower():

@@ -162,8 +162,12 @@ class CVqaConfig(ctypes.Structure):
         ("max_slots", ctypes.c_int32), ("max_ctx", ctypes.c_int32), ("max_rows", ctypes.c_int32),
         ("max_images", ctypes.c_int32),
         ("decode_weight_bits", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 7),
+        ("decode_weight_format", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 6),
     ]
+
+
+WFMT_W4G128 = 1      # VSTAR_VQA_WFMT_W4G128 (include/vstar_vqa.h)
 
 
 @dataclass
@@ -193,6 +197,11 @@ class VQAConfig:
     max_rows: int = 8192
     max_images: int = 16
     decode_weight_bits: int = 0     # 8: int8 weight-only decode of the LLaMA block linears; 0: fp16 everywhere
+    # 1 (WFMT_W4G128): int4 weight-only decode with one fp16 scale per 128 input channels; needs decode_weight_bits
+    # == 0 and llm_hidden, llm_mlp multiples of 128.  VQAConfig(decode_weight_bits=4) STAYS INVALID: this class mirrors the C struct
+    # field for field, where the value 4 is pinned to fail at create (the int8 pull request's tests); "4 bits" at the user-facing
+    # level (VQA_LLM, load_pretrained_model, the tools) is translated by with_decode_bits(4).
+    decode_weight_format: int = 0
 
     @property
     def n_img_tokens(self) -> int:
@@ -202,6 +211,19 @@ class VQAConfig:
     def feat_rows(self) -> int:
         """Rows of one feature-table slot: P long rows then pcv_latents short rows."""
         return self.n_img_tokens + self.pcv_latents
+
+    def with_decode_bits(self, bits: int) -> "VQAConfig":
+        """The user-facing spelling of the weight-only decode modes: 0 = fp16, 8 = int8 per row (decode_weight_bits = 8), 4 = int4 in
+        groups of 128 (decode_weight_format = WFMT_W4G128 with decode_weight_bits = 0)."""
+        import dataclasses
+        bits = int(bits)
+        if bits not in (0, 4, 8):
+            raise ValueError("decode bits must be 0, 4 or 8")
+        return dataclasses.replace(self, decode_weight_bits=8 if bits == 8 else 0, decode_weight_format=WFMT_W4G128 if bits == 4 else 0)
+
+    def decode_bits(self) -> int:
+        """Inverse of with_decode_bits for a valid configuration."""
+        return 4 if self.decode_weight_format == WFMT_W4G128 else self.decode_weight_bits
 
     def to_c(self) -> CVqaConfig:
         c = CVqaConfig()

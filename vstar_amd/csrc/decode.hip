@@ -56,8 +56,38 @@ __device__ __forceinline__ f32x4 w8_scale_cols(f32x4 acc, const float* __restric
   return acc * sc;
 }
 
-template <int EPI, bool OUT_F32, int MT, bool W8 = false>
+// W4 form (GemmParams::Wq4): the lane's 8 k-elements of a W row are ONE 32-bit word of offset nibbles u = q + 8,
+// element e in nibble (e >> 1) + 4 (e & 1).  With that order `x & 0x000F000F | 0x64006400` is the fp16 pair (1024 + u_e0,
+// 1024 + u_e1) and a packed subtraction of 1032 leaves (q_e0, q_e1); nibbles 1 / 5 are taken unshifted, `x & 0x00F000F0 | 0x6400...`
+// = 1024 + 16 u, and a packed fma by 1/16 and -72 leaves q exactly; one shift by 8 serves nibbles 2 / 6 and 3 / 7 the same way.
+// Then ONE packed fp16 multiply by the group scale per pair: the MFMA operand is exactly fp16(fp16(q) * s), the dequantised weight.
+__device__ __forceinline__ lpx8 w4_to_f16x8(unsigned x, lp_t scale_bits) {
+  typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+  const _Float16 sc = __builtin_bit_cast(_Float16, scale_bits);
+  const h2 s2 = {sc, sc};
+  const h2 off = {(_Float16)1032.0f, (_Float16)1032.0f};
+  const h2 r16 = {(_Float16)0.0625f, (_Float16)0.0625f}, m72 = {(_Float16)-72.0f, (_Float16)-72.0f};
+  const unsigned y = x >> 8;
+  const h2 q01 = __builtin_bit_cast(h2, (x & 0x000F000Fu) | 0x64006400u) - off;
+  const h2 q23 = __builtin_elementwise_fma(__builtin_bit_cast(h2, (x & 0x00F000F0u) | 0x64006400u), r16, m72);
+  const h2 q45 = __builtin_bit_cast(h2, (y & 0x000F000Fu) | 0x64006400u) - off;
+  const h2 q67 = __builtin_elementwise_fma(__builtin_bit_cast(h2, (y & 0x00F000F0u) | 0x64006400u), r16, m72);
+  u32x4 o;
+  o[0] = __builtin_bit_cast(unsigned, q01 * s2);
+  o[1] = __builtin_bit_cast(unsigned, q23 * s2);
+  o[2] = __builtin_bit_cast(unsigned, q45 * s2);
+  o[3] = __builtin_bit_cast(unsigned, q67 * s2);
+  return __builtin_bit_cast(lpx8, o);
+}
+
+// The W4 tile-major image (GemmParams::Wq4_tiled): per workgroup, pair j of own double steps and wave w one slot per tile.
+constexpr int W4_SLOT = 1024 + 64;          // 64 lanes x 4 words | 16 rows x 2 fp16 scales
+__host__ __device__ __forceinline__ int w4_tile_pairs(int K) { return (((K >> 6) + SK_WAVES - 1) / SK_WAVES + 1) >> 1; }
+
+// WQ: 0 = fp16 / bf16 weights (GemmParams::W), 8 = the W8 form (Wq), 4 = the W4 form (Wq4)
+template <int EPI, bool OUT_F32, int MT, int WQ = 0>
 __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmParams p) {
+  constexpr bool W8 = WQ == 8, W4 = WQ == 4;
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
   __shared__ float red[SK_WAVES][MT][64][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -66,11 +96,20 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
 
   const lp_t* wp[NT];
   const int8_t* wq[NT];            // W8: the same row and k offset, one byte per element
+  const uint32_t* w4[NT];          // W4: the same row and k offset, one word per 8 elements ...
+  const lp_t* s4[NT];              // ... and the row's group scales (a double step of 64 lies inside one group of 128)
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    wp[t] = W8 ? nullptr : p.W + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8;
+    wp[t] = WQ ? nullptr : p.W + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8;
     wq[t] = W8 ? p.Wq + (int64_t)(n0 + t * 16 + fr) * p.K + g * 8 : nullptr;
+    w4[t] = W4 ? p.Wq4 + (int64_t)(n0 + t * 16 + fr) * (p.K >> 3) + g : nullptr;
+    s4[t] = W4 ? p.wq4_scale + (int64_t)(n0 + t * 16 + fr) * (p.K >> 7) : nullptr;
   }
+  // W4, tile-major image (GemmParams::Wq4_tiled, or null): this wave's slots, pair j of tile t at img + (j * 8 NT + t) * W4_SLOT —
+  // the lane's 16 bytes are its four words of its own double steps ds = wave + 16 j and ds + 8, the two scales follow the 1 KiB
+  const char* img = (W4 && p.Wq4_tiled)
+      ? (const char*)p.Wq4_tiled + ((int64_t)blockIdx.x * w4_tile_pairs(p.K) * SK_WAVES + wave) * (NT * W4_SLOT) + lane * 16 : nullptr;
+  const int img_sc = 1024 + fr * 4 - lane * 16;          // from the lane's words to its row's scale pair
   const lp_t* ap[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
@@ -121,17 +160,40 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
 
   // K is walked in DOUBLE steps of 64 elements (two MFMA k-steps = one whole 128-byte line of every W row), interleaved
   // over the 8 waves; UH double steps (2*UH k-steps) are in flight per wave before the first MFMA consumes them.
-  constexpr int UH = (MT == 2) ? 2 : (MT == 1 ? 1 : 2);
+  // (W4: whole PAIRS of own double steps, the unit of the tile-major image; MT = 1: two pairs, 32 weight bytes per lane and tile)
+  constexpr int UH = (MT == 2) ? 2 : (MT == 1 ? (W4 ? 4 : 1) : 2);
   const int nd = p.K >> 6;
   int ds = wave;
   for (; ds + (UH - 1) * SK_WAVES < nd; ds += UH * SK_WAVES) {
     lpx8 wf[2 * UH][NT], af[2 * UH][MT];
+    u32x4 raw[W4 ? UH / 2 : 1][NT];          // W4: per pair the words of (ds, u = 0), (ds, 1), (ds + 8, 0), (ds + 8, 1) ...
+    unsigned sc2[W4 ? UH / 2 : 1][NT];       // ... and the scales of ds (low half) and ds + 8 (high half)
+    if constexpr (W4) {
+#pragma unroll
+      for (int pj = 0; pj < UH / 2; ++pj)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          if (img) {
+            const char* sl = img + ((int64_t)(((ds - wave) >> 4) + pj) * (SK_WAVES * NT) + t) * W4_SLOT;
+            raw[pj][t] = __builtin_nontemporal_load((const u32x4*)sl);
+            sc2[pj][t] = *(const unsigned*)(sl + img_sc);
+          } else {
+            const int d0 = ds + 2 * pj * SK_WAVES, d1 = d0 + SK_WAVES;
+            raw[pj][t][0] = __builtin_nontemporal_load(w4[t] + d0 * 8);
+            raw[pj][t][1] = __builtin_nontemporal_load(w4[t] + d0 * 8 + 4);
+            raw[pj][t][2] = __builtin_nontemporal_load(w4[t] + d1 * 8);
+            raw[pj][t][3] = __builtin_nontemporal_load(w4[t] + d1 * 8 + 4);
+            sc2[pj][t] = (unsigned)s4[t][d0 >> 1] | ((unsigned)s4[t][d1 >> 1] << 16);
+          }
+        }
+    }
 #pragma unroll
     for (int u = 0; u < 2 * UH; ++u) {
       const int k = (ds + (u >> 1) * SK_WAVES) * 64 + (u & 1) * 32;
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if constexpr (W8) wf[u][t] = w8_to_f16x8(__builtin_nontemporal_load((const u32x2*)(wq[t] + k)));
+        else if constexpr (W4) wf[u][t] = w4_to_f16x8(raw[W4 ? u >> 2 : 0][t][u & 3], (lp_t)(sc2[W4 ? u >> 2 : 0][t] >> (16 * ((u >> 1) & 1))));
         else wf[u][t] = __builtin_nontemporal_load((const lpx8*)(wp[t] + k));   // streamed once
       }
 #pragma unroll
@@ -153,6 +215,9 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
         for (int m = 0; m < MT; ++m) acc[t][m] = mfma_16x16x32(wf[u][t], af[u][m], acc[t][m]);
   }
   for (; ds < nd; ds += SK_WAVES) {
+    // (W4, image: own double step i = (ds - wave) / 8 is half i & 1 of pair i / 2)
+    const int i4 = (ds - wave) >> 3;
+    const char* sl = img ? img + (int64_t)(i4 >> 1) * (SK_WAVES * NT * W4_SLOT) + (i4 & 1) * 8 : nullptr;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int k = ds * 64 + h * 32;
@@ -160,6 +225,10 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_skinny_kernel(const GemmPa
       for (int t = 0; t < NT; ++t) {
         lpx8 wf;
         if constexpr (W8) wf = w8_to_f16x8(*(const u32x2*)(wq[t] + k));
+        else if constexpr (W4) {
+          if (img) wf = w4_to_f16x8(*(const unsigned*)(sl + t * W4_SLOT + h * 4), *(const lp_t*)(sl + t * W4_SLOT + img_sc - (i4 & 1) * 6));
+          else wf = w4_to_f16x8(w4[t][k >> 3], s4[t][k >> 7]);
+        }
         else wf = *(const lpx8*)(wp[t] + k);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -492,6 +561,76 @@ __global__ void skinny_tile_pack_w8_kernel(const int8_t* __restrict__ Wq, int8_t
   const int chunk = (lane & 3) ^ ((row16 >> 2) & 3);          // the source-side swizzle of the W8 ring kernel's requests
   *(u32x4*)(Wt + idx * 16) = *(const u32x4*)(Wq + row * K + ks * 64 + chunk * 16);
 }
+
+// ------------------------------------------------ int4 group-scaled weight-only decode: quantiser ------------------------
+// One workgroup per row of W [rows, K], K % 128 == 0.  A thread holds 8 consecutive elements = one word of the image; the 16
+// threads of a 128-element group are 16 consecutive lanes of one wave (K / 8 is a multiple of 16, so a group is wholly inside the
+// loop or wholly outside).  Pass 1: the group's absolute maximum over those lanes, s = min(fp16(a / 7), 9352), 1 when that is 0.
+// Pass 2, from the same registers: q = clamp(rint(w / s), +-7), the word of offset nibbles (element e in nibble (e >> 1) +
+// 4 (e & 1)), and What = fp16(q) * s as one fp16 multiply — the product w4_to_f16x8 feeds the MFMAs.  What may alias W (no
+// __restrict__ on either): a thread reads its 8 elements before it writes them and nobody else reads them.
+__global__ __launch_bounds__(256) void quantize_groups_w4_kernel(const lp_t* W, int K, uint32_t* __restrict__ q,
+                                                                 lp_t* __restrict__ scale, lp_t* What) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const lp_t* wr = W + (int64_t)row * K;
+  for (int v = tid; v * 8 < K; v += 256) {
+    const lpx8 t = *(const lpx8*)(wr + v * 8);
+    float a = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a = fmaxf(a, fabsf(lp2f((lp_t)t[e])));
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 16));
+    _Float16 sh = (_Float16)__fdiv_rn(a, 7.0f);
+    if (sh > (_Float16)9352.0f) sh = (_Float16)9352.0f;
+    if (sh == (_Float16)0.0f) sh = (_Float16)1.0f;
+    const float sc = (float)sh;
+    if ((tid & 15) == 0) scale[(int64_t)row * (K >> 7) + (v >> 4)] = __builtin_bit_cast(unsigned short, sh);
+    unsigned word = 0u;
+    lpx8 back;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float r = rintf(__fdiv_rn(lp2f((lp_t)t[e]), sc));
+      r = fminf(fmaxf(r, -7.f), 7.f);
+      const int qi = (int)r;
+      word |= (unsigned)(qi + 8) << (4 * ((e >> 1) + 4 * (e & 1)));
+      back[e] = (short)__builtin_bit_cast(unsigned short, (_Float16)((_Float16)qi * sh));
+    }
+    q[(int64_t)row * (K >> 3) + v] = word;
+    if (What) *(lpx8*)(What + (int64_t)row * K + v * 8) = back;
+  }
+}
+
+// one thread per lane of a slot of the tile-major int4 image (see GemmParams::Wq4_tiled): its four words, and (lanes 0..15) its row's
+// two scales.  Halves past the end of K (a wave with an odd count of double steps, or none) hold q = 0 (u = 8) and s = 1; the
+// kernel never reads them.
+__global__ void skinny_tile_pack_w4_kernel(const uint32_t* __restrict__ q, const lp_t* __restrict__ scale, char* __restrict__ Wt,
+                                           int K, int nt, int64_t n_threads) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_threads) return;
+  const int lane = (int)(idx & 63), fr = lane & 15, g = lane >> 4;
+  const int64_t slot = idx >> 6;
+  const int nd = K >> 6, npair = w4_tile_pairs(K);
+  const int t = (int)(slot % nt);
+  const int64_t r = slot / nt;
+  const int w = (int)(r % SK_WAVES);
+  const int64_t r2 = r / SK_WAVES;
+  const int j = (int)(r2 % npair);
+  const int64_t wg = r2 / npair;
+  const int64_t row = wg * 16 * nt + t * 16 + fr;
+  u32x4 words;
+  unsigned sc = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ds = w + 16 * j + 8 * h;
+    const bool in = ds < nd;
+    words[2 * h] = in ? q[row * (K >> 3) + ds * 8 + g] : 0x88888888u;
+    words[2 * h + 1] = in ? q[row * (K >> 3) + ds * 8 + 4 + g] : 0x88888888u;
+    sc |= (unsigned)(in ? scale[row * (K >> 7) + (ds >> 1)] : (lp_t)0x3C00) << (16 * h);
+  }
+  char* sl = Wt + slot * W4_SLOT;
+  *(u32x4*)(sl + lane * 16) = words;
+  if (g == 0) *(unsigned*)(sl + 1024 + fr * 4) = sc;
+}
 #endif
 
 template <int EPI, bool OUT_F32, bool W8 = false>
@@ -514,20 +653,24 @@ hipError_t launch_skinny_ring(const GemmParams& p0, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int EPI, bool OUT_F32, bool W8 = false>
-hipError_t launch_skinny(const GemmParams& p, hipStream_t s) {
+template <int EPI, bool OUT_F32, int WQ = 0>
+hipError_t launch_skinny(const GemmParams& p0, hipStream_t s) {
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
+  GemmParams p = p0;
+  if (p.N % (16 * NT)) p.Wq4_tiled = nullptr;                   // whole 16 NT-row tiles only, like the ring's images
   const int blocks = (p.N + 16 * NT - 1) / (16 * NT);
   const int mt = (p.M + 15) / 16;
   // M <= 8 (decode steps of up to 8 sequences; 7 with the fused norm): the LDS-ring variant, bit-identical (VSTAR_SKINNY_RING=0: the register-streaming kernel, A/B and tests);
   // the W rows it reads are padded to 256, so whole 16-row tiles exist for every workgroup
   static const bool ring = [] { const char* e = getenv("VSTAR_SKINNY_RING"); return !e || atoi(e) != 0; }();
-  if (ring && p.M <= (p.norm_w ? 7 : 8) && p.K >= 512 && p.tile_force != -1) return launch_skinny_ring<EPI, OUT_F32, W8>(p, s);   // tile_force -1: tests
+  // (WQ == 4: there is no W4 ring, the register kernel below serves every M <= 64 — bit-identical)
+  if constexpr (WQ != 4)
+    if (ring && p.M <= (p.norm_w ? 7 : 8) && p.K >= 512 && p.tile_force != -1) return launch_skinny_ring<EPI, OUT_F32, WQ == 8>(p, s);   // tile_force -1: tests
   switch (mt) {
-    case 1: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 1, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 2: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 2, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 3: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 3, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
-    case 4: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 4, W8>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 1: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 1, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 2: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 2, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 3: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 3, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
+    case 4: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 4, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1131,19 +1274,50 @@ hipError_t skinny_pack_tiles_w8(const int8_t* Wq, int8_t* Wt, int n_rows, int K,
   hipLaunchKernelGGL(skinny_tile_pack_w8_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, Wq, Wt, K, nt, n_chunks);
   return hipGetLastError();
 }
+
+size_t skinny_tiles_w4_bytes(int n_rows, int K, int nt) {
+  return (size_t)(n_rows / (16 * nt)) * w4_tile_pairs(K) * SK_WAVES * nt * W4_SLOT;
+}
+
+hipError_t skinny_pack_tiles_w4(const uint32_t* q, const lp_t* scale, void* Wt, int n_rows, int K, int nt, hipStream_t s) {
+  if (!q || !scale || !Wt || n_rows <= 0 || K <= 0 || K % 128 || (nt != 1 && nt != 2) || n_rows % (16 * nt)) return hipErrorInvalidValue;
+  const int64_t n_threads = (int64_t)(skinny_tiles_w4_bytes(n_rows, K, nt) / W4_SLOT) * 64;
+  hipLaunchKernelGGL(skinny_tile_pack_w4_kernel, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, s, q, scale, (char*)Wt, K, nt,
+                     n_threads);
+  return hipGetLastError();
+}
+
+hipError_t quantize_groups_w4(const lp_t* W, int rows, int K, uint32_t* q, lp_t* scale, lp_t* What, hipStream_t s) {
+  if (!W || !q || !scale || rows <= 0 || K <= 0 || K % 128) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(quantize_groups_w4_kernel, dim3(rows), dim3(256), 0, s, W, K, q, scale, What);
+  return hipGetLastError();
+}
 #endif
 
 hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
   if (!gemm_skinny_eligible(p)) return hipErrorInvalidValue;
+  if (p.Wq4) {             // int4 group-scaled weights (GemmParams::Wq4): fp16 build, 16-bit output, whole groups of 128
+#ifdef VSTAR_LP_F16
+    if (p.Wq || !p.wq4_scale || out_f32 || p.K % 128) return hipErrorInvalidValue;
+    switch (epilogue) {
+      case VSTAR_EPI_NONE: return launch_skinny<VSTAR_EPI_NONE, false, 4>(p, s);
+      case VSTAR_EPI_QUICK_GELU: return launch_skinny<VSTAR_EPI_QUICK_GELU, false, 4>(p, s);
+      case VSTAR_EPI_GELU: return launch_skinny<VSTAR_EPI_GELU, false, 4>(p, s);
+      case VSTAR_EPI_RELU: return launch_skinny<VSTAR_EPI_RELU, false, 4>(p, s);
+      case VSTAR_EPI_SILU_MUL: return launch_skinny<VSTAR_EPI_SILU_MUL, false, 4>(p, s);
+    }
+#endif
+    return hipErrorInvalidValue;
+  }
   if (p.Wq) {              // int8 weights (GemmParams::Wq): fp16 build, 16-bit output
 #ifdef VSTAR_LP_F16
     if (!p.wq_scale || out_f32) return hipErrorInvalidValue;
     switch (epilogue) {
-      case VSTAR_EPI_NONE: return launch_skinny<VSTAR_EPI_NONE, false, true>(p, s);
-      case VSTAR_EPI_QUICK_GELU: return launch_skinny<VSTAR_EPI_QUICK_GELU, false, true>(p, s);
-      case VSTAR_EPI_GELU: return launch_skinny<VSTAR_EPI_GELU, false, true>(p, s);
-      case VSTAR_EPI_RELU: return launch_skinny<VSTAR_EPI_RELU, false, true>(p, s);
-      case VSTAR_EPI_SILU_MUL: return launch_skinny<VSTAR_EPI_SILU_MUL, false, true>(p, s);
+      case VSTAR_EPI_NONE: return launch_skinny<VSTAR_EPI_NONE, false, 8>(p, s);
+      case VSTAR_EPI_QUICK_GELU: return launch_skinny<VSTAR_EPI_QUICK_GELU, false, 8>(p, s);
+      case VSTAR_EPI_GELU: return launch_skinny<VSTAR_EPI_GELU, false, 8>(p, s);
+      case VSTAR_EPI_RELU: return launch_skinny<VSTAR_EPI_RELU, false, 8>(p, s);
+      case VSTAR_EPI_SILU_MUL: return launch_skinny<VSTAR_EPI_SILU_MUL, false, 8>(p, s);
     }
 #endif
     return hipErrorInvalidValue;

@@ -63,6 +63,18 @@ struct GemmParams {
   // (l % 4) ^ ((row / 4) % 4) of that row's 64 bytes, so that LDS holds row r at r * 64 with its 16-byte chunks swizzled by
   // (r / 4) % 4 and the 8-byte fragment reads of rows r, r + 4, r + 8, r + 12 fall into different banks (skinny_pack_tiles_w8).
   const int8_t* Wq; const float* wq_scale; const int8_t* Wq_tiled;
+  // gemm_skinny_kernel only, fp16 build: int4 group-scaled weights with fp16 activations (W4A16, groups of 128).
+  // Wq4 != null => the weight operand is Wq4 [ceil(N/256)*256, K / 8] 32-bit words (eight offset nibbles u = q + 8 each: element e of
+  // a word in nibble (e >> 1) + 4 (e & 1)) and wq4_scale [ceil(N/256)*256, K / 128] fp16 bits, one scale per row and 128 k
+  // (K % 128 == 0).  Every MFMA sees fp16(fp16(q) * s), ONE fp16 multiply per weight in registers, in place of W: the kernel is
+  // bit-identical to the fp16 kernel on the dequantised weights, there is no post-scale.  W is then not read.
+  // Wq4_tiled (or null): the TILE-MAJOR image, read INSTEAD of Wq4 / wq4_scale: [N / (16 NT)][pairs][8 waves][NT] slots of 1088 B,
+  // pairs = ceil(ceil(K / 64 / 8) / 2).  Slot (j, w, t) belongs to wave w: lane l = fr + 16 g holds at l * 16 its four words of its
+  // OWN two consecutive double steps ds = w + 16 j and ds + 8 of row fr of tile t — (ds, k-step 0), (ds, 1), (ds + 8, 0), (ds + 8, 1)
+  // — so a wave fetches them with ONE fully coalesced 1-KiB load where the row-major words cost four loads of 16 rows x 16 B; the
+  // 64 bytes behind them are the rows' scale pairs (s[ds / 2], s[(ds + 8) / 2]) at 1024 + fr * 4 (skinny_pack_tiles_w4).  Wave
+  // ownership of the double steps, and with it the MFMA order, is unchanged.
+  const uint32_t* Wq4; const uint16_t* wq4_scale; const void* Wq4_tiled;
   // gemm4w only, W8A8 with block-scaled activations (mx.hpp; round 6).  a_mx != null: A holds fp8 bytes whose E8M0
   // block scales (one per row and 32 k, tile-major: mx_scale_offset with m128 = M / 128) are applied inside the MFMA; w_scale as above.
   // c_mx != null (VSTAR_EPI_SILU_MUL): the epilogue writes SiLU(gate) * up as fp8 bytes to (uint8_t*)C (ldc in bytes) and the block
@@ -110,6 +122,15 @@ hipError_t skinny_pack_tiles(const lp_t* W, lp_t* Wt, int n_rows, int K, int nt,
 hipError_t quantize_rows_w8(const lp_t* W, int rows, int K, int8_t* q, float* scale, lp_t* What, hipStream_t s);
 // the tile-major int8 image (GemmParams::Wq_tiled) of the row-major Wq [n_rows][K]; n_rows % (16 nt) == 0, K % 64 == 0
 hipError_t skinny_pack_tiles_w8(const int8_t* Wq, int8_t* Wt, int n_rows, int K, int nt, hipStream_t s);
+// ---- int4 group-scaled weight-only decode (W4A16; fp16 build only) ----
+// Per row n of W [rows, K] (fp16, K % 128 == 0) and group j of 128 k: a = max|W[n, 128 j ..]|, s = min(fp16(float(a) / 7.0f), 9352),
+// 1 when that is 0; q = clamp(rint(float(W) / float(s)), -7, 7).  q [rows, K / 8] words (GemmParams::Wq4), scale [rows, K / 128]
+// fp16.  What (nullable, may alias W): fp16(q) * s, one fp16 multiply.  One workgroup per row.
+hipError_t quantize_groups_w4(const lp_t* W, int rows, int K, uint32_t* q, lp_t* scale, lp_t* What, hipStream_t s);
+// the tile-major int4 image (GemmParams::Wq4_tiled) of the row-major q [n_rows][K / 8] and scale [n_rows][K / 128];
+// n_rows % (16 nt) == 0, K % 128 == 0; Wt holds skinny_tiles_w4_bytes(n_rows, K, nt) bytes
+size_t skinny_tiles_w4_bytes(int n_rows, int K, int nt);
+hipError_t skinny_pack_tiles_w4(const uint32_t* q, const lp_t* scale, void* Wt, int n_rows, int K, int nt, hipStream_t s);
 #endif
 
 // ---- KV-cached language model + Perceiver resampler (decode.hip) ----

@@ -86,12 +86,16 @@ struct LlmCachedCfg {
   int hidden = 0, heads = 0, mlp = 0, layers = 0, vocab = 0;
   float rms_eps = 1e-6f, rope_theta = 10000.f;
   int max_slots = 1, max_ctx = 1024, max_rows = 1024;
-  int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only)
+  int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only);
+                            // 4: int4 with one fp16 scale per group of 128 (fp16 build only)
 };
 
 // int8 decode copies of one block linear: row-major q [Npad, K] + per-row scales [Npad] for the register kernel
 // and the row-major ring, and the tile-major image for the ring (null where the fp16 path would have none either)
 struct LinW8 { int8_t* q = nullptr; float* s = nullptr; int8_t* qt = nullptr; };
+// int4 decode copies of one block linear: row-major words q [Npad, K / 8] + group scales s [Npad, K / 128] (fp16)
+// and the tile-major image of both (GemmParams::Wq4_tiled; null with VSTAR_DECODE_TILED=0 or without whole 16 NT-row tiles)
+struct LinW4 { uint32_t* q = nullptr; lp_t* s = nullptr; void* qt = nullptr; };
 
 struct LlmCached {
   EngineBase* e = nullptr;
@@ -154,6 +158,10 @@ struct LlmCached {
   std::vector<LinW8> w8_qkv, w8_o, w8_gate_up, w8_down;
   int build_w8();
   const LinW8* w8(const std::vector<LinW8>& v, int i) const { return v.empty() ? nullptr : &v[(size_t)i]; }
+  // ---- int4 group-scaled weight-only decode (cfg.weight_bits == 4): the same arrangement ----
+  std::vector<LinW4> w4_qkv, w4_o, w4_gate_up, w4_down;
+  int build_w4();
+  const LinW4* w4(const std::vector<LinW4>& v, int i) const { return v.empty() ? nullptr : &v[(size_t)i]; }
 
   void set_error(const std::string& m) { e->set_error(m); }
   int init(EngineBase* owner, const LlmCachedCfg& c, const lp_t* embed_, const std::vector<LlmBlock>* blocks_,
@@ -170,9 +178,10 @@ struct LlmCached {
   int decode_step_body(int keys_bound);
   int decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids, int* n_out, bool* used);
   int lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
-               const lp_t* res = nullptr, int64_t ldr = 0, const lp_t* Wt = nullptr, const LinW8* q8 = nullptr);
+               const lp_t* res = nullptr, int64_t ldr = 0, const lp_t* Wt = nullptr, const LinW8* q8 = nullptr,
+               const LinW4* q4 = nullptr);
   int lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M, int epi,
-               const lp_t* Wt = nullptr, const LinW8* q8 = nullptr);
+               const lp_t* Wt = nullptr, const LinW8* q8 = nullptr, const LinW4* q4 = nullptr);
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
@@ -258,7 +267,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
      // OPTIONAL: the row-major weights serve the same GEMV (W_tiled == nullptr), so a failed allocation or pack — ~11.8 GB more at
      // 7B — drops the copies, clears the error and continues row-major instead of failing generate().
     const char* env = getenv("VSTAR_DECODE_TILED");
-    const bool on = !(env && atoi(env) == 0) && c.weight_bits != 8;      // (the int8 mode builds its own images: build_w8)
+    const bool on = !(env && atoi(env) == 0) && c.weight_bits == 0;      // (the int8 mode builds its own images: build_w8; int4 has none)
     wt_qkv.clear(); wt_gate_up.clear(); wt_down.clear();      // a retried init starts from empty lists: wt_*[i] is layer i or nothing
     std::vector<void*> mine;                                  // this block's allocations, freed together if any step fails
     bool ok = true;
@@ -296,6 +305,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
     }
   }
   if (c.weight_bits == 8) RC(build_w8());
+  else if (c.weight_bits == 4) RC(build_w4());
   else if (c.weight_bits != 0) { set_error("decode_weight_bits must be 0 or 8"); return VSTAR_ERR_INVALID; }
   ready = true;
   return 0;
@@ -371,6 +381,74 @@ inline int LlmCached::build_w8() {
 #endif
 }
 
+// The int4 group-scaled decode mode: build_w8's rules.  Every int4 buffer is allocated and filled first (a failure
+// there is an error with the fp16 masters untouched), then the masters are overwritten with fp16(q) * s; a failure during that
+// overwrite leaves `ready` false.  Scales belong to rows of the packed matrices, whose gate|up interleave and q|k|v concatenation
+// only permute rows of the original ones.
+inline int LlmCached::build_w4() {
+#ifdef VSTAR_LP_F16
+  const LlmCachedCfg& c = cfg;
+  std::vector<void*> mine;
+  auto fail = [&](const std::string& m, int rc) {
+    for (void* q : mine) hipFree(q);
+    (void)hipGetLastError();
+    w4_qkv.clear(); w4_o.clear(); w4_gate_up.clear(); w4_down.clear();
+    set_error(m);
+    return rc;
+  };
+  auto take = [&](size_t bytes) -> void* {
+    void* t = nullptr;
+    if (hipMalloc(&t, bytes) != hipSuccess) return nullptr;
+    mine.push_back(t);
+    return t;
+  };
+  const char* env = getenv("VSTAR_DECODE_TILED");
+  const bool tiled_on = !(env && atoi(env) == 0);
+  auto quant = [&](const Lin& L, int nt, LinW4* out) -> int {
+    const int npad = (L.N + 255) / 256 * 256;
+    if (L.K % 128) return VSTAR_ERR_INVALID;
+    out->q = (uint32_t*)take((size_t)npad * (L.K / 8) * sizeof(uint32_t));
+    out->s = (lp_t*)take((size_t)npad * (L.K / 128) * sizeof(lp_t));
+    if (!out->q || !out->s) return VSTAR_ERR_NOMEM;
+    if (quantize_groups_w4(L.W, npad, L.K, out->q, out->s, nullptr, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    if (tiled_on && L.N % (16 * nt) == 0) {
+      out->qt = take(skinny_tiles_w4_bytes(L.N, L.K, nt));
+      if (!out->qt) return VSTAR_ERR_NOMEM;
+      if (skinny_pack_tiles_w4(out->q, out->s, out->qt, L.N, L.K, nt, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    }
+    return 0;
+  };
+  w4_qkv.assign((size_t)c.layers, LinW4{}); w4_o.assign((size_t)c.layers, LinW4{});
+  w4_gate_up.assign((size_t)c.layers, LinW4{}); w4_down.assign((size_t)c.layers, LinW4{});
+  for (int i = 0; i < c.layers; ++i) {
+    const LlmBlock& b = (*blocks)[i];
+    int rc = quant(b.qkv, 1, &w4_qkv[i]);
+    if (!rc) rc = quant(b.o, 1, &w4_o[i]);
+    if (!rc) rc = quant(b.gate_up, 2, &w4_gate_up[i]);
+    if (!rc) rc = quant(b.down, 1, &w4_down[i]);
+    if (rc) return fail("int4 decode weights (decode_weight_format = 1): allocation or quantiser launch failed (layer " + std::to_string(i) + ")", rc);
+  }
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int4 decode weights: quantiser failed", VSTAR_ERR_HIP);
+  // every int4 buffer exists: now the masters become the dequantised weights (same q, same scales: deterministic)
+  for (int i = 0; i < c.layers; ++i) {
+    const LlmBlock& b = (*blocks)[i];
+    const Lin* ls[4] = {&b.qkv, &b.o, &b.gate_up, &b.down};
+    const LinW4* qs[4] = {&w4_qkv[i], &w4_o[i], &w4_gate_up[i], &w4_down[i]};
+    for (int j = 0; j < 4; ++j) {
+      const int npad = (ls[j]->N + 255) / 256 * 256;
+      if (quantize_groups_w4(ls[j]->W, npad, ls[j]->K, qs[j]->q, qs[j]->s, ls[j]->W, e->stream) != hipSuccess)
+        return fail("int4 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+    }
+  }
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int4 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+  for (void* q : mine) e->allocs.push_back(q);
+  return 0;
+#else
+  set_error("decode_weight_format = 1 needs the fp16 engine");
+  return VSTAR_ERR_INVALID;
+#endif
+}
+
 #define LCHK(expr)                                                                           \
   do {                                                                                       \
     hipError_t _e = (expr);                                                                  \
@@ -382,12 +460,13 @@ inline int LlmCached::build_w8() {
 
 // GEMM dispatch for the language model: weight-streaming kernel for decode-sized M, MFMA tile kernels otherwise
 inline int LlmCached::lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi, const lp_t* res,
-                               int64_t ldr, const lp_t* Wt, const LinW8* q8) {
+                               int64_t ldr, const lp_t* Wt, const LinW8* q8, const LinW4* q4) {
   GemmParams p{};
   p.A = A; p.lda = lda; p.W = L.W; p.bias = L.b; p.res = res; p.ldr = ldr; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
   p.W_tiled = Wt;
   if (gemm_skinny_eligible(p)) {
     if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }      // int8 decode mode: the W8 forms of the same kernels
+    if (q4) { p.Wq4 = q4->q; p.wq4_scale = q4->s; p.Wq4_tiled = q4->qt; }   // int4 decode mode: the W4 form of the register kernel
     const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
     if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
     return 0;
@@ -398,7 +477,7 @@ inline int LlmCached::lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C
 // RMSNorm + Linear: for decode-sized M the norm is fused into the weight-streaming GEMM's operand load (bit-identical to
 // the two-kernel form), otherwise norm kernel into `scratch`, then the GEMM
 inline int LlmCached::lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M,
-                               int epi, const lp_t* Wt, const LinW8* q8) {
+                               int epi, const lp_t* Wt, const LinW8* q8, const LinW4* q4) {
   const int H = cfg.hidden;
   GemmParams p{};
   p.A = x; p.lda = H; p.W = L.W; p.bias = L.b; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
@@ -406,12 +485,13 @@ inline int LlmCached::lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch,
   if (M <= 16 && L.K == H && gemm_skinny_eligible(p)) {
     p.norm_w = norm_w; p.norm_eps = cfg.rms_eps;
     if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }
+    if (q4) { p.Wq4 = q4->q; p.wq4_scale = q4->s; p.Wq4_tiled = q4->qt; }
     const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
     if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
     return 0;
   }
   LCHK(rmsnorm_lp(x, norm_w, scratch, M, H, cfg.rms_eps, nullptr, e->stream));
-  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, Wt, q8);
+  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, Wt, q8, q4);
 }
 
 inline int LlmCached::llm_layers_prefill(int nseq, int S) {
@@ -442,15 +522,17 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
     const LlmBlock& b = (*blocks)[i];
     lp_t* kc = kcache + (int64_t)i * layer_stride;
     lp_t* vc = vcache + (int64_t)i * layer_stride;
-    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i], w8(w8_qkv, i)));
+    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i], w8(w8_qkv, i),
+                w4(w4_qkv, i)));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
     if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream));
     LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
                           c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc));
-    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, nullptr, w8(w8_o, i)));
+    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, nullptr, w8(w8_o, i), w4(w4_o, i)));
     RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i],
-                w8(w8_gate_up, i)));
-    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i], w8(w8_down, i)));
+                w8(w8_gate_up, i), w4(w4_gate_up, i)));
+    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i], w8(w8_down, i),
+                w4(w4_down, i)));
   }
   return 0;
 }

@@ -146,7 +146,7 @@ int vstar_vqa_engine::finalize() {
     rc.hidden = H; rc.heads = c.llm_heads; rc.mlp = c.llm_mlp; rc.layers = c.llm_layers; rc.vocab = c.llm_vocab;
     rc.rms_eps = c.llm_rms_eps; rc.rope_theta = c.llm_rope_theta;
     rc.max_slots = c.max_slots; rc.max_ctx = c.max_ctx; rc.max_rows = c.max_rows;
-    rc.weight_bits = c.decode_weight_bits;
+    rc.weight_bits = c.decode_weight_format == VSTAR_VQA_WFMT_W4G128 ? 4 : c.decode_weight_bits;
     RC(run.init(this, rc, embed, &llm, final_norm, &lm_head));
     run.feats = feats;
     run.n_feat_rows = (int64_t)c.max_images * (P + L);
@@ -262,6 +262,12 @@ int vstar_vqa_create(const vstar_vqa_config* cfg, int device, vstar_vqa_handle**
   }
   if (cfg->decode_weight_bits != 0 && cfg->decode_weight_bits != 8) {
     tls_error() = "decode_weight_bits must be 0 (fp16 weights) or 8 (int8 weight-only decode)";
+    return VSTAR_ERR_INVALID;
+  }
+  if (cfg->decode_weight_format != 0 &&
+      (cfg->decode_weight_format != VSTAR_VQA_WFMT_W4G128 || cfg->decode_weight_bits != 0 || cfg->llm_hidden % 128 || cfg->llm_mlp % 128)) {
+    tls_error() = "decode_weight_format must be 0 or 1 (int4, groups of 128: needs decode_weight_bits == 0, llm_hidden % 128 == 0 and "
+                  "llm_mlp % 128 == 0)";
     return VSTAR_ERR_INVALID;
   }
   int n = 0;
@@ -489,7 +495,10 @@ int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void
   return op_result(e, "vstar_vqa_op_gemm");
 }
 
-int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h) { return (h && h->finalized && !h->run.w8_qkv.empty()) ? 8 : 0; }
+int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h) {
+  if (!h || !h->finalized) return 0;
+  return !h->run.w4_qkv.empty() ? 4 : (!h->run.w8_qkv.empty() ? 8 : 0);
+}
 
 int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q_i8, float* dev_scale_f32, void* dev_What_f16) {
   if (!dev_W_f16 || !dev_q_i8 || !dev_scale_f32 || rows <= 0 || K <= 0 || K % 8) {
@@ -523,6 +532,40 @@ int vstar_vqa_op_gemm_w8(const void* A, const void* Wq, const float* scale, cons
   if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, false, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   return op_result(e, "vstar_vqa_op_gemm_w8");
+}
+
+int vstar_vqa_op_quantize_w4(const void* dev_W_f16, int rows, int K, void* dev_q_u32, void* dev_scale_f16, void* dev_What_f16) {
+  if (!dev_W_f16 || !dev_q_u32 || !dev_scale_f16 || rows <= 0 || K <= 0 || K % 128) {
+    tls_error() = "vstar_vqa_op_quantize_w4: bad argument (K must be a multiple of 128)";
+    return VSTAR_ERR_INVALID;
+  }
+  hipError_t e = quantize_groups_w4((const lp_t*)dev_W_f16, rows, K, (uint32_t*)dev_q_u32, (lp_t*)dev_scale_f16, (lp_t*)dev_What_f16, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, "vstar_vqa_op_quantize_w4");
+}
+
+int vstar_vqa_op_gemm_w4(const void* A, const void* Wq, const void* scale, const void* bias, const void* res, void* C, int M, int N,
+                         int K, int epilogue, int kernel, const void* norm_w, float norm_eps, int layout) {
+  if (!A || !Wq || !scale || !C || M <= 0 || N <= 0 || K <= 0 || K % 128 || (kernel != 1 && kernel != 3) || (layout != 0 && layout != 1)) {
+    tls_error() = "vstar_vqa_op_gemm_w4: bad argument (kernel 1 or 3, layout 0 or 1, K % 128 == 0, weights and scales not null)";
+    return VSTAR_ERR_INVALID;
+  }
+  const int nt = epilogue == VSTAR_EPI_SILU_MUL ? 2 : 1;
+  GemmParams p{};
+  const int n_out = epilogue == VSTAR_EPI_SILU_MUL ? N / 2 : N;
+  p.A = (const lp_t*)A; p.lda = K; p.Wq4 = (const uint32_t*)Wq; p.wq4_scale = (const uint16_t*)scale; p.bias = (const lp_t*)bias;
+  p.res = (const lp_t*)res; p.ldr = n_out; p.C = C; p.ldc = n_out; p.M = M; p.N = N; p.K = K;
+  p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
+  if (kernel == 3) p.tile_force = -1;
+  if (!gemm_skinny_eligible(p)) { tls_error() = "vstar_vqa_op_gemm_w4: outside the weight-streaming kernels' domain (M <= 64)"; return VSTAR_ERR_INVALID; }
+  if (layout == 1 && N % (16 * nt)) { tls_error() = "vstar_vqa_op_gemm_w4: the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
+  hipError_t e = hipSuccess;
+  OpBuf<char> tiles(e, skinny_tiles_w4_bytes(N, K, nt), layout == 1);
+  if (layout == 1 && e == hipSuccess) e = skinny_pack_tiles_w4((const uint32_t*)Wq, (const lp_t*)scale, tiles, N, K, nt, nullptr);
+  p.Wq4_tiled = tiles;
+  if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, false, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, "vstar_vqa_op_gemm_w4");
 }
 
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t cap) {

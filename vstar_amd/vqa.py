@@ -125,8 +125,8 @@ class VQA_LLM:
                  tokenizer=None, engine: Optional[VqaEngine] = None, device: int = 0, decode_weight_bits: Optional[int] = None):
         """args: the reference's namespace (vqa_model_path, conv_type).  With a local checkpoint directory the weights and
         tokenizer are read from it; offline pass `state_dict` (+ optionally `tokenizer`).  decode_weight_bits=8 builds the
-        engine in the int8 weight-only decode mode (None = what `cfg` says, 0 by default)."""
-        import dataclasses
+        engine in the int8 weight-only decode mode, 4 in the int4 group-scaled mode (§8.6: translated to
+        decode_weight_format=1 by VQAConfig.with_decode_bits); None = what `cfg` says, 0 by default."""
         import os
         from .weights import load_vqa_checkpoint_dir, vqa_config_from_dir
         path = getattr(args, "vqa_model_path", None) if args is not None else None
@@ -139,10 +139,10 @@ class VQA_LLM:
                 tokenizer = AutoTokenizer.from_pretrained(path, use_fast=False)
                 tokenizer.add_tokens(["<im_patch>"], special_tokens=True)      # mm_use_im_patch_token default (builder.py:131-133)
         self.cfg = cfg or (engine.cfg if engine is not None else VQAConfig.seal_7b())
-        if decode_weight_bits is not None and decode_weight_bits != self.cfg.decode_weight_bits:
+        if decode_weight_bits is not None and decode_weight_bits != self.cfg.decode_bits():
             if engine is not None:
                 raise ValueError("decode_weight_bits is fixed when the engine is built: pass it in the engine's VQAConfig")
-            self.cfg = dataclasses.replace(self.cfg, decode_weight_bits=int(decode_weight_bits))
+            self.cfg = self.cfg.with_decode_bits(decode_weight_bits)
         self.conv_type = getattr(args, "conv_type", "v1") if args is not None else "v1"
         if self.conv_type != "v1":
             raise ValueError("only the 'v1' conversation template of the reference evaluation is implemented")

@@ -220,7 +220,8 @@ class VqaEngine:
         _lib.check_vqa(self.lib.vstar_vqa_kv_copy(self.handle, int(dst), int(src), int(lo), int(hi)), self.handle)
 
     def decode_weight_bits(self) -> int:
-        """8 when the int8 weight-only decode mode is active (finalized engine built with decode_weight_bits=8), else 0."""
+        """8 when the int8 weight-only decode mode is active (finalized engine built with decode_weight_bits=8), 4 in the int4
+        group-scaled mode (decode_weight_format=1), else 0."""
         return int(self.lib.vstar_vqa_decode_weight_bits(self.handle))
 
     def last_forward_ms(self) -> float:

@@ -25,8 +25,9 @@ def parse_args(argv):
     p.add_argument("--vqa-llm", default=None, help="module:factory providing another VQA-LLM implementation")
     p.add_argument("--vsm-factory", default=None, help="module:factory(args, device) providing another VSM implementation")
     p.add_argument("--device", default=0, type=int)
-    p.add_argument("--vqa-decode-bits", dest="vqa_decode_bits", default=0, type=int, choices=[0, 8],
-                   help="8: the VQA-LLM's int8 weight-only decode mode (DESIGN.md 8.4); 0: fp16 weights everywhere")
+    p.add_argument("--vqa-decode-bits", dest="vqa_decode_bits", default=0, type=int, choices=[0, 4, 8],
+                   help="8: the VQA-LLM's int8 weight-only decode mode (DESIGN.md 8.4); 4: its int4 group-scaled mode (8.6); "
+                        "0: fp16 weights everywhere")
     p.add_argument("--search-window", dest="search_window", default=0, type=int, help="concurrent visual searches per engine batch "
                    "(cross-image lock step); 0 = one engine batch, 1 = one image at a time like the reference")
     p.add_argument("--vqa-batch", dest="vqa_batch", default=1, type=int, help="questions per VQA-LLM engine call in the free-form and "
