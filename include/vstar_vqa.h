@@ -61,10 +61,16 @@ typedef struct vstar_vqa_config {
   int32_t decode_weight_format; /* 0 (default) = decode_weight_bits alone decides; VSTAR_VQA_WFMT_W4G128 (1) = int4 group-scaled
                                * weight-only decode (one fp16 scale per 128 input channels): needs decode_weight_bits
                                * == 0, llm_hidden % 128 == 0 and llm_mlp % 128 == 0; anything else fails at create */
-  int32_t reserved[6];
+  int32_t kv_cache_format;    /* 0 (default) = fp16 KV cache; VSTAR_VQA_KVFMT_MXFP8 (1) = block-scaled fp8 (MX e4m3, blocks of 32: 132
+                               * bytes per cached row instead of 256); VSTAR_VQA_KVFMT_MXFP8_EMULATED (2) = the same values held in the
+                               * fp16 cache (yardstick / study tool), see vstar_vqa_kv_cache_format; anything else fails at create.
+                               * Independent of decode_weight_bits / decode_weight_format */
+  int32_t reserved[5];
 } vstar_vqa_config;
 
 #define VSTAR_VQA_WFMT_W4G128 1 /* vstar_vqa_config.decode_weight_format */
+#define VSTAR_VQA_KVFMT_MXFP8 1          /* vstar_vqa_config.kv_cache_format */
+#define VSTAR_VQA_KVFMT_MXFP8_EMULATED 2
 
 typedef struct vstar_vqa_engine vstar_vqa_handle;
 
@@ -255,7 +261,31 @@ int vstar_vqa_op_gemm_w4(const void* dev_A, const void* dev_Wq, const void* dev_
                          const void* dev_residual, void* dev_C, int M, int N, int K, int epilogue, int kernel,
                          const void* dev_norm_w, float norm_eps, int layout);
 
-/* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float. Returns elements written. */
+/* Block-scaled fp8 KV cache, opt-in through vstar_vqa_config.kv_cache_format.  Every cached row — the 128 values of
+ * one (layer, slot, head, position) of K (after RoPE) and likewise of V — is cut into 4 blocks of 32 consecutive head-dim elements;
+ * a block stores one E8M0 byte e, 2^(e - 127) being the smallest power of two that brings the block's largest magnitude to <= 448
+ * (integer arithmetic on the fp32 bits of amax = 1.f x 2^E: e = E + 127 - 8, one more when 1.f > 1.75; 0 for an all-zero block), and
+ * the OCP e4m3 codes rne_e4m3(x * 2^(127 - e)).  The row's value is code * 2^(e - 127) from then on, for every reader: the prefill
+ * attends to the round-tripped K and V too, and a decode step attends to its own row's round-tripped values.
+ *   VSTAR_VQA_KVFMT_MXFP8 (1): codes u8 [layer][slot][head][ctx][128] and scale bytes u8 [layer][slot][head][ctx][4], for K and for V;
+ *     the attention kernels decode in registers (one exact fp32 multiply per element) and are otherwise the fp16 kernels: same lane
+ *     geometry, same accumulation order.
+ *   VSTAR_VQA_KVFMT_MXFP8_EMULATED (2): the fp16 cache and the fp16 readers; the writers store fp16(code * 2^(e - 127)).
+ * For fp16 inputs with |x| < 63488 the decoded value is exactly representable in fp16, so an engine in mode 1 is BIT-IDENTICAL to one in
+ * mode 2 in every call.  Rows holding |x| >= 63488 (the top grid point decodes to 65536, +inf in fp16) or non-finite values are outside
+ * that claim; they do not fault.  fp16 engine only.  Returns the active format (the config's value). */
+int vstar_vqa_kv_cache_format(const vstar_vqa_handle* h);
+/* Bytes of K plus V storage of a finalized engine, scale bytes included: 2 * layers * max_slots * heads * max_ctx * 128 * 2 in formats 0
+ * and 2, 2 * layers * max_slots * heads * max_ctx * 132 in format 1 (0 before finalize_weights). */
+int64_t vstar_vqa_kv_cache_bytes(const vstar_vqa_handle* h);
+/* Op-level quantiser (tests): DEVICE x [rows, 128] fp16 -> codes u8 [rows, 128], scale bytes u8 [rows, 4] and (nullable, may alias x)
+ * xhat fp16 [rows, 128] = the decoded row, through the device function every mode-1 / mode-2 writer quantises with.  Null stream,
+ * synchronises. */
+int vstar_vqa_op_kv_quantize(const void* dev_x_f16, int rows, void* dev_codes_u8, void* dev_scales_u8, void* dev_xhat_f16);
+
+/* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float; "kv:<layer>:<slot>" = the DECODED K then V
+ * cache of that layer and slot as floats [2][llm_heads][max_ctx][128], in every kv_cache_format (an index out of range is an error).
+ * Returns elements written. */
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t capacity);
 /* Timing of the last forward call in milliseconds (HIP events on the engine stream). */
 double vstar_vqa_last_forward_ms(const vstar_vqa_handle* h);

@@ -18,6 +18,10 @@ weight-only decode mode and the int4 group-scaled mode (§8.6)
 --rounds times at every batch size; tokens/s and the effective weight stream of each (bytes a step actually reads: the quantised
 block linears with their scales + the fp16 lm_head), the ratios against fp16 (and 4-bit against 8-bit) and the spread over the
 rounds.  The yardsticks of the 4-bit mode are the same process's fp16 and 8-bit engines.
+--kv-bits 0,8 runs `decode_kv` ALONE: for every weight mode of --decode-bits (default 0 alone) two engines in one
+process on the same weights — the fp16 KV cache and the block-scaled fp8 cache — greedy decode blocks of --steps alternated --rounds
+times at every batch size, each sequence holding --ctx cached positions (700: an image, a prompt and an answer; 1800: near the 2048
+context); tokens/s of both (median over the blocks), their ratio, the spread, and the K/V bytes a step reads in each format.
 --spec 1,3,6 runs `decode_spec` ALONE: one sequence (~300 cached positions), first a plain greedy decode of
 --spec-tokens tokens, then for every draft length d and every share of corrupted draft positions in --spec-corrupt (a replay
 drafter proposing that output: 1.0 = acceptance 0, 0.0 = acceptance 1) `VQA_LLM.speculative_decode` blocks alternated --rounds
@@ -57,6 +61,9 @@ def main():
     ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
     ap.add_argument("--only-score", action="store_true", help="run the --score leg alone")
     ap.add_argument("--decode-bits", default="", help="'0,8' or '0,8,4': fp16 against the int8 / int4 weight-only decode modes, alternated blocks (runs alone)")
+    ap.add_argument("--kv-bits", default="", help="'0,8': the fp16 KV cache against the block-scaled fp8 cache, alternated blocks, crossed "
+                    "with --decode-bits (runs alone)")
+    ap.add_argument("--ctx", type=int, default=296, help="--kv-bits: cached positions per sequence when the decode blocks start")
     ap.add_argument("--spec", default="", help="comma-separated draft lengths: speculative against plain greedy decode (runs alone)")
     ap.add_argument("--spec-tokens", type=int, default=64, help="--spec: tokens decoded per block")
     ap.add_argument("--spec-corrupt", default="1.0,0.5,0.0", help="--spec: shares of corrupted draft positions")
@@ -66,6 +73,14 @@ def main():
     score_b = [int(x) for x in a.score.split(",")] if a.score else []
     if a.only_score and not score_b:
         ap.error("--only-score needs --score B[,B...]")
+    if a.kv_bits:
+        if [int(x) for x in a.kv_bits.split(",")] != [0, 8]:
+            ap.error("--kv-bits takes 0,8")
+        wbits = [int(x) for x in a.decode_bits.split(",")] if a.decode_bits else [0]
+        if not set(wbits) <= {0, 4, 8}:
+            ap.error("--decode-bits takes 0, 8 and 4")
+        out = {"decode_kv": decode_kv(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds, wbits, a.ctx)}
+        return finish(out, a)
     if a.decode_bits:
         bits = [int(x) for x in a.decode_bits.split(",")]
         if bits[0] != 0 or len(set(bits)) != len(bits) or not set(bits) <= {0, 4, 8} or len(bits) < 2:
@@ -260,6 +275,67 @@ def decode_bits(layers, batches, steps, rounds, modes=(0, 8)):
                 leg[f"bits{x}_over_bits{y}_tokens_per_s"] = round(leg[f"bits{x}"]["tokens_per_s"] / leg[f"bits{y}"]["tokens_per_s"], 3)
                 leg[f"bits{x}_over_bits{y}_device_time"] = round(leg[f"bits{x}"]["device_ms_per_step"] / leg[f"bits{y}"]["device_ms_per_step"], 3)
         res[f"B{B}"] = leg
+    return res
+
+
+def decode_kv(layers, batches, steps, rounds, weight_modes, ctx):
+    """The fp16 KV cache against the block-scaled fp8 cache per weight mode: two engines on the same seeded weights,
+    greedy steps of B sequences with `ctx` cached positions each, blocks of `steps` alternated `rounds` times in one process (round 0
+    warms up and is dropped); the engines of a weight mode are released before the next mode is built."""
+    import gc
+    res = {}
+    B_max = max(batches + [1])
+    max_ctx = (ctx + (rounds + 1) * steps * len(batches) + 64 + 63) // 64 * 64
+    g = torch.Generator().manual_seed(0)
+    rows = torch.randint(3, 30000, (ctx,), generator=g).tolist()
+    for wb in weight_modes:
+        engs = {}
+        for kvb in (0, 8):
+            cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=B_max, max_ctx=max_ctx, max_rows=max(16384, ctx * 8),
+                                    max_images=1).with_decode_bits(wb).with_kv_bits(kvb)
+            engs[kvb] = VqaEngine(cfg, 0)
+            engs[kvb].load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
+            assert engs[kvb].decode_weight_bits() == wb and engs[kvb].kv_cache_format() == (1 if kvb else 0)
+        H, L = cfg.llm_hidden, cfg.llm_layers
+        leg_w = {"config": {"layers": L, "hidden": H, "ctx": ctx, "max_ctx": max_ctx,
+                            "kv_cache_GB": {str(k): round(e.kv_cache_bytes() / 1e9, 2) for k, e in engs.items()}}}
+        for B in batches:
+            nxt, pos = {}, {}
+            for kvb, eng in engs.items():
+                for i0 in range(0, B, 8):                     # prefill in chunks of 8 sequences (max_rows)
+                    n = min(8, B - i0)
+                    _, t = eng.forward([Seq(rows, kv_slot=i0 + i) for i in range(n)], [(i, -1) for i in range(n)], logits=False)
+                    nxt[kvb] = t if i0 == 0 else np.concatenate([nxt[kvb], t])
+                pos[kvb] = len(rows)
+            want = [(i, 0) for i in range(B)]
+            dev = {k: [] for k in engs}
+            blocks = {k: [] for k in engs}
+            for r in range(rounds + 1):
+                for kvb, eng in engs.items():
+                    t0 = time.time()
+                    d = []
+                    for s in range(steps):
+                        _, nxt[kvb] = eng.forward([Seq([int(nxt[kvb][i])], kv_slot=i, past_len=pos[kvb]) for i in range(B)], want, logits=False)
+                        d.append(eng.last_forward_ms())
+                        pos[kvb] += 1
+                    if r:
+                        blocks[kvb].append((time.time() - t0) / steps * 1e3)
+                        dev[kvb] += d
+            leg = {"positions": [len(rows), pos[0]]}
+            for kvb in engs:
+                w, d = float(np.median(blocks[kvb])), float(np.median(dev[kvb]))
+                per_row = 132 if kvb else 256                 # bytes of one cached row of K (or V)
+                kv_gb = 2.0 * L * B * cfg.llm_heads * (len(rows) + pos[kvb]) / 2 * per_row / 1e9
+                leg[f"kv{kvb}"] = {"device_ms_per_step": round(d, 3), "wall_ms_per_step": round(w, 3), "tokens_per_s": round(B / w * 1e3, 1),
+                                   "wall_ms_per_step_blocks": [round(x, 3) for x in blocks[kvb]],
+                                   "spread": round((max(blocks[kvb]) - min(blocks[kvb])) / w, 3), "kv_GB_per_step": round(kv_gb, 3)}
+            leg["kv8_over_kv0_tokens_per_s"] = round(leg["kv8"]["tokens_per_s"] / leg["kv0"]["tokens_per_s"], 3)
+            leg["kv8_over_kv0_device_time"] = round(leg["kv8"]["device_ms_per_step"] / leg["kv0"]["device_ms_per_step"], 3)
+            leg_w[f"B{B}"] = leg
+        res[f"bits{wb}"] = leg_w
+        engs.clear()
+        del eng
+        gc.collect()
     return res
 
 

@@ -1,9 +1,10 @@
 """Logits error and option rankings of the int8 weight-only decode mode, or with --bits 4 of the int4 group-scaled
-mode (§8.6), against the unquantised fp16 engine on the inputs of tests/golden/vqa_tiny_*.npz.  Reported, not asserted: the weights
+mode (§8.6), or with --kv-bits 8 of the block-scaled fp8 KV cache (§8.7, fp16 weights), against the unquantised fp16 engine on the inputs of tests/golden/vqa_tiny_*.npz.  Reported, not asserted: the weights
 are seeded random numbers, which says little about a trained checkpoint.  Prints one JSON object.
 
   python tools/vqa_w8_accuracy.py [--out profiles/vqa_w8_accuracy.json]
   python tools/vqa_w8_accuracy.py --bits 4 [--out profiles/vqa_w4_accuracy.json]
+  python tools/vqa_w8_accuracy.py --kv-bits 8 [--out profiles/vqa_kv8_accuracy.json]
 """
 import argparse
 import ast
@@ -62,12 +63,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--bits", type=int, default=8, choices=[4, 8], help="the quantised mode compared with fp16")
+    ap.add_argument("--kv-bits", type=int, default=0, choices=[0, 8], help="8: compare the fp8 KV cache (fp16 weights) with fp16 instead")
     a = ap.parse_args()
     out = {}
-    B, w = a.bits, f"w{a.bits}"
+    B, w = (a.bits, f"w{a.bits}") if not a.kv_bits else ("kv8", "kv8")
+    mode = lambda cfg, b: cfg if b == 0 else (cfg.with_kv_bits(8) if b == "kv8" else cfg.with_decode_bits(b))      # noqa: E731
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "vqa_tiny_*.npz"))):
         z, cfg, pix, ids, opts, n_obj, il, ol = load_case(path)
-        res = {b: run(cfg.with_decode_bits(b), int(z["weight_seed"]), pix, ids, opts, n_obj, il, ol) for b in (0, B)}
+        res = {b: run(mode(cfg, b), int(z["weight_seed"]), pix, ids, opts, n_obj, il, ol) for b in (0, B)}
         rank = {b: np.argsort(res[b][2]).tolist() for b in (0, B)}
         out[os.path.basename(path)] = {
             f"q_logits_rel_l2_{w}_vs_fp16": rel_l2(res[B][0], res[0][0]), f"opt_logits_rel_l2_{w}_vs_fp16": rel_l2(res[B][1], res[0][1]),

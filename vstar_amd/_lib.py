@@ -39,6 +39,7 @@ EXPORTS_VQA = [
     "vstar_vqa_op_beam_select", "vstar_vqa_forward_score", "vstar_vqa_op_score",
     "vstar_vqa_decode_weight_bits", "vstar_vqa_op_quantize_w8", "vstar_vqa_op_gemm_w8",
     "vstar_vqa_op_quantize_w4", "vstar_vqa_op_gemm_w4",
+    "vstar_vqa_kv_cache_format", "vstar_vqa_kv_cache_bytes", "vstar_vqa_op_kv_quantize",
     "vstar_vqa_forward_verify", "vstar_vqa_op_verify",
 ]
 
@@ -258,6 +259,12 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_gemm_w8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int]
     lib.vstar_vqa_op_gemm_w8.restype = c_int
+    lib.vstar_vqa_kv_cache_format.argtypes = [H]
+    lib.vstar_vqa_kv_cache_format.restype = c_int
+    lib.vstar_vqa_kv_cache_bytes.argtypes = [H]
+    lib.vstar_vqa_kv_cache_bytes.restype = ctypes.c_int64
+    lib.vstar_vqa_op_kv_quantize.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_kv_quantize.restype = c_int
     lib.vstar_vqa_op_quantize_w4.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.vstar_vqa_op_quantize_w4.restype = c_int
     lib.vstar_vqa_op_gemm_w4.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -286,12 +286,13 @@ class LlavaSearchModel:
 
 def load_pretrained_model(model_path, model_base=None, model_name: str = "", load_8bit: bool = False, load_4bit: bool = False,
                           device_map="auto", device="cuda", *, cfg=None, state_dict=None, tokenizer=None, vision_tower=None,
-                          decode_weight_bits=0):
+                          decode_weight_bits=0, kv_cache_bits=0):
     """Same signature and return tuple as LLaVA/llava/model/builder.py:26-151: (tokenizer, model, image_processor, context_len).
     `model_path`: LOCAL checkpoint directory of craigwu/seal_vqa_7b (offline: `cfg` + `state_dict` [+ `tokenizer`]).
     decode_weight_bits=8: the engine's own int8 weight-only decode mode (DESIGN.md §8.4), not bitsandbytes' LLM.int8;
     decode_weight_bits=4: its int4 mode with one fp16 scale per 128 input channels (§8.6; the GPTQ / AWQ layout, quantised here by
-    round-to-nearest), not bitsandbytes' NF4 — load_4bit keeps raising."""
+    round-to-nearest), not bitsandbytes' NF4 — load_4bit keeps raising.  kv_cache_bits=8: the block-scaled fp8 KV cache (§8.7), with
+    any of the weight modes."""
     if load_8bit or load_4bit:
         raise NotImplementedError("bitsandbytes 8-bit / 4-bit loading is out of scope: the engine runs fp16 (builder.py:43); "
                                   "its own weight-only decode modes are decode_weight_bits=8 (int8 per row) and "
@@ -303,7 +304,7 @@ def load_pretrained_model(model_path, model_base=None, model_name: str = "", loa
     from .vqa import VQA_LLM
     llm = VQA_LLM(SimpleNamespace(vqa_model_path=model_path, conv_type="v1", vision_tower=vision_tower), cfg=cfg,
                   state_dict=state_dict, tokenizer=tokenizer, device=_device_index(device),
-                  decode_weight_bits=decode_weight_bits or None)
+                  decode_weight_bits=decode_weight_bits or None, kv_cache_bits=kv_cache_bits or None)
     return llm.tokenizer, LlavaSearchModel(llm), llm.image_processor, llm.context_len
 
 

@@ -163,11 +163,15 @@ class CVqaConfig(ctypes.Structure):
         ("max_images", ctypes.c_int32),
         ("decode_weight_bits", ctypes.c_int32),
         ("decode_weight_format", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 6),
+        ("kv_cache_format", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 5),
     ]
 
 
 WFMT_W4G128 = 1      # VSTAR_VQA_WFMT_W4G128 (include/vstar_vqa.h)
+KVFMT_F16 = 0
+KVFMT_MXFP8 = 1              # VSTAR_VQA_KVFMT_MXFP8: block-scaled fp8 KV cache (MX e4m3, blocks of 32)
+KVFMT_MXFP8_EMULATED = 2     # VSTAR_VQA_KVFMT_MXFP8_EMULATED: the same values held in the fp16 cache (yardstick / study tool)
 
 
 @dataclass
@@ -202,6 +206,9 @@ class VQAConfig:
     # field for field, where the value 4 is pinned to fail at create (the int8 pull request's tests); "4 bits" at the user-facing
     # level (VQA_LLM, load_pretrained_model, the tools) is translated by with_decode_bits(4).
     decode_weight_format: int = 0
+    # KVFMT_MXFP8 (1): block-scaled fp8 KV cache, 132 bytes per cached row instead of 256; KVFMT_MXFP8_EMULATED (2): the same values in
+    # the fp16 cache; independent of the two weight fields
+    kv_cache_format: int = 0
 
     @property
     def n_img_tokens(self) -> int:
@@ -220,6 +227,18 @@ class VQAConfig:
         if bits not in (0, 4, 8):
             raise ValueError("decode bits must be 0, 4 or 8")
         return dataclasses.replace(self, decode_weight_bits=8 if bits == 8 else 0, decode_weight_format=WFMT_W4G128 if bits == 4 else 0)
+
+    def with_kv_bits(self, bits: int) -> "VQAConfig":
+        """The user-facing spelling of the KV-cache formats: 0 (or 16) = fp16, 8 = block-scaled fp8 (kv_cache_format = KVFMT_MXFP8)."""
+        import dataclasses
+        bits = int(bits)
+        if bits not in (0, 8, 16):
+            raise ValueError("KV cache bits must be 0 (fp16) or 8")
+        return dataclasses.replace(self, kv_cache_format=KVFMT_MXFP8 if bits == 8 else KVFMT_F16)
+
+    def kv_bits(self) -> int:
+        """Inverse of with_kv_bits: 8 for the fp8 cache, else 0 (the emulated format stores fp16)."""
+        return 8 if self.kv_cache_format == KVFMT_MXFP8 else 0
 
     def decode_bits(self) -> int:
         """Inverse of with_decode_bits for a valid configuration."""

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "gemm_epilogue.hpp"
+#include "mx.hpp"
 
 namespace VS_NS {
 
@@ -694,11 +695,110 @@ __global__ void embed_rows_kernel(const int32_t* __restrict__ src, const lp_t* _
   *(lpx8*)(x + (int64_t)r * C + v * 8) = o;
 }
 
+// ------------------------------------------------ block-scaled fp8 KV rows ------------------------------------------------
+// KV-cache formats (KvFormat, kernels.hpp) as the template parameter KVF of every kernel that touches the cache:
+//   0  fp16 rows [128]: the kernels as they always were
+//   1  MX e4m3: a row is 128 code bytes + 4 E8M0 bytes (one per block of 32 head-dim elements, mx.hpp's arithmetic); the cache
+//      pointers then address BYTES with the same element strides, the scale bytes live at (element offset / 32) of their own array
+//   2  the fp16 cache holding fp16(decoded): format 1's values through format 0's readers (the yardstick of the bit-identity tests)
+// kv8_quant is the ONE place a value is quantised: every writer of formats 1 and 2 and the op-level quantiser call it with the
+// block's amax, however their lane geometry reduced it.  The decoded value code x 2^(e - 127) is exact in fp32 and, for fp16 inputs
+// below 63488, exactly representable in fp16 — so the two formats hold the same numbers.
+__device__ __forceinline__ float kv8_scale(uint32_t e) { return __uint_as_float(e << 23); }      // 2^(e - 127); e = 0: all-zero block
+__device__ __forceinline__ uint32_t kv8_quant(float x, float amax, uint32_t* e_out, float* xhat) {
+  const uint32_t e = mx_e8m0(amax);
+  const uint32_t c = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x * mx_inv_scale(e), 0.f, 0, false) & 0xffu;
+  *e_out = e;
+  // (the sign is taken from the code: a value that rounds to zero keeps its sign bit in the code, and so does the decoded row)
+  *xhat = __uint_as_float(__float_as_uint(fabsf(__builtin_amdgcn_cvt_f32_fp8((int)c, 0)) * kv8_scale(e)) | ((c & 0x80u) << 24));
+  return c;
+}
+// max over the 2^LOG2 neighbouring lanes of a block (all of them active)
+template <int LOG2>
+__device__ __forceinline__ float kv8_lanes_max(float v) {
+#pragma unroll
+  for (int o = 1 << (LOG2 - 1); o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// one element of a cached row held by one lane (the fused writers: 32 neighbouring lanes hold a block): quantise, store at element
+// offset `off` of the layer's cache, return the value the row now has
+template <int KVF>
+__device__ __forceinline__ float kv8_put(lp_t* cache, uint8_t* scales, int64_t off, float x) {
+  uint32_t e;
+  float xhat;
+  const uint32_t c = kv8_quant(x, kv8_lanes_max<5>(fabsf(x)), &e, &xhat);
+  if constexpr (KVF == 1) {
+    ((uint8_t*)cache)[off] = (uint8_t)c;
+    if ((off & 31) == 0) scales[off >> 5] = (uint8_t)e;
+  } else {
+    cache[off] = f2lp(xhat);
+  }
+  return xhat;
+}
+// a lane's 8 consecutive elements of a cached row, as loaded / as fp32
+template <int KVF> struct KvFrag { lpx8 v; };
+template <> struct KvFrag<1> { uint2 c; uint32_t s; };
+template <int KVF> struct KvCell { typedef lp_t type; };
+template <> struct KvCell<1> { typedef uint8_t type; };
+template <int KVF>
+__device__ __forceinline__ KvFrag<KVF> kv_frag_zero() {
+  KvFrag<KVF> f;
+  if constexpr (KVF == 1) { f.c = make_uint2(0u, 0u); f.s = 0u; }
+  else f.v = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
+  return f;
+}
+// row = the cached row (kv_row), base = the layer's cache, l16 = the lane's 8-vector
+template <int KVF>
+__device__ __forceinline__ KvFrag<KVF> kv_frag_load(const typename KvCell<KVF>::type* row, const typename KvCell<KVF>::type* base,
+                                                    const uint8_t* scales, int l16) {
+  KvFrag<KVF> f;
+  if constexpr (KVF == 1) {
+    f.c = *(const uint2*)(row + l16 * 8);
+    f.s = *(const uint32_t*)(scales + ((row - base) >> 5));       // the row's 4 scale bytes
+  } else {
+    f.v = *(const lpx8*)(row + l16 * 8);
+  }
+  return f;
+}
+// format 1: the 8 codes -> fp32 and ONE exact multiply by the block's power of two
+__device__ __forceinline__ void kv8_frag_f32(const KvFrag<1>& f, int l16, float* x) {
+  const float s = kv8_scale((f.s >> ((l16 >> 2) * 8)) & 0xffu);
+  const auto p0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)f.c.x, false), p1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)f.c.x, true);
+  const auto p2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)f.c.y, false), p3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)f.c.y, true);
+  x[0] = p0[0] * s; x[1] = p0[1] * s; x[2] = p1[0] * s; x[3] = p1[1] * s;
+  x[4] = p2[0] * s; x[5] = p2[1] * s; x[6] = p3[0] * s; x[7] = p3[1] * s;
+}
+template <int KVF>
+__device__ __forceinline__ void kv_frag_f32(const KvFrag<KVF>& f, int l16, float* x) {
+  if constexpr (KVF == 1) kv8_frag_f32(f, l16, x);
+  else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = lp2f((lp_t)f.v[e]);
+  }
+}
+
+// [rows, 128] fp16 -> codes [rows, 128], E8M0 bytes [rows, 4], (nullable, may alias x) xhat: one lane per element
+__global__ __launch_bounds__(256) void kv_quantize_rows_kernel(const lp_t* x, int64_t n, uint8_t* __restrict__ codes,
+                                                               uint8_t* __restrict__ scales, lp_t* xhat) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;                                  // n % 128 == 0: the 32 lanes of a block stay together
+  uint32_t e;
+  float xh;
+  const float v = lp2f(x[idx]);
+  const uint32_t c = kv8_quant(v, kv8_lanes_max<5>(fabsf(v)), &e, &xh);
+  codes[idx] = (uint8_t)c;
+  if ((idx & 31) == 0) scales[idx >> 5] = (uint8_t)e;
+  if (xhat) xhat[idx] = f2lp(xh);
+}
+
 // ------------------------------------------------ RoPE + KV-cache append ------------------------------------------------
 // One thread per (row, q|k|v, head, 8-vector of the FIRST half of the head dim); handles d0 and d0 + D/2 together.
+// KVF != 0: a block of 32 is the 8-vectors of 4 neighbouring threads; the round-tripped k AND v also replace the row's k / v in
+// `qkv`, which the prefill attention reads — a position has one value whoever reads it.
+template <int KVF>
 __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __restrict__ cos_sin, const int32_t* __restrict__ row_pos,
                                       const int32_t* __restrict__ row_slot, lp_t* __restrict__ kc, lp_t* __restrict__ vc,
-                                      int64_t slot_stride, int ctx, int R, int H) {
+                                      int64_t slot_stride, int ctx, int R, int H, uint8_t* __restrict__ ks, uint8_t* __restrict__ vs) {
   constexpr int D = 128, HALF = 64, VPH = HALF / 8;
   const int per_row = 3 * H * VPH;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -723,13 +823,52 @@ __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __rest
       o1[e] = (short)f2lp(rlp(a * cs) + rlp(-b * si));
       o2[e] = (short)f2lp(rlp(b * cs) + rlp(a * si));
     }
-    *(lpx8*)(base + d0) = o1;
-    *(lpx8*)(base + d0 + HALF) = o2;
+    if (KVF == 0 || which == 0) {
+      *(lpx8*)(base + d0) = o1;
+      *(lpx8*)(base + d0 + HALF) = o2;
+    }
     if (which == 0) return;
   }
-  lp_t* dst = (which == 1 ? kc : vc) + (int64_t)row_slot[row] * slot_stride + ((int64_t)h * ctx + pos) * D;
-  *(lpx8*)(dst + d0) = o1;
-  *(lpx8*)(dst + d0 + HALF) = o2;
+  if constexpr (KVF == 0) {
+    lp_t* dst = (which == 1 ? kc : vc) + (int64_t)row_slot[row] * slot_stride + ((int64_t)h * ctx + pos) * D;
+    *(lpx8*)(dst + d0) = o1;
+    *(lpx8*)(dst + d0 + HALF) = o2;
+  } else {
+    float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      a1 = fmaxf(a1, fabsf(lp2f((lp_t)o1[e])));
+      a2 = fmaxf(a2, fabsf(lp2f((lp_t)o2[e])));
+    }
+    a1 = kv8_lanes_max<2>(a1);
+    a2 = kv8_lanes_max<2>(a2);
+    uint32_t c1[8], c2[8], e1 = 0, e2 = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float h1, h2;
+      c1[e] = kv8_quant(lp2f((lp_t)o1[e]), a1, &e1, &h1);
+      c2[e] = kv8_quant(lp2f((lp_t)o2[e]), a2, &e2, &h2);
+      o1[e] = (short)f2lp(h1);
+      o2[e] = (short)f2lp(h2);
+    }
+    *(lpx8*)(base + d0) = o1;
+    *(lpx8*)(base + d0 + HALF) = o2;
+    const int64_t off = (int64_t)row_slot[row] * slot_stride + ((int64_t)h * ctx + pos) * D;
+    if constexpr (KVF == 1) {
+      uint8_t* dst = (uint8_t*)(which == 1 ? kc : vc) + off;
+      *(uint2*)(dst + d0) = make_uint2(c1[0] | (c1[1] << 8) | (c1[2] << 16) | (c1[3] << 24), c1[4] | (c1[5] << 8) | (c1[6] << 16) | (c1[7] << 24));
+      *(uint2*)(dst + d0 + HALF) = make_uint2(c2[0] | (c2[1] << 8) | (c2[2] << 16) | (c2[3] << 24), c2[4] | (c2[5] << 8) | (c2[6] << 16) | (c2[7] << 24));
+      if ((d0 & 31) == 0) {
+        uint8_t* sc = (which == 1 ? ks : vs) + (off >> 5);
+        sc[d0 >> 5] = (uint8_t)e1;
+        sc[2 + (d0 >> 5)] = (uint8_t)e2;
+      }
+    } else {
+      lp_t* dst = (which == 1 ? kc : vc) + off;
+      *(lpx8*)(dst + d0) = o1;
+      *(lpx8*)(dst + d0 + HALF) = o2;
+    }
+  }
 }
 
 // ------------------------------------------------ attention over the KV cache ------------------------------------------------
@@ -737,22 +876,24 @@ __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __rest
 // k, appends k and v to the cache and attends to them from LDS — rope_kv_append's work without its launch.
 // ANC (beam search): key / value row j of a sequence lives in slot anc[kv_slot * ctx + j] (the KV ancestry
 // table) instead of `j < past ? prefix : own`; the caller has set the entries of the rows it writes to kv_slot.
-template <bool ANC>
-__device__ __forceinline__ const lp_t* kv_row(const lp_t* head0, const lp_t* pre, const lp_t* own, const int32_t* arow, int j, int past,
-                                              int64_t slot_stride) {
+template <bool ANC, class T>
+__device__ __forceinline__ const T* kv_row(const T* head0, const T* pre, const T* own, const int32_t* arow, int j, int past,
+                                           int64_t slot_stride) {
   constexpr int D = 128;
   if constexpr (ANC) return head0 + (int64_t)arow[j] * slot_stride + (int64_t)j * D;
   else return (j < past ? pre : own) + (int64_t)j * D;
 }
 
-template <bool FUSED, bool ANC>
+template <bool FUSED, bool ANC, int KVF = 0>
 __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc,
                                                           const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_pos,
                                                           const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix,
                                                           const int32_t* __restrict__ seq_past, const lp_t* __restrict__ cos_sin,
                                                           lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride,
-                                                          float inv_scale, const int32_t* __restrict__ anc) {
+                                                          float inv_scale, const int32_t* __restrict__ anc,
+                                                          uint8_t* __restrict__ ks, uint8_t* __restrict__ vs) {
   constexpr int D = 128;
+  typedef typename KvCell<KVF>::type cell_t;  // fp16 element or code byte: same element strides
   extern __shared__ float dyn[];            // [D] q | [nk] scores/probabilities
   __shared__ float redbuf[8];
   __shared__ float part[16][D];
@@ -763,12 +904,12 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   const int seq = row_seq[r];
   const int past = seq_past[seq], nk = pos + 1;
   const int nkc = FUSED ? pos : nk;         // keys that come from the cache
-  lp_t* kown = kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* kpre = kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* vpre = vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* kh0 = kc + (int64_t)h * ctx * D;
-  const lp_t* vh0 = vc + (int64_t)h * ctx * D;
+  cell_t* kown = (cell_t*)kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* kpre = (const cell_t*)kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  cell_t* vown = (cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* vpre = (const cell_t*)vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* kh0 = (const cell_t*)kc + (int64_t)h * ctx * D;
+  const cell_t* vh0 = (const cell_t*)vc + (int64_t)h * ctx * D;
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   float* qs = dyn;
   float* sc = dyn + D;
@@ -783,17 +924,26 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
       if (which == 0) {
         qs[d] = lp2f(o1);
         qs[d + 64] = lp2f(o2);
-      } else {
+      } else if constexpr (KVF == 0) {
         own_k[d] = lp2f(o1);
         own_k[d + 64] = lp2f(o2);
         kown[(int64_t)pos * D + d] = o1;
         kown[(int64_t)pos * D + d + 64] = o2;
+      } else {                                // the whole of wave 1: 32 lanes per block
+        const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
+        own_k[d] = kv8_put<KVF>(kc, ks, own_off + d, lp2f(o1));
+        own_k[d + 64] = kv8_put<KVF>(kc, ks, own_off + d + 64, lp2f(o2));
       }
     } else {
       const int d = tid - 128;
       const lp_t v = rowp[2 * H * D + d];
-      own_v[d] = lp2f(v);
-      vown[(int64_t)pos * D + d] = v;
+      if constexpr (KVF == 0) {
+        own_v[d] = lp2f(v);
+        vown[(int64_t)pos * D + d] = v;
+      } else {                                // the whole of waves 2 and 3
+        const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
+        own_v[d] = kv8_put<KVF>(vc, vs, own_off + d, lp2f(v));
+      }
     }
   } else if (tid < D) {
     qs[tid] = lp2f(rowp[tid]);
@@ -806,19 +956,21 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   for (int e = 0; e < 8; ++e) qv[e] = qs[l16 * 8 + e];
   float mx = -3.0e38f;
   for (int j0 = 0; j0 < nkc; j0 += 64) {
-    lpx8 kv8[4];
+    KvFrag<KVF> kv8[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
-      kv8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (j < nkc) kv8[u] = *(const lpx8*)(kv_row<ANC>(kh0, kpre, kown, arow, j, past, slot_stride) + l16 * 8);
+      kv8[u] = kv_frag_zero<KVF>();
+      if (j < nkc)
+        kv8[u] = kv_frag_load<KVF>(kv_row<ANC>(kh0, kpre, (const cell_t*)kown, arow, j, past, slot_stride), (const cell_t*)kc, ks, l16);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
-      float a = 0.f;
+      float a = 0.f, kx[8];
+      kv_frag_f32<KVF>(kv8[u], l16, kx);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) a += qv[e] * lp2f((lp_t)kv8[u][e]);
+      for (int e = 0; e < 8; ++e) a += qv[e] * kx[e];
       a += __shfl_xor(a, 8, 64);
       a += __shfl_xor(a, 4, 64);
       a += __shfl_xor(a, 2, 64);
@@ -862,22 +1014,25 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
   for (int j0 = grp; j0 < nkc; j0 += 64) {
-    lpx8 v8[4];
+    KvFrag<KVF> v8[4];
     float pr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16;
-      v8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
+      v8[u] = kv_frag_zero<KVF>();
       pr[u] = 0.f;
       if (j < nkc) {
-        v8[u] = *(const lpx8*)(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride) + l16 * 8);
+        v8[u] = kv_frag_load<KVF>(kv_row<ANC>(vh0, vpre, (const cell_t*)vown, arow, j, past, slot_stride), (const cell_t*)vc, vs, l16);
         pr[u] = rlp(sc[j] * inv);
       }
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
+    for (int u = 0; u < 4; ++u) {
+      float vx[8];
+      kv_frag_f32<KVF>(v8[u], l16, vx);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += pr[u] * lp2f((lp_t)v8[u][e]);
+      for (int e = 0; e < 8; ++e) o[e] += pr[u] * vx[e];
+    }
   }
   if (FUSED && grp == 0) {
     const float pr = rlp(sc[pos] * inv);
@@ -914,13 +1069,15 @@ __device__ __forceinline__ void split_range(int nkc, int p, int* lo, int* hi) {
   *hi = *lo + span < nkc ? *lo + span : nkc;
 }
 
-template <bool ANC>
+template <bool ANC, int KVF = 0>
 __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
     const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc, const int32_t* __restrict__ row_seq,
     const int32_t* __restrict__ row_pos, const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix,
     const int32_t* __restrict__ seq_past, const lp_t* __restrict__ cos_sin, float* __restrict__ ws_scores, float* __restrict__ ws_stats,
-    int H, int ctx, int64_t slot_stride, float inv_scale, const int32_t* __restrict__ anc) {
+    int H, int ctx, int64_t slot_stride, float inv_scale, const int32_t* __restrict__ anc, uint8_t* __restrict__ ks,
+    uint8_t* __restrict__ vs) {
   constexpr int D = 128;
+  typedef typename KvCell<KVF>::type cell_t;
   extern __shared__ float dyn[];            // this partition's scores (span + 1)
   __shared__ float qs[D], own_k[D], redbuf[8];
   const int r = blockIdx.x, h = blockIdx.y, p = blockIdx.z, tid = threadIdx.x;
@@ -928,10 +1085,10 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   if (pos < 0) return;
   const int seq = row_seq[r];
   const int past = seq_past[seq], nkc = pos;
-  lp_t* kown = kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* kpre = kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* kh0 = kc + (int64_t)h * ctx * D;
+  cell_t* kown = (cell_t*)kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* kpre = (const cell_t*)kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  cell_t* vown = (cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* kh0 = (const cell_t*)kc + (int64_t)h * ctx * D;
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const lp_t* rowp = qkv + (int64_t)r * (3 * H * D) + h * D;
   const bool last = p == SPLIT_P - 1;
@@ -945,16 +1102,25 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
       if (which == 0) {
         qs[d] = lp2f(o1);
         qs[d + 64] = lp2f(o2);
-      } else {
+      } else if constexpr (KVF == 0) {
         own_k[d] = lp2f(o1);
         own_k[d + 64] = lp2f(o2);
         kown[(int64_t)pos * D + d] = o1;
         kown[(int64_t)pos * D + d + 64] = o2;
+      } else {                                // the whole of wave 1: 32 lanes per block
+        const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
+        own_k[d] = kv8_put<KVF>(kc, ks, own_off + d, lp2f(o1));
+        own_k[d + 64] = kv8_put<KVF>(kc, ks, own_off + d + 64, lp2f(o2));
       }
     }
   } else if (last) {
     const int d = tid - 128;
-    vown[(int64_t)pos * D + d] = rowp[2 * H * D + d];
+    if constexpr (KVF == 0) {
+      vown[(int64_t)pos * D + d] = rowp[2 * H * D + d];
+    } else {                                  // the whole of waves 2 and 3
+      const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
+      kv8_put<KVF>(vc, vs, own_off + d, lp2f(rowp[2 * H * D + d]));
+    }
   }
   __syncthreads();
   int j_lo, j_hi;
@@ -966,19 +1132,21 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   for (int e = 0; e < 8; ++e) qv[e] = qs[l16 * 8 + e];
   float mx = -3.0e38f;
   for (int j0 = j_lo; j0 < j_hi; j0 += 64) {
-    lpx8 kv8[4];
+    KvFrag<KVF> kv8[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
-      kv8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (j < j_hi) kv8[u] = *(const lpx8*)(kv_row<ANC>(kh0, kpre, kown, arow, j, past, slot_stride) + l16 * 8);
+      kv8[u] = kv_frag_zero<KVF>();
+      if (j < j_hi)
+        kv8[u] = kv_frag_load<KVF>(kv_row<ANC>(kh0, kpre, (const cell_t*)kown, arow, j, past, slot_stride), (const cell_t*)kc, ks, l16);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16 + grp;
-      float a = 0.f;
+      float a = 0.f, kx[8];
+      kv_frag_f32<KVF>(kv8[u], l16, kx);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) a += qv[e] * lp2f((lp_t)kv8[u][e]);
+      for (int e = 0; e < 8; ++e) a += qv[e] * kx[e];
       a += __shfl_xor(a, 8, 64);
       a += __shfl_xor(a, 4, 64);
       a += __shfl_xor(a, 2, 64);
@@ -1022,13 +1190,14 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   }
 }
 
-template <bool ANC>
+template <bool ANC, int KVF = 0>
 __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
     const lp_t* __restrict__ vc, const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_pos,
     const int32_t* __restrict__ seq_kv, const int32_t* __restrict__ seq_prefix, const int32_t* __restrict__ seq_past,
     const float* __restrict__ ws_scores, const float* __restrict__ ws_stats, float* __restrict__ ws_opart, int* __restrict__ ws_cnt,
-    lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride, const int32_t* __restrict__ anc) {
+    lp_t* __restrict__ out, int H, int ctx, int64_t slot_stride, const int32_t* __restrict__ anc, const uint8_t* __restrict__ vs) {
   constexpr int D = 128;
+  typedef typename KvCell<KVF>::type cell_t;
   __shared__ float part[16][D];
   __shared__ int ticket;
   const int r = blockIdx.x, h = blockIdx.y, p = blockIdx.z, tid = threadIdx.x;
@@ -1036,9 +1205,9 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
   if (pos < 0) return;
   const int seq = row_seq[r];
   const int past = seq_past[seq], nkc = pos;
-  const lp_t* vown = vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* vpre = vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  const lp_t* vh0 = vc + (int64_t)h * ctx * D;
+  const cell_t* vown = (const cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* vpre = (const cell_t*)vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  const cell_t* vh0 = (const cell_t*)vc + (int64_t)h * ctx * D;
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const float* st = ws_stats + ((int64_t)r * H + h) * SPLIT_P * 2;
   float M = -3.0e38f;
@@ -1057,22 +1226,25 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
   for (int j0 = j_lo + grp; j0 < j_hi; j0 += 64) {
-    lpx8 v8[4];
+    KvFrag<KVF> v8[4];
     float pr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 16;
-      v8[u] = (lpx8){0, 0, 0, 0, 0, 0, 0, 0};
+      v8[u] = kv_frag_zero<KVF>();
       pr[u] = 0.f;
       if (j < j_hi) {
-        v8[u] = *(const lpx8*)(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride) + l16 * 8);
+        v8[u] = kv_frag_load<KVF>(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride), (const cell_t*)vc, vs, l16);
         pr[u] = rlp(__expf(gsc[j] - M) * inv);     // probabilities rounded to the storage type (HF .to(query.dtype))
       }
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
+    for (int u = 0; u < 4; ++u) {
+      float vx[8];
+      kv_frag_f32<KVF>(v8[u], l16, vx);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += pr[u] * lp2f((lp_t)v8[u][e]);
+      for (int e = 0; e < 8; ++e) o[e] += pr[u] * vx[e];
+    }
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) part[grp][l16 * 8 + e] = o[e];
@@ -1204,8 +1376,11 @@ __global__ void kv_anc_scatter_kernel(int32_t* __restrict__ anc, const int32_t* 
 }
 
 // K / V rows [lo, lo + w) of every layer and head: dst's own rows <- the rows src's ancestry points at (16 B per thread)
+// (KVF == 1: 8 code bytes per thread, and the first thread of a row moves its 4 scale bytes)
+template <int KVF>
 __global__ void kv_copy_rows_kernel(lp_t* __restrict__ kc, lp_t* __restrict__ vc, const int32_t* __restrict__ anc, int dst, int src,
-                                    int lo, int w, int H, int ctx, int64_t slot_stride, int64_t layer_stride, int64_t n) {
+                                    int lo, int w, int H, int ctx, int64_t slot_stride, int64_t layer_stride, int64_t n,
+                                    uint8_t* __restrict__ ks, uint8_t* __restrict__ vs) {
   constexpr int D = 128;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
@@ -1217,9 +1392,19 @@ __global__ void kv_copy_rows_kernel(lp_t* __restrict__ kc, lp_t* __restrict__ vc
   rest /= H;
   const int which = (int)(rest & 1);
   const int64_t layer = rest >> 1;
-  lp_t* base = (which ? vc : kc) + layer * layer_stride + (int64_t)h * ctx * D + (int64_t)p * D + v8 * 8;
   const int from = anc[(int64_t)src * ctx + p];
-  *(lpx8*)(base + (int64_t)dst * slot_stride) = *(const lpx8*)(base + (int64_t)from * slot_stride);
+  if constexpr (KVF == 1) {
+    const int64_t off = layer * layer_stride + (int64_t)h * ctx * D + (int64_t)p * D;
+    uint8_t* base = (uint8_t*)(which ? vc : kc) + off + v8 * 8;
+    *(uint2*)(base + (int64_t)dst * slot_stride) = *(const uint2*)(base + (int64_t)from * slot_stride);
+    if (v8 == 0) {
+      uint8_t* sb = (which ? vs : ks) + (off >> 5);
+      *(uint32_t*)(sb + (((int64_t)dst * slot_stride) >> 5)) = *(const uint32_t*)(sb + (((int64_t)from * slot_stride) >> 5));
+    }
+  } else {
+    lp_t* base = (which ? vc : kc) + layer * layer_stride + (int64_t)h * ctx * D + (int64_t)p * D + v8 * 8;
+    *(lpx8*)(base + (int64_t)dst * slot_stride) = *(const lpx8*)(base + (int64_t)from * slot_stride);
+  }
 }
 
 __global__ void argmax_rows_lp_kernel(const lp_t* __restrict__ x, int cols, int64_t ld, int32_t* __restrict__ out) {
@@ -1345,25 +1530,57 @@ hipError_t embed_rows(const int32_t* src, const lp_t* table, int vocab, const lp
   return hipGetLastError();
 }
 
+// a valid KvFormat of this build: formats beyond fp16 exist in the fp16 instantiation only, KV_FMT_MXFP8 needs its scale arrays
+static bool kv_format_ok(const KvFormat& f) {
+#ifdef VSTAR_LP_F16
+  return f.fmt == KV_FMT_F16 || f.fmt == KV_FMT_MXFP8_EMU || (f.fmt == KV_FMT_MXFP8 && f.ks && f.vs);
+#else
+  return f.fmt == KV_FMT_F16;
+#endif
+}
+
+// KV_DISPATCH(fmt, CALL): CALL with the constant KVF = the runtime format fmt (the format-0 instantiation is the only one of
+// the bf16 build)
+#ifdef VSTAR_LP_F16
+#define KV_DISPATCH(fmt, CALL)                          \
+  switch (fmt) {                                        \
+    case KV_FMT_MXFP8: { constexpr int KVF = 1; CALL; break; }      \
+    case KV_FMT_MXFP8_EMU: { constexpr int KVF = 2; CALL; break; }  \
+    default: { constexpr int KVF = 0; CALL; break; }    \
+  }
+#else
+#define KV_DISPATCH(fmt, CALL) { constexpr int KVF = 0; CALL; }
+#endif
+
 hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const int32_t* row_pos, const int32_t* row_slot, lp_t* kc, lp_t* vc,
-                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s) {
+                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s, const KvFormat& kvf) {
+  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
   const int64_t n = (int64_t)R * 3 * H * 8;
-  hipLaunchKernelGGL(rope_kv_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, qkv, cos_sin, row_pos, row_slot,
-                     kc, vc, slot_stride, ctx, R, H);
+  KV_DISPATCH(kvf.fmt, hipLaunchKernelGGL(rope_kv_append_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, qkv, cos_sin,
+                                          row_pos, row_slot, kc, vc, slot_stride, ctx, R, H, kvf.ks, kvf.vs));
   return hipGetLastError();
 }
+
+#ifdef VSTAR_LP_F16
+hipError_t kv_quantize_rows(const lp_t* x, int rows, uint8_t* codes, uint8_t* scales, lp_t* xhat, hipStream_t s) {
+  if (!x || !codes || !scales || rows <= 0) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)rows * 128;
+  hipLaunchKernelGGL(kv_quantize_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, codes, scales, xhat);
+  return hipGetLastError();
+}
+#endif
 
 size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx) {
   const size_t rh = (size_t)max_rows * H;
   return rh * ((size_t)ctx * 4 + SPLIT_P * 2 * 4 + SPLIT_P * 128 * 4 + 4) + 256;
 }
 
-template <bool ANC>
+template <bool ANC, int KVF>
 static hipError_t cached_attention_t(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
                                      const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
                                      lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
-                                     int split_max_rows, const int32_t* anc) {
+                                     int split_max_rows, const int32_t* anc, uint8_t* ks, uint8_t* vs) {
   static const bool split_on = [] { const char* v = getenv("VSTAR_DECODE_SPLIT_KV"); return !v || atoi(v) != 0; }();
   // decode steps of few sequences: P partitions per (row, head) so that the K / V streams of a head run on 8 CUs instead of one
   if (split_on && fused_cos_sin && split_ws && R <= split_max_rows && R * H <= 128 && max_keys >= 256) {
@@ -1373,34 +1590,41 @@ static hipError_t cached_attention_t(const lp_t* qkv, lp_t* kc, lp_t* vc, const 
     float* ws_opart = ws_stats + rh * SPLIT_P * 2;
     int* ws_cnt = (int*)(ws_opart + rh * SPLIT_P * 128);
     const int span = ((((max_keys + SPLIT_P - 1) / SPLIT_P) + 63) & ~63) + 1;
-    hipLaunchKernelGGL(cached_attn_split_scores_kernel<ANC>, dim3(R, H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s, qkv, kc,
-                       vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, ws_scores, ws_stats, H, ctx, slot_stride,
-                       sqrtf(128.0f), anc);
-    hipLaunchKernelGGL(cached_attn_split_pv_kernel<ANC>, dim3(R, H, SPLIT_P), dim3(256), 0, s, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, ws_scores, ws_stats, ws_opart, ws_cnt, out, H, ctx, slot_stride, anc);
+    hipLaunchKernelGGL((cached_attn_split_scores_kernel<ANC, KVF>), dim3(R, H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s, qkv,
+                       kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, ws_scores, ws_stats, H, ctx, slot_stride,
+                       sqrtf(128.0f), anc, ks, vs);
+    hipLaunchKernelGGL((cached_attn_split_pv_kernel<ANC, KVF>), dim3(R, H, SPLIT_P), dim3(256), 0, s, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, ws_scores, ws_stats, ws_opart, ws_cnt, out, H, ctx, slot_stride, anc, vs);
     return hipGetLastError();
   }
   const size_t lds = (size_t)(128 + max_keys) * sizeof(float);
   if (lds > 40 * 1024) return hipErrorInvalidValue;
   if (fused_cos_sin)
-    hipLaunchKernelGGL((cached_attn_kernel<true, ANC>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc);
+    hipLaunchKernelGGL((cached_attn_kernel<true, ANC, KVF>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc, ks, vs);
   else
-    hipLaunchKernelGGL((cached_attn_kernel<false, ANC>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc);
+    hipLaunchKernelGGL((cached_attn_kernel<false, ANC, KVF>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
+                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc, ks, vs);
   return hipGetLastError();
 }
 
 hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
                             const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
                             lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
-                            int split_max_rows, const int32_t* anc) {
+                            int split_max_rows, const int32_t* anc, const KvFormat& kvf) {
+  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
-  if (anc)
-    return cached_attention_t<true>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, out, R, H, ctx,
-                                    slot_stride, max_keys, s, split_ws, split_max_rows, anc);
-  return cached_attention_t<false>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, out, R, H, ctx,
-                                   slot_stride, max_keys, s, split_ws, split_max_rows, nullptr);
+  hipError_t e = hipErrorInvalidValue;
+  if (anc) {
+    KV_DISPATCH(kvf.fmt, e = (cached_attention_t<true, KVF>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin,
+                                                            out, R, H, ctx, slot_stride, max_keys, s, split_ws, split_max_rows, anc,
+                                                            kvf.ks, kvf.vs)));
+  } else {
+    KV_DISPATCH(kvf.fmt, e = (cached_attention_t<false, KVF>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin,
+                                                             out, R, H, ctx, slot_stride, max_keys, s, split_ws, split_max_rows, nullptr,
+                                                             kvf.ks, kvf.vs)));
+  }
+  return e;
 }
 
 // ---- KV ancestry table (beam search): anc[slot * ctx + p] = the slot whose cache holds position p ----
@@ -1429,11 +1653,12 @@ hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, cons
 }
 
 hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
-                        int64_t slot_stride, int64_t layer_stride, hipStream_t s) {
+                        int64_t slot_stride, int64_t layer_stride, hipStream_t s, const KvFormat& kvf) {
+  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
   if (hi <= lo) return hipSuccess;
   const int64_t n = (int64_t)2 * layers * H * (hi - lo) * 16;
-  hipLaunchKernelGGL(kv_copy_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kc, vc, anc, dst, src, lo, hi - lo, H, ctx,
-                     slot_stride, layer_stride, n);
+  KV_DISPATCH(kvf.fmt, hipLaunchKernelGGL(kv_copy_rows_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kc, vc, anc, dst,
+                                          src, lo, hi - lo, H, ctx, slot_stride, layer_stride, n, kvf.ks, kvf.vs));
   return hipGetLastError();
 }
 

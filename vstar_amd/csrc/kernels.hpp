@@ -134,20 +134,26 @@ hipError_t skinny_pack_tiles_w4(const uint32_t* q, const lp_t* scale, void* Wt, 
 #endif
 
 // ---- KV-cached language model + Perceiver resampler (decode.hip) ----
+// KV-cache format of a layer (fp16 build only beyond KV_FMT_F16).  KV_FMT_MXFP8: kc / vc address code BYTES
+// [slot][H][ctx][128] (same element strides as the fp16 cache) and ks / vs the E8M0 bytes [slot][H][ctx][4] of this layer, one per
+// block of 32 head-dim elements (mx.hpp).  KV_FMT_MXFP8_EMU: the fp16 cache, every writer storing the round-tripped row.
+enum { KV_FMT_F16 = 0, KV_FMT_MXFP8 = 1, KV_FMT_MXFP8_EMU = 2 };
+struct KvFormat { int fmt = KV_FMT_F16; uint8_t* ks = nullptr; uint8_t* vs = nullptr; };
 // x[r,:] = src[r] >= 0 ? table[src[r]] : (src[r] == INT32_MIN ? 0 : feats[-(src[r]+1)])
 hipError_t embed_rows(const int32_t* src, const lp_t* table, int vocab, const lp_t* feats, int64_t n_feat_rows, lp_t* x, int R,
                       int C, hipStream_t s);
 // in-place RoPE on q,k of qkv [R, 3*H*128] at row_pos[r] (rows with row_pos < 0 are skipped) and K/V rows appended to the
 // cache of slot row_slot[r]: kc/vc = this layer's [slot][H][ctx][128]
 hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const int32_t* row_pos, const int32_t* row_slot, lp_t* kc, lp_t* vc,
-                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s);
+                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s, const KvFormat& kvf = KvFormat());
 // causal attention of R new rows against the cache: keys [0, seq_past) come from seq_prefix's slot, the rest from seq_kv's.
 // fused_cos_sin != null (only when every sequence has exactly ONE new row): the kernel also does rope_kv_append's work for
 // its row (RoPE on q,k, K/V appended to the cache) — qkv then holds the raw projection.
 hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
                             const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
                             lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s,
-                            void* split_ws = nullptr, int split_max_rows = 0, const int32_t* anc = nullptr);
+                            void* split_ws = nullptr, int split_max_rows = 0, const int32_t* anc = nullptr,
+                            const KvFormat& kvf = KvFormat());
 // KV ancestry table of beam search (anc: [slots, ctx] int32, entry (slot, p) = the slot whose cache holds position p of the
 // sequence in `slot`; cached_attention reads K/V through it when `anc` is given).  mark: entry (row_slot[r], row_pos[r]) =
 // row_slot[r] for every row; fill: slot's entries [lo, hi) = value; reorder: entries [lo, hi) of dst[i] = those of src[i], every
@@ -158,7 +164,12 @@ hipError_t kv_anc_fill(int32_t* anc, int slot, int value, int lo, int hi, int ct
 hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, const int32_t* d_src, int n, int lo, int hi, int ctx,
                           hipStream_t s);
 hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
-                        int64_t slot_stride, int64_t layer_stride, hipStream_t s);
+                        int64_t slot_stride, int64_t layer_stride, hipStream_t s, const KvFormat& kvf = KvFormat());
+#ifdef VSTAR_LP_F16
+// x [rows, 128] fp16 -> e4m3 codes [rows, 128], E8M0 bytes [rows, 4] and (nullable, may alias x) xhat = fp16(decoded): the device
+// function every KV_FMT_MXFP8 writer quantises with
+hipError_t kv_quantize_rows(const lp_t* x, int rows, uint8_t* codes, uint8_t* scales, lp_t* xhat, hipStream_t s);
+#endif
 // workspace of the split-KV decode path (scores, partial statistics / outputs, tickets) for up to max_rows new rows per step;
 // must be zero-filled once
 size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx);

@@ -88,6 +88,7 @@ struct LlmCachedCfg {
   int max_slots = 1, max_ctx = 1024, max_rows = 1024;
   int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only);
                             // 4: int4 with one fp16 scale per group of 128 (fp16 build only)
+  int kv_format = KV_FMT_F16;   // KV_FMT_MXFP8 / KV_FMT_MXFP8_EMU: block-scaled fp8 KV cache (fp16 build only)
 };
 
 // int8 decode copies of one block linear: row-major q [Npad, K] + per-row scales [Npad] for the register kernel
@@ -111,8 +112,20 @@ struct LlmCached {
   int64_t n_feat_rows = 0;
   // owned
   lp_t* rope = nullptr;                          // [max_ctx, 128] cos | sin
-  lp_t *kcache = nullptr, *vcache = nullptr;     // [layers][slots][heads][ctx][128]
+  lp_t *kcache = nullptr, *vcache = nullptr;     // [layers][slots][heads][ctx][128] (KV_FMT_MXFP8: code bytes, same element strides)
+  uint8_t *kscale = nullptr, *vscale = nullptr;  // KV_FMT_MXFP8: E8M0 bytes [layers][slots][heads][ctx][4]
   int64_t slot_stride = 0, layer_stride = 0;
+  int64_t kv_bytes = 0;                          // K + V storage, scale bytes included
+  // layer i's K / V cache and its format descriptor (the scale arrays of that layer)
+  lp_t* kv_layer(lp_t* base, int i) const {
+    return cfg.kv_format == KV_FMT_MXFP8 ? (lp_t*)((uint8_t*)base + (int64_t)i * layer_stride) : base + (int64_t)i * layer_stride;
+  }
+  KvFormat kv_fmt(int i) const {
+    KvFormat f;
+    f.fmt = cfg.kv_format;
+    if (kscale) { f.ks = kscale + (int64_t)i * (layer_stride / 32); f.vs = vscale + (int64_t)i * (layer_stride / 32); }
+    return f;
+  }
   lp_t *lx = nullptr, *lh = nullptr, *lqkv = nullptr, *latt = nullptr, *lact = nullptr;
   lp_t *wsel = nullptr, *wnorm = nullptr, *logits = nullptr;
   int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_seq = nullptr, *d_want = nullptr,
@@ -215,8 +228,29 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   }
   slot_stride = (int64_t)c.heads * c.max_ctx * 128;
   layer_stride = slot_stride * c.max_slots;
-  RC(e->dalloc(&kcache, (size_t)layer_stride * c.layers));
-  RC(e->dalloc(&vcache, (size_t)layer_stride * c.layers));
+  if (c.kv_format == KV_FMT_MXFP8) {
+#ifdef VSTAR_LP_F16
+    const size_t n = (size_t)layer_stride * c.layers;
+    RC(e->dalloc((uint8_t**)&kcache, n));
+    RC(e->dalloc((uint8_t**)&vcache, n));
+    RC(e->dalloc(&kscale, n / 32));
+    RC(e->dalloc(&vscale, n / 32));
+    kv_bytes = (int64_t)(2 * (n + n / 32));
+#else
+    set_error("kv_cache_format: the block-scaled fp8 KV cache needs the fp16 engine");
+    return VSTAR_ERR_INVALID;
+#endif
+  } else if (c.kv_format == KV_FMT_F16 || c.kv_format == KV_FMT_MXFP8_EMU) {
+#ifndef VSTAR_LP_F16
+    if (c.kv_format != KV_FMT_F16) { set_error("kv_cache_format: the block-scaled fp8 KV cache needs the fp16 engine"); return VSTAR_ERR_INVALID; }
+#endif
+    RC(e->dalloc(&kcache, (size_t)layer_stride * c.layers));
+    RC(e->dalloc(&vcache, (size_t)layer_stride * c.layers));
+    kv_bytes = (int64_t)layer_stride * c.layers * 2 * 2;
+  } else {
+    set_error("kv_cache_format must be 0 (fp16), 1 (MX fp8) or 2 (MX fp8 emulated in fp16)");
+    return VSTAR_ERR_INVALID;
+  }
   const size_t R = (size_t)c.max_rows;
   RC(e->dalloc(&lx, R * H));
   RC(e->dalloc(&lh, R * H));
@@ -502,8 +536,8 @@ inline int LlmCached::llm_layers_prefill(int nseq, int S) {
     const LlmBlock& b = (*blocks)[i];
     LCHK(rmsnorm_lp(lx, b.in_norm, lh, rows, H, c.rms_eps, nullptr, e->stream));
     RC(e->lin(lh, H, b.qkv, lqkv, 3 * H, rows));
-    LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kcache + (int64_t)i * layer_stride, vcache + (int64_t)i * layer_stride,
-                        slot_stride, c.max_ctx, rows, c.heads, e->stream));
+    LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kv_layer(kcache, i), kv_layer(vcache, i), slot_stride, c.max_ctx, rows,
+                        c.heads, e->stream, kv_fmt(i)));
     LCHK(attn_forward(lqkv, latt, nseq, S, c.heads, 128, 1, att_scale, e->stream));
     RC(e->lin(latt, H, b.o, lx, H, rows, VSTAR_EPI_NONE, lx, H));
     LCHK(rmsnorm_lp(lx, b.post_norm, lh, rows, H, c.rms_eps, nullptr, e->stream));
@@ -520,14 +554,15 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
   (void)nseq;
   for (int i = 0; i < c.layers; ++i) {
     const LlmBlock& b = (*blocks)[i];
-    lp_t* kc = kcache + (int64_t)i * layer_stride;
-    lp_t* vc = vcache + (int64_t)i * layer_stride;
+    lp_t* kc = kv_layer(kcache, i);
+    lp_t* vc = kv_layer(vcache, i);
+    const KvFormat kvf = kv_fmt(i);
     RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i], w8(w8_qkv, i),
                 w4(w4_qkv, i)));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
-    if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream));
+    if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream, kvf));
     LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
-                          c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc));
+                          c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc, kvf));
     RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, nullptr, w8(w8_o, i), w4(w4_o, i)));
     RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i],
                 w8(w8_gate_up, i), w4(w4_gate_up, i)));
@@ -782,7 +817,8 @@ inline int LlmCached::kv_copy(int dst, int src, int lo, int hi) {
     return VSTAR_ERR_INVALID;
   }
   LCHK(hipSetDevice(e->device));
-  LCHK(kv_copy_rows(kcache, vcache, d_anc, dst, src, lo, hi, c.layers, c.heads, c.max_ctx, slot_stride, layer_stride, e->stream));
+  LCHK(kv_copy_rows(kcache, vcache, d_anc, dst, src, lo, hi, c.layers, c.heads, c.max_ctx, slot_stride, layer_stride, e->stream,
+                    kv_fmt(0)));
   LCHK(kv_anc_fill(d_anc, dst, dst, 0, c.max_ctx, c.max_ctx, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
   anc_flag[dst] = 0;

@@ -8,6 +8,7 @@
 #ifndef VSTAR_LP_F16
 #error "vqa_engine.hip is the fp16 instantiation: build with -DVSTAR_LP_F16"
 #endif
+#include <algorithm>
 #include <type_traits>
 #include "llm_cached.hpp"
 #include "../../include/vstar_vqa.h"
@@ -147,6 +148,7 @@ int vstar_vqa_engine::finalize() {
     rc.rms_eps = c.llm_rms_eps; rc.rope_theta = c.llm_rope_theta;
     rc.max_slots = c.max_slots; rc.max_ctx = c.max_ctx; rc.max_rows = c.max_rows;
     rc.weight_bits = c.decode_weight_format == VSTAR_VQA_WFMT_W4G128 ? 4 : c.decode_weight_bits;
+    rc.kv_format = c.kv_cache_format;      // VSTAR_VQA_KVFMT_* == KV_FMT_*
     RC(run.init(this, rc, embed, &llm, final_norm, &lm_head));
     run.feats = feats;
     run.n_feat_rows = (int64_t)c.max_images * (P + L);
@@ -268,6 +270,11 @@ int vstar_vqa_create(const vstar_vqa_config* cfg, int device, vstar_vqa_handle**
       (cfg->decode_weight_format != VSTAR_VQA_WFMT_W4G128 || cfg->decode_weight_bits != 0 || cfg->llm_hidden % 128 || cfg->llm_mlp % 128)) {
     tls_error() = "decode_weight_format must be 0 or 1 (int4, groups of 128: needs decode_weight_bits == 0, llm_hidden % 128 == 0 and "
                   "llm_mlp % 128 == 0)";
+    return VSTAR_ERR_INVALID;
+  }
+  static_assert(VSTAR_VQA_KVFMT_MXFP8 == KV_FMT_MXFP8 && VSTAR_VQA_KVFMT_MXFP8_EMULATED == KV_FMT_MXFP8_EMU, "KV format codes");
+  if (cfg->kv_cache_format != 0 && cfg->kv_cache_format != VSTAR_VQA_KVFMT_MXFP8 && cfg->kv_cache_format != VSTAR_VQA_KVFMT_MXFP8_EMULATED) {
+    tls_error() = "kv_cache_format must be 0 (fp16), 1 (block-scaled fp8: MX e4m3, blocks of 32) or 2 (the same values emulated in fp16)";
     return VSTAR_ERR_INVALID;
   }
   int n = 0;
@@ -568,11 +575,69 @@ int vstar_vqa_op_gemm_w4(const void* A, const void* Wq, const void* scale, const
   return op_result(e, "vstar_vqa_op_gemm_w4");
 }
 
+int vstar_vqa_kv_cache_format(const vstar_vqa_handle* h) { return h ? h->cfg.kv_cache_format : 0; }
+
+int64_t vstar_vqa_kv_cache_bytes(const vstar_vqa_handle* h) { return h && h->finalized ? h->run.kv_bytes : 0; }
+
+int vstar_vqa_op_kv_quantize(const void* dev_x_f16, int rows, void* dev_codes_u8, void* dev_scales_u8, void* dev_xhat_f16) {
+  if (!dev_x_f16 || !dev_codes_u8 || !dev_scales_u8 || rows <= 0 || rows > (1 << 24)) {
+    tls_error() = "vstar_vqa_op_kv_quantize: bad argument (x, codes and scales not null, 0 < rows <= 2^24)";
+    return VSTAR_ERR_INVALID;
+  }
+  hipError_t e = kv_quantize_rows((const lp_t*)dev_x_f16, rows, (uint8_t*)dev_codes_u8, (uint8_t*)dev_scales_u8, (lp_t*)dev_xhat_f16, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, "vstar_vqa_op_kv_quantize");
+}
+
+// "kv:<layer>:<slot>": the decoded K then V cache of one layer and slot, [2][heads][ctx][128]
+static int64_t debug_read_kv(vstar_vqa_handle* h, const std::string& n, float* out, int64_t cap) {
+  int layer = -1, slot = -1;
+  char tail = 0;
+  if (sscanf(n.c_str(), "kv:%d:%d%c", &layer, &slot, &tail) != 2 || layer < 0 || layer >= h->cfg.llm_layers || slot < 0 ||
+      slot >= h->cfg.max_slots) {
+    h->set_error("debug_read: bad KV tensor name (kv:<layer>:<slot>, indices in range): " + n);
+    return VSTAR_ERR_INVALID;
+  }
+  const LlmCached& r = h->run;
+  const int64_t per = r.slot_stride;                       // elements of one slot of K (or V)
+  const int64_t cnt = std::min<int64_t>(2 * per, cap);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->set_error("debug_read: HIP failure"); return VSTAR_ERR_HIP; }
+  const int64_t off = (int64_t)layer * r.layer_stride + (int64_t)slot * per;
+  for (int which = 0; which < 2; ++which) {
+    const int64_t lo = which * per, m = std::min(per, cnt - lo);
+    if (m <= 0) break;
+    if (h->cfg.kv_cache_format == VSTAR_VQA_KVFMT_MXFP8) {
+      std::vector<uint8_t> codes((size_t)per), sc((size_t)per / 32);
+      if (hipMemcpy(codes.data(), (const uint8_t*)(which ? r.vcache : r.kcache) + off, codes.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(sc.data(), (which ? r.vscale : r.kscale) + off / 32, sc.size(), hipMemcpyDeviceToHost) != hipSuccess) {
+        h->set_error("debug_read: HIP failure");
+        return VSTAR_ERR_HIP;
+      }
+      for (int64_t i = 0; i < m; ++i) {                    // OCP e4m3: 1-4-3, bias 7, subnormals, 0x7f / 0xff = NaN
+        const uint8_t c = codes[(size_t)i];
+        const int ex = (c >> 3) & 15, mant = c & 7;
+        float v = ex == 15 && mant == 7 ? NAN : (ex ? ldexpf((float)(8 + mant), ex - 10) : ldexpf((float)mant, -9));
+        v = ldexpf(v, (int)sc[(size_t)(i >> 5)] - 127);
+        out[lo + i] = (c & 0x80) ? -v : v;
+      }
+    } else {
+      std::vector<lp_t> tmp((size_t)m);
+      if (hipMemcpy(tmp.data(), (which ? r.vcache : r.kcache) + off, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) {
+        h->set_error("debug_read: HIP failure");
+        return VSTAR_ERR_HIP;
+      }
+      for (int64_t i = 0; i < m; ++i) out[lo + i] = lp2f(tmp[(size_t)i]);
+    }
+  }
+  return cnt;
+}
+
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t cap) {
   if (!h || !name || !out) { tls_error() = "bad argument"; return VSTAR_ERR_INVALID; }
   if (!h->finalized) { h->set_error("weights not finalized"); return VSTAR_ERR_STATE; }
   hipSetDevice(h->device);
   const std::string n(name);
+  if (n.rfind("kv:", 0) == 0) return debug_read_kv(h, n, out, cap);
   const lp_t* src = nullptr;
   int64_t cnt = 0;
   if (n == "features") { src = h->feats; cnt = (int64_t)h->cfg.max_images * (h->clip.P + h->cfg.pcv_latents) * h->cfg.llm_hidden; }

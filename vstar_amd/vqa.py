@@ -122,11 +122,13 @@ class _ImageProcessor:
 
 class VQA_LLM:
     def __init__(self, args=None, cfg: Optional[VQAConfig] = None, state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 tokenizer=None, engine: Optional[VqaEngine] = None, device: int = 0, decode_weight_bits: Optional[int] = None):
+                 tokenizer=None, engine: Optional[VqaEngine] = None, device: int = 0, decode_weight_bits: Optional[int] = None,
+                 kv_cache_bits: Optional[int] = None):
         """args: the reference's namespace (vqa_model_path, conv_type).  With a local checkpoint directory the weights and
         tokenizer are read from it; offline pass `state_dict` (+ optionally `tokenizer`).  decode_weight_bits=8 builds the
         engine in the int8 weight-only decode mode, 4 in the int4 group-scaled mode (§8.6: translated to
-        decode_weight_format=1 by VQAConfig.with_decode_bits); None = what `cfg` says, 0 by default."""
+        decode_weight_format=1 by VQAConfig.with_decode_bits); None = what `cfg` says, 0 by default.  kv_cache_bits=8 builds it
+        with the block-scaled fp8 KV cache (§8.7; VQAConfig.with_kv_bits), independently of the weight mode; None = what `cfg` says."""
         import os
         from .weights import load_vqa_checkpoint_dir, vqa_config_from_dir
         path = getattr(args, "vqa_model_path", None) if args is not None else None
@@ -143,6 +145,10 @@ class VQA_LLM:
             if engine is not None:
                 raise ValueError("decode_weight_bits is fixed when the engine is built: pass it in the engine's VQAConfig")
             self.cfg = self.cfg.with_decode_bits(decode_weight_bits)
+        if kv_cache_bits is not None and kv_cache_bits != self.cfg.kv_bits():
+            if engine is not None:
+                raise ValueError("kv_cache_bits is fixed when the engine is built: pass it in the engine's VQAConfig")
+            self.cfg = self.cfg.with_kv_bits(kv_cache_bits)
         self.conv_type = getattr(args, "conv_type", "v1") if args is not None else "v1"
         if self.conv_type != "v1":
             raise ValueError("only the 'v1' conversation template of the reference evaluation is implemented")

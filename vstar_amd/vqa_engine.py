@@ -224,6 +224,19 @@ class VqaEngine:
         group-scaled mode (decode_weight_format=1), else 0."""
         return int(self.lib.vstar_vqa_decode_weight_bits(self.handle))
 
+    def kv_cache_format(self) -> int:
+        """The active KV-cache format: 0 = fp16, 1 = block-scaled fp8 (config.KVFMT_MXFP8), 2 = the same values emulated in fp16."""
+        return int(self.lib.vstar_vqa_kv_cache_format(self.handle))
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of K plus V storage of the finalized engine, scale bytes included: what max_slots and max_ctx cost."""
+        return int(self.lib.vstar_vqa_kv_cache_bytes(self.handle))
+
+    def kv_rows(self, layer: int, slot: int) -> np.ndarray:
+        """The DECODED K and V cache of one layer and slot, float32 [2, heads, max_ctx, 128], in every format (parity tests)."""
+        H, C = self.cfg.llm_heads, self.cfg.max_ctx
+        return self.debug_read(f"kv:{int(layer)}:{int(slot)}", 2 * H * C * 128).reshape(2, H, C, 128)
+
     def last_forward_ms(self) -> float:
         return float(self.lib.vstar_vqa_last_forward_ms(self.handle))
 

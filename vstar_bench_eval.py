@@ -28,6 +28,9 @@ def parse_args(argv):
     p.add_argument("--vqa-decode-bits", dest="vqa_decode_bits", default=0, type=int, choices=[0, 4, 8],
                    help="8: the VQA-LLM's int8 weight-only decode mode (DESIGN.md 8.4); 4: its int4 group-scaled mode (8.6); "
                         "0: fp16 weights everywhere")
+    p.add_argument("--vqa-kv-bits", dest="vqa_kv_bits", default=0, type=int, choices=[0, 8],
+                   help="8: the VQA-LLM's block-scaled fp8 KV cache (MX e4m3, blocks of 32: 132 bytes per cached row instead of 256; "
+                        "DESIGN.md 8.7); 0: the fp16 cache.  Independent of --vqa-decode-bits")
     p.add_argument("--search-window", dest="search_window", default=0, type=int, help="concurrent visual searches per engine batch "
                    "(cross-image lock step); 0 = one engine batch, 1 = one image at a time like the reference")
     p.add_argument("--vqa-batch", dest="vqa_batch", default=1, type=int, help="questions per VQA-LLM engine call in the free-form and "
@@ -61,7 +64,8 @@ def main(argv):
             vqa_llm = getattr(importlib.import_module(mod), fn)(args)
         else:
             from vstar_amd.vqa import VQA_LLM
-            vqa_llm = VQA_LLM(args, device=local_rank if world > 1 else args.device, decode_weight_bits=args.vqa_decode_bits or None)
+            vqa_llm = VQA_LLM(args, device=local_rank if world > 1 else args.device, decode_weight_bits=args.vqa_decode_bits or None,
+                              kv_cache_bits=args.vqa_kv_bits or None)
         from vstar_amd.bench_eval import eval_model, make_vsm
         vsm = None
         if args.vsm_factory:
