@@ -203,6 +203,52 @@ int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_o
 int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
                         const int32_t* draft, const vstar_vqa_sampling* params, int32_t* n_accept_out, int32_t* tokens_out);
 
+/* Logits edits: HF generate's logits processors — repetition_penalty, no_repeat_ngram_size, bad_words_ids,
+ * min_new_tokens, suppress_tokens, prefix_allowed_tokens_fn — reduced by the caller to three token lists per wanted row and applied
+ * on the device to that row's logits x (storage type T) between lm_head and the tail that picks a token:
+ *   1. penalised t:  x[t] = T(f32(x[t]) < 0 ? f32(x[t]) * theta : f32(x[t]) / theta), IEEE fp32 multiply / divide, then one
+ *      round-to-nearest-even to T (NaN stays NaN, -0 takes the divide): transformers' RepetitionPenaltyLogitsProcessor, bit for bit
+ *   2. banned t:     x[t] = -inf
+ *   3. a non-empty allowed list:  x[t] = -inf for every t in [0, llm_vocab) not in it
+ * in this order: a ban wins over a penalty, a token both allowed and banned is -inf.  All arrays HOST, one CSR array for the lists:
+ *   off[3 * n_want + 1]  non-decreasing, off[0] == 0; wanted row j's penalised ids are tok[off[3j] .. off[3j+1]), its banned ids
+ *                        tok[off[3j+1] .. off[3j+2]), its allowed ids tok[off[3j+2] .. off[3j+3])
+ *   tok[off[3 n_want]]   every list strictly increasing, ids in [0, llm_vocab)
+ *   penalty[n_want]      theta per row, finite and > 0; read only where the row's penalised list is non-empty
+ * A row whose three lists are empty keeps its logits untouched. */
+typedef struct vstar_vqa_logit_edits {
+  const int32_t* off;
+  const int32_t* tok;
+  const float*   penalty;
+} vstar_vqa_logit_edits;
+
+/* vstar_vqa_forward / _forward_sample / _forward_verify with the edits applied to the wanted rows' logits ahead of the arg-max /
+ * draw / verify choice; edits == NULL is the plain call, bit for bit.  logits_f16 of the first returns the EDITED logits (HF's
+ * `scores`).  Errors (VSTAR_ERR_INVALID, before any device work, the engine stays usable): lists that break the rules above, or more
+ * than vstar_vqa_logit_edit_capacity ids in one call.  The device arrays for the lists are allocated by the first call that
+ * carries edits (a failed allocation is VSTAR_ERR_NOMEM and leaves the engine usable); an engine that never sees edits allocates and
+ * launches nothing for them.  The beam and scoring tails take no edits: HF applies the processors to the log-softmax output in beam
+ * search, with the log-sum-exp of the unedited row, which an edit ahead of the beam select would not reproduce (open follow-up);
+ * a target's likelihood under edited logits has no reference meaning. */
+int vstar_vqa_forward_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                            uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits);
+int vstar_vqa_forward_sample_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src,
+                                   const int32_t* kv_slot, const int32_t* prefix_slot, const int32_t* past_len,
+                                   int n_want, const int32_t* want, const vstar_vqa_sampling* params, int32_t* tokens,
+                                   const vstar_vqa_logit_edits* edits);
+int vstar_vqa_forward_verify_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                   const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                   const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                   int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits);
+/* The most token ids (the three lists of all wanted rows together) one call with edits may carry: 256 * (max_ctx + 2048). */
+int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h);
+/* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22, rows <= 65535, any ld >=
+ * vocab), edited in place — columns [vocab, ld) are never written; host off / tok / penalty as above with n_want = rows, checked
+ * before any device work.  Null stream, synchronises. */
+int vstar_vqa_op_edit(void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok,
+                      const float* penalty);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

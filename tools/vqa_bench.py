@@ -27,6 +27,8 @@ context); tokens/s of both (median over the blocks), their ratio, the spread, an
 drafter proposing that output: 1.0 = acceptance 0, 0.0 = acceptance 1) `VQA_LLM.speculative_decode` blocks alternated --rounds
 times with `greedy_decode` blocks of the same process; tokens/s of both (median over the blocks), their ratio, the spread of the
 blocks, the acceptance counters, and the device time of a verify step against its row count (1 .. 16 rows).
+--rules: one engine, greedy decode steps with logits rules (repetition penalty + bigram ban over --ctx history tokens, DESIGN.md
+§8.8) alternated with plain steps in blocks of --steps; device and wall ms per step of both and the host planning time.
 --spec-kernels R (under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py --layers 2 --spec-kernels R`): 20 one-sequence
 steps of R rows with the arg-max tail on R wanted rows and 20 with the greedy and the sampled verify tail, for the per-kernel
 statistics of the verify kernels against argmax_rows_lp.
@@ -67,12 +69,17 @@ def main():
     ap.add_argument("--spec", default="", help="comma-separated draft lengths: speculative against plain greedy decode (runs alone)")
     ap.add_argument("--spec-tokens", type=int, default=64, help="--spec: tokens decoded per block")
     ap.add_argument("--spec-corrupt", default="1.0,0.5,0.0", help="--spec: shares of corrupted draft positions")
+    ap.add_argument("--rules", action="store_true", help="greedy decode steps with logits rules (repetition penalty + bigram ban over --ctx "
+                    "history tokens) against plain ones, alternated blocks (runs alone)")
     ap.add_argument("--spec-kernels", type=int, default=0, help="rows: the arg-max and verify tails alone, for a kernel trace")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
     score_b = [int(x) for x in a.score.split(",")] if a.score else []
     if a.only_score and not score_b:
         ap.error("--only-score needs --score B[,B...]")
+    if a.rules:
+        out = {"decode_rules": decode_rules(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds, a.ctx)}
+        return finish(out, a)
     if a.kv_bits:
         if [int(x) for x in a.kv_bits.split(",")] != [0, 8]:
             ap.error("--kv-bits takes 0,8")
@@ -336,6 +343,63 @@ def decode_kv(layers, batches, steps, rounds, weight_modes, ctx):
         engs.clear()
         del eng
         gc.collect()
+    return res
+
+
+def decode_rules(layers, batches, steps, rounds, ctx):
+    """Greedy decode steps with logits rules against plain ones: one engine, B sequences whose history is `ctx`
+    text ids, repetition_penalty 1.2 + no_repeat_ngram_size 2 planned over that history plus what was generated; blocks of `steps`
+    alternated `rounds` times in one process (round 0 warms up and is dropped).  Per batch: device ms per step of both (HIP events
+    inside the engine: the edit launch is inside the bracket), wall ms per step, and the host time of plan + pack per step, which the
+    ruled wall time contains."""
+    from vstar_amd.logits import LogitRules
+    B_max = max(batches + [1])
+    max_ctx = (ctx + (rounds + 1) * steps * 2 * len(batches) + 64 + 63) // 64 * 64
+    cfg = VQAConfig.seal_7b(llm_layers=layers, max_slots=B_max, max_ctx=max_ctx, max_rows=max(16384, ctx * 8), max_images=1)
+    eng = VqaEngine(cfg, 0)
+    eng.load_state_dict(random_state_dict(cfg, 0, torch.float16, share_layers=True))
+    rules = LogitRules(repetition_penalty=1.2, no_repeat_ngram_size=2)
+    g = torch.Generator().manual_seed(0)
+    res = {"config": {"layers": cfg.llm_layers, "hidden": cfg.llm_hidden, "vocab": cfg.llm_vocab, "history": ctx,
+                      "rules": "repetition_penalty=1.2, no_repeat_ngram_size=2", "edit_capacity": eng.logit_edit_capacity()}}
+    for B in batches:
+        hist = [torch.randint(3, 30000, (ctx,), generator=g).tolist() for _ in range(B)]
+        nxt = None
+        for i0 in range(0, B, 8):                             # prefill in chunks of 8 sequences (max_rows)
+            n = min(8, B - i0)
+            _, t = eng.forward([Seq(hist[i0 + i], kv_slot=i0 + i) for i in range(n)], [(i, -1) for i in range(n)], logits=False)
+            nxt = t if i0 == 0 else np.concatenate([nxt, t])
+        pos, want = ctx, [(i, 0) for i in range(B)]
+        dev, blocks, plan_ms, ids_per_step = {0: [], 1: []}, {0: [], 1: []}, [], []
+        for r in range(rounds + 1):
+            for on in (0, 1):
+                t0, d = time.time(), []
+                for s in range(steps):
+                    for i in range(B):
+                        hist[i].append(int(nxt[i]))
+                    edits = None
+                    if on:
+                        tp = time.time()
+                        edits = LogitRules.pack([rules.plan(hist[i], pos + 1 - ctx, None, i) for i in range(B)])
+                        if r:
+                            plan_ms.append((time.time() - tp) * 1e3)
+                            ids_per_step.append(int(edits[0][-1]))
+                    _, nxt = eng.forward([Seq([hist[i][-1]], kv_slot=i, past_len=pos) for i in range(B)], want, logits=False, edits=edits)
+                    d.append(eng.last_forward_ms())
+                    pos += 1
+                if r:
+                    blocks[on].append((time.time() - t0) / steps * 1e3)
+                    dev[on] += d
+        leg = {"positions": [ctx, pos], "host_plan_pack_ms_per_step": round(float(np.median(plan_ms)), 3),
+               "edit_ids_per_step": int(np.median(ids_per_step))}
+        for on, name in ((0, "plain"), (1, "rules")):
+            w, d = float(np.median(blocks[on])), float(np.median(dev[on]))
+            leg[name] = {"device_ms_per_step": round(d, 3), "wall_ms_per_step": round(w, 3),
+                         "wall_ms_per_step_blocks": [round(x, 3) for x in blocks[on]],
+                         "spread": round((max(blocks[on]) - min(blocks[on])) / w, 3)}
+        leg["rules_minus_plain_device_ms"] = round(leg["rules"]["device_ms_per_step"] - leg["plain"]["device_ms_per_step"], 3)
+        leg["rules_over_plain_wall"] = round(leg["rules"]["wall_ms_per_step"] / leg["plain"]["wall_ms_per_step"], 3)
+        res[f"B{B}"] = leg
     return res
 
 

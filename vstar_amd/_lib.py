@@ -41,6 +41,8 @@ EXPORTS_VQA = [
     "vstar_vqa_op_quantize_w4", "vstar_vqa_op_gemm_w4",
     "vstar_vqa_kv_cache_format", "vstar_vqa_kv_cache_bytes", "vstar_vqa_op_kv_quantize",
     "vstar_vqa_forward_verify", "vstar_vqa_op_verify",
+    "vstar_vqa_forward_edits", "vstar_vqa_forward_sample_edits", "vstar_vqa_forward_verify_edits", "vstar_vqa_op_edit",
+    "vstar_vqa_logit_edit_capacity",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -72,6 +74,15 @@ class VqaSampling(ctypes.Structure):
         ("step", ctypes.c_uint32),
         ("seed", ctypes.c_uint64),
         ("stream", ctypes.c_uint64),
+    ]
+
+
+class VqaLogitEdits(ctypes.Structure):
+    """vstar_vqa_logit_edits (include/vstar_vqa.h): the host CSR arrays of one call's logits edits, three pointers."""
+    _fields_ = [
+        ("off", c_void_p),
+        ("tok", c_void_p),
+        ("penalty", c_void_p),
     ]
 
 
@@ -249,6 +260,16 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_verify.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p]
     lib.vstar_vqa_op_verify.restype = c_int
+    lib.vstar_vqa_forward_edits.argtypes = lib.vstar_vqa_forward.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_edits.restype = c_int
+    lib.vstar_vqa_forward_sample_edits.argtypes = lib.vstar_vqa_forward_sample.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_sample_edits.restype = c_int
+    lib.vstar_vqa_forward_verify_edits.argtypes = lib.vstar_vqa_forward_verify.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_verify_edits.restype = c_int
+    lib.vstar_vqa_op_edit.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_edit.restype = c_int
+    lib.vstar_vqa_logit_edit_capacity.argtypes = [H]
+    lib.vstar_vqa_logit_edit_capacity.restype = c_int64
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int

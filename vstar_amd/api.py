@@ -243,16 +243,32 @@ class LlavaSearchModel:
     def generate(self, input_ids, images=None, object_features=None, images_long=None, objects_long=None, do_sample: bool = False,
                  num_beams: int = 1, temperature: float = 0, top_p=None, max_new_tokens: int = 200, use_cache: bool = True,
                  stopping_criteria=None, top_k=50, seed=None, length_penalty: float = 1.0, early_stopping=False,
-                 num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, **unused):
+                 num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None, allowed_tokens_fn=None,
+                 prefix_allowed_tokens_fn=None, **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
         — the same draws as VQA_LLM.free_form_inference(seed=seed).  Beam sampling is not implemented.
         prompt_lookup_num_tokens = d > 0 (<= 15; num_beams 1): speculative decoding with up to d draft tokens per step from
         `draft_fn` (default: prompt lookup over the text ids, vstar_amd/spec.py — our matching rule, not HF's), greedy or
-        sampled; the same ids as VQA_LLM.free_form_inference(speculative=d)."""
+        sampled; the same ids as VQA_LLM.free_form_inference(speculative=d).
+        repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens, allowed_tokens_fn (HF's name
+        prefix_allowed_tokens_fn is accepted too): HF's logits processors of these names, applied to the logits on the device
+        ahead of the arg-max / draw / verify choice (vstar_amd/logits.py); validated as HF validates them
+        (repetition_penalty <= 0 raises ValueError).  The history the rules see is the text of input_ids — the <image> /
+        <object> placeholders left out — plus the generated tokens; allowed_tokens_fn(batch_id, history ids) gets that list.
+        At their defaults no edits are built.  With num_beams > 1 an active rule raises NotImplementedError: HF applies the
+        processors to the log-softmax output in beam search, with the log-sum-exp of the unedited row."""
+        from .logits import BEAM_RULES_MESSAGE, rules_from_kwargs
         from .vqa import check_spec_tokens, resolve_seed, sampling_params
         from .vqa_engine import Seq
+        if allowed_tokens_fn is not None and prefix_allowed_tokens_fn is not None:
+            raise ValueError("pass allowed_tokens_fn or prefix_allowed_tokens_fn, not both")
+        rules = rules_from_kwargs(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens,
+                                  allowed_tokens_fn if allowed_tokens_fn is not None else prefix_allowed_tokens_fn)
+        if rules is not None and num_beams > 1:
+            raise NotImplementedError(BEAM_RULES_MESSAGE)
         if num_beams != 1 and do_sample:
             raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not implemented")
         if num_beams < 1:
@@ -267,10 +283,10 @@ class LlavaSearchModel:
         if spec and num_beams > 1:
             raise ValueError("prompt_lookup_num_tokens > 0 cannot be combined with beam search (num_beams > 1)")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
+        text = [[t for t in ids if t >= 0]]
         if spec:
             p = [sampling_params(temperature, top_k, top_p, resolve_seed(seed))] if do_sample else None
-            new = self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], [[t for t in ids if t >= 0]], max_new_tokens, spec,
-                                               p, draft_fn)[0]
+            new = self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], text, max_new_tokens, spec, p, draft_fn, rules)[0]
             return torch.tensor([ids + new], dtype=torch.long)
         if num_beams > 1:
             outs = self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
@@ -278,9 +294,9 @@ class LlavaSearchModel:
             return torch.tensor([ids + o for o in outs], dtype=torch.long)
         if do_sample:
             p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
-            new = self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p])[0]
+            new = self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text)[0]
         else:
-            new = self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens)[0]
+            new = self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text)[0]
         return torch.tensor([ids + new], dtype=torch.long)
 
 

@@ -147,6 +147,12 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     window = int(getattr(args, "search_window", 0) or 0)
     spec_tokens = int(getattr(args, "vqa_spec_tokens", 0) or 0)     # `--vqa-spec-tokens d`: speculative free-form decode
     spec_kw = {"speculative": spec_tokens} if spec_tokens else {}   # (0: the call other VQA-LLM implementations also take)
+    # `--vqa-repetition-penalty` / `--vqa-no-repeat-ngram`: logits rules of the free-form pass; off = no keyword
+    theta, ngram = float(getattr(args, "vqa_repetition_penalty", 1.0) or 1.0), int(getattr(args, "vqa_no_repeat_ngram", 0) or 0)
+    if theta != 1.0:
+        spec_kw["repetition_penalty"] = theta
+    if ngram:
+        spec_kw["no_repeat_ngram_size"] = ngram
     max_found = getattr(args, "max_found_objects", None)        # (tests: tiny engines hold few object crops)
     entries = []
     for split in ("direct_attributes", "relative_position"):

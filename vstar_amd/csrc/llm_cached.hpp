@@ -60,6 +60,16 @@ struct LlmVerifyArgs {
   int32_t* tokens = nullptr;
 };
 
+// The logits edits of forward() (edit.hip): host arrays, one triple of sorted token lists per wanted row in one CSR
+// array — row j's penalised ids tok[off[3j] .. off[3j+1]), banned ids tok[off[3j+1] .. off[3j+2]), allowed ids tok[off[3j+2] ..
+// off[3j+3]) — and penalty[n_want], read where the penalised list is non-empty.  Applied to the wanted rows' logits between
+// lm_head and the tail, which then sees the edited rows; ARGMAX, SAMPLE and VERIFY tails only.
+struct LlmEdits {
+  const int32_t* off = nullptr;
+  const int32_t* tok = nullptr;
+  const float* penalty = nullptr;
+};
+
 struct LlmCached;
 
 // What forward() does with the wanted rows' logits: exactly one of the five tails, built by the function of its name — so a call
@@ -135,6 +145,10 @@ struct LlmCached {
   int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
   float* d_nll = nullptr;                        // [max_rows]
   int32_t *d_vdraft = nullptr, *d_vflag = nullptr, *d_vtok = nullptr, *d_vacc = nullptr;   // [max_want] the verify tail's drafts / flags / outputs
+  // ---- logits edits: allocated by the first forward() that carries edits, never by an engine that sees none ----
+  int32_t *d_eoff = nullptr, *d_etok = nullptr;  // [3 max_want + 1] offsets, [edit_capacity()] ids
+  float* d_epen = nullptr;                       // [max_want]
+  int64_t edit_capacity() const { return (int64_t)max_want * (cfg.max_ctx + 2048); }     // ids of one call, the three lists of all rows together
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
   // ---- beam search ----
@@ -200,9 +214,10 @@ struct LlmCached {
   // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
   struct TailCopy { void* dev = nullptr; const void* in = nullptr; void* out = nullptr; size_t bytes = 0; };
   size_t vpad() const { return (size_t)(cfg.vocab + 255) / 256 * 256; }      // row stride of the logits buffer
-  int forward(const LlmRows& rw, const LlmTail& tail);
+  int forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits = nullptr);
   int head(int w0, int m);
   int tail_check(const LlmRows& r, const LlmTail& t);
+  int edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed);
   std::array<TailCopy, 5> tail_copies(const LlmTail& t, int n_want);
   int tail_launch(const LlmTail& t, int w0, int m);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
@@ -619,6 +634,38 @@ inline int LlmCached::tail_check(const LlmRows& r, const LlmTail& t) {
   return 0;
 }
 
+// The edits of a call, validated next to its tail (after the rows: the row fault is the one reported) and before any device work;
+// the device arrays for the lists are allocated here, by the first call that carries edits.
+inline int LlmCached::edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed) {
+  if (t.kind == LlmTail::BEAM) {
+    e->set_error("logits edits with the beam tail are not supported: HF applies the processors to the log-softmax output, whose "
+                 "log-sum-exp is that of the UNEDITED row; editing the logits ahead of the beam select would compute something else");
+    return VSTAR_ERR_INVALID;
+  }
+  if (t.kind == LlmTail::SCORE) {
+    e->set_error("logits edits with the scoring tail are not supported: a target's likelihood under edited logits has no reference meaning");
+    return VSTAR_ERR_INVALID;
+  }
+  if (r.n_want < 1) { e->set_error("logits edits: no wanted rows"); return VSTAR_ERR_INVALID; }
+  // (the size first: a call above the capacity is refused for its size, without walking lists that long)
+  if (ed.off && (int64_t)ed.off[3 * r.n_want] > edit_capacity()) {
+    e->set_error("logits edits: " + std::to_string(ed.off[3 * r.n_want]) + " token ids in one call exceed the capacity of " +
+                 std::to_string(edit_capacity()) + " (max_want * (max_ctx + 2048))");
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_edit_check(r.n_want, cfg.vocab, ed.off, ed.tok, ed.penalty)) { e->set_error(std::string("logits edits: ") + m); return VSTAR_ERR_INVALID; }
+  if (!d_eoff) {      // one block: a failed allocation leaves nothing behind and the engine as it was
+    const size_t n_off = (size_t)3 * max_want + 1, n_words = n_off + (size_t)max_want + (size_t)edit_capacity();
+    int32_t* blk = nullptr;
+    const int rc = e->dalloc(&blk, n_words);
+    if (rc) { (void)hipGetLastError(); return rc; }
+    d_eoff = blk;
+    d_epen = (float*)(blk + n_off);
+    d_etok = blk + n_off + max_want;
+  }
+  return 0;
+}
+
 // A tail's copies, in stream order: uploads (`in`, host -> dev) go out with the row metadata before the layers, downloads (dev ->
 // `out`, host) behind the tail.  An entry whose host pointer is null (an output the caller did not ask for, greedy verify's
 // params, the unused entries of the array) or that has zero bytes is no copy.
@@ -665,7 +712,7 @@ inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
   return 0;
 }
 
-inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail) {
+inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
   const int nseq = rw.nseq, n_want = rw.n_want;
@@ -694,6 +741,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail) {
   for (int j = 0; j < n_want; ++j)
     if (want[j] < 0 || want[j] >= R) { e->set_error("want row out of range"); return VSTAR_ERR_INVALID; }
   RC(tail_check(rw, tail));
+  if (edits) RC(edits_check(rw, tail, *edits));
   // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
   bool use_anc = false;
   for (int i = 0; i < nseq; ++i) {
@@ -755,6 +803,12 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail) {
   const std::array<TailCopy, 5> copies = tail_copies(tail, n_want);
   for (const TailCopy& x : copies)
     if (x.in && x.bytes) LCHK(hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, e->stream));
+  if (edits) {
+    const size_t n_tok = (size_t)edits->off[3 * n_want];
+    LCHK(hipMemcpyAsync(d_eoff, edits->off, ((size_t)3 * n_want + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    if (n_tok) LCHK(hipMemcpyAsync(d_etok, edits->tok, n_tok * 4, hipMemcpyHostToDevice, e->stream));
+    if (edits->penalty) LCHK(hipMemcpyAsync(d_epen, edits->penalty, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+  }
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
@@ -766,6 +820,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail) {
   for (int w0 = 0; w0 < n_want; w0 += max_want) {
     const int m = n_want - w0 < max_want ? n_want - w0 : max_want;
     RC(head(w0, m));
+    if (edits) LCHK(vstar_edit_rows_lp(logits, m, c.vocab, (int64_t)vpad(), d_eoff + 3 * w0, d_etok, d_epen + w0, e->stream));
     RC(tail_launch(tail, w0, m));
   }
   LCHK(hipEventRecord(ev1, e->stream));

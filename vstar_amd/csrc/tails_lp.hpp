@@ -1,4 +1,4 @@
-// tails_lp.hpp — the four decode tails (sample / beam / score / spec .hip) under `_lp` names, as argmax_rows_lp has one: each
+// tails_lp.hpp — the four decode tails (sample / beam / score / spec .hip) and the logits-edit stage (edit.hip) under `_lp` names, as argmax_rows_lp has one: each
 // forwards to the launcher of the including instantiation's storage type (VSTAR_LP_F16: fp16, else bf16).  The .hip files stay
 // compiled once, dtype-explicit; the arguments are documented at the launchers (sample.hpp, beam.hpp, score.hpp, spec.hpp).
 #pragma once
@@ -7,6 +7,7 @@
 #include "beam.hpp"
 #include "score.hpp"
 #include "spec.hpp"
+#include "edit.hpp"
 
 #ifdef VSTAR_LP_F16
 #define VSTAR_TAIL_LP(name) name##_f16
@@ -30,6 +31,10 @@ inline hipError_t vstar_verify_rows_lp(const lp_t* x, int rows, int vocab, int64
                                        const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag, int32_t* n_accept, int32_t* tokens,
                                        hipStream_t s) {
   return VSTAR_TAIL_LP(vstar_verify_rows)(x, rows, vocab, ld, group_off, n_groups, draft, params, choice, flag, n_accept, tokens, s);
+}
+inline hipError_t vstar_edit_rows_lp(lp_t* x, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok, const float* penalty,
+                                     hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_edit_rows)(x, rows, vocab, ld, off, tok, penalty, s);
 }
 }  // namespace VS_NS
 #undef VSTAR_TAIL_LP

@@ -326,16 +326,39 @@ int vstar_vqa_encode_images(vstar_vqa_handle* h, int n, const uint16_t* pixels_f
 int vstar_vqa_forward(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                       const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                       uint16_t* logits_f16, int32_t* argmax) {
+  return vstar_vqa_forward_edits(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, argmax, nullptr);
+}
+
+// the three forms with logits edits; the plain entries pass NULL
+static const LlmEdits* edits_of(const vstar_vqa_logit_edits* ed, LlmEdits* out) {
+  if (!ed) return nullptr;
+  *out = LlmEdits{ed->off, ed->tok, ed->penalty};
+  return out;
+}
+
+int vstar_vqa_forward_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                            const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                            uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits) {
   if (int rc = vqa_ready(h)) return rc;
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::argmax(logits_f16, argmax));
+  LlmEdits ed;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::argmax(logits_f16, argmax),
+                        edits_of(edits, &ed));
 }
 
 int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                              const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                              const vstar_vqa_sampling* params, int32_t* tokens) {
+  return vstar_vqa_forward_sample_edits(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, tokens, nullptr);
+}
+
+int vstar_vqa_forward_sample_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                   const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                   const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_logit_edits* edits) {
   if (int rc = vqa_ready(h)) return rc;
   if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::sample(params, tokens));
+  LlmEdits ed;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::sample(params, tokens),
+                        edits_of(edits, &ed));
 }
 
 int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
@@ -364,14 +387,26 @@ int vstar_vqa_forward_verify(vstar_vqa_handle* h, int nseq, const int32_t* row_o
                              const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                              const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
                              int32_t* n_accept_out, int32_t* tokens_out) {
+  return vstar_vqa_forward_verify_edits(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, group_off, n_groups,
+                                        draft, n_accept_out, tokens_out, nullptr);
+}
+
+int vstar_vqa_forward_verify_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                   const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                   const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                   int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits) {
   if (int rc = vqa_ready(h)) return rc;
   if (!group_off || !draft || !n_accept_out || !tokens_out) {
     h->set_error("forward_verify: group_off, draft and the outputs are required");
     return VSTAR_ERR_INVALID;
   }
   const LlmVerifyArgs v{n_groups, group_off, draft, n_accept_out, tokens_out};
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::verify_rows(v, params));
+  LlmEdits ed;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::verify_rows(v, params),
+                        edits_of(edits, &ed));
 }
+
+int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h) { return h ? h->run.edit_capacity() : 0; }
 
 int vstar_vqa_kv_reorder(vstar_vqa_handle* h, int n, const int32_t* dst_slot, const int32_t* src_slot, int lo, int hi) {
   if (int rc = vqa_ready(h)) return rc;
@@ -482,6 +517,27 @@ int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, 
   d_ac.download(n_accept_out);
   d_tok.download(tokens_out);
   return op_result(e, "vstar_vqa_op_verify");
+}
+
+int vstar_vqa_op_edit(void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok,
+                      const float* penalty) {
+  if (!dev_logits || rows > 65535 || ld < vocab || (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_edit: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_edit_check(rows, vocab, off, tok, penalty)) {
+    tls_error() = std::string("vstar_vqa_op_edit: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
+  hipError_t e = hipSuccess;
+  const size_t n_tok = (size_t)off[3 * rows];
+  OpBuf<int32_t> d_off(e, (size_t)3 * rows + 1), d_tok(e, n_tok, n_tok != 0);
+  OpBuf<float> d_pen(e, rows, penalty != nullptr);
+  d_off.upload(off);
+  d_tok.upload(tok);
+  d_pen.upload(penalty);
+  op_launch(e, dtype, vstar_edit_rows_f16, vstar_edit_rows_bf16, (uint16_t*)dev_logits, rows, vocab, ld, d_off, d_tok, d_pen, nullptr);
+  return op_result(e, "vstar_vqa_op_edit");
 }
 
 int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,

@@ -23,6 +23,7 @@ from PIL import Image
 
 from ._lib import VqaSampling
 from .config import IMAGE_TOKEN_INDEX, OBJECT_TOKEN_INDEX, VQAConfig
+from .logits import BEAM_RULES_MESSAGE, LogitRules, rules_from_kwargs
 from .preprocess import CLIP_MEAN, CLIP_STD, SyntheticTokenizer, _normalise
 from .vqa_engine import Seq, VqaEngine
 
@@ -207,29 +208,43 @@ class VQA_LLM:
     # ---- free-form answer (vstar_bench_eval.py:78-113) ----
     def free_form_inference(self, image, question, temperature=0, top_p=None, num_beams=1, max_new_tokens=200,
                             object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None, speculative=0,
-                            draft_fn=None) -> str:
+                            draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+                            suppress_tokens=None, allowed_tokens_fn=None) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
         so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
         4.31 beam search; beam sampling (num_beams > 1 with temperature > 0) is not implemented.
         speculative = d > 0: speculative decoding with up to d (<= 15) draft tokens per step from `draft_fn` (default: prompt
-        lookup, vstar_amd/spec.py), greedy or sampled; 0 is the plain decode."""
+        lookup, vstar_amd/spec.py), greedy or sampled; 0 is the plain decode.
+        repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens, allowed_tokens_fn: HF generate's
+        logits processors of these names (allowed_tokens_fn = prefix_allowed_tokens_fn), applied to the logits on the device ahead
+        of the pick (vstar_amd/logits.py); the defaults mean no rules, and num_beams > 1 with a rule raises."""
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
                                           objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
-                                    top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn)[0]
+                                    top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn,
+                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                    bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
+                                    allowed_tokens_fn=allowed_tokens_fn)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
                         seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, speculative: int = 0,
-                        draft_fn=None) -> List[str]:
+                        draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+                        suppress_tokens=None, allowed_tokens_fn=None) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
         single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
         i*k .. i*k+k-1 (n*k <= max_slots), one group per sample in every step's forward.  speculative = d > 0 (num_beams 1):
-        `speculative_decode` with up to d drafts per sequence and step; 0 (default) is the plain path."""
+        `speculative_decode` with up to d drafts per sequence and step; 0 (default) is the plain path.  The logits rules
+        (repetition_penalty .. allowed_tokens_fn, see free_form_inference) apply to every sample, sample i with batch_id i and
+        its own history; all at their defaults: no edits are built and the engine calls are the plain ones."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if num_beams < 1:
             raise ValueError(f"num_beams must be >= 1, got {num_beams}")
+        rules = rules_from_kwargs(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens,
+                                  allowed_tokens_fn)
+        if rules is not None and num_beams > 1:
+            raise NotImplementedError(BEAM_RULES_MESSAGE)
         speculative = check_spec_tokens(speculative)
         if speculative and num_beams > 1:
             raise ValueError("speculative decoding (speculative > 0) cannot be combined with beam search (num_beams > 1)")
@@ -256,14 +271,14 @@ class VQA_LLM:
             text_ids.append([t for t in ids if t >= 0])
         if speculative:
             self.generated_ids = self.speculative_decode(seqs, lens, text_ids, max_new_tokens, speculative,
-                                                         params if temperature > 0 else None, draft_fn)
+                                                         params if temperature > 0 else None, draft_fn, rules)
         elif num_beams > 1:
             outs = self.beam_decode(seqs, lens, id_lens, max_new_tokens, num_beams, length_penalty, early_stopping)
             self.generated_ids = [o[0] for o in outs]
         elif temperature > 0:
-            self.generated_ids = self.sample_decode(seqs, lens, max_new_tokens, params)
+            self.generated_ids = self.sample_decode(seqs, lens, max_new_tokens, params, rules, text_ids)
         else:
-            self.generated_ids = self.greedy_decode(seqs, lens, max_new_tokens)
+            self.generated_ids = self.greedy_decode(seqs, lens, max_new_tokens, rules, text_ids)
         texts = []
         for ids in self.generated_ids:
             out = self.tokenizer.batch_decode([ids], skip_special_tokens=True)[0].strip()
@@ -272,19 +287,30 @@ class VQA_LLM:
             texts.append(out.strip())
         return texts
 
-    def greedy_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int) -> List[List[int]]:
-        """model.generate(do_sample=False, use_cache=True) for every sequence."""
-        return self._decode(seqs, lens, max_new_tokens, lambda step, want, idx, t: self.engine.forward(step, want, logits=False)[1])
+    def _edits(self, rules: Optional[LogitRules], rows):
+        """The packed edits of one engine call: rows = one (history ids, n_generated, batch_id) per wanted row; None without
+        active rules (the call is then the plain one)."""
+        if rules is None or not rules.active:
+            return None
+        return LogitRules.pack([rules.plan(h, g, self.eos_token_id, b) for h, g, b in rows])
 
-    def sample_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, params) -> List[List[int]]:
+    def greedy_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, rules: Optional[LogitRules] = None,
+                      histories=None) -> List[List[int]]:
+        """model.generate(do_sample=False, use_cache=True) for every sequence.  rules + histories: see `_decode`."""
+        return self._decode(seqs, lens, max_new_tokens,
+                            lambda step, want, idx, t, edits: self.engine.forward(step, want, logits=False, edits=edits)[1], rules, histories)
+
+    def sample_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, params, rules: Optional[LogitRules] = None,
+                      histories=None) -> List[List[int]]:
         """model.generate(do_sample=True, use_cache=True): params[i] (`_lib.VqaSampling`) drives sequence i; the Philox step
-        of a draw is the index of the token it generates (0 = the token drawn from the prefill's last row)."""
-        def choose(step, want, idx, t):
-            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx])
-        return self._decode(seqs, lens, max_new_tokens, choose)
+        of a draw is the index of the token it generates (0 = the token drawn from the prefill's last row).  rules + histories:
+        see `_decode`."""
+        def choose(step, want, idx, t, edits):
+            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx], edits=edits)
+        return self._decode(seqs, lens, max_new_tokens, choose, rules, histories)
 
     def speculative_decode(self, seqs: Sequence[Seq], lens: Sequence[int], ids: Sequence[Sequence[int]], max_new_tokens: int,
-                           d: int, params=None, draft_fn=None) -> List[List[int]]:
+                           d: int, params=None, draft_fn=None, rules: Optional[LogitRules] = None) -> List[List[int]]:
         """Speculative decoding: greedy (params None) or sampled (params[i] drives sequence i as in
         `sample_decode`).  ids[i]: the un-expanded text ids of sequence i (placeholders left out) — what the drafter sees, with
         the generated tokens appended.  Every engine call feeds each live sequence the rows [cur, draft_0 .. draft_{k-1}] at
@@ -292,17 +318,23 @@ class VQA_LLM:
         count a and a + 1 tokens, and pos += a + 1.  The rows of rejected drafts stay in the cache behind pos and are overwritten
         by the next call.  k is cut so that the sequence's context, the call's rows (max_rows, 256 wanted rows) and
         max_new_tokens are respected.  The tokens are those of the logits of the verify forward: greedy picks their arg-max,
-        sampled draws follow their kept distribution.  self.spec_stats = calls / drafted / accepted / tokens of this run."""
+        sampled draws follow their kept distribution.  rules (vstar_amd/logits.py): every wanted row's logits are
+        edited ahead of its choice with the plan of ITS history — row r of a group sees ids[i] + out + drafts[:r] and n_generated
+        = len(out) + r, what a plain decode would see once those drafts are accepted; batch_id = i.
+        self.spec_stats = calls / drafted / accepted / tokens of this run."""
         from .spec import prompt_lookup_draft
         cfg, eng = self.cfg, self.engine
         d = check_spec_tokens(d)
         draft_fn = draft_fn or prompt_lookup_draft
+        if rules is not None and not rules.active:
+            rules = None
         n = len(seqs)
         want0 = [(i, -1) for i in range(n)]
+        ed0 = self._edits(rules, [(list(ids[i]), 0, i) for i in range(n)])
         if params is None:
-            first = eng.forward(seqs, want0, logits=False)[1]
+            first = eng.forward(seqs, want0, logits=False, edits=ed0)[1]
         else:
-            first = eng.forward_sample(seqs, want0, [_with_step(params[i], 0) for i in range(n)])
+            first = eng.forward_sample(seqs, want0, [_with_step(params[i], 0) for i in range(n)], edits=ed0)
         stats = dict(calls=1, drafted=0, accepted=0, tokens=0)
         out: List[List[int]] = [[int(first[i])] for i in range(n)]
         pos = list(lens)
@@ -314,7 +346,7 @@ class VQA_LLM:
         live = [i for i in range(n) if alive(i)]
         while live:
             spare = row_cap - len(live)                 # rows left for drafts once every live sequence has its current token
-            step, wanted, groups, draft, prm = [], [], [0], [], []
+            step, wanted, groups, draft, prm, plan_rows = [], [], [0], [], [], []
             for j, i in enumerate(live):
                 k = min(d, max_new_tokens - len(out[i]) - 1, cfg.max_ctx - pos[i] - 2, max(spare, 0))
                 guess: List[int] = []
@@ -333,7 +365,11 @@ class VQA_LLM:
                 if params is not None:
                     prm += [_with_step(params[i], len(out[i]) + r) for r in range(len(rows))]
                 stats["drafted"] += len(guess)
-            acc, tok = eng.forward_verify(step, wanted, groups, draft, prm if params is not None else None)
+                if rules is not None:
+                    base = list(ids[i]) + out[i]
+                    plan_rows += [(base + guess[:r], len(out[i]) + r, i) for r in range(len(rows))]
+            acc, tok = eng.forward_verify(step, wanted, groups, draft, prm if params is not None else None,
+                                          edits=self._edits(rules, plan_rows))
             stats["calls"] += 1
             for j, i in enumerate(live):
                 a = int(acc[j])
@@ -389,12 +425,21 @@ class VQA_LLM:
                 pos[i] += 1
         return [b.finalize(num_return_sequences) for b in bs]
 
-    def _decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, choose) -> List[List[int]]:
-        """The generate() loop over a token chooser choose(step_seqs, want, sequence indices, token index) -> tokens; a
-        sequence stops at EOS (the reference's keyword criterion stops on '</s>', the decoded EOS) or when the context is full."""
+    def _decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, choose, rules: Optional[LogitRules] = None,
+                histories=None) -> List[List[int]]:
+        """The generate() loop over a token chooser choose(step_seqs, want, sequence indices, token index, edits) -> tokens; a
+        sequence stops at EOS (the reference's keyword criterion stops on '</s>', the decoded EOS) or when the context is full.
+        rules (active) need histories[i], the text ids of sequence i's prompt with the placeholders left out: every step builds
+        one plan per wanted row from histories[i] + what i has generated (batch_id = i) and hands the packed edits to `choose`;
+        without rules `edits` is None and the engine calls are the plain ones."""
         cfg = self.cfg
         n = len(seqs)
-        nxt = choose(seqs, [(i, -1) for i in range(n)], list(range(n)), 0)
+        if rules is not None and not rules.active:
+            rules = None
+        if rules is not None and (histories is None or len(histories) != n):
+            raise ValueError("logits rules need one history (the prompt's text ids) per sequence")
+        nxt = choose(seqs, [(i, -1) for i in range(n)], list(range(n)), 0,
+                     self._edits(rules, [(histories[i], 0, i) for i in range(n)]) if rules is not None else None)
         out: List[List[int]] = [[] for _ in range(n)]
         pos = list(lens)
         live = list(range(n))
@@ -409,7 +454,8 @@ class VQA_LLM:
             if not live or len(out[live[0]]) >= max_new_tokens:
                 break
             step = [Seq([cur[i]], kv_slot=seqs[i].kv_slot, past_len=pos[i]) for i in live]
-            nxt = choose(step, [(j, 0) for j in range(len(live))], live, len(out[live[0]]))
+            nxt = choose(step, [(j, 0) for j in range(len(live))], live, len(out[live[0]]),
+                         self._edits(rules, [(list(histories[i]) + out[i], len(out[i]), i) for i in live]) if rules is not None else None)
             for j, i in enumerate(live):
                 cur[i] = int(nxt[j])
                 pos[i] += 1

@@ -133,26 +133,57 @@ class VqaEngine:
             raise ValueError(f"{len(params)} sampling records for {nw} wanted rows")
         return (_lib.VqaSampling * max(nw, 1))(*params)
 
-    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True):
+    @staticmethod
+    def _edits_struct(edits, nw: int):
+        """`edits` = the packed arrays (off, tok, penalty) of `LogitRules.pack`, one plan per wanted row -> the
+        vstar_vqa_logit_edits record behind the C pointer, and the arrays to keep alive while the call runs."""
+        off, tok, pen = edits
+        off = np.ascontiguousarray(off, np.int32)
+        tok = np.ascontiguousarray(tok, np.int32)
+        pen = np.ascontiguousarray(pen, np.float32)
+        if off.shape != (3 * nw + 1,) or pen.shape != (nw,):
+            raise ValueError(f"logits edits for {(off.size - 1) // 3} rows ({pen.size} penalties) given for {nw} wanted rows")
+        if off.size and tok.size < int(off.max(initial=0)):
+            raise ValueError(f"logits edits: the offsets reach {int(off.max())} but only {tok.size} token ids are given")
+        st = _lib.VqaLogitEdits(off.ctypes.data, tok.ctypes.data if tok.size else None, pen.ctypes.data)
+        return st, (off, tok, pen)
+
+    def logit_edit_capacity(self) -> int:
+        """The most token ids (the three lists of all wanted rows together) one call with edits may carry."""
+        return int(self.lib.vstar_vqa_logit_edit_capacity(self.handle))
+
+    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True, edits=None):
         """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
+        edits: None, or the packed arrays of `LogitRules.pack` (one plan per wanted row): the logits are edited on the device
+        ahead of the arg-max (csrc/edit.hip) and the returned logits are the edited ones (HF's `scores`).
         Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want])."""
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
         out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if (logits and nw) else None
         out_arg = np.empty((max(nw, 1),), np.int32)
-        _lib.check_vqa(self.lib.vstar_vqa_forward(self.handle, *args, _ptr(out_logits), _ptr(out_arg)), self.handle)
+        if edits is None:
+            _lib.check_vqa(self.lib.vstar_vqa_forward(self.handle, *args, _ptr(out_logits), _ptr(out_arg)), self.handle)
+        else:
+            st, _keep2 = self._edits_struct(edits, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_edits(self.handle, *args, _ptr(out_logits), _ptr(out_arg), ctypes.byref(st)),
+                           self.handle)
         return out_logits, out_arg[:nw]
 
-    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params) -> np.ndarray:
+    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None) -> np.ndarray:
         """`forward` with the arg-max replaced by the on-device sampling tail (csrc/sample.hip): `params` holds one
-        `_lib.VqaSampling` per wanted row (or one record for all of them).  Returns the drawn tokens, int32 [n_want]; the
-        logits never leave the device."""
+        `_lib.VqaSampling` per wanted row (or one record for all of them); edits as in `forward` (the draw sees the edited
+        logits).  Returns the drawn tokens, int32 [n_want]; the logits never leave the device."""
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
         prm = self._sampling_array(params, nw)
         out = np.empty((max(nw, 1),), np.int32)
-        _lib.check_vqa(self.lib.vstar_vqa_forward_sample(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out)),
-                       self.handle)
+        if edits is None:
+            _lib.check_vqa(self.lib.vstar_vqa_forward_sample(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out)),
+                           self.handle)
+        else:
+            st, _keep2 = self._edits_struct(edits, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_sample_edits(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out),
+                                                                   ctypes.byref(st)), self.handle)
         return out[:nw]
 
     def forward_beam(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], beam_scores, group_off, n_cand: int,
@@ -188,12 +219,13 @@ class VqaEngine:
         _lib.check_vqa(self.lib.vstar_vqa_forward_score(self.handle, *args, _ptr(tg), _ptr(nll), _ptr(rk)), self.handle)
         return (nll[:nw], rk[:nw]) if rank else nll[:nw]
 
-    def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None):
+    def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None, edits=None):
         """`forward` with the arg-max replaced by the on-device verify tail of speculative decoding (csrc/spec.hip, DESIGN.md
         §8.5): wanted rows groups[g] .. groups[g+1]-1 are the rows of one sequence in position order (its current token and the
         drafts fed behind it), draft[j] the token wanted row j's choice is compared with (-1 on a group's last row).  params:
-        None = greedy, else one `_lib.VqaSampling` per wanted row (or one record for all).  Returns (n_accept int32 [n_groups],
-        tokens int32 [n_want]): per group the accepted drafts and one more token, -1 behind them."""
+        None = greedy, else one `_lib.VqaSampling` per wanted row (or one record for all).  edits as in `forward`: every row's
+        choice sees its edited logits.  Returns (n_accept int32 [n_groups], tokens int32 [n_want]): per group the accepted drafts
+        and one more token, -1 behind them."""
         args, _keep = self._rows_args(step, wanted)
         nw = args[6]
         go = np.ascontiguousarray(groups, np.int32)
@@ -202,8 +234,12 @@ class VqaEngine:
         prm = self._sampling_array(params, nw) if params is not None else None
         acc = np.empty((max(ng, 1),), np.int32)
         tok = np.empty((max(nw, 1),), np.int32)
-        _lib.check_vqa(self.lib.vstar_vqa_forward_verify(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None,
-                                                         _ptr(go), ng, _ptr(dr), _ptr(acc), _ptr(tok)), self.handle)
+        tail = (ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None, _ptr(go), ng, _ptr(dr), _ptr(acc), _ptr(tok))
+        if edits is None:
+            _lib.check_vqa(self.lib.vstar_vqa_forward_verify(self.handle, *args, *tail), self.handle)
+        else:
+            st, _keep2 = self._edits_struct(edits, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_verify_edits(self.handle, *args, *tail, ctypes.byref(st)), self.handle)
         return acc[:ng], tok[:nw]
 
     def kv_reorder(self, dst_slots: Sequence[int], src_slots: Sequence[int], lo: int, hi: int) -> None:

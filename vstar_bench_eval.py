@@ -37,6 +37,10 @@ def parse_args(argv):
                    "option-ranking passes (free_form_batch / multiple_choices_batch, option losses reduced on the device); 1 = one "
                    "question at a time like the reference.  The free-form pass sends at most min(N, max_slots, max_images) questions per call; the "
                    "option-ranking pass splits a batch by itself when it exceeds max_slots / max_images / max_rows")
+    p.add_argument("--vqa-repetition-penalty", dest="vqa_repetition_penalty", default=1.0, type=float, help="theta > 0: HF's "
+                   "repetition_penalty on the free-form pass, applied to the logits on the device (DESIGN.md 8.8); 1.0 = off")
+    p.add_argument("--vqa-no-repeat-ngram", dest="vqa_no_repeat_ngram", default=0, type=int, help="n > 0: HF's no_repeat_ngram_size "
+                   "on the free-form pass (DESIGN.md 8.8); 0 = off")
     p.add_argument("--vqa-spec-tokens", dest="vqa_spec_tokens", default=0, type=int, help="d > 0 (<= 15): the free-form pass decodes "
                    "speculatively with up to d prompt-lookup draft tokens per step (DESIGN.md 8.5; 3 keeps every kernel of a one-row "
                    "step at 7B); 0 = the plain greedy decode")
