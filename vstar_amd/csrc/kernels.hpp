@@ -8,6 +8,38 @@
 
 namespace VS_NS {
 
+// What the weight-streaming GEMV (gemm_skinny_lp, skinny.hip) streams as its weight operand: one format tag and the format's
+// three device images.
+enum {
+  // fp16 / bf16 weights: GemmParams::W is read, q and scale are null.
+  // tiled (gemm_skinny_ring_kernel only (round 5), or null): a TILE-MAJOR copy of W for the decode GEMV — [N / (16 NT)][K / 64][2 NT]
+  // pieces of 1 KiB, each in the lane order of the LDS-DMA request that fetches it (skinny_pack_tiles): a workgroup then streams ONE
+  // sequential region of HBM instead of 16 / 32 row streams 2 K bytes apart (tools/probes/stream_layout_probe.hip: gate|up 5.4 -> 7.0 TB/s)
+  SKINNY_W_F16 = 0,
+  // gemm_skinny_kernel / gemm_skinny_ring_kernel, fp16 build: int8 weights with fp16 activations (W8A16).
+  // The weight operand is q [ceil(N/256)*256, K] int8, K-contiguous like W, and scale [ceil(N/256)*256] fp32 one scale per packed
+  // row: every MFMA sees fp16(q) (exact: |q| <= 127) in place of W, and the reduced accumulator of column n is multiplied once by
+  // scale[n] before gemm_epilogue_store.  W is then not read.
+  // tiled (ring kernel, or null): the TILE-MAJOR int8 image, [N / (16 NT)][K / 64][NT] pieces of 1 KiB.  A piece is ONE LDS-DMA
+  // request (16 rows x 64 B, where fp16 needs two of 8 rows x 128 B): lane l carries 16 bytes of row l / 4, namely chunk
+  // (l % 4) ^ ((row / 4) % 4) of that row's 64 bytes, so that LDS holds row r at r * 64 with its 16-byte chunks swizzled by
+  // (r / 4) % 4 and the 8-byte fragment reads of rows r, r + 4, r + 8, r + 12 fall into different banks (skinny_pack_tiles_w8).
+  SKINNY_W_INT8 = 8,
+  // gemm_skinny_kernel only, fp16 build: int4 group-scaled weights with fp16 activations (W4A16, groups of 128; DESIGN.md §8.6).
+  // The weight operand is q [ceil(N/256)*256, K / 8] 32-bit words (eight offset nibbles u = q + 8 each: element e of a word in
+  // nibble (e >> 1) + 4 (e & 1)) and scale [ceil(N/256)*256, K / 128] fp16 bits, one scale per row and 128 k (K % 128 == 0).
+  // Every MFMA sees fp16(fp16(q) * s), ONE fp16 multiply per weight in registers, in place of W: the kernel is bit-identical to the
+  // fp16 kernel on the dequantised weights, there is no post-scale.  W is then not read.
+  // tiled (or null): the TILE-MAJOR image, read INSTEAD of q / scale: [N / (16 NT)][pairs][8 waves][NT] slots of 1088 B,
+  // pairs = ceil(ceil(K / 64 / 8) / 2).  Slot (j, w, t) belongs to wave w: lane l = fr + 16 g holds at l * 16 its four words of its
+  // OWN two consecutive double steps ds = w + 16 j and ds + 8 of row fr of tile t — (ds, k-step 0), (ds, 1), (ds + 8, 0), (ds + 8, 1)
+  // — so a wave fetches them with ONE fully coalesced 1-KiB load where the row-major words cost four loads of 16 rows x 16 B; the
+  // 64 bytes behind them are the rows' scale pairs (s[ds / 2], s[(ds + 8) / 2]) at 1024 + fr * 4 (skinny_pack_tiles_w4).  Wave
+  // ownership of the double steps, and with it the MFMA order, is unchanged.
+  SKINNY_W_INT4G128 = 4
+};
+struct SkinnyWeights { int fmt; const void* q; const void* scale; const void* tiled; };
+
 // Row maps let a GEMM read/write a strided sub-sequence without a gather pass:
 //   mapped(r) = (r / group) * gstride + off + r % group      (group <= 0: identity)
 struct GemmParams {
@@ -50,31 +82,6 @@ struct GemmParams {
   // kernel choice: 0 = the dispatcher decides, 128 / 256 = force that tile (256 fails with hipErrorInvalidValue when the shape
   // is not gemm256_eligible).  Process-wide default for 0 calls: environment VSTAR_GEMM_TILE (A/B runs).
   int tile_force;
-  // gemm_skinny_ring_kernel only (round 5): a TILE-MAJOR copy of W for the decode GEMV, or null — [N / (16 NT)][K / 64][2 NT] pieces of
-  // 1 KiB, each in the lane order of the LDS-DMA request that fetches it (skinny_pack_tiles): a workgroup then streams ONE sequential
-  // region of HBM instead of 16 / 32 row streams 2 K bytes apart (tools/probes/stream_layout_probe.hip: gate|up 5.4 -> 7.0 TB/s)
-  const lp_t* W_tiled;
-  // gemm_skinny_kernel / gemm_skinny_ring_kernel only, fp16 build: int8 weights with fp16 activations (W8A16).
-  // Wq != null => the weight operand is Wq [ceil(N/256)*256, K] int8, K-contiguous like W, and wq_scale [ceil(N/256)*256] fp32 one
-  // scale per packed row: every MFMA sees fp16(q) (exact: |q| <= 127) in place of W, and the reduced accumulator of column n is
-  // multiplied once by wq_scale[n] before gemm_epilogue_store.  W is then not read.
-  // Wq_tiled (ring kernel, or null): the TILE-MAJOR int8 image, [N / (16 NT)][K / 64][NT] pieces of 1 KiB.  A piece is ONE LDS-DMA
-  // request (16 rows x 64 B, where fp16 needs two of 8 rows x 128 B): lane l carries 16 bytes of row l / 4, namely chunk
-  // (l % 4) ^ ((row / 4) % 4) of that row's 64 bytes, so that LDS holds row r at r * 64 with its 16-byte chunks swizzled by
-  // (r / 4) % 4 and the 8-byte fragment reads of rows r, r + 4, r + 8, r + 12 fall into different banks (skinny_pack_tiles_w8).
-  const int8_t* Wq; const float* wq_scale; const int8_t* Wq_tiled;
-  // gemm_skinny_kernel only, fp16 build: int4 group-scaled weights with fp16 activations (W4A16, groups of 128; DESIGN.md §8.6).
-  // Wq4 != null => the weight operand is Wq4 [ceil(N/256)*256, K / 8] 32-bit words (eight offset nibbles u = q + 8 each: element e of
-  // a word in nibble (e >> 1) + 4 (e & 1)) and wq4_scale [ceil(N/256)*256, K / 128] fp16 bits, one scale per row and 128 k
-  // (K % 128 == 0).  Every MFMA sees fp16(fp16(q) * s), ONE fp16 multiply per weight in registers, in place of W: the kernel is
-  // bit-identical to the fp16 kernel on the dequantised weights, there is no post-scale.  W is then not read.
-  // Wq4_tiled (or null): the TILE-MAJOR image, read INSTEAD of Wq4 / wq4_scale: [N / (16 NT)][pairs][8 waves][NT] slots of 1088 B,
-  // pairs = ceil(ceil(K / 64 / 8) / 2).  Slot (j, w, t) belongs to wave w: lane l = fr + 16 g holds at l * 16 its four words of its
-  // OWN two consecutive double steps ds = w + 16 j and ds + 8 of row fr of tile t — (ds, k-step 0), (ds, 1), (ds + 8, 0), (ds + 8, 1)
-  // — so a wave fetches them with ONE fully coalesced 1-KiB load where the row-major words cost four loads of 16 rows x 16 B; the
-  // 64 bytes behind them are the rows' scale pairs (s[ds / 2], s[(ds + 8) / 2]) at 1024 + fr * 4 (skinny_pack_tiles_w4).  Wave
-  // ownership of the double steps, and with it the MFMA order, is unchanged.
-  const uint32_t* Wq4; const uint16_t* wq4_scale; const void* Wq4_tiled;
   // gemm4w only, W8A8 with block-scaled activations (mx.hpp; round 6).  a_mx != null: A holds fp8 bytes whose E8M0
   // block scales (one per row and 32 k, tile-major: mx_scale_offset with m128 = M / 128) are applied inside the MFMA; w_scale as above.
   // c_mx != null (VSTAR_EPI_SILU_MUL): the epilogue writes SiLU(gate) * up as fp8 bytes to (uint8_t*)C (ldc in bytes) and the block
@@ -85,6 +92,8 @@ struct GemmParams {
   // [M, ldc8] their block-scaled fp8 copy (scales to c_mx) — the next linear's A operand, whose RMSNorm is folded: its weight into that
   // linear's W, its 1 / rms applied as a_scale (allowed next to a_mx) from the sum-of-squares partials this epilogue writes (sumsq_out).
   uint8_t* c8; int64_t ldc8;
+  // gemm_skinny_lp only (the tile kernels never read it): what the skinny kernels stream instead of / next to W
+  SkinnyWeights dw;
 };
 bool gemm_mx_supported(const GemmParams& p, int epilogue);
 hipError_t gemm_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s);
@@ -109,7 +118,7 @@ bool gemm_plan_only();
 int gemm_last_mode();
 bool gemm256_eligible(const GemmParams& p);   // true: gemm_lp runs the 256^2 kernel (the only one that honours rope_cs)
 
-// decode-sized GEMM (decode.hip): M <= 64, identity row maps; same operands/epilogues as gemm_lp
+// decode-sized GEMM (skinny.hip): M <= 64, identity row maps; same operands/epilogues as gemm_lp
 bool gemm_skinny_eligible(const GemmParams& p);
 hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s);
 // Wt <- tile-major image of the packed row-major W [n_rows][K] for gemm_skinny_ring_kernel (nt = 2 for SiLU(gate)*up weights whose
@@ -120,14 +129,14 @@ hipError_t skinny_pack_tiles(const lp_t* W, lp_t* Wt, int n_rows, int K, int nt,
 // Per row n of W [rows, K] (fp16): a = max|W[n,:]|, s = a / 127 (one correctly rounded fp32 divide; 1 when a == 0),
 // q = clamp(rint(float(W) / s), -127, 127).  What (nullable, may alias W): fp16(float(q) * s).  One workgroup per row.
 hipError_t quantize_rows_w8(const lp_t* W, int rows, int K, int8_t* q, float* scale, lp_t* What, hipStream_t s);
-// the tile-major int8 image (GemmParams::Wq_tiled) of the row-major Wq [n_rows][K]; n_rows % (16 nt) == 0, K % 64 == 0
+// the tile-major int8 image (SKINNY_W_INT8's `tiled`) of the row-major Wq [n_rows][K]; n_rows % (16 nt) == 0, K % 64 == 0
 hipError_t skinny_pack_tiles_w8(const int8_t* Wq, int8_t* Wt, int n_rows, int K, int nt, hipStream_t s);
 // ---- int4 group-scaled weight-only decode (W4A16; fp16 build only) ----
 // Per row n of W [rows, K] (fp16, K % 128 == 0) and group j of 128 k: a = max|W[n, 128 j ..]|, s = min(fp16(float(a) / 7.0f), 9352),
-// 1 when that is 0; q = clamp(rint(float(W) / float(s)), -7, 7).  q [rows, K / 8] words (GemmParams::Wq4), scale [rows, K / 128]
+// 1 when that is 0; q = clamp(rint(float(W) / float(s)), -7, 7).  q [rows, K / 8] words (SKINNY_W_INT4G128's `q`), scale [rows, K / 128]
 // fp16.  What (nullable, may alias W): fp16(q) * s, one fp16 multiply.  One workgroup per row.
 hipError_t quantize_groups_w4(const lp_t* W, int rows, int K, uint32_t* q, lp_t* scale, lp_t* What, hipStream_t s);
-// the tile-major int4 image (GemmParams::Wq4_tiled) of the row-major q [n_rows][K / 8] and scale [n_rows][K / 128];
+// the tile-major int4 image (SKINNY_W_INT4G128's `tiled`) of the row-major q [n_rows][K / 8] and scale [n_rows][K / 128];
 // n_rows % (16 nt) == 0, K % 128 == 0; Wt holds skinny_tiles_w4_bytes(n_rows, K, nt) bytes
 size_t skinny_tiles_w4_bytes(int n_rows, int K, int nt);
 hipError_t skinny_pack_tiles_w4(const uint32_t* q, const lp_t* scale, void* Wt, int n_rows, int K, int nt, hipStream_t s);

@@ -101,12 +101,10 @@ struct LlmCachedCfg {
   int kv_format = KV_FMT_F16;   // KV_FMT_MXFP8 / KV_FMT_MXFP8_EMU: block-scaled fp8 KV cache (fp16 build only)
 };
 
-// int8 decode copies of one block linear: row-major q [Npad, K] + per-row scales [Npad] for the register kernel
-// and the row-major ring, and the tile-major image for the ring (null where the fp16 path would have none either)
-struct LinW8 { int8_t* q = nullptr; float* s = nullptr; int8_t* qt = nullptr; };
-// int4 decode copies of one block linear: row-major words q [Npad, K / 8] + group scales s [Npad, K / 128] (fp16)
-// and the tile-major image of both (GemmParams::Wq4_tiled; null with VSTAR_DECODE_TILED=0 or without whole 16 NT-row tiles)
-struct LinW4 { uint32_t* q = nullptr; lp_t* s = nullptr; void* qt = nullptr; };
+// What the decode GEMV streams for one layer's four block linears (SkinnyWeights, kernels.hpp).  fp16 (cfg.weight_bits == 0):
+// only the tile-major copies of q|k|v, gate|up and down, where built.  int8 / int4: the row-major q + scales
+// of all four and the tile-major images the format's rules allow (LlmCached::build_quantised); null where there is none.
+struct DecodeLayerW { SkinnyWeights qkv, o, gate_up, down; };
 
 struct LlmCached {
   EngineBase* e = nullptr;
@@ -172,23 +170,19 @@ struct LlmCached {
   int dec_keys_bound = 0;                        // context bound the captured attention launch was sized for
   int32_t* d_dec = nullptr;                      // coherent HOST memory: [0] = tokens emitted so far, [1..] = the tokens
   int dec_cap = 0;
-  // ---- tile-major copies of the big decode weights (round 5; GemmParams::W_tiled) ----
-  // The weight-streaming GEMV gives a workgroup 16 (gate|up: 32) ROWS of the row-major matrix, i.e. 16 - 32 sequential streams 2 K
-  // bytes apart and 4096 - 22016 of them over the chip; laid out tile-major the same bytes stream at 6.5 - 7.0 TB/s instead of
-  // 5.4 - 6.5 (profiles/r05_stream_layout_probe.txt).  HBM has the room for a second copy (q|k|v, gate|up, down: 11.8 GB at 7B);
-  // built when the runner is initialised, VSTAR_DECODE_TILED=0 keeps the row-major streams (A/B, tests: bit-identical).
-  std::vector<lp_t*> wt_qkv, wt_gate_up, wt_down;
-  bool tiled_fallback = false;      // the tile-major copies were wanted but did not fit / pack: decode runs on the row-major weights
-  // ---- int8 weight-only decode (cfg.weight_bits == 8) ----
-  // Per layer the int8 copies of q|k|v, o, gate|up and down; the fp16 masters then hold the DEQUANTISED weights (prefill and every
-  // call of more than 64 rows run the same quantised model on the tile kernels) and the fp16 tile-major copies above are not built.
-  std::vector<LinW8> w8_qkv, w8_o, w8_gate_up, w8_down;
-  int build_w8();
-  const LinW8* w8(const std::vector<LinW8>& v, int i) const { return v.empty() ? nullptr : &v[(size_t)i]; }
-  // ---- int4 group-scaled weight-only decode (cfg.weight_bits == 4): the same arrangement ----
-  std::vector<LinW4> w4_qkv, w4_o, w4_gate_up, w4_down;
-  int build_w4();
-  const LinW4* w4(const std::vector<LinW4>& v, int i) const { return v.empty() ? nullptr : &v[(size_t)i]; }
+  // ---- the decode GEMV's weight descriptors: empty (row-major fp16 weights only), or one record per layer ----
+  // Tile-major copies of the big decode weights (round 5; SKINNY_W_F16): the weight-streaming GEMV gives a workgroup 16 (gate|up: 32)
+  // ROWS of the row-major matrix, i.e. 16 - 32 sequential streams 2 K bytes apart and 4096 - 22016 of them over the chip; laid out
+  // tile-major the same bytes stream at 6.5 - 7.0 TB/s instead of 5.4 - 6.5 (profiles/r05_stream_layout_probe.txt).  HBM has the room
+  // for a second copy (q|k|v, gate|up, down: 11.8 GB at 7B); built when the runner is initialised, VSTAR_DECODE_TILED=0 keeps the
+  // row-major streams (A/B, tests: bit-identical).
+  // Weight-only decode (cfg.weight_bits == 8 / 4): per layer the int8 / int4 copies of q|k|v, o, gate|up and
+  // down; the fp16 masters then hold the DEQUANTISED weights (prefill and every call of more than 64 rows run the same quantised
+  // model on the tile kernels) and the fp16 tile-major copies are not built.
+  std::vector<DecodeLayerW> dec_w;
+  const DecodeLayerW& dec(int i) const { static const DecodeLayerW none{}; return dec_w.empty() ? none : dec_w[(size_t)i]; }
+  bool tiled_fallback = false;      // the fp16 tile-major copies were wanted but did not fit / pack: decode runs on the row-major weights
+  int build_quantised(int fmt);
 
   void set_error(const std::string& m) { e->set_error(m); }
   int init(EngineBase* owner, const LlmCachedCfg& c, const lp_t* embed_, const std::vector<LlmBlock>* blocks_,
@@ -205,10 +199,10 @@ struct LlmCached {
   int decode_step_body(int keys_bound);
   int decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids, int* n_out, bool* used);
   int lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
-               const lp_t* res = nullptr, int64_t ldr = 0, const lp_t* Wt = nullptr, const LinW8* q8 = nullptr,
-               const LinW4* q4 = nullptr);
+               const lp_t* res = nullptr, int64_t ldr = 0, const SkinnyWeights* dw = nullptr);
   int lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M, int epi,
-               const lp_t* Wt = nullptr, const LinW8* q8 = nullptr, const LinW4* q4 = nullptr);
+               const SkinnyWeights* dw = nullptr);
+  int lin_skinny(GemmParams& p, int epi, const SkinnyWeights* dw);
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
@@ -313,21 +307,21 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   }
   if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { set_error("hipEventCreate failed"); return VSTAR_ERR_HIP; }
   {  // tile-major copies of q|k|v, gate|up and down for the decode GEMV (o_proj's 33 MB live in the Infinity Cache either way).
-     // OPTIONAL: the row-major weights serve the same GEMV (W_tiled == nullptr), so a failed allocation or pack — ~11.8 GB more at
+     // OPTIONAL: the row-major weights serve the same GEMV (dw.tiled == nullptr), so a failed allocation or pack — ~11.8 GB more at
      // 7B — drops the copies, clears the error and continues row-major instead of failing generate().
     const char* env = getenv("VSTAR_DECODE_TILED");
-    const bool on = !(env && atoi(env) == 0) && c.weight_bits == 0;      // (the int8 mode builds its own images: build_w8; int4 has none)
-    wt_qkv.clear(); wt_gate_up.clear(); wt_down.clear();      // a retried init starts from empty lists: wt_*[i] is layer i or nothing
+    const bool on = !(env && atoi(env) == 0) && c.weight_bits == 0;      // (the quantised modes build their own images: build_quantised)
+    dec_w.clear();                                            // a retried init starts from an empty list: dec_w[i] is layer i or nothing
     std::vector<void*> mine;                                  // this block's allocations, freed together if any step fails
     bool ok = true;
-    auto tile = [&](const Lin& L, int nt, std::vector<lp_t*>& out) {
+    auto tile = [&](const Lin& L, int nt, SkinnyWeights& out) {
       const int rows = (L.N + 16 * nt - 1) / (16 * nt) * (16 * nt);     // (the packed W is padded to 256 rows)
-      if (L.N % (16 * nt) || L.K % 64) { out.push_back(nullptr); return; }
+      if (L.N % (16 * nt) || L.K % 64) return;
       void* t = nullptr;
       if (hipMalloc(&t, (size_t)rows * L.K * sizeof(lp_t)) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
       mine.push_back(t);
       if (skinny_pack_tiles(L.W, (lp_t*)t, rows, L.K, nt, e->stream) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
-      out.push_back((lp_t*)t);
+      out.tiled = t;
     };
     if (on && c.hidden >= 512) {
       size_t need = 0, free_b = 0, total_b = 0;
@@ -337,111 +331,86 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
       }
       // keep 1 GiB of headroom for the caller's later allocations (KV growth happens above; this is the last big block of init)
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)1 << 30)) { (void)hipGetLastError(); ok = false; }
+      dec_w.assign((size_t)c.layers, DecodeLayerW{});
       for (int i = 0; ok && i < c.layers; ++i) {
         const LlmBlock& b = (*blocks)[i];
-        tile(b.qkv, 1, wt_qkv);
-        if (ok) tile(b.gate_up, 2, wt_gate_up);
-        if (ok) tile(b.down, 1, wt_down);
+        tile(b.qkv, 1, dec_w[i].qkv);
+        if (ok) tile(b.gate_up, 2, dec_w[i].gate_up);
+        if (ok) tile(b.down, 1, dec_w[i].down);
       }
       if (hipStreamSynchronize(e->stream) != hipSuccess) { (void)hipGetLastError(); ok = false; }
       if (ok) {
         for (void* q : mine) e->allocs.push_back(q);            // owned by the engine from here on
       } else {
         for (void* q : mine) hipFree(q);
-        wt_qkv.clear(); wt_gate_up.clear(); wt_down.clear();    // row-major decode (callers test .empty())
+        dec_w.clear();                                          // row-major decode
         tiled_fallback = true;
       }
     }
   }
-  if (c.weight_bits == 8) RC(build_w8());
-  else if (c.weight_bits == 4) RC(build_w4());
+  if (c.weight_bits == 8 || c.weight_bits == 4) RC(build_quantised(c.weight_bits));
   else if (c.weight_bits != 0) { set_error("decode_weight_bits must be 0 or 8"); return VSTAR_ERR_INVALID; }
   ready = true;
   return 0;
 }
 
-// The int8 decode mode, once, on the device, from the packed fp16 weights: every int8 buffer is allocated and filled FIRST (a
-// failed allocation or launch is an error with the fp16 masters untouched: there is no fp16 fallback behind the caller's back),
-// then the masters are overwritten with the dequantised weights.  A launch or the synchronise failing DURING that overwrite leaves
-// some masters dequantised and others not: the error is returned, `ready` stays false, every forward of the engine then fails
-// with VSTAR_ERR_STATE, and the weights have to be loaded again.  VSTAR_DECODE_TILED=0 and the fp16 path's eligibility rules
-// (whole 16 NT-row tiles, hidden >= 512; o_proj has no tile-major copy) decide which linears get a tile-major image.
-inline int LlmCached::build_w8() {
 #ifdef VSTAR_LP_F16
-  const LlmCachedCfg& c = cfg;
-  const char* env = getenv("VSTAR_DECODE_TILED");
-  const bool tiled_on = !(env && atoi(env) == 0) && c.hidden >= 512;
-  std::vector<void*> mine;
-  auto fail = [&](const std::string& m, int rc) {
-    for (void* q : mine) hipFree(q);
-    (void)hipGetLastError();
-    w8_qkv.clear(); w8_o.clear(); w8_gate_up.clear(); w8_down.clear();
-    set_error(m);
-    return rc;
+// What differs between the quantised decode formats; everything else of build_quantised is shared.
+struct DecodeFmt {
+  int fmt;                     // SkinnyWeights::fmt = cfg.weight_bits
+  const char* what;            // message prefix
+  int k_mult;                  // K of every block linear must be a multiple of it
+  size_t (*q_bytes)(int K);    // bytes of q / of the scales per row of the packed (256-padded) matrix
+  size_t (*scale_bytes)(int K);
+  hipError_t (*quantise)(const lp_t* W, int rows, int K, void* q, void* scale, lp_t* What, hipStream_t s);
+  size_t (*tile_bytes)(int N, int K, int nt);
+  hipError_t (*pack)(const void* q, const void* scale, void* Wt, int N, int K, int nt, hipStream_t s);
+  // Which linears get a tile-major image (VSTAR_DECODE_TILED=0: none; always whole 16 NT-row tiles only).  The two formats differ on
+  // purpose: the int8 image feeds the LDS-ring kernel, which runs from K = 512 on and gains nothing for o_proj (its 33 MB at 7B live
+  // in the Infinity Cache either way) — the fp16 path's rules; the int4 image is read by the register kernel, which serves every
+  // width and every linear, and replaces four 16-byte row loads per lane by one coalesced load wherever it exists.
+  bool tiles_need_hidden_512;
+  bool tiles_for_o;
+};
+inline const DecodeFmt* decode_fmt(int fmt) {
+  static const DecodeFmt table[] = {
+      {SKINNY_W_INT8, "int8 decode weights", 64,
+       [](int K) { return (size_t)K; }, [](int) { return sizeof(float); },
+       [](const lp_t* W, int rows, int K, void* q, void* sc, lp_t* What, hipStream_t s) { return quantize_rows_w8(W, rows, K, (int8_t*)q, (float*)sc, What, s); },
+       [](int N, int K, int) { return (size_t)N * K; },
+       [](const void* q, const void*, void* Wt, int N, int K, int nt, hipStream_t s) { return skinny_pack_tiles_w8((const int8_t*)q, (int8_t*)Wt, N, K, nt, s); },
+       true, false},
+      {SKINNY_W_INT4G128, "int4 decode weights (decode_weight_format = 1)", 128,
+       [](int K) { return (size_t)(K / 8) * sizeof(uint32_t); }, [](int K) { return (size_t)(K / 128) * sizeof(lp_t); },
+       [](const lp_t* W, int rows, int K, void* q, void* sc, lp_t* What, hipStream_t s) { return quantize_groups_w4(W, rows, K, (uint32_t*)q, (lp_t*)sc, What, s); },
+       [](int N, int K, int nt) { return skinny_tiles_w4_bytes(N, K, nt); },
+       [](const void* q, const void* sc, void* Wt, int N, int K, int nt, hipStream_t s) { return skinny_pack_tiles_w4((const uint32_t*)q, (const lp_t*)sc, Wt, N, K, nt, s); },
+       false, true},
   };
-  auto take = [&](size_t bytes) -> void* {
-    void* t = nullptr;
-    if (hipMalloc(&t, bytes) != hipSuccess) return nullptr;
-    mine.push_back(t);
-    return t;
-  };
-  auto quant = [&](const Lin& L, int nt, bool want_tiles, LinW8* out) -> int {
-    const int npad = (L.N + 255) / 256 * 256;
-    if (L.K % 64) return VSTAR_ERR_INVALID;
-    out->q = (int8_t*)take((size_t)npad * L.K);
-    out->s = (float*)take((size_t)npad * sizeof(float));
-    if (!out->q || !out->s) return VSTAR_ERR_NOMEM;
-    if (quantize_rows_w8(L.W, npad, L.K, out->q, out->s, nullptr, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
-    if (want_tiles && L.N % (16 * nt) == 0) {
-      out->qt = (int8_t*)take((size_t)L.N * L.K);
-      if (!out->qt) return VSTAR_ERR_NOMEM;
-      if (skinny_pack_tiles_w8(out->q, out->qt, L.N, L.K, nt, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
-    }
-    return 0;
-  };
-  w8_qkv.assign((size_t)c.layers, LinW8{}); w8_o.assign((size_t)c.layers, LinW8{});
-  w8_gate_up.assign((size_t)c.layers, LinW8{}); w8_down.assign((size_t)c.layers, LinW8{});
-  for (int i = 0; i < c.layers; ++i) {
-    const LlmBlock& b = (*blocks)[i];
-    int rc = quant(b.qkv, 1, tiled_on, &w8_qkv[i]);
-    if (!rc) rc = quant(b.o, 1, false, &w8_o[i]);
-    if (!rc) rc = quant(b.gate_up, 2, tiled_on, &w8_gate_up[i]);
-    if (!rc) rc = quant(b.down, 1, tiled_on, &w8_down[i]);
-    if (rc) return fail("int8 decode weights: allocation or quantiser launch failed (layer " + std::to_string(i) + ")", rc);
-  }
-  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int8 decode weights: quantiser failed", VSTAR_ERR_HIP);
-  // every int8 buffer exists: now the masters become the dequantised weights (same q, same scales: deterministic)
-  for (int i = 0; i < c.layers; ++i) {
-    const LlmBlock& b = (*blocks)[i];
-    const Lin* ls[4] = {&b.qkv, &b.o, &b.gate_up, &b.down};
-    const LinW8* qs[4] = {&w8_qkv[i], &w8_o[i], &w8_gate_up[i], &w8_down[i]};
-    for (int j = 0; j < 4; ++j) {
-      const int npad = (ls[j]->N + 255) / 256 * 256;
-      if (quantize_rows_w8(ls[j]->W, npad, ls[j]->K, qs[j]->q, qs[j]->s, ls[j]->W, e->stream) != hipSuccess)
-        return fail("int8 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
-    }
-  }
-  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int8 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
-  for (void* q : mine) e->allocs.push_back(q);
-  return 0;
-#else
-  set_error("decode_weight_bits = 8 needs the fp16 engine");
-  return VSTAR_ERR_INVALID;
-#endif
+  for (const DecodeFmt& f : table)
+    if (f.fmt == fmt) return &f;
+  return nullptr;
 }
+#endif
 
-// The int4 group-scaled decode mode: build_w8's rules.  Every int4 buffer is allocated and filled first (a failure
-// there is an error with the fp16 masters untouched), then the masters are overwritten with fp16(q) * s; a failure during that
-// overwrite leaves `ready` false.  Scales belong to rows of the packed matrices, whose gate|up interleave and q|k|v concatenation
-// only permute rows of the original ones.
-inline int LlmCached::build_w4() {
+// The weight-only decode modes, once, on the device, from the packed fp16 weights: every quantised
+// buffer is allocated and filled FIRST (a failed allocation or launch is an error with the fp16 masters untouched: there is no fp16
+// fallback behind the caller's back), then the masters are overwritten with the dequantised weights.  A launch or the synchronise
+// failing DURING that overwrite leaves some masters dequantised and others not: the error is returned, `ready` stays false, every
+// forward of the engine then fails with VSTAR_ERR_STATE, and the weights have to be loaded again.  Scales belong to rows of the
+// packed matrices, whose gate|up interleave and q|k|v concatenation only permute rows of the original ones.
+inline int LlmCached::build_quantised(int fmt) {
 #ifdef VSTAR_LP_F16
   const LlmCachedCfg& c = cfg;
+  const DecodeFmt& f = *decode_fmt(fmt);
+  const std::string what = f.what;
+  const char* env = getenv("VSTAR_DECODE_TILED");
+  const bool tiled_on = !(env && atoi(env) == 0) && (!f.tiles_need_hidden_512 || c.hidden >= 512);
   std::vector<void*> mine;
   auto fail = [&](const std::string& m, int rc) {
     for (void* q : mine) hipFree(q);
     (void)hipGetLastError();
-    w4_qkv.clear(); w4_o.clear(); w4_gate_up.clear(); w4_down.clear();
+    dec_w.clear();
     set_error(m);
     return rc;
   };
@@ -451,49 +420,48 @@ inline int LlmCached::build_w4() {
     mine.push_back(t);
     return t;
   };
-  const char* env = getenv("VSTAR_DECODE_TILED");
-  const bool tiled_on = !(env && atoi(env) == 0);
-  auto quant = [&](const Lin& L, int nt, LinW4* out) -> int {
+  auto quant = [&](const Lin& L, int nt, bool want_tiles, SkinnyWeights* out) -> int {
     const int npad = (L.N + 255) / 256 * 256;
-    if (L.K % 128) return VSTAR_ERR_INVALID;
-    out->q = (uint32_t*)take((size_t)npad * (L.K / 8) * sizeof(uint32_t));
-    out->s = (lp_t*)take((size_t)npad * (L.K / 128) * sizeof(lp_t));
-    if (!out->q || !out->s) return VSTAR_ERR_NOMEM;
-    if (quantize_groups_w4(L.W, npad, L.K, out->q, out->s, nullptr, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
-    if (tiled_on && L.N % (16 * nt) == 0) {
-      out->qt = take(skinny_tiles_w4_bytes(L.N, L.K, nt));
-      if (!out->qt) return VSTAR_ERR_NOMEM;
-      if (skinny_pack_tiles_w4(out->q, out->s, out->qt, L.N, L.K, nt, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    if (L.K % f.k_mult) return VSTAR_ERR_INVALID;
+    void* q = take((size_t)npad * f.q_bytes(L.K));
+    void* sc = take((size_t)npad * f.scale_bytes(L.K));
+    if (!q || !sc) return VSTAR_ERR_NOMEM;
+    *out = SkinnyWeights{f.fmt, q, sc, nullptr};
+    if (f.quantise(L.W, npad, L.K, q, sc, nullptr, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
+    if (want_tiles && L.N % (16 * nt) == 0) {
+      void* t = take(f.tile_bytes(L.N, L.K, nt));
+      if (!t) return VSTAR_ERR_NOMEM;
+      out->tiled = t;
+      if (f.pack(q, sc, t, L.N, L.K, nt, e->stream) != hipSuccess) return VSTAR_ERR_HIP;
     }
     return 0;
   };
-  w4_qkv.assign((size_t)c.layers, LinW4{}); w4_o.assign((size_t)c.layers, LinW4{});
-  w4_gate_up.assign((size_t)c.layers, LinW4{}); w4_down.assign((size_t)c.layers, LinW4{});
+  dec_w.assign((size_t)c.layers, DecodeLayerW{});
   for (int i = 0; i < c.layers; ++i) {
     const LlmBlock& b = (*blocks)[i];
-    int rc = quant(b.qkv, 1, &w4_qkv[i]);
-    if (!rc) rc = quant(b.o, 1, &w4_o[i]);
-    if (!rc) rc = quant(b.gate_up, 2, &w4_gate_up[i]);
-    if (!rc) rc = quant(b.down, 1, &w4_down[i]);
-    if (rc) return fail("int4 decode weights (decode_weight_format = 1): allocation or quantiser launch failed (layer " + std::to_string(i) + ")", rc);
+    int rc = quant(b.qkv, 1, tiled_on, &dec_w[i].qkv);
+    if (!rc) rc = quant(b.o, 1, tiled_on && f.tiles_for_o, &dec_w[i].o);
+    if (!rc) rc = quant(b.gate_up, 2, tiled_on, &dec_w[i].gate_up);
+    if (!rc) rc = quant(b.down, 1, tiled_on, &dec_w[i].down);
+    if (rc) return fail(what + ": allocation or quantiser launch failed (layer " + std::to_string(i) + ")", rc);
   }
-  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int4 decode weights: quantiser failed", VSTAR_ERR_HIP);
-  // every int4 buffer exists: now the masters become the dequantised weights (same q, same scales: deterministic)
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(what + ": quantiser failed", VSTAR_ERR_HIP);
+  // every quantised buffer exists: now the masters become the dequantised weights (same q, same scales: deterministic)
   for (int i = 0; i < c.layers; ++i) {
     const LlmBlock& b = (*blocks)[i];
     const Lin* ls[4] = {&b.qkv, &b.o, &b.gate_up, &b.down};
-    const LinW4* qs[4] = {&w4_qkv[i], &w4_o[i], &w4_gate_up[i], &w4_down[i]};
+    const SkinnyWeights* qs[4] = {&dec_w[i].qkv, &dec_w[i].o, &dec_w[i].gate_up, &dec_w[i].down};
     for (int j = 0; j < 4; ++j) {
       const int npad = (ls[j]->N + 255) / 256 * 256;
-      if (quantize_groups_w4(ls[j]->W, npad, ls[j]->K, qs[j]->q, qs[j]->s, ls[j]->W, e->stream) != hipSuccess)
-        return fail("int4 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+      if (f.quantise(ls[j]->W, npad, ls[j]->K, (void*)qs[j]->q, (void*)qs[j]->scale, ls[j]->W, e->stream) != hipSuccess)
+        return fail(what + ": dequantising the fp16 masters failed", VSTAR_ERR_HIP);
     }
   }
-  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("int4 decode weights: dequantising the fp16 masters failed", VSTAR_ERR_HIP);
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(what + ": dequantising the fp16 masters failed", VSTAR_ERR_HIP);
   for (void* q : mine) e->allocs.push_back(q);
   return 0;
 #else
-  set_error("decode_weight_format = 1 needs the fp16 engine");
+  set_error(fmt == 8 ? "decode_weight_bits = 8 needs the fp16 engine" : "decode_weight_format = 1 needs the fp16 engine");
   return VSTAR_ERR_INVALID;
 #endif
 }
@@ -507,40 +475,36 @@ inline int LlmCached::build_w4() {
     }                                                                                        \
   } while (0)
 
+// the weight-streaming GEMV on the weights `dw` describes (null: L's row-major fp16 / bf16 weights)
+inline int LlmCached::lin_skinny(GemmParams& p, int epi, const SkinnyWeights* dw) {
+  if (dw) p.dw = *dw;
+  const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
+  if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
+  return 0;
+}
+
 // GEMM dispatch for the language model: weight-streaming kernel for decode-sized M, MFMA tile kernels otherwise
 inline int LlmCached::lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi, const lp_t* res,
-                               int64_t ldr, const lp_t* Wt, const LinW8* q8, const LinW4* q4) {
+                               int64_t ldr, const SkinnyWeights* dw) {
   GemmParams p{};
   p.A = A; p.lda = lda; p.W = L.W; p.bias = L.b; p.res = res; p.ldr = ldr; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
-  p.W_tiled = Wt;
-  if (gemm_skinny_eligible(p)) {
-    if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }      // int8 decode mode: the W8 forms of the same kernels
-    if (q4) { p.Wq4 = q4->q; p.wq4_scale = q4->s; p.Wq4_tiled = q4->qt; }   // int4 decode mode: the W4 form of the register kernel
-    const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
-    if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
-    return 0;
-  }
+  if (gemm_skinny_eligible(p)) return lin_skinny(p, epi, dw);
   return e->gemm(p, epi, false);
 }
 
 // RMSNorm + Linear: for decode-sized M the norm is fused into the weight-streaming GEMM's operand load (bit-identical to
 // the two-kernel form), otherwise norm kernel into `scratch`, then the GEMM
 inline int LlmCached::lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M,
-                               int epi, const lp_t* Wt, const LinW8* q8, const LinW4* q4) {
+                               int epi, const SkinnyWeights* dw) {
   const int H = cfg.hidden;
   GemmParams p{};
   p.A = x; p.lda = H; p.W = L.W; p.bias = L.b; p.C = C; p.ldc = ldc; p.M = M; p.N = L.N; p.K = L.K;
-  p.W_tiled = Wt;
   if (M <= 16 && L.K == H && gemm_skinny_eligible(p)) {
     p.norm_w = norm_w; p.norm_eps = cfg.rms_eps;
-    if (q8) { p.Wq = q8->q; p.wq_scale = q8->s; p.Wq_tiled = q8->qt; }
-    if (q4) { p.Wq4 = q4->q; p.wq4_scale = q4->s; p.Wq4_tiled = q4->qt; }
-    const hipError_t he = gemm_skinny_lp(p, epi, false, e->stream);
-    if (he != hipSuccess) { set_error(std::string("skinny gemm launch: ") + hipGetErrorString(he)); return VSTAR_ERR_HIP; }
-    return 0;
+    return lin_skinny(p, epi, dw);
   }
   LCHK(rmsnorm_lp(x, norm_w, scratch, M, H, cfg.rms_eps, nullptr, e->stream));
-  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, Wt, q8, q4);
+  return lin_auto(scratch, H, L, C, ldc, M, epi, nullptr, 0, dw);
 }
 
 inline int LlmCached::llm_layers_prefill(int nseq, int S) {
@@ -572,17 +536,15 @@ inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool sing
     lp_t* kc = kv_layer(kcache, i);
     lp_t* vc = kv_layer(vcache, i);
     const KvFormat kvf = kv_fmt(i);
-    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, wt_qkv.empty() ? nullptr : wt_qkv[i], w8(w8_qkv, i),
-                w4(w4_qkv, i)));
+    const DecodeLayerW& dw = dec(i);
+    RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, &dw.qkv));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
     if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream, kvf));
     LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
                           c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc, kvf));
-    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, nullptr, w8(w8_o, i), w4(w4_o, i)));
-    RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, wt_gate_up.empty() ? nullptr : wt_gate_up[i],
-                w8(w8_gate_up, i), w4(w4_gate_up, i)));
-    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, wt_down.empty() ? nullptr : wt_down[i], w8(w8_down, i),
-                w4(w4_down, i)));
+    RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.o));
+    RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, &dw.gate_up));
+    RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.down));
   }
   return 0;
 }

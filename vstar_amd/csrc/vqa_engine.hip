@@ -560,7 +560,7 @@ int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void
 
 int vstar_vqa_decode_weight_bits(const vstar_vqa_handle* h) {
   if (!h || !h->finalized) return 0;
-  return !h->run.w4_qkv.empty() ? 4 : (!h->run.w8_qkv.empty() ? 8 : 0);
+  return h->run.dec(0).qkv.fmt;
 }
 
 int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q_i8, float* dev_scale_f32, void* dev_What_f16) {
@@ -573,28 +573,39 @@ int vstar_vqa_op_quantize_w8(const void* dev_W_f16, int rows, int K, void* dev_q
   return op_result(e, "vstar_vqa_op_quantize_w8");
 }
 
-int vstar_vqa_op_gemm_w8(const void* A, const void* Wq, const float* scale, const void* bias, const void* res, void* C, int M, int N,
-                         int K, int epilogue, int kernel, const void* norm_w, float norm_eps, int layout) {
-  if (!A || !Wq || !scale || !C || M <= 0 || N <= 0 || K <= 0 || K % 64 || (kernel != 1 && kernel != 3) || (layout != 0 && layout != 1)) {
-    tls_error() = "vstar_vqa_op_gemm_w8: bad argument (kernel 1 or 3, layout 0 or 1, K % 64 == 0)";
+// the body of vstar_vqa_op_gemm_w8 / _w4: the quantised skinny GEMV on row-major q + scale (layout 0) or on the tile-major image
+// packed here from them (layout 1)
+static int op_gemm_wq(int fmt, const char* fn, const char* bad_arg, const void* A, const void* Wq, const void* scale, const void* bias,
+                      const void* res, void* C, int M, int N, int K, int epilogue, int kernel, const void* norm_w, float norm_eps, int layout) {
+  const bool w4 = fmt == SKINNY_W_INT4G128;
+  if (!A || !Wq || !scale || !C || M <= 0 || N <= 0 || K <= 0 || K % (w4 ? 128 : 64) || (kernel != 1 && kernel != 3) || (layout != 0 && layout != 1)) {
+    tls_error() = std::string(fn) + bad_arg;
     return VSTAR_ERR_INVALID;
   }
   const int nt = epilogue == VSTAR_EPI_SILU_MUL ? 2 : 1;
   GemmParams p{};
   const int n_out = epilogue == VSTAR_EPI_SILU_MUL ? N / 2 : N;
-  p.A = (const lp_t*)A; p.lda = K; p.Wq = (const int8_t*)Wq; p.wq_scale = scale; p.bias = (const lp_t*)bias;
+  p.A = (const lp_t*)A; p.lda = K; p.bias = (const lp_t*)bias;
   p.res = (const lp_t*)res; p.ldr = n_out; p.C = C; p.ldc = n_out; p.M = M; p.N = N; p.K = K;
   p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
   if (kernel == 3) p.tile_force = -1;
-  if (!gemm_skinny_eligible(p)) { tls_error() = "vstar_vqa_op_gemm_w8: outside the weight-streaming kernels' domain (M <= 64)"; return VSTAR_ERR_INVALID; }
-  if (layout == 1 && N % (16 * nt)) { tls_error() = "vstar_vqa_op_gemm_w8: the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
+  if (!gemm_skinny_eligible(p)) { tls_error() = std::string(fn) + ": outside the weight-streaming kernels' domain (M <= 64)"; return VSTAR_ERR_INVALID; }
+  if (layout == 1 && N % (16 * nt)) { tls_error() = std::string(fn) + ": the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
   hipError_t e = hipSuccess;
-  OpBuf<int8_t> tiles(e, (size_t)N * K, layout == 1);
-  if (layout == 1 && e == hipSuccess) e = skinny_pack_tiles_w8((const int8_t*)Wq, tiles, N, K, nt, nullptr);
-  p.Wq_tiled = tiles;
+  OpBuf<char> tiles(e, w4 ? skinny_tiles_w4_bytes(N, K, nt) : (size_t)N * K, layout == 1);
+  if (layout == 1 && e == hipSuccess)
+    e = w4 ? skinny_pack_tiles_w4((const uint32_t*)Wq, (const lp_t*)scale, tiles.p, N, K, nt, nullptr)
+           : skinny_pack_tiles_w8((const int8_t*)Wq, (int8_t*)tiles.p, N, K, nt, nullptr);
+  p.dw = SkinnyWeights{fmt, Wq, scale, tiles.p};
   if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, false, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  return op_result(e, "vstar_vqa_op_gemm_w8");
+  return op_result(e, fn);
+}
+
+int vstar_vqa_op_gemm_w8(const void* A, const void* Wq, const float* scale, const void* bias, const void* res, void* C, int M, int N,
+                         int K, int epilogue, int kernel, const void* norm_w, float norm_eps, int layout) {
+  return op_gemm_wq(SKINNY_W_INT8, "vstar_vqa_op_gemm_w8", ": bad argument (kernel 1 or 3, layout 0 or 1, K % 64 == 0)", A, Wq, scale, bias, res,
+                    C, M, N, K, epilogue, kernel, norm_w, norm_eps, layout);
 }
 
 int vstar_vqa_op_quantize_w4(const void* dev_W_f16, int rows, int K, void* dev_q_u32, void* dev_scale_f16, void* dev_What_f16) {
@@ -609,26 +620,9 @@ int vstar_vqa_op_quantize_w4(const void* dev_W_f16, int rows, int K, void* dev_q
 
 int vstar_vqa_op_gemm_w4(const void* A, const void* Wq, const void* scale, const void* bias, const void* res, void* C, int M, int N,
                          int K, int epilogue, int kernel, const void* norm_w, float norm_eps, int layout) {
-  if (!A || !Wq || !scale || !C || M <= 0 || N <= 0 || K <= 0 || K % 128 || (kernel != 1 && kernel != 3) || (layout != 0 && layout != 1)) {
-    tls_error() = "vstar_vqa_op_gemm_w4: bad argument (kernel 1 or 3, layout 0 or 1, K % 128 == 0, weights and scales not null)";
-    return VSTAR_ERR_INVALID;
-  }
-  const int nt = epilogue == VSTAR_EPI_SILU_MUL ? 2 : 1;
-  GemmParams p{};
-  const int n_out = epilogue == VSTAR_EPI_SILU_MUL ? N / 2 : N;
-  p.A = (const lp_t*)A; p.lda = K; p.Wq4 = (const uint32_t*)Wq; p.wq4_scale = (const uint16_t*)scale; p.bias = (const lp_t*)bias;
-  p.res = (const lp_t*)res; p.ldr = n_out; p.C = C; p.ldc = n_out; p.M = M; p.N = N; p.K = K;
-  p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
-  if (kernel == 3) p.tile_force = -1;
-  if (!gemm_skinny_eligible(p)) { tls_error() = "vstar_vqa_op_gemm_w4: outside the weight-streaming kernels' domain (M <= 64)"; return VSTAR_ERR_INVALID; }
-  if (layout == 1 && N % (16 * nt)) { tls_error() = "vstar_vqa_op_gemm_w4: the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles"; return VSTAR_ERR_INVALID; }
-  hipError_t e = hipSuccess;
-  OpBuf<char> tiles(e, skinny_tiles_w4_bytes(N, K, nt), layout == 1);
-  if (layout == 1 && e == hipSuccess) e = skinny_pack_tiles_w4((const uint32_t*)Wq, (const lp_t*)scale, tiles, N, K, nt, nullptr);
-  p.Wq4_tiled = tiles;
-  if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, false, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  return op_result(e, "vstar_vqa_op_gemm_w4");
+  return op_gemm_wq(SKINNY_W_INT4G128, "vstar_vqa_op_gemm_w4",
+                    ": bad argument (kernel 1 or 3, layout 0 or 1, K % 128 == 0, weights and scales not null)", A, Wq, scale, bias, res, C, M, N,
+                    K, epilogue, kernel, norm_w, norm_eps, layout);
 }
 
 int vstar_vqa_kv_cache_format(const vstar_vqa_handle* h) { return h ? h->cfg.kv_cache_format : 0; }
