@@ -2,11 +2,16 @@
 // llava_search_llama.py:56-113 driven by vstar_bench_eval.py:78-165; HF LlamaAttention 4.31 with past_key_values) and of the
 // object-feature Perceiver resampler (LLaVA/llava/model/multimodal_projector/perceiver.py:25-121).
 //
+// Every launcher that touches the KV cache takes one layer's view of it (KvLayer, kernels.hpp: format, cells, scale bytes, strides)
+// and the rows of the call (KvRows: per-row position / sequence / slot, per-sequence own slot / prefix slot / past length, the
+// nullable ancestry table); the kernels receive the fields as separate __restrict__ parameters.
+//
 //   rope_kv_append       rotate-half RoPE (HF rounding points) on q,k in place at per-row absolute positions + K/V rows
 //                        written into the per-slot cache [slot][head][ctx][128].
 //   cached_attn_kernel   one workgroup per (new row, head): scores against the cached keys (prefix slot below `past`, own
 //                        slot from there on — option scoring forks a shared question prefix without copying it), fp32
 //                        softmax, probabilities rounded to the storage type like HF, PV from the cached values.
+//   cached_attn_split_*  the same for decode steps of few sequences, the keys of a (row, head) cut into 8 partitions.
 //   perceiver_attn       32 latents x (256 media + 32 latent) keys, 16 heads x 96 dims: one wave per (image, head, latent).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,7 +45,7 @@ __global__ void embed_rows_kernel(const int32_t* __restrict__ src, const lp_t* _
 }
 
 // ------------------------------------------------ block-scaled fp8 KV rows ------------------------------------------------
-// KV-cache formats (KvFormat, kernels.hpp) as the template parameter KVF of every kernel that touches the cache:
+// KV-cache formats (KvLayer::fmt, kernels.hpp) as the template parameter KVF of every kernel that touches the cache:
 //   0  fp16 rows [128]: the kernels as they always were
 //   1  MX e4m3: a row is 128 code bytes + 4 E8M0 bytes (one per block of 32 head-dim elements, mx.hpp's arithmetic); the cache
 //      pointers then address BYTES with the same element strides, the scale bytes live at (element offset / 32) of their own array
@@ -220,6 +225,14 @@ __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __rest
 // k, appends k and v to the cache and attends to them from LDS — rope_kv_append's work without its launch.
 // ANC (beam search): key / value row j of a sequence lives in slot anc[kv_slot * ctx + j] (the KV ancestry
 // table) instead of `j < past ? prefix : own`; the caller has set the entries of the rows it writes to kv_slot.
+// The launchers take the layer's KvLayer and the call's KvRows and hand the kernels their fields as separate __restrict__ parameters.
+//
+// The three attention kernels repeat five pieces: the slot pointers of a (sequence, head), the q / k half of the RoPE + append
+// prologue, the score pass, the own-key score and the PV pass.  Each exists ONCE, below — as a macro, not as a function: with every
+// piece a __forceinline__ function (functors for the store of a score and the probability of a key, in three variants) each kernel
+// kept its values bit for bit but not its instruction stream, and the un-fused continuation of the fp8 cache measured 0.15 % slower
+// per step; textual sharing leaves all three kernels the machine code they had with the copies written out
+// (profiles/kv_views_machine_code.txt).  The pieces use the kernels' common names (seq, h, pos, past, arow, tid, l16, grp, qv, mx, ...).
 template <bool ANC, class T>
 __device__ __forceinline__ const T* kv_row(const T* head0, const T* pre, const T* own, const int32_t* arow, int j, int past,
                                            int64_t slot_stride) {
@@ -227,6 +240,90 @@ __device__ __forceinline__ const T* kv_row(const T* head0, const T* pre, const T
   if constexpr (ANC) return head0 + (int64_t)arow[j] * slot_stride + (int64_t)j * D;
   else return (j < past ? pre : own) + (int64_t)j * D;
 }
+// head h of the sequence's own slot / of its prefix slot / of slot 0 in `cache`: p##own, p##pre, p##h0
+#define KV_SLOT_PTRS(p, cache)                                                                                   \
+  cell_t* p##own = (cell_t*)(cache) + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;                 \
+  const cell_t* p##pre = (const cell_t*)(cache) + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D; \
+  const cell_t* p##h0 = (const cell_t*)(cache) + (int64_t)h * ctx * D
+// lane d of q (which == 0) or k (which == 1): rotate-half RoPE with HF's rounding points; q -> qs, k -> the cache (formats 1 / 2:
+// kv8_put, the whole of wave 1: 32 lanes per block) and, as the value the cache now holds, own_k
+#define KV_ROPE_QK()                                                                                   \
+  const lp_t* base = rowp + which * (H * D);                                                           \
+  const float x1 = lp2f(base[d]), x2 = lp2f(base[d + 64]);                                             \
+  const float cs = lp2f(cos_sin[(int64_t)pos * D + d]), si = lp2f(cos_sin[(int64_t)pos * D + 64 + d]); \
+  const lp_t o1 = f2lp(rlp(x1 * cs) + rlp(-x2 * si)), o2 = f2lp(rlp(x2 * cs) + rlp(x1 * si));          \
+  if (which == 0) {                                                                                    \
+    qs[d] = lp2f(o1);                                                                                  \
+    qs[d + 64] = lp2f(o2);                                                                             \
+  } else if constexpr (KVF == 0) {                                                                     \
+    own_k[d] = lp2f(o1);                                                                               \
+    own_k[d + 64] = lp2f(o2);                                                                          \
+    kown[(int64_t)pos * D + d] = o1;                                                                   \
+    kown[(int64_t)pos * D + d + 64] = o2;                                                              \
+  } else {                                                                                             \
+    const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;         \
+    own_k[d] = kv8_put<KVF>(kc, ks, own_off + d, lp2f(o1));                                            \
+    own_k[d + 64] = kv8_put<KVF>(kc, ks, own_off + d + 64, lp2f(o2));                                  \
+  }
+// scores of the cached keys [J_LO, J_HI): 16 lanes per key, 16 key groups, 4 keys per group and pass (64 keys in flight per pass);
+// STORE runs on the first lane of key j with its score sv (HF: matmul output in the storage type, then / sqrt(head_dim))
+#define KV_SCORE_PASS(J_LO, J_HI, STORE)                                                                                                 \
+  for (int j0 = J_LO; j0 < J_HI; j0 += 64) {                                                                                             \
+    KvFrag<KVF> kv8[4];                                                                                                                  \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                                      \
+      const int j = j0 + u * 16 + grp;                                                                                                   \
+      kv8[u] = kv_frag_zero<KVF>();                                                                                                      \
+      if (j < J_HI)                                                                                                                      \
+        kv8[u] = kv_frag_load<KVF>(kv_row<ANC>(kh0, kpre, (const cell_t*)kown, arow, j, past, slot_stride), (const cell_t*)kc, ks, l16); \
+    }                                                                                                                                    \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                                      \
+      const int j = j0 + u * 16 + grp;                                                                                                   \
+      float a = 0.f, kx[8];                                                                                                              \
+      kv_frag_f32<KVF>(kv8[u], l16, kx);                                                                                                 \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) a += qv[e] * kx[e];                                                                  \
+      a += __shfl_xor(a, 8, 64);                                                                                                         \
+      a += __shfl_xor(a, 4, 64);                                                                                                         \
+      a += __shfl_xor(a, 2, 64);                                                                                                         \
+      a += __shfl_xor(a, 1, 64);                                                                                                         \
+      if (j < J_HI) {                                                                                                                    \
+        const float sv = rlp(rlp(a) / inv_scale);                                                                                        \
+        if (l16 == 0) { STORE; }                                                                                                         \
+        mx = fmaxf(mx, sv);                                                                                                              \
+      }                                                                                                                                  \
+    }                                                                                                                                    \
+  }
+// the score of the row's own key, from LDS (key group 0)
+#define KV_OWN_SCORE(STORE)                                                      \
+  float a = 0.f;                                                                 \
+  _Pragma("unroll") for (int e = 0; e < 8; ++e) a += qv[e] * own_k[l16 * 8 + e]; \
+  a += __shfl_xor(a, 8, 64);                                                     \
+  a += __shfl_xor(a, 4, 64);                                                     \
+  a += __shfl_xor(a, 2, 64);                                                     \
+  a += __shfl_xor(a, 1, 64);                                                     \
+  const float sv = rlp(rlp(a) / inv_scale);                                      \
+  if (l16 == 0) { STORE; }                                                       \
+  mx = fmaxf(mx, sv)
+// o += P.V over the cached keys J_FIRST, J_FIRST + 16, ... < J_HI of this key group: lane = 8 output dims (16-byte V loads), 4 keys in
+// flight; PROB is key j's probability, rounded to the storage type (HF .to(query.dtype))
+#define KV_PV_PASS(J_FIRST, J_HI, PROB)                                                                                                 \
+  for (int j0 = J_FIRST; j0 < J_HI; j0 += 64) {                                                                                         \
+    KvFrag<KVF> v8[4];                                                                                                                  \
+    float pr[4];                                                                                                                        \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                                     \
+      const int j = j0 + u * 16;                                                                                                        \
+      v8[u] = kv_frag_zero<KVF>();                                                                                                      \
+      pr[u] = 0.f;                                                                                                                      \
+      if (j < J_HI) {                                                                                                                   \
+        v8[u] = kv_frag_load<KVF>(kv_row<ANC>(vh0, vpre, (const cell_t*)vown, arow, j, past, slot_stride), (const cell_t*)vc, vs, l16); \
+        pr[u] = PROB;                                                                                                                   \
+      }                                                                                                                                 \
+    }                                                                                                                                   \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                                     \
+      float vx[8];                                                                                                                      \
+      kv_frag_f32<KVF>(v8[u], l16, vx);                                                                                                 \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) o[e] += pr[u] * vx[e];                                                              \
+    }                                                                                                                                   \
+  }
 
 template <bool FUSED, bool ANC, int KVF = 0>
 __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc,
@@ -248,12 +345,8 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   const int seq = row_seq[r];
   const int past = seq_past[seq], nk = pos + 1;
   const int nkc = FUSED ? pos : nk;         // keys that come from the cache
-  cell_t* kown = (cell_t*)kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* kpre = (const cell_t*)kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  cell_t* vown = (cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* vpre = (const cell_t*)vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* kh0 = (const cell_t*)kc + (int64_t)h * ctx * D;
-  const cell_t* vh0 = (const cell_t*)vc + (int64_t)h * ctx * D;
+  KV_SLOT_PTRS(k, kc);
+  KV_SLOT_PTRS(v, vc);
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   float* qs = dyn;
   float* sc = dyn + D;
@@ -261,23 +354,7 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   if (FUSED) {
     if (tid < 128) {                         // rotate-half RoPE with HF's rounding points: tid 0-63 q pairs, 64-127 k pairs
       const int which = tid >> 6, d = tid & 63;
-      const lp_t* base = rowp + which * (H * D);
-      const float x1 = lp2f(base[d]), x2 = lp2f(base[d + 64]);
-      const float cs = lp2f(cos_sin[(int64_t)pos * D + d]), si = lp2f(cos_sin[(int64_t)pos * D + 64 + d]);
-      const lp_t o1 = f2lp(rlp(x1 * cs) + rlp(-x2 * si)), o2 = f2lp(rlp(x2 * cs) + rlp(x1 * si));
-      if (which == 0) {
-        qs[d] = lp2f(o1);
-        qs[d + 64] = lp2f(o2);
-      } else if constexpr (KVF == 0) {
-        own_k[d] = lp2f(o1);
-        own_k[d + 64] = lp2f(o2);
-        kown[(int64_t)pos * D + d] = o1;
-        kown[(int64_t)pos * D + d + 64] = o2;
-      } else {                                // the whole of wave 1: 32 lanes per block
-        const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
-        own_k[d] = kv8_put<KVF>(kc, ks, own_off + d, lp2f(o1));
-        own_k[d + 64] = kv8_put<KVF>(kc, ks, own_off + d + 64, lp2f(o2));
-      }
+      KV_ROPE_QK();
     } else {
       const int d = tid - 128;
       const lp_t v = rowp[2 * H * D + d];
@@ -299,44 +376,9 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
 #pragma unroll
   for (int e = 0; e < 8; ++e) qv[e] = qs[l16 * 8 + e];
   float mx = -3.0e38f;
-  for (int j0 = 0; j0 < nkc; j0 += 64) {
-    KvFrag<KVF> kv8[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16 + grp;
-      kv8[u] = kv_frag_zero<KVF>();
-      if (j < nkc)
-        kv8[u] = kv_frag_load<KVF>(kv_row<ANC>(kh0, kpre, (const cell_t*)kown, arow, j, past, slot_stride), (const cell_t*)kc, ks, l16);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16 + grp;
-      float a = 0.f, kx[8];
-      kv_frag_f32<KVF>(kv8[u], l16, kx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a += qv[e] * kx[e];
-      a += __shfl_xor(a, 8, 64);
-      a += __shfl_xor(a, 4, 64);
-      a += __shfl_xor(a, 2, 64);
-      a += __shfl_xor(a, 1, 64);
-      if (j < nkc) {
-        const float sv = rlp(rlp(a) / inv_scale);    // HF: matmul output in the storage type, then / sqrt(head_dim)
-        if (l16 == 0) sc[j] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    }
-  }
+  KV_SCORE_PASS(0, nkc, sc[j] = sv);
   if (FUSED && grp == 0) {                     // the row's own key, from LDS
-    float a = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a += qv[e] * own_k[l16 * 8 + e];
-    a += __shfl_xor(a, 8, 64);
-    a += __shfl_xor(a, 4, 64);
-    a += __shfl_xor(a, 2, 64);
-    a += __shfl_xor(a, 1, 64);
-    const float sv = rlp(rlp(a) / inv_scale);
-    if (l16 == 0) sc[pos] = sv;
-    mx = fmaxf(mx, sv);
+    KV_OWN_SCORE(sc[pos] = sv);
   }
   mx = wave_max(mx);
   if ((tid & 63) == 0) redbuf[tid >> 6] = mx;
@@ -357,27 +399,7 @@ __global__ __launch_bounds__(256) void cached_attn_kernel(const lp_t* __restrict
   float o[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int j0 = grp; j0 < nkc; j0 += 64) {
-    KvFrag<KVF> v8[4];
-    float pr[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16;
-      v8[u] = kv_frag_zero<KVF>();
-      pr[u] = 0.f;
-      if (j < nkc) {
-        v8[u] = kv_frag_load<KVF>(kv_row<ANC>(vh0, vpre, (const cell_t*)vown, arow, j, past, slot_stride), (const cell_t*)vc, vs, l16);
-        pr[u] = rlp(sc[j] * inv);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float vx[8];
-      kv_frag_f32<KVF>(v8[u], l16, vx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += pr[u] * vx[e];
-    }
-  }
+  KV_PV_PASS(grp, nkc, rlp(sc[j] * inv));
   if (FUSED && grp == 0) {
     const float pr = rlp(sc[pos] * inv);
 #pragma unroll
@@ -413,6 +435,19 @@ __device__ __forceinline__ void split_range(int nkc, int p, int* lo, int* hi) {
   *hi = *lo + span < nkc ? *lo + span : nkc;
 }
 
+// the workspace of cached_attention_split_ws_bytes(max_rows, H, ctx), cut up
+struct SplitWs {
+  float *scores, *stats, *opart;      // [rows * H] x [ctx] / [SPLIT_P][2] / [SPLIT_P][128]
+  int* cnt;                           // [rows * H] tickets
+  SplitWs(void* ws, int max_rows, int H, int ctx) {
+    const size_t rh = (size_t)max_rows * H;
+    scores = (float*)ws;
+    stats = scores + rh * ctx;
+    opart = stats + rh * SPLIT_P * 2;
+    cnt = (int*)(opart + rh * SPLIT_P * 128);
+  }
+};
+
 template <bool ANC, int KVF = 0>
 __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
     const lp_t* __restrict__ qkv, lp_t* __restrict__ kc, lp_t* __restrict__ vc, const int32_t* __restrict__ row_seq,
@@ -429,33 +464,15 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
   if (pos < 0) return;
   const int seq = row_seq[r];
   const int past = seq_past[seq], nkc = pos;
-  cell_t* kown = (cell_t*)kc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* kpre = (const cell_t*)kc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
+  KV_SLOT_PTRS(k, kc);
   cell_t* vown = (cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* kh0 = (const cell_t*)kc + (int64_t)h * ctx * D;
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const lp_t* rowp = qkv + (int64_t)r * (3 * H * D) + h * D;
   const bool last = p == SPLIT_P - 1;
   if (tid < 128) {                           // rotate-half RoPE with HF's rounding points: tid 0-63 q pairs, 64-127 k pairs
     const int which = tid >> 6, d = tid & 63;
     if (which == 0 || last) {
-      const lp_t* base = rowp + which * (H * D);
-      const float x1 = lp2f(base[d]), x2 = lp2f(base[d + 64]);
-      const float cs = lp2f(cos_sin[(int64_t)pos * D + d]), si = lp2f(cos_sin[(int64_t)pos * D + 64 + d]);
-      const lp_t o1 = f2lp(rlp(x1 * cs) + rlp(-x2 * si)), o2 = f2lp(rlp(x2 * cs) + rlp(x1 * si));
-      if (which == 0) {
-        qs[d] = lp2f(o1);
-        qs[d + 64] = lp2f(o2);
-      } else if constexpr (KVF == 0) {
-        own_k[d] = lp2f(o1);
-        own_k[d + 64] = lp2f(o2);
-        kown[(int64_t)pos * D + d] = o1;
-        kown[(int64_t)pos * D + d + 64] = o2;
-      } else {                                // the whole of wave 1: 32 lanes per block
-        const int64_t own_off = (int64_t)seq_kv[seq] * slot_stride + ((int64_t)h * ctx + pos) * D;
-        own_k[d] = kv8_put<KVF>(kc, ks, own_off + d, lp2f(o1));
-        own_k[d + 64] = kv8_put<KVF>(kc, ks, own_off + d + 64, lp2f(o2));
-      }
+      KV_ROPE_QK();
     }
   } else if (last) {
     const int d = tid - 128;
@@ -475,46 +492,11 @@ __global__ __launch_bounds__(256) void cached_attn_split_scores_kernel(
 #pragma unroll
   for (int e = 0; e < 8; ++e) qv[e] = qs[l16 * 8 + e];
   float mx = -3.0e38f;
-  for (int j0 = j_lo; j0 < j_hi; j0 += 64) {
-    KvFrag<KVF> kv8[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16 + grp;
-      kv8[u] = kv_frag_zero<KVF>();
-      if (j < j_hi)
-        kv8[u] = kv_frag_load<KVF>(kv_row<ANC>(kh0, kpre, (const cell_t*)kown, arow, j, past, slot_stride), (const cell_t*)kc, ks, l16);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16 + grp;
-      float a = 0.f, kx[8];
-      kv_frag_f32<KVF>(kv8[u], l16, kx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a += qv[e] * kx[e];
-      a += __shfl_xor(a, 8, 64);
-      a += __shfl_xor(a, 4, 64);
-      a += __shfl_xor(a, 2, 64);
-      a += __shfl_xor(a, 1, 64);
-      if (j < j_hi) {
-        const float sv = rlp(rlp(a) / inv_scale);    // HF: matmul output in the storage type, then / sqrt(head_dim)
-        if (l16 == 0) { dyn[j - j_lo] = sv; gsc[j] = sv; }
-        mx = fmaxf(mx, sv);
-      }
-    }
-  }
+  KV_SCORE_PASS(j_lo, j_hi, dyn[j - j_lo] = sv; gsc[j] = sv);
   int n_loc = j_hi - j_lo;
   if (last) {                                  // the row's own key, from LDS
     if (grp == 0) {
-      float a = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a += qv[e] * own_k[l16 * 8 + e];
-      a += __shfl_xor(a, 8, 64);
-      a += __shfl_xor(a, 4, 64);
-      a += __shfl_xor(a, 2, 64);
-      a += __shfl_xor(a, 1, 64);
-      const float sv = rlp(rlp(a) / inv_scale);
-      if (l16 == 0) { dyn[n_loc] = sv; gsc[pos] = sv; }
-      mx = fmaxf(mx, sv);
+      KV_OWN_SCORE(dyn[n_loc] = sv; gsc[pos] = sv);
     }
     n_loc += 1;
   }
@@ -549,9 +531,7 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
   if (pos < 0) return;
   const int seq = row_seq[r];
   const int past = seq_past[seq], nkc = pos;
-  const cell_t* vown = (const cell_t*)vc + (int64_t)seq_kv[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* vpre = (const cell_t*)vc + (int64_t)seq_prefix[seq] * slot_stride + (int64_t)h * ctx * D;
-  const cell_t* vh0 = (const cell_t*)vc + (int64_t)h * ctx * D;
+  KV_SLOT_PTRS(v, vc);
   const int32_t* arow = ANC ? anc + (int64_t)seq_kv[seq] * ctx : nullptr;
   const float* st = ws_stats + ((int64_t)r * H + h) * SPLIT_P * 2;
   float M = -3.0e38f;
@@ -569,27 +549,7 @@ __global__ __launch_bounds__(256) void cached_attn_split_pv_kernel(
   float o[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int j0 = j_lo + grp; j0 < j_hi; j0 += 64) {
-    KvFrag<KVF> v8[4];
-    float pr[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * 16;
-      v8[u] = kv_frag_zero<KVF>();
-      pr[u] = 0.f;
-      if (j < j_hi) {
-        v8[u] = kv_frag_load<KVF>(kv_row<ANC>(vh0, vpre, vown, arow, j, past, slot_stride), (const cell_t*)vc, vs, l16);
-        pr[u] = rlp(__expf(gsc[j] - M) * inv);     // probabilities rounded to the storage type (HF .to(query.dtype))
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float vx[8];
-      kv_frag_f32<KVF>(v8[u], l16, vx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += pr[u] * vx[e];
-    }
-  }
+  KV_PV_PASS(j_lo + grp, j_hi, rlp(__expf(gsc[j] - M) * inv));     // (the own key included: appended by the scores kernel)
 #pragma unroll
   for (int e = 0; e < 8; ++e) part[grp][l16 * 8 + e] = o[e];
   __syncthreads();
@@ -788,35 +748,34 @@ hipError_t embed_rows(const int32_t* src, const lp_t* table, int vocab, const lp
   return hipGetLastError();
 }
 
-// a valid KvFormat of this build: formats beyond fp16 exist in the fp16 instantiation only, KV_FMT_MXFP8 needs its scale arrays
-static bool kv_format_ok(const KvFormat& f) {
+bool kv_format_ok(const KvLayer& kv) {
 #ifdef VSTAR_LP_F16
-  return f.fmt == KV_FMT_F16 || f.fmt == KV_FMT_MXFP8_EMU || (f.fmt == KV_FMT_MXFP8 && f.ks && f.vs);
+  return kv.fmt == KV_FMT_F16 || kv.fmt == KV_FMT_MXFP8_EMU || (kv.fmt == KV_FMT_MXFP8 && kv.ks && kv.vs);
 #else
-  return f.fmt == KV_FMT_F16;
+  return kv.fmt == KV_FMT_F16;
 #endif
 }
 
 // KV_DISPATCH(fmt, CALL): CALL with the constant KVF = the runtime format fmt (the format-0 instantiation is the only one of
 // the bf16 build)
 #ifdef VSTAR_LP_F16
-#define KV_DISPATCH(fmt, CALL)                          \
-  switch (fmt) {                                        \
-    case KV_FMT_MXFP8: { constexpr int KVF = 1; CALL; break; }      \
-    case KV_FMT_MXFP8_EMU: { constexpr int KVF = 2; CALL; break; }  \
-    default: { constexpr int KVF = 0; CALL; break; }    \
+#define KV_DISPATCH(fmt, ...)                                              \
+  switch (fmt) {                                                           \
+    case KV_FMT_MXFP8: { constexpr int KVF = 1; __VA_ARGS__; break; }      \
+    case KV_FMT_MXFP8_EMU: { constexpr int KVF = 2; __VA_ARGS__; break; }  \
+    default: { constexpr int KVF = 0; __VA_ARGS__; break; }                \
   }
 #else
-#define KV_DISPATCH(fmt, CALL) { constexpr int KVF = 0; CALL; }
+#define KV_DISPATCH(fmt, ...) { constexpr int KVF = 0; __VA_ARGS__; }
 #endif
 
-hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const int32_t* row_pos, const int32_t* row_slot, lp_t* kc, lp_t* vc,
-                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s, const KvFormat& kvf) {
-  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
+hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const KvLayer& kv, const KvRows& rows, int R, hipStream_t s) {
+  if (!kv_format_ok(kv)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
-  const int64_t n = (int64_t)R * 3 * H * 8;
-  KV_DISPATCH(kvf.fmt, hipLaunchKernelGGL(rope_kv_append_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, qkv, cos_sin,
-                                          row_pos, row_slot, kc, vc, slot_stride, ctx, R, H, kvf.ks, kvf.vs));
+  const int64_t n = (int64_t)R * 3 * kv.H * 8;
+  KV_DISPATCH(kv.fmt, hipLaunchKernelGGL(rope_kv_append_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, qkv, cos_sin,
+                                         rows.row_pos, rows.row_slot, (lp_t*)kv.k, (lp_t*)kv.v, kv.slot_stride, kv.ctx, R, kv.H, kv.ks,
+                                         kv.vs));
   return hipGetLastError();
 }
 
@@ -835,53 +794,38 @@ size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx) {
 }
 
 template <bool ANC, int KVF>
-static hipError_t cached_attention_t(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
-                                     const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
-                                     lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
-                                     int split_max_rows, const int32_t* anc, uint8_t* ks, uint8_t* vs) {
+static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
+                                     int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
   static const bool split_on = [] { const char* v = getenv("VSTAR_DECODE_SPLIT_KV"); return !v || atoi(v) != 0; }();
+  const float inv_scale = sqrtf(128.0f);
+  lp_t *kc = (lp_t*)kv.k, *vc = (lp_t*)kv.v;      // (the kernels' cell type is their KVF's)
   // decode steps of few sequences: P partitions per (row, head) so that the K / V streams of a head run on 8 CUs instead of one
-  if (split_on && fused_cos_sin && split_ws && R <= split_max_rows && R * H <= 128 && max_keys >= 256) {
-    const size_t rh = (size_t)split_max_rows * H;
-    float* ws_scores = (float*)split_ws;
-    float* ws_stats = ws_scores + rh * ctx;
-    float* ws_opart = ws_stats + rh * SPLIT_P * 2;
-    int* ws_cnt = (int*)(ws_opart + rh * SPLIT_P * 128);
+  if (split_on && fused_cos_sin && split_ws && R <= split_max_rows && R * kv.H <= 128 && max_keys >= 256) {
+    const SplitWs ws(split_ws, split_max_rows, kv.H, kv.ctx);
     const int span = ((((max_keys + SPLIT_P - 1) / SPLIT_P) + 63) & ~63) + 1;
-    hipLaunchKernelGGL((cached_attn_split_scores_kernel<ANC, KVF>), dim3(R, H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s, qkv,
-                       kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin, ws_scores, ws_stats, H, ctx, slot_stride,
-                       sqrtf(128.0f), anc, ks, vs);
-    hipLaunchKernelGGL((cached_attn_split_pv_kernel<ANC, KVF>), dim3(R, H, SPLIT_P), dim3(256), 0, s, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, ws_scores, ws_stats, ws_opart, ws_cnt, out, H, ctx, slot_stride, anc, vs);
+    hipLaunchKernelGGL((cached_attn_split_scores_kernel<ANC, KVF>), dim3(R, kv.H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s,
+                       qkv, kc, vc, rows.row_seq, rows.row_pos, rows.seq_kv, rows.seq_prefix, rows.seq_past, fused_cos_sin, ws.scores,
+                       ws.stats, kv.H, kv.ctx, kv.slot_stride, inv_scale, rows.anc, kv.ks, kv.vs);
+    hipLaunchKernelGGL((cached_attn_split_pv_kernel<ANC, KVF>), dim3(R, kv.H, SPLIT_P), dim3(256), 0, s, vc, rows.row_seq, rows.row_pos,
+                       rows.seq_kv, rows.seq_prefix, rows.seq_past, ws.scores, ws.stats, ws.opart, ws.cnt, out, kv.H, kv.ctx,
+                       kv.slot_stride, rows.anc, kv.vs);
     return hipGetLastError();
   }
   const size_t lds = (size_t)(128 + max_keys) * sizeof(float);
   if (lds > 40 * 1024) return hipErrorInvalidValue;
-  if (fused_cos_sin)
-    hipLaunchKernelGGL((cached_attn_kernel<true, ANC, KVF>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc, ks, vs);
-  else
-    hipLaunchKernelGGL((cached_attn_kernel<false, ANC, KVF>), dim3(R, H), dim3(256), lds, s, qkv, kc, vc, row_seq, row_pos, seq_kv,
-                       seq_prefix, seq_past, fused_cos_sin, out, H, ctx, slot_stride, sqrtf(128.0f), anc, ks, vs);
+  hipLaunchKernelGGL((fused_cos_sin ? cached_attn_kernel<true, ANC, KVF> : cached_attn_kernel<false, ANC, KVF>), dim3(R, kv.H), dim3(256),
+                     lds, s, qkv, kc, vc, rows.row_seq, rows.row_pos, rows.seq_kv, rows.seq_prefix, rows.seq_past, fused_cos_sin, out, kv.H,
+                     kv.ctx, kv.slot_stride, inv_scale, rows.anc, kv.ks, kv.vs);
   return hipGetLastError();
 }
 
-hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
-                            const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
-                            lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s, void* split_ws,
-                            int split_max_rows, const int32_t* anc, const KvFormat& kvf) {
-  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
+hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
+                            int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
+  if (!kv_format_ok(kv)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
   hipError_t e = hipErrorInvalidValue;
-  if (anc) {
-    KV_DISPATCH(kvf.fmt, e = (cached_attention_t<true, KVF>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin,
-                                                            out, R, H, ctx, slot_stride, max_keys, s, split_ws, split_max_rows, anc,
-                                                            kvf.ks, kvf.vs)));
-  } else {
-    KV_DISPATCH(kvf.fmt, e = (cached_attention_t<false, KVF>(qkv, kc, vc, row_seq, row_pos, seq_kv, seq_prefix, seq_past, fused_cos_sin,
-                                                             out, R, H, ctx, slot_stride, max_keys, s, split_ws, split_max_rows, nullptr,
-                                                             kvf.ks, kvf.vs)));
-  }
+  KV_DISPATCH(kv.fmt, e = rows.anc ? cached_attention_t<true, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows)
+                                   : cached_attention_t<false, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows));
   return e;
 }
 
@@ -910,13 +854,14 @@ hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, cons
   return hipGetLastError();
 }
 
-hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
-                        int64_t slot_stride, int64_t layer_stride, hipStream_t s, const KvFormat& kvf) {
-  if (!kv_format_ok(kvf)) return hipErrorInvalidValue;
+hipError_t kv_copy_rows(const KvLayer& kv0, int layers, int64_t layer_stride, const int32_t* anc, int dst, int src, int lo, int hi,
+                        hipStream_t s) {
+  if (!kv_format_ok(kv0)) return hipErrorInvalidValue;
   if (hi <= lo) return hipSuccess;
-  const int64_t n = (int64_t)2 * layers * H * (hi - lo) * 16;
-  KV_DISPATCH(kvf.fmt, hipLaunchKernelGGL(kv_copy_rows_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kc, vc, anc, dst,
-                                          src, lo, hi - lo, H, ctx, slot_stride, layer_stride, n, kvf.ks, kvf.vs));
+  const int64_t n = (int64_t)2 * layers * kv0.H * (hi - lo) * 16;
+  KV_DISPATCH(kv0.fmt, hipLaunchKernelGGL(kv_copy_rows_kernel<KVF>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (lp_t*)kv0.k,
+                                          (lp_t*)kv0.v, anc, dst, src, lo, hi - lo, kv0.H, kv0.ctx, kv0.slot_stride, layer_stride, n,
+                                          kv0.ks, kv0.vs));
   return hipGetLastError();
 }
 

@@ -143,37 +143,54 @@ hipError_t skinny_pack_tiles_w4(const uint32_t* q, const lp_t* scale, void* Wt, 
 #endif
 
 // ---- KV-cached language model + Perceiver resampler (decode.hip) ----
-// KV-cache format of a layer (fp16 build only beyond KV_FMT_F16).  KV_FMT_MXFP8: kc / vc address code BYTES
-// [slot][H][ctx][128] (same element strides as the fp16 cache) and ks / vs the E8M0 bytes [slot][H][ctx][4] of this layer, one per
-// block of 32 head-dim elements (mx.hpp).  KV_FMT_MXFP8_EMU: the fp16 cache, every writer storing the round-tripped row.
+// One layer of the KV cache: K and V as [slot][H][ctx][128] cells, slot_stride cells apart, in the format `fmt`
+// (beyond KV_FMT_F16: fp16 build only).
+//   KV_FMT_F16        a cell is an lp_t.
+//   KV_FMT_MXFP8      a cell is an e4m3 code BYTE — k / v then address bytes with the same element strides — and ks / vs hold the
+//                     E8M0 bytes [slot][H][ctx][4] of this layer, one per block of 32 head-dim elements (mx.hpp), at
+//                     (cell offset / 32) of their own arrays.
+//   KV_FMT_MXFP8_EMU  lp_t cells, every writer storing the round-tripped row: format 1's values through format 0's readers.
 enum { KV_FMT_F16 = 0, KV_FMT_MXFP8 = 1, KV_FMT_MXFP8_EMU = 2 };
-struct KvFormat { int fmt = KV_FMT_F16; uint8_t* ks = nullptr; uint8_t* vs = nullptr; };
+struct KvLayer {
+  int fmt = KV_FMT_F16;
+  void *k = nullptr, *v = nullptr;             // cells, untyped: the format decides
+  uint8_t *ks = nullptr, *vs = nullptr;        // KV_FMT_MXFP8 only, else null
+  int64_t slot_stride = 0;                     // H * ctx * 128
+  int H = 0, ctx = 0;
+};
+// a valid view for this build: formats beyond fp16 exist in the fp16 instantiation only, KV_FMT_MXFP8 needs its scale arrays
+bool kv_format_ok(const KvLayer& kv);
+// The rows of one call (device arrays): row r is position row_pos[r] (< 0: a padding row, skipped) of sequence row_seq[r] and is
+// stored in slot row_slot[r]; sequence i writes slot seq_kv[i] and reads keys [0, seq_past[i]) from slot seq_prefix[i], the rest
+// from its own.  anc (nullable): the KV ancestry table of beam search, see kv_anc_mark below.
+struct KvRows {
+  const int32_t *row_seq = nullptr, *row_pos = nullptr, *row_slot = nullptr;
+  const int32_t *seq_kv = nullptr, *seq_prefix = nullptr, *seq_past = nullptr;
+  const int32_t* anc = nullptr;
+};
 // x[r,:] = src[r] >= 0 ? table[src[r]] : (src[r] == INT32_MIN ? 0 : feats[-(src[r]+1)])
 hipError_t embed_rows(const int32_t* src, const lp_t* table, int vocab, const lp_t* feats, int64_t n_feat_rows, lp_t* x, int R,
                       int C, hipStream_t s);
-// in-place RoPE on q,k of qkv [R, 3*H*128] at row_pos[r] (rows with row_pos < 0 are skipped) and K/V rows appended to the
-// cache of slot row_slot[r]: kc/vc = this layer's [slot][H][ctx][128]
-hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const int32_t* row_pos, const int32_t* row_slot, lp_t* kc, lp_t* vc,
-                          int64_t slot_stride, int ctx, int R, int H, hipStream_t s, const KvFormat& kvf = KvFormat());
-// causal attention of R new rows against the cache: keys [0, seq_past) come from seq_prefix's slot, the rest from seq_kv's.
+// in-place RoPE on q,k of qkv [R, 3*H*128] at rows.row_pos (padding rows are skipped) and K/V rows appended to the cache of slot
+// rows.row_slot[r]
+hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const KvLayer& kv, const KvRows& rows, int R, hipStream_t s);
+// causal attention of R new rows against the cache: keys [0, seq_past) come from seq_prefix's slot, the rest from seq_kv's
+// (rows.anc given: through the ancestry table).
 // fused_cos_sin != null (only when every sequence has exactly ONE new row): the kernel also does rope_kv_append's work for
 // its row (RoPE on q,k, K/V appended to the cache) — qkv then holds the raw projection.
-hipError_t cached_attention(const lp_t* qkv, lp_t* kc, lp_t* vc, const int32_t* row_seq, const int32_t* row_pos,
-                            const int32_t* seq_kv, const int32_t* seq_prefix, const int32_t* seq_past, const lp_t* fused_cos_sin,
-                            lp_t* out, int R, int H, int ctx, int64_t slot_stride, int max_keys, hipStream_t s,
-                            void* split_ws = nullptr, int split_max_rows = 0, const int32_t* anc = nullptr,
-                            const KvFormat& kvf = KvFormat());
+hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
+                            int max_keys, hipStream_t s, void* split_ws = nullptr, int split_max_rows = 0);
 // KV ancestry table of beam search (anc: [slots, ctx] int32, entry (slot, p) = the slot whose cache holds position p of the
-// sequence in `slot`; cached_attention reads K/V through it when `anc` is given).  mark: entry (row_slot[r], row_pos[r]) =
+// sequence in `slot`; cached_attention reads K/V through it when KvRows::anc is given).  mark: entry (row_slot[r], row_pos[r]) =
 // row_slot[r] for every row; fill: slot's entries [lo, hi) = value; reorder: entries [lo, hi) of dst[i] = those of src[i], every
 // source read before any destination is written (tmp: n * (hi - lo) ints); copy_rows: K/V rows [lo, hi) of every layer of
-// `dst` = the rows src's entries point at (a physical copy).
+// `dst` = the rows src's entries point at (a physical copy) — kv0 is layer 0's view, layer i lies i * layer_stride cells behind it.
 hipError_t kv_anc_mark(const int32_t* row_slot, const int32_t* row_pos, int R, int32_t* anc, int ctx, hipStream_t s);
 hipError_t kv_anc_fill(int32_t* anc, int slot, int value, int lo, int hi, int ctx, hipStream_t s);
 hipError_t kv_anc_reorder(int32_t* anc, int32_t* tmp, const int32_t* d_dst, const int32_t* d_src, int n, int lo, int hi, int ctx,
                           hipStream_t s);
-hipError_t kv_copy_rows(lp_t* kc, lp_t* vc, const int32_t* anc, int dst, int src, int lo, int hi, int layers, int H, int ctx,
-                        int64_t slot_stride, int64_t layer_stride, hipStream_t s, const KvFormat& kvf = KvFormat());
+hipError_t kv_copy_rows(const KvLayer& kv0, int layers, int64_t layer_stride, const int32_t* anc, int dst, int src, int lo, int hi,
+                        hipStream_t s);
 #ifdef VSTAR_LP_F16
 // x [rows, 128] fp16 -> e4m3 codes [rows, 128], E8M0 bytes [rows, 4] and (nullable, may alias x) xhat = fp16(decoded): the device
 // function every KV_FMT_MXFP8 writer quantises with

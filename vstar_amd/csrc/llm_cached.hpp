@@ -106,6 +106,88 @@ struct LlmCachedCfg {
 // of all four and the tile-major images the format's rules allow (LlmCached::build_quantised); null where there is none.
 struct DecodeLayerW { SkinnyWeights qkv, o, gate_up, down; };
 
+// The KV cache of a runner: K and V as [layers][slots][heads][ctx][128] cells in one format (KvLayer, kernels.hpp), layer i
+// `layer_stride` cells behind layer 0 (KV_FMT_MXFP8: its scale bytes layer_stride / 32 bytes behind layer 0's).
+struct KvCache {
+  KvLayer l0;                  // layer 0's view
+  int layers = 0;
+  int64_t layer_stride = 0;
+  int64_t bytes = 0;           // K + V storage, scale bytes included
+  int alloc(EngineBase* e, int fmt, int layers_, int slots, int heads, int ctx);
+  KvLayer layer(int i) const {
+    KvLayer l = l0;
+    const int64_t off = (int64_t)i * layer_stride;
+    if (l0.fmt == KV_FMT_MXFP8) { l.k = (uint8_t*)l0.k + off; l.v = (uint8_t*)l0.v + off; l.ks = l0.ks + off / 32; l.vs = l0.vs + off / 32; }
+    else { l.k = (lp_t*)l0.k + off; l.v = (lp_t*)l0.v + off; }
+    return l;
+  }
+  // the decoded K then V of one slot of one layer, [2][heads][ctx][128] floats, cut at cap; waits for `s` first.  Returns the
+  // count, or -1 after a HIP failure.
+  int64_t read(int layer_i, int slot, float* out, int64_t cap, hipStream_t s) const;
+};
+
+inline int KvCache::alloc(EngineBase* e, int fmt, int layers_, int slots, int heads, int ctx) {
+  if (fmt != KV_FMT_F16 && fmt != KV_FMT_MXFP8 && fmt != KV_FMT_MXFP8_EMU) {
+    e->set_error("kv_cache_format must be 0 (fp16), 1 (MX fp8) or 2 (MX fp8 emulated in fp16)");
+    return VSTAR_ERR_INVALID;
+  }
+#ifndef VSTAR_LP_F16
+  if (fmt != KV_FMT_F16) { e->set_error("kv_cache_format: the block-scaled fp8 KV cache needs the fp16 engine"); return VSTAR_ERR_INVALID; }
+#endif
+  l0 = KvLayer{};
+  l0.fmt = fmt; l0.H = heads; l0.ctx = ctx;
+  l0.slot_stride = (int64_t)heads * ctx * 128;
+  layers = layers_;
+  layer_stride = l0.slot_stride * slots;
+  const size_t n = (size_t)layer_stride * layers;
+  if (fmt == KV_FMT_MXFP8) {
+    uint8_t *k = nullptr, *v = nullptr;
+    RC(e->dalloc(&k, n));
+    RC(e->dalloc(&v, n));
+    RC(e->dalloc(&l0.ks, n / 32));
+    RC(e->dalloc(&l0.vs, n / 32));
+    l0.k = k; l0.v = v;
+    bytes = (int64_t)(2 * (n + n / 32));
+  } else {
+    lp_t *k = nullptr, *v = nullptr;
+    RC(e->dalloc(&k, n));
+    RC(e->dalloc(&v, n));
+    l0.k = k; l0.v = v;
+    bytes = (int64_t)n * 2 * 2;
+  }
+  return 0;
+}
+
+inline int64_t KvCache::read(int layer_i, int slot, float* out, int64_t cap, hipStream_t s) const {
+  const int64_t per = l0.slot_stride;                      // cells of one slot of K (or V)
+  const int64_t cnt = std::min<int64_t>(2 * per, cap);
+  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  const KvLayer l = layer(layer_i);
+  const int64_t off = (int64_t)slot * per;
+  for (int which = 0; which < 2; ++which) {
+    const int64_t lo = which * per, m = std::min(per, cnt - lo);
+    if (m <= 0) break;
+    if (l.fmt == KV_FMT_MXFP8) {
+      std::vector<uint8_t> codes((size_t)per), sc((size_t)per / 32);
+      if (hipMemcpy(codes.data(), (const uint8_t*)(which ? l.v : l.k) + off, codes.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(sc.data(), (which ? l.vs : l.ks) + off / 32, sc.size(), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+      for (int64_t i = 0; i < m; ++i) {                    // OCP e4m3: 1-4-3, bias 7, subnormals, 0x7f / 0xff = NaN
+        const uint8_t c = codes[(size_t)i];
+        const int ex = (c >> 3) & 15, mant = c & 7;
+        float v = ex == 15 && mant == 7 ? NAN : (ex ? ldexpf((float)(8 + mant), ex - 10) : ldexpf((float)mant, -9));
+        v = ldexpf(v, (int)sc[(size_t)(i >> 5)] - 127);
+        out[lo + i] = (c & 0x80) ? -v : v;
+      }
+    } else {
+      std::vector<lp_t> tmp((size_t)m);
+      if (hipMemcpy(tmp.data(), (const lp_t*)(which ? l.v : l.k) + off, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+      for (int64_t i = 0; i < m; ++i) out[lo + i] = lp2f(tmp[(size_t)i]);
+    }
+  }
+  return cnt;
+}
+
 struct LlmCached {
   EngineBase* e = nullptr;
   LlmCachedCfg cfg;
@@ -120,24 +202,21 @@ struct LlmCached {
   int64_t n_feat_rows = 0;
   // owned
   lp_t* rope = nullptr;                          // [max_ctx, 128] cos | sin
-  lp_t *kcache = nullptr, *vcache = nullptr;     // [layers][slots][heads][ctx][128] (KV_FMT_MXFP8: code bytes, same element strides)
-  uint8_t *kscale = nullptr, *vscale = nullptr;  // KV_FMT_MXFP8: E8M0 bytes [layers][slots][heads][ctx][4]
-  int64_t slot_stride = 0, layer_stride = 0;
-  int64_t kv_bytes = 0;                          // K + V storage, scale bytes included
-  // layer i's K / V cache and its format descriptor (the scale arrays of that layer)
-  lp_t* kv_layer(lp_t* base, int i) const {
-    return cfg.kv_format == KV_FMT_MXFP8 ? (lp_t*)((uint8_t*)base + (int64_t)i * layer_stride) : base + (int64_t)i * layer_stride;
-  }
-  KvFormat kv_fmt(int i) const {
-    KvFormat f;
-    f.fmt = cfg.kv_format;
-    if (kscale) { f.ks = kscale + (int64_t)i * (layer_stride / 32); f.vs = vscale + (int64_t)i * (layer_stride / 32); }
-    return f;
-  }
+  KvCache kv;
   lp_t *lx = nullptr, *lh = nullptr, *lqkv = nullptr, *latt = nullptr, *lact = nullptr;
   lp_t *wsel = nullptr, *wnorm = nullptr, *logits = nullptr;
-  int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_seq = nullptr, *d_want = nullptr,
-          *d_argmax = nullptr;
+  int32_t *d_src = nullptr, *d_row_pos = nullptr, *d_row_slot = nullptr, *d_row_seq = nullptr, *d_want = nullptr, *d_argmax = nullptr;
+  // the per-sequence metadata [3][seq_cap()] = own slot | prefix slot | past length, uploaded as one block, and the row view over it
+  // and the three row arrays above (anc null: a call that attends through the ancestry table sets it in its copy)
+  int seq_cap() const { return cfg.max_slots * 4; }
+  int32_t* d_seq = nullptr;
+  // d_seq and its host images are [3][seq_cap()]: k = 0 own slot, 1 prefix slot, 2 past length
+  size_t seq_index(int k, int i) const { return (size_t)k * seq_cap() + i; }
+  int32_t* seq_array(int k) const { return d_seq + seq_index(k, 0); }
+  KvRows kv_rows;
+  void seq_set(std::vector<int32_t>& image, int i, int slot, int prefix, int past) const {
+    image[seq_index(0, i)] = slot; image[seq_index(1, i)] = prefix; image[seq_index(2, i)] = past;
+  }
   vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of the SAMPLE and sampled VERIFY tails
   int max_want = 256;                            // wanted rows of one lm_head call (the scoring tail chunks by it, up to max_rows)
   int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
@@ -204,7 +283,7 @@ struct LlmCached {
                const SkinnyWeights* dw = nullptr);
   int lin_skinny(GemmParams& p, int epi, const SkinnyWeights* dw);
   int llm_layers_prefill(int nseq, int S);
-  int llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc = nullptr);
+  int llm_layers_cached(int R, int max_keys, bool single_rows, const int32_t* anc = nullptr);
   // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
   struct TailCopy { void* dev = nullptr; const void* in = nullptr; void* out = nullptr; size_t bytes = 0; };
   size_t vpad() const { return (size_t)(cfg.vocab + 255) / 256 * 256; }      // row stride of the logits buffer
@@ -235,31 +314,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
     RC(e->dalloc(&rope, tab.size()));
     if (hipMemcpy(rope, tab.data(), tab.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { set_error("rope table upload failed"); return VSTAR_ERR_HIP; }
   }
-  slot_stride = (int64_t)c.heads * c.max_ctx * 128;
-  layer_stride = slot_stride * c.max_slots;
-  if (c.kv_format == KV_FMT_MXFP8) {
-#ifdef VSTAR_LP_F16
-    const size_t n = (size_t)layer_stride * c.layers;
-    RC(e->dalloc((uint8_t**)&kcache, n));
-    RC(e->dalloc((uint8_t**)&vcache, n));
-    RC(e->dalloc(&kscale, n / 32));
-    RC(e->dalloc(&vscale, n / 32));
-    kv_bytes = (int64_t)(2 * (n + n / 32));
-#else
-    set_error("kv_cache_format: the block-scaled fp8 KV cache needs the fp16 engine");
-    return VSTAR_ERR_INVALID;
-#endif
-  } else if (c.kv_format == KV_FMT_F16 || c.kv_format == KV_FMT_MXFP8_EMU) {
-#ifndef VSTAR_LP_F16
-    if (c.kv_format != KV_FMT_F16) { set_error("kv_cache_format: the block-scaled fp8 KV cache needs the fp16 engine"); return VSTAR_ERR_INVALID; }
-#endif
-    RC(e->dalloc(&kcache, (size_t)layer_stride * c.layers));
-    RC(e->dalloc(&vcache, (size_t)layer_stride * c.layers));
-    kv_bytes = (int64_t)layer_stride * c.layers * 2 * 2;
-  } else {
-    set_error("kv_cache_format must be 0 (fp16), 1 (MX fp8) or 2 (MX fp8 emulated in fp16)");
-    return VSTAR_ERR_INVALID;
-  }
+  RC(kv.alloc(e, c.kv_format, c.layers, c.max_slots, c.heads, c.max_ctx));
   const size_t R = (size_t)c.max_rows;
   RC(e->dalloc(&lx, R * H));
   RC(e->dalloc(&lh, R * H));
@@ -273,7 +328,8 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&d_row_pos, R));
   RC(e->dalloc(&d_row_slot, R));
   RC(e->dalloc(&d_row_seq, R));
-  RC(e->dalloc(&d_seq, (size_t)3 * c.max_slots * 4));
+  RC(e->dalloc(&d_seq, (size_t)3 * seq_cap()));
+  kv_rows = KvRows{d_row_seq, d_row_pos, d_row_slot, seq_array(0), seq_array(1), seq_array(2), nullptr};
   RC(e->dalloc(&d_want, std::max(R, (size_t)max_want)));     // (the scoring tail wants up to max_rows rows)
   RC(e->dalloc(&d_starget, R));
   RC(e->dalloc(&d_srank, R));
@@ -515,8 +571,7 @@ inline int LlmCached::llm_layers_prefill(int nseq, int S) {
     const LlmBlock& b = (*blocks)[i];
     LCHK(rmsnorm_lp(lx, b.in_norm, lh, rows, H, c.rms_eps, nullptr, e->stream));
     RC(e->lin(lh, H, b.qkv, lqkv, 3 * H, rows));
-    LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kv_layer(kcache, i), kv_layer(vcache, i), slot_stride, c.max_ctx, rows,
-                        c.heads, e->stream, kv_fmt(i)));
+    LCHK(rope_kv_append(lqkv, rope, kv.layer(i), kv_rows, rows, e->stream));
     LCHK(attn_forward(lqkv, latt, nseq, S, c.heads, 128, 1, att_scale, e->stream));
     RC(e->lin(latt, H, b.o, lx, H, rows, VSTAR_EPI_NONE, lx, H));
     LCHK(rmsnorm_lp(lx, b.post_norm, lh, rows, H, c.rms_eps, nullptr, e->stream));
@@ -526,22 +581,19 @@ inline int LlmCached::llm_layers_prefill(int nseq, int S) {
   return 0;
 }
 
-inline int LlmCached::llm_layers_cached(int R, int nseq, int max_keys, bool single_rows, const int32_t* anc) {
+inline int LlmCached::llm_layers_cached(int R, int max_keys, bool single_rows, const int32_t* anc) {
   const LlmCachedCfg& c = cfg;
   const int H = c.hidden;
-  const int32_t *d_kv = d_seq, *d_prefix = d_seq + c.max_slots * 4, *d_past = d_seq + 2 * c.max_slots * 4;
-  (void)nseq;
+  KvRows rw = kv_rows;
+  rw.anc = anc;
   for (int i = 0; i < c.layers; ++i) {
     const LlmBlock& b = (*blocks)[i];
-    lp_t* kc = kv_layer(kcache, i);
-    lp_t* vc = kv_layer(vcache, i);
-    const KvFormat kvf = kv_fmt(i);
+    const KvLayer kl = kv.layer(i);
     const DecodeLayerW& dw = dec(i);
     RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, &dw.qkv));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
-    if (!single_rows) LCHK(rope_kv_append(lqkv, rope, d_row_pos, d_row_slot, kc, vc, slot_stride, c.max_ctx, R, c.heads, e->stream, kvf));
-    LCHK(cached_attention(lqkv, kc, vc, d_row_seq, d_row_pos, d_kv, d_prefix, d_past, single_rows ? rope : nullptr, latt, R,
-                          c.heads, c.max_ctx, slot_stride, max_keys, e->stream, split_ws, SPLIT_ROWS, anc, kvf));
+    if (!single_rows) LCHK(rope_kv_append(lqkv, rope, kl, rw, R, e->stream));
+    LCHK(cached_attention(lqkv, kl, rw, single_rows ? rope : nullptr, latt, R, max_keys, e->stream, split_ws, SPLIT_ROWS));
     RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.o));
     RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, &dw.gate_up));
     RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.down));
@@ -679,7 +731,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   const LlmCachedCfg& c = cfg;
   const int nseq = rw.nseq, n_want = rw.n_want;
   const int32_t *row_off = rw.row_off, *src = rw.src, *kv_slot = rw.kv_slot, *prefix_slot = rw.prefix_slot, *past_len = rw.past_len, *want = rw.want;
-  if (nseq <= 0 || nseq > c.max_slots * 4 || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
+  if (nseq <= 0 || nseq > seq_cap() || !row_off || !src || !kv_slot || !prefix_slot || !past_len || n_want < 0 ||
       (tail.kind != LlmTail::SCORE && n_want > max_want) || (n_want && !want)) {
     e->set_error("llm forward: bad argument");
     return VSTAR_ERR_INVALID;
@@ -750,12 +802,8 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
     }
   }
   for (int j = 0; j < n_want; ++j) h_want[j] = remap[want[j]];
-  std::vector<int32_t> h_seqmeta((size_t)3 * c.max_slots * 4, 0);
-  for (int i = 0; i < nseq; ++i) {
-    h_seqmeta[i] = kv_slot[i];
-    h_seqmeta[(size_t)c.max_slots * 4 + i] = prefix_slot[i];
-    h_seqmeta[(size_t)2 * c.max_slots * 4 + i] = past_len[i];
-  }
+  std::vector<int32_t> h_seqmeta((size_t)3 * seq_cap(), 0);
+  for (int i = 0; i < nseq; ++i) seq_set(h_seqmeta, i, kv_slot[i], prefix_slot[i], past_len[i]);
   LCHK(hipMemcpyAsync(d_src, h_src.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_row_pos, h_pos.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_row_slot, h_slot.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
@@ -777,7 +825,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, rows, c.hidden, e->stream));
   if (use_anc) LCHK(kv_anc_mark(d_row_slot, d_row_pos, rows, d_anc, c.max_ctx, e->stream));   // the new rows live in their own slot
   if (prefill) RC(llm_layers_prefill(nseq, maxT));
-  else RC(llm_layers_cached(rows, nseq, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
+  else RC(llm_layers_cached(rows, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
   // ---- head + tail, max_want wanted rows at a time: one pass, except for the scoring tail (CHUNKING RULE, LlmScoreArgs) ----
   for (int w0 = 0; w0 < n_want; w0 += max_want) {
     const int m = n_want - w0 < max_want ? n_want - w0 : max_want;
@@ -834,8 +882,7 @@ inline int LlmCached::kv_copy(int dst, int src, int lo, int hi) {
     return VSTAR_ERR_INVALID;
   }
   LCHK(hipSetDevice(e->device));
-  LCHK(kv_copy_rows(kcache, vcache, d_anc, dst, src, lo, hi, c.layers, c.heads, c.max_ctx, slot_stride, layer_stride, e->stream,
-                    kv_fmt(0)));
+  LCHK(kv_copy_rows(kv.l0, kv.layers, kv.layer_stride, d_anc, dst, src, lo, hi, e->stream));
   LCHK(kv_anc_fill(d_anc, dst, dst, 0, c.max_ctx, c.max_ctx, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
   anc_flag[dst] = 0;
@@ -865,11 +912,10 @@ inline int LlmCached::decode_step_body(int keys_bound) {
   const LlmCachedCfg& c = cfg;
   const int H = c.hidden;
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, 1, H, e->stream));
-  RC(llm_layers_cached(1, 1, keys_bound, true));
+  RC(llm_layers_cached(1, keys_bound, true));
   RC(head(0, 1));
   LCHK(argmax_rows_lp(logits, 1, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
-  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos,
-                     d_seq + 2 * c.max_slots * 4, d_dec, dec_cap);
+  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_dec, dec_cap);
   LCHK(hipGetLastError());
   return 0;
 }
@@ -907,8 +953,8 @@ inline int LlmCached::decode_greedy_graph(int32_t first_token, int past, int slo
   volatile int32_t* log = d_dec;
   const int keys_bound = c.max_ctx;                  // sizes the attention launch's LDS (4 B per key): fixed for the graph's lifetime
   // ---- per-call state of row 0 ----
-  std::vector<int32_t> seqmeta((size_t)3 * c.max_slots * 4, 0);
-  seqmeta[0] = slot; seqmeta[(size_t)c.max_slots * 4] = slot; seqmeta[(size_t)2 * c.max_slots * 4] = past;
+  std::vector<int32_t> seqmeta((size_t)3 * seq_cap(), 0);
+  seq_set(seqmeta, 0, slot, slot, past);
   const int32_t zero = 0, pos0 = past, slot0 = slot, tok0 = first_token;
   LCHK(hipMemcpyAsync(d_src, &tok0, 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_row_pos, &pos0, 4, hipMemcpyHostToDevice, e->stream));

@@ -627,7 +627,7 @@ int vstar_vqa_op_gemm_w4(const void* A, const void* Wq, const void* scale, const
 
 int vstar_vqa_kv_cache_format(const vstar_vqa_handle* h) { return h ? h->cfg.kv_cache_format : 0; }
 
-int64_t vstar_vqa_kv_cache_bytes(const vstar_vqa_handle* h) { return h && h->finalized ? h->run.kv_bytes : 0; }
+int64_t vstar_vqa_kv_cache_bytes(const vstar_vqa_handle* h) { return h && h->finalized ? h->run.kv.bytes : 0; }
 
 int vstar_vqa_op_kv_quantize(const void* dev_x_f16, int rows, void* dev_codes_u8, void* dev_scales_u8, void* dev_xhat_f16) {
   if (!dev_x_f16 || !dev_codes_u8 || !dev_scales_u8 || rows <= 0 || rows > (1 << 24)) {
@@ -648,37 +648,8 @@ static int64_t debug_read_kv(vstar_vqa_handle* h, const std::string& n, float* o
     h->set_error("debug_read: bad KV tensor name (kv:<layer>:<slot>, indices in range): " + n);
     return VSTAR_ERR_INVALID;
   }
-  const LlmCached& r = h->run;
-  const int64_t per = r.slot_stride;                       // elements of one slot of K (or V)
-  const int64_t cnt = std::min<int64_t>(2 * per, cap);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->set_error("debug_read: HIP failure"); return VSTAR_ERR_HIP; }
-  const int64_t off = (int64_t)layer * r.layer_stride + (int64_t)slot * per;
-  for (int which = 0; which < 2; ++which) {
-    const int64_t lo = which * per, m = std::min(per, cnt - lo);
-    if (m <= 0) break;
-    if (h->cfg.kv_cache_format == VSTAR_VQA_KVFMT_MXFP8) {
-      std::vector<uint8_t> codes((size_t)per), sc((size_t)per / 32);
-      if (hipMemcpy(codes.data(), (const uint8_t*)(which ? r.vcache : r.kcache) + off, codes.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(sc.data(), (which ? r.vscale : r.kscale) + off / 32, sc.size(), hipMemcpyDeviceToHost) != hipSuccess) {
-        h->set_error("debug_read: HIP failure");
-        return VSTAR_ERR_HIP;
-      }
-      for (int64_t i = 0; i < m; ++i) {                    // OCP e4m3: 1-4-3, bias 7, subnormals, 0x7f / 0xff = NaN
-        const uint8_t c = codes[(size_t)i];
-        const int ex = (c >> 3) & 15, mant = c & 7;
-        float v = ex == 15 && mant == 7 ? NAN : (ex ? ldexpf((float)(8 + mant), ex - 10) : ldexpf((float)mant, -9));
-        v = ldexpf(v, (int)sc[(size_t)(i >> 5)] - 127);
-        out[lo + i] = (c & 0x80) ? -v : v;
-      }
-    } else {
-      std::vector<lp_t> tmp((size_t)m);
-      if (hipMemcpy(tmp.data(), (which ? r.vcache : r.kcache) + off, (size_t)m * 2, hipMemcpyDeviceToHost) != hipSuccess) {
-        h->set_error("debug_read: HIP failure");
-        return VSTAR_ERR_HIP;
-      }
-      for (int64_t i = 0; i < m; ++i) out[lo + i] = lp2f(tmp[(size_t)i]);
-    }
-  }
+  const int64_t cnt = h->run.kv.read(layer, slot, out, cap, h->stream);
+  if (cnt < 0) { h->set_error("debug_read: HIP failure"); return VSTAR_ERR_HIP; }
   return cnt;
 }
 
