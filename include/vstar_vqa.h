@@ -249,6 +249,54 @@ int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h);
 int vstar_vqa_op_edit(void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok,
                       const float* penalty);
 
+/* Per-token log-probabilities and top-n alternatives: HF generate's output_scores / compute_transition_scores
+ * without a vocabulary row crossing to the host.  Behind the arg-max, the draw or the verify choice, on the logits row x that tail
+ * just read and the token t it just chose, per wanted row j:
+ *   lse              = max + log(sum exp(x_i - max)) in double, fixed summation order: vstar_vqa_forward_score's, bit for bit
+ *   token_logprob[j] = (float)(x[t] - lse), one rounding: the sign-flipped nll of vstar_vqa_forward_score for target t.  x[t] = -inf
+ *                      gives -inf, NaN logits give NaN, a row whose maximum is +inf gives NaN
+ *   token_rank[j]    = #{i : x_i > x[t]} (nullable; 0: t is the arg-max)
+ *   top_token / top_logprob [j, 0 .. n), n = min(n_top, llm_vocab): the n largest elements under (value descending, index
+ *                      ascending), in that order, compared by VALUE (-0 and +0 tie, the lower index first; a NaN sorts as -inf),
+ *                      top_logprob = (float)(x[i] - lse); entries [n, n_top) are -1 / NaN
+ *   a verify row behind the acceptance (tokens_out[j] = -1) is not read: token_logprob NaN, token_rank -1, top_token -1, top_logprob NaN
+ * With edits the row is the EDITED row: the log-probabilities are of the distribution the pick was made from.  Under sampling the
+ * row is the edited, UN-WARPED, temperature-1 row (HF's `scores` under sampling are the warped ones: a stated deviation). */
+#define VSTAR_VQA_MAX_TOP_LOGPROBS 32
+typedef struct vstar_vqa_logprobs {   /* all HOST arrays */
+  int32_t  n_top;          /* 0 .. 32 */
+  float*   token_logprob;  /* [n_want] */
+  int32_t* token_rank;     /* [n_want], nullable */
+  float*   top_logprob;    /* [n_want, n_top], null iff n_top == 0 */
+  int32_t* top_token;      /* [n_want, n_top], null iff n_top == 0 */
+} vstar_vqa_logprobs;
+
+/* vstar_vqa_forward_edits / _forward_sample_edits / _forward_verify_edits with the log-probability outputs; edits stays nullable,
+ * lp == NULL is the _edits call bit for bit.  Errors (VSTAR_ERR_INVALID, before any device work, the engine stays usable): n_top
+ * outside [0, 32], a missing token_logprob, top arrays that do not match n_top.  The device arrays for the outputs are allocated by
+ * the first call that asks (a failed allocation is VSTAR_ERR_NOMEM and leaves the engine usable); an engine that never asks allocates,
+ * launches and copies nothing for them.  The beam and scoring tails have no such entry: beam candidates carry their scores, the
+ * scoring tail returns the target's nll and rank. */
+int vstar_vqa_forward_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                               uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits,
+                               const vstar_vqa_logprobs* lp);
+int vstar_vqa_forward_sample_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src,
+                                      const int32_t* kv_slot, const int32_t* prefix_slot, const int32_t* past_len,
+                                      int n_want, const int32_t* want, const vstar_vqa_sampling* params, int32_t* tokens,
+                                      const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp);
+int vstar_vqa_forward_verify_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                      const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                      const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                      int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits,
+                                      const vstar_vqa_logprobs* lp);
+/* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22, rows <= 65535, any ld >=
+ * vocab); host tokens[rows] (a negative token: the row is not read) and outputs as above with n_want = rows; token_rank nullable,
+ * top_logprob / top_token null iff n_top == 0.  n_top outside [0, 32] or a token >= vocab is VSTAR_ERR_INVALID with a message, before
+ * any device work.  Null stream, synchronises. */
+int vstar_vqa_op_logprobs(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* tokens, int n_top,
+                          float* token_logprob, int32_t* token_rank, float* top_logprob, int32_t* top_token);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

@@ -2,6 +2,8 @@
 KV-cached decode steps at several batch sizes, forked option scoring.  Prints one JSON object.
 
   python tools/vqa_bench.py [--out profiles/r01_vqa_bench.json] [--layers 32] [--sample]
+--logprobs 0,5 runs `decode_logprobs` alone: greedy decode steps without and with the on-device log-probability stage (logprobs=0 /
+logprobs=5), alternated in blocks of --steps at the --batches sizes, and each mode's tokens/s over the plain one's.
 --sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
 sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio.
 --beams 1,2,4,8 adds `decode_beams`: beam-search steps of one prompt with k beams (forward_beam's select tail, the host scorer,
@@ -71,6 +73,8 @@ def main():
     ap.add_argument("--spec-corrupt", default="1.0,0.5,0.0", help="--spec: shares of corrupted draft positions")
     ap.add_argument("--rules", action="store_true", help="greedy decode steps with logits rules (repetition penalty + bigram ban over --ctx "
                     "history tokens) against plain ones, alternated blocks (runs alone)")
+    ap.add_argument("--logprobs", default="", help="comma-separated n (e.g. '0,5'): greedy decode steps without and with the on-device "
+                    "log-probability stage asking for n alternatives, alternated blocks (DESIGN.md 8.9; runs alone)")
     ap.add_argument("--spec-kernels", type=int, default=0, help="rows: the arg-max and verify tails alone, for a kernel trace")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
@@ -126,6 +130,10 @@ def main():
     long_rows = text[:10] + eng.feature_rows(0, True) + text[10:25] + eng.feature_rows(1, True) + eng.feature_rows(2, True) + text[25:]
     short_rows = text[:10] + eng.feature_rows(0, False) + text[10:25] + eng.feature_rows(1, True) + eng.feature_rows(2, True) + text[25:]
     plain_rows = text[:10] + eng.feature_rows(0, True) + text[10:]
+    if a.logprobs:
+        out["decode_logprobs"] = decode_logprobs(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds,
+                                                 [int(x) for x in a.logprobs.split(",")])
+        return finish(out, a)
     res = {}
     for name, rows in (("plain_296", plain_rows), ("objects_584", short_rows)):
         for B in (1, 8):
@@ -511,6 +519,40 @@ def decode_sample(eng, rows, batches, steps, rounds):
                          "tokens_per_s": round(B / w * 1e3, 1)}
         leg["sample_over_greedy_tokens_per_s"] = round(leg["sample"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
         leg["sample_minus_greedy_device_ms"] = round(leg["sample"]["device_ms_per_step"] - leg["greedy"]["device_ms_per_step"], 4)
+        res[f"B{B}"] = leg
+    return res
+
+
+def decode_logprobs(eng, rows, batches, steps, rounds, ns):
+    """Greedy decode steps of B sequences without (`off`) and with the log-probability stage (`n<k>`: logprobs=k),
+    alternated in blocks of `steps` (the same KV positions advance; the tokens are the same in every mode)."""
+    modes = ["off"] + [f"n{n}" for n in ns]
+    res = {}
+    for B in batches:
+        seqs = [Seq(rows, kv_slot=i) for i in range(B)]
+        _, nxt = eng.forward(seqs, [(i, -1) for i in range(B)], logits=False)
+        eng.forward(seqs, [(i, -1) for i in range(B)], logits=False, logprobs=max(ns))      # (the stage's buffers exist before the timing)
+        pos = len(rows)
+        want = [(i, 0) for i in range(B)]
+        dev = {m: [] for m in modes}
+        wall = {m: 0.0 for m in modes}
+        for r in range(rounds):
+            for m in modes:
+                t0 = time.time()
+                for s in range(steps):
+                    step = [Seq([int(nxt[i])], kv_slot=i, past_len=pos) for i in range(B)]
+                    nxt = eng.forward(step, want, logits=False, **({} if m == "off" else {"logprobs": int(m[1:])}))[1]
+                    dev[m].append(eng.last_forward_ms())
+                    pos += 1
+                wall[m] += time.time() - t0
+        leg = {}
+        for m in modes:
+            w = wall[m] / (rounds * steps) * 1e3
+            leg[m] = {"device_ms_per_step": round(float(np.median(dev[m])), 3), "wall_ms_per_step": round(w, 3),
+                      "tokens_per_s": round(B / w * 1e3, 1)}
+        for m in modes[1:]:
+            leg[m]["over_off_tokens_per_s"] = round(leg[m]["tokens_per_s"] / leg["off"]["tokens_per_s"], 4)
+            leg[m]["minus_off_device_ms"] = round(leg[m]["device_ms_per_step"] - leg["off"]["device_ms_per_step"], 4)
         res[f"B{B}"] = leg
     return res
 

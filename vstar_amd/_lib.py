@@ -43,6 +43,7 @@ EXPORTS_VQA = [
     "vstar_vqa_forward_verify", "vstar_vqa_op_verify",
     "vstar_vqa_forward_edits", "vstar_vqa_forward_sample_edits", "vstar_vqa_forward_verify_edits", "vstar_vqa_op_edit",
     "vstar_vqa_logit_edit_capacity",
+    "vstar_vqa_forward_logprobs", "vstar_vqa_forward_sample_logprobs", "vstar_vqa_forward_verify_logprobs", "vstar_vqa_op_logprobs",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -83,6 +84,20 @@ class VqaLogitEdits(ctypes.Structure):
         ("off", c_void_p),
         ("tok", c_void_p),
         ("penalty", c_void_p),
+    ]
+
+
+MAX_TOP_LOGPROBS = 32       # VSTAR_VQA_MAX_TOP_LOGPROBS
+
+
+class VqaLogprobs(ctypes.Structure):
+    """vstar_vqa_logprobs (include/vstar_vqa.h): n_top and the four host output arrays of one call's log-probabilities."""
+    _fields_ = [
+        ("n_top", c_int32),
+        ("token_logprob", c_void_p),
+        ("token_rank", c_void_p),
+        ("top_logprob", c_void_p),
+        ("top_token", c_void_p),
     ]
 
 
@@ -270,6 +285,15 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_edit.restype = c_int
     lib.vstar_vqa_logit_edit_capacity.argtypes = [H]
     lib.vstar_vqa_logit_edit_capacity.restype = c_int64
+    lib.vstar_vqa_forward_logprobs.argtypes = lib.vstar_vqa_forward_edits.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_logprobs.restype = c_int
+    lib.vstar_vqa_forward_sample_logprobs.argtypes = lib.vstar_vqa_forward_sample_edits.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_sample_logprobs.restype = c_int
+    lib.vstar_vqa_forward_verify_logprobs.argtypes = lib.vstar_vqa_forward_verify_edits.argtypes + [c_void_p]
+    lib.vstar_vqa_forward_verify_logprobs.restype = c_int
+    lib.vstar_vqa_op_logprobs.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]
+    lib.vstar_vqa_op_logprobs.restype = c_int
     lib.vstar_vqa_op_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float]
     lib.vstar_vqa_op_gemm.restype = c_int

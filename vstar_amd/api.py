@@ -245,7 +245,8 @@ class LlavaSearchModel:
                  stopping_criteria=None, top_k=50, seed=None, length_penalty: float = 1.0, early_stopping=False,
                  num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None, allowed_tokens_fn=None,
-                 prefix_allowed_tokens_fn=None, **unused):
+                 prefix_allowed_tokens_fn=None, return_dict_in_generate: bool = False, output_scores: bool = False, top_logprobs=None,
+                 **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
@@ -259,10 +260,18 @@ class LlavaSearchModel:
         (repetition_penalty <= 0 raises ValueError).  The history the rules see is the text of input_ids — the <image> /
         <object> placeholders left out — plus the generated tokens; allowed_tokens_fn(batch_id, history ids) gets that list.
         At their defaults no edits are built.  With num_beams > 1 an active rule raises NotImplementedError: HF applies the
-        processors to the log-softmax output in beam search, with the log-sum-exp of the unedited row."""
+        processors to the log-softmax output in beam search, with the log-sum-exp of the unedited row.
+        return_dict_in_generate=True: a SimpleNamespace with `sequences` (the tensor otherwise returned; without the flag the
+        return is that tensor, as in HF).  With output_scores=True (and top_logprobs = n in [0, 32], default 0) it also carries,
+        computed on the device, `transition_scores` fp32 [1, T] — the log-probability of each of the T generated
+        tokens, for greedy decode HF's compute_transition_scores(normalize_logits=True); under sampling the log-probability under
+        the edited, un-warped, temperature-1 distribution, where HF's are the warped ones — `token_ranks` int32 [1, T] (0: the
+        token is the arg-max), `top_tokens` int32 / `top_logprobs` fp32 [1, T, n], the n most likely tokens of each step, and
+        `scores` = None: the full vocabulary rows HF returns there deliberately do not cross to the host.  num_beams > 1 with
+        output_scores raises NotImplementedError (beam hypotheses carry their own scores; exposing those is a follow-up)."""
         from .logits import BEAM_RULES_MESSAGE, rules_from_kwargs
         from .vqa import check_spec_tokens, resolve_seed, sampling_params
-        from .vqa_engine import Seq
+        from .vqa_engine import Seq, check_logprobs
         if allowed_tokens_fn is not None and prefix_allowed_tokens_fn is not None:
             raise ValueError("pass allowed_tokens_fn or prefix_allowed_tokens_fn, not both")
         rules = rules_from_kwargs(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens,
@@ -282,22 +291,41 @@ class LlavaSearchModel:
         spec = check_spec_tokens(prompt_lookup_num_tokens or 0)
         if spec and num_beams > 1:
             raise ValueError("prompt_lookup_num_tokens > 0 cannot be combined with beam search (num_beams > 1)")
+        n_top = check_logprobs(top_logprobs)
+        lp = (n_top or 0) if return_dict_in_generate and (output_scores or n_top is not None) else None
+        if lp is not None and num_beams > 1:
+            raise NotImplementedError("output_scores with beam search (num_beams > 1) is not implemented: beam hypotheses carry "
+                                      "their own scores, and exposing those is a follow-up")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
         text = [[t for t in ids if t >= 0]]
+
+        def result(news, rec=None):
+            seqs = torch.tensor([ids + o for o in news], dtype=torch.long)
+            if not return_dict_in_generate:
+                return seqs
+            out = SimpleNamespace(sequences=seqs)
+            if rec is not None:
+                out.scores = None
+                out.transition_scores = torch.from_numpy(rec.token_logprob.copy())[None]
+                out.token_ranks = torch.from_numpy(rec.rank.copy())[None]
+                out.top_tokens = torch.from_numpy(rec.top_token.copy())[None]
+                out.top_logprobs = torch.from_numpy(rec.top_logprob.copy())[None]
+            return out
+
+        def one(res):       # a decode loop's result for the one sequence: (ids, record or None)
+            return ([res[0][0]], res[1][0]) if lp is not None else ([res[0]], None)
+
         if spec:
             p = [sampling_params(temperature, top_k, top_p, resolve_seed(seed))] if do_sample else None
-            new = self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], text, max_new_tokens, spec, p, draft_fn, rules)[0]
-            return torch.tensor([ids + new], dtype=torch.long)
+            return result(*one(self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], text, max_new_tokens, spec, p, draft_fn,
+                                                            rules, logprobs=lp)))
         if num_beams > 1:
-            outs = self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
-                                         early_stopping, num_return_sequences)[0]
-            return torch.tensor([ids + o for o in outs], dtype=torch.long)
+            return result(self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
+                                                early_stopping, num_return_sequences)[0])
         if do_sample:
             p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
-            new = self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text)[0]
-        else:
-            new = self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text)[0]
-        return torch.tensor([ids + new], dtype=torch.long)
+            return result(*one(self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text, logprobs=lp)))
+        return result(*one(self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text, logprobs=lp)))
 
 
 def load_pretrained_model(model_path, model_base=None, model_name: str = "", load_8bit: bool = False, load_4bit: bool = False,

@@ -153,6 +153,17 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
         spec_kw["repetition_penalty"] = theta
     if ngram:
         spec_kw["no_repeat_ngram_size"] = ngram
+    # `--vqa-logprobs N`: the free-form pass also records each answer's per-token log-probabilities and N alternatives
+    n_lp = getattr(args, "vqa_logprobs", None)
+    if n_lp is not None:
+        spec_kw["logprobs"] = int(n_lp)
+
+    def confidence(i):      # sample i of the free-form call just made, as JSON values
+        rec = vqa_llm.generated_logprobs[i]
+        lp = [float(v) for v in rec.token_logprob]
+        return {"mean_token_logprob": float(np.mean(lp)) if lp else None, "token_ids": [int(t) for t in vqa_llm.generated_ids[i]],
+                "token_logprob": lp, "token_rank": rec.rank.tolist(), "top_tokens": rec.top_token.tolist(),
+                "top_logprobs": [[float(v) for v in row] for row in rec.top_logprob]}
     max_found = getattr(args, "max_found_objects", None)        # (tests: tiny engines hold few object crops)
     entries = []
     for split in ("direct_attributes", "relative_position"):
@@ -164,7 +175,7 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
             if vqa_batch == 1:
                 square, _, _ = expand2square_centered(Image.open(path).convert("RGB"), mean_color)
                 prediction = vqa_llm.free_form_inference(square, ann["question"], **spec_kw)
-            entries.append({"split": split, "image_file": image_file, "path": path, "question": ann["question"], "options": ann["options"],
+            entries.append({**({"logprobs": confidence(0)} if n_lp is not None and vqa_batch == 1 else {}), "split": split, "image_file": image_file, "path": path, "question": ann["question"], "options": ann["options"],
                             "prediction": prediction, "missing": parse_missing_objects(prediction) if vqa_batch == 1 else None})
     # pass 1, batched: free_form_batch takes one KV slot and one feature slot per question, so its chunks are capped by the engine
     cfg = getattr(vqa_llm, "cfg", None)
@@ -172,8 +183,10 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     for k in range(0, len(entries) if vqa_batch > 1 else 0, ff_batch):
         chunk = entries[k:k + ff_batch]
         squares = [expand2square_centered(Image.open(e["path"]).convert("RGB"), mean_color)[0] for e in chunk]
-        for e, prediction in zip(chunk, vqa_llm.free_form_batch([dict(image=im, question=e["question"]) for im, e in zip(squares, chunk)], **spec_kw)):
+        for i, (e, prediction) in enumerate(zip(chunk, vqa_llm.free_form_batch([dict(image=im, question=e["question"]) for im, e in zip(squares, chunk)], **spec_kw))):
             e["prediction"], e["missing"] = prediction, parse_missing_objects(prediction)
+            if n_lp is not None:
+                e["logprobs"] = confidence(i)
     todo = [e for e in entries if e["missing"]]
     if window == 1:
         founds = [search_objects(vsm, e["path"], e["missing"], args) for e in todo]
@@ -206,7 +219,8 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
             everything.append(correct)
             results[split].append({"question": question, "options": options, "image": e["image_file"],
                                    "prediction_freeform": e["prediction"], "missing_objects": missing, "search_result": found,
-                                   "option_chosen": chosen, "correct": correct})
+                                   "option_chosen": chosen, "correct": correct,
+                                   **({"freeform_logprobs": e["logprobs"]} if n_lp is not None else {})})
         if rank == 0:
             print(split, np.mean(per_type[split]))
     if rank == 0:

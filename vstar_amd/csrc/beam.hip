@@ -19,6 +19,7 @@
 #include <cmath>
 #include "beam.hpp"
 #include "row_lse.hpp"
+#include "row_select.hpp"
 
 namespace {
 
@@ -26,6 +27,8 @@ using rowlse::bits2f;
 using rowlse::CACHE;                   // rows up to this length stay in LDS (64 KiB)
 using rowlse::THREADS;
 using rowlse::WAVES;
+using rowsel::block_scan;
+using rowsel::select_bin;
 constexpr int MAX_VOCAB = 1 << 22;
 constexpr int MERGE_THREADS = VSTAR_BEAM_MAX_K * VSTAR_BEAM_MAX_CAND;
 
@@ -64,53 +67,6 @@ template <bool BF16> __device__ __forceinline__ uint32_t lp_key(uint32_t x, doub
 }
 template <bool BF16> __device__ __forceinline__ float key_lp(uint32_t key) {
   return bits2f<BF16>((key & 0x8000u) ? (key & 0x7fffu) : (~key & 0xffffu));
-}
-
-// exclusive prefix of v in thread order, and the block total
-template <typename Sm> __device__ __forceinline__ void block_scan(Sm& sm, uint32_t v, uint32_t& excl, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t n = __shfl_up(inc, o, 64); if (lane >= o) inc += n; }
-  if (lane == 63) sm.wu[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < WAVES; ++w) { const uint32_t x = sm.wu[w]; base += w < wave ? x : 0; tot += x; }
-  __syncthreads();
-  excl = base + inc - v;
-  total = tot;
-}
-
-// The bin b of sm.hist with above(b) < need <= above(b) + hist[b] (above(b) = the count in the bins > b).  Wave 0 scans;
-// the histogram is cleared for the next select.
-template <typename Sm> __device__ __forceinline__ void select_bin(Sm& sm, uint32_t need, int& bin, uint32_t& above) {
-  __syncthreads();                                   // histogram complete
-  if (threadIdx.x < 64) {
-    const int l = threadIdx.x;
-    uint32_t h[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { h[j] = sm.hist[4 * l + j]; s += h[j]; }
-    uint32_t suf = s;                                // sum over lanes >= l
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t n = __shfl_down(suf, o, 64); if (l + o < 64) suf += n; }
-    uint32_t a = suf - s;
-    int found = -1;
-    uint32_t fa = 0;
-#pragma unroll
-    for (int j = 3; j >= 0; --j) {
-      if (a < need && need <= a + h[j]) { found = 4 * l + j; fa = a; }
-      a += h[j];
-    }
-    const uint64_t any = __ballot(found >= 0);
-    if (found >= 0) { sm.sel = found; sm.sel_above = fa; }
-    if (l == 0 && !any) sm.sel = -1;
-  }
-  __syncthreads();
-  bin = sm.sel;
-  above = sm.sel_above;
-  __syncthreads();
-  if (threadIdx.x < 256) sm.hist[threadIdx.x] = 0;
-  __syncthreads();
 }
 
 template <bool BF16, bool CACHED>

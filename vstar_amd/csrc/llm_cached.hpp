@@ -70,6 +70,18 @@ struct LlmEdits {
   const float* penalty = nullptr;
 };
 
+// The log-probability stage of forward() (logprob.hip): host arrays.  Behind an ARGMAX, SAMPLE or VERIFY tail, on
+// the logits rows that tail just read (the EDITED rows when the call carries edits) and the tokens it just chose: per wanted row j
+// the chosen token's log-probability lp_out[j] and rank rank_out[j] (nullable), and the n_top (0 .. 32) best alternatives
+// top_tok_out / top_lp_out [n_want, n_top] (null iff n_top == 0).  A verify row behind the acceptance (token -1) gives NaN / -1.
+struct LlmLogprobArgs {
+  int n_top = 0;
+  float* lp_out = nullptr;
+  int32_t* rank_out = nullptr;
+  float* top_lp_out = nullptr;
+  int32_t* top_tok_out = nullptr;
+};
+
 struct LlmCached;
 
 // What forward() does with the wanted rows' logits: exactly one of the five tails, built by the function of its name — so a call
@@ -81,8 +93,10 @@ struct LlmTail {
   static LlmTail beam_select(const LlmBeamArgs& b, uint16_t* logits_out) { LlmTail t; t.kind = BEAM; t.beam = b; t.logits_out = logits_out; return t; }
   static LlmTail score_rows(const LlmScoreArgs& sc) { LlmTail t; t.kind = SCORE; t.score = sc; return t; }
   static LlmTail verify_rows(const LlmVerifyArgs& v, const vstar_vqa_sampling* params) { LlmTail t; t.kind = VERIFY; t.verify = v; t.params = params; return t; }
+  // the tail with the log-probability stage behind it (null: the tail as it is); refused on BEAM and SCORE by tail_check
+  LlmTail with_logprobs(const LlmLogprobArgs* lp) const { LlmTail t = *this; t.has_lp = lp != nullptr; if (lp) t.lp = *lp; return t; }
 
- private:      // only the five functions above fill these, only LlmCached reads them
+ private:      // only the functions above fill these, only LlmCached reads them
   friend struct LlmCached;
   LlmTail() = default;
   Kind kind = ARGMAX;
@@ -90,6 +104,8 @@ struct LlmTail {
   int32_t* tokens_out = nullptr;                 // ARGMAX (nullable): the arg-max; SAMPLE: the drawn tokens (sample.hip)
   const vstar_vqa_sampling* params = nullptr;    // SAMPLE; VERIFY (nullable: greedy): one record per wanted row
   LlmBeamArgs beam; LlmScoreArgs score; LlmVerifyArgs verify;      // the kind's own host arrays
+  bool has_lp = false;                           // ARGMAX, SAMPLE, VERIFY: the log-probability stage runs behind the tail
+  LlmLogprobArgs lp;
 };
 
 struct LlmCachedCfg {
@@ -226,6 +242,9 @@ struct LlmCached {
   int32_t *d_eoff = nullptr, *d_etok = nullptr;  // [3 max_want + 1] offsets, [edit_capacity()] ids
   float* d_epen = nullptr;                       // [max_want]
   int64_t edit_capacity() const { return (int64_t)max_want * (cfg.max_ctx + 2048); }     // ids of one call, the three lists of all rows together
+  // ---- log-probabilities: allocated by the first forward() that asks for them, never by an engine that does not ----
+  float *d_lp = nullptr, *d_lp_top = nullptr;    // [max_want], [max_want, 32] (row stride: the call's n_top)
+  int32_t *d_lp_rank = nullptr, *d_lp_tok = nullptr;
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   char* split_ws = nullptr;
   // ---- beam search ----
@@ -291,6 +310,7 @@ struct LlmCached {
   int head(int w0, int m);
   int tail_check(const LlmRows& r, const LlmTail& t);
   int edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed);
+  int logprobs_check(const LlmRows& r, const LlmTail& t);
   std::array<TailCopy, 5> tail_copies(const LlmTail& t, int n_want);
   int tail_launch(const LlmTail& t, int w0, int m);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
@@ -680,6 +700,37 @@ inline int LlmCached::edits_check(const LlmRows& r, const LlmTail& t, const LlmE
   return 0;
 }
 
+// The log-probability stage of a call, validated behind its tail and edits and before any device work; its device arrays are
+// allocated here, by the first call that asks.
+inline int LlmCached::logprobs_check(const LlmRows& r, const LlmTail& t) {
+  if (t.kind == LlmTail::BEAM) {
+    e->set_error("log-probabilities with the beam tail are not supported: the beam candidates already carry their scores");
+    return VSTAR_ERR_INVALID;
+  }
+  if (t.kind == LlmTail::SCORE) {
+    e->set_error("log-probabilities with the scoring tail are not supported: it already returns the target's nll and rank");
+    return VSTAR_ERR_INVALID;
+  }
+  const LlmLogprobArgs& a = t.lp;
+  if (r.n_want < 1 || !a.lp_out) { e->set_error("logprobs: no wanted rows / token_logprob output"); return VSTAR_ERR_INVALID; }
+  if (const char* m = vstar_logprob_check(r.n_want, cfg.vocab, nullptr, a.n_top)) { e->set_error(m); return VSTAR_ERR_INVALID; }
+  if ((a.n_top > 0) != (a.top_lp_out && a.top_tok_out) || (a.n_top == 0 && (a.top_lp_out || a.top_tok_out))) {
+    e->set_error("logprobs: top_logprob and top_token are required with n_top > 0 and must be null with n_top == 0");
+    return VSTAR_ERR_INVALID;
+  }
+  if (!d_lp) {        // one block: a failed allocation leaves nothing behind and the engine as it was
+    const size_t W = (size_t)max_want, n_words = 2 * W + 2 * W * VSTAR_LOGPROB_MAX_TOP;
+    int32_t* blk = nullptr;
+    const int rc = e->dalloc(&blk, n_words);
+    if (rc) { (void)hipGetLastError(); return rc; }
+    d_lp = (float*)blk;
+    d_lp_rank = blk + W;
+    d_lp_top = (float*)(blk + 2 * W);
+    d_lp_tok = blk + 2 * W + W * VSTAR_LOGPROB_MAX_TOP;
+  }
+  return 0;
+}
+
 // A tail's copies, in stream order: uploads (`in`, host -> dev) go out with the row metadata before the layers, downloads (dev ->
 // `out`, host) behind the tail.  An entry whose host pointer is null (an output the caller did not ask for, greedy verify's
 // params, the unused entries of the array) or that has zero bytes is no copy.
@@ -756,6 +807,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
     if (want[j] < 0 || want[j] >= R) { e->set_error("want row out of range"); return VSTAR_ERR_INVALID; }
   RC(tail_check(rw, tail));
   if (edits) RC(edits_check(rw, tail, *edits));
+  if (tail.has_lp) RC(logprobs_check(rw, tail));
   // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
   bool use_anc = false;
   for (int i = 0; i < nseq; ++i) {
@@ -832,6 +884,9 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
     RC(head(w0, m));
     if (edits) LCHK(vstar_edit_rows_lp(logits, m, c.vocab, (int64_t)vpad(), d_eoff + 3 * w0, d_etok, d_epen + w0, e->stream));
     RC(tail_launch(tail, w0, m));
+    if (tail.has_lp)      // (one chunk: w0 == 0) the row the tail just read, the token it just chose
+      LCHK(vstar_logprob_rows_lp(logits, m, c.vocab, (int64_t)vpad(), tail.kind == LlmTail::VERIFY ? d_vtok : d_argmax, tail.lp.n_top, d_lp,
+                                 tail.lp.rank_out ? d_lp_rank : nullptr, d_lp_top, d_lp_tok, e->stream));
   }
   LCHK(hipEventRecord(ev1, e->stream));
   if (n_want && tail.logits_out)
@@ -839,6 +894,16 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
                             hipMemcpyDeviceToHost, e->stream));
   for (const TailCopy& x : copies)
     if (x.out && x.bytes) LCHK(hipMemcpyAsync(x.out, x.dev, x.bytes, hipMemcpyDeviceToHost, e->stream));
+  if (tail.has_lp) {
+    const LlmLogprobArgs& a = tail.lp;
+    const size_t nt4 = (size_t)n_want * a.n_top * 4;
+    LCHK(hipMemcpyAsync(a.lp_out, d_lp, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+    if (a.rank_out) LCHK(hipMemcpyAsync(a.rank_out, d_lp_rank, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+    if (nt4) {
+      LCHK(hipMemcpyAsync(a.top_lp_out, d_lp_top, nt4, hipMemcpyDeviceToHost, e->stream));
+      LCHK(hipMemcpyAsync(a.top_tok_out, d_lp_tok, nt4, hipMemcpyDeviceToHost, e->stream));
+    }
+  }
   LCHK(hipStreamSynchronize(e->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) last_ms = ms;

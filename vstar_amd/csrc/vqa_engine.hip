@@ -339,10 +339,24 @@ static const LlmEdits* edits_of(const vstar_vqa_logit_edits* ed, LlmEdits* out) 
 int vstar_vqa_forward_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                             uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits) {
+  return vstar_vqa_forward_logprobs(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, argmax, edits, nullptr);
+}
+
+// the three forms with the log-probability stage behind the tail; the _edits entries pass NULL
+static const LlmLogprobArgs* logprobs_of(const vstar_vqa_logprobs* lp, LlmLogprobArgs* out) {
+  if (!lp) return nullptr;
+  *out = LlmLogprobArgs{lp->n_top, lp->token_logprob, lp->token_rank, lp->top_logprob, lp->top_token};
+  return out;
+}
+
+int vstar_vqa_forward_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                               const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                               uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   LlmEdits ed;
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::argmax(logits_f16, argmax),
-                        edits_of(edits, &ed));
+  LlmLogprobArgs la;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
+                        LlmTail::argmax(logits_f16, argmax).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
 int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
@@ -354,11 +368,19 @@ int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_o
 int vstar_vqa_forward_sample_edits(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                                    const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                                    const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_logit_edits* edits) {
+  return vstar_vqa_forward_sample_logprobs(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, tokens, edits, nullptr);
+}
+
+int vstar_vqa_forward_sample_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                      const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                      const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_logit_edits* edits,
+                                      const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
   LlmEdits ed;
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::sample(params, tokens),
-                        edits_of(edits, &ed));
+  LlmLogprobArgs la;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
+                        LlmTail::sample(params, tokens).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
 int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
@@ -395,6 +417,15 @@ int vstar_vqa_forward_verify_edits(vstar_vqa_handle* h, int nseq, const int32_t*
                                    const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                                    const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
                                    int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits) {
+  return vstar_vqa_forward_verify_logprobs(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, group_off, n_groups,
+                                           draft, n_accept_out, tokens_out, edits, nullptr);
+}
+
+int vstar_vqa_forward_verify_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                      const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                      const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                      int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits,
+                                      const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   if (!group_off || !draft || !n_accept_out || !tokens_out) {
     h->set_error("forward_verify: group_off, draft and the outputs are required");
@@ -402,8 +433,9 @@ int vstar_vqa_forward_verify_edits(vstar_vqa_handle* h, int nseq, const int32_t*
   }
   const LlmVerifyArgs v{n_groups, group_off, draft, n_accept_out, tokens_out};
   LlmEdits ed;
-  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::verify_rows(v, params),
-                        edits_of(edits, &ed));
+  LlmLogprobArgs la;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
+                        LlmTail::verify_rows(v, params).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
 int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h) { return h ? h->run.edit_capacity() : 0; }
@@ -538,6 +570,34 @@ int vstar_vqa_op_edit(void* dev_logits, int dtype, int rows, int vocab, int64_t 
   d_pen.upload(penalty);
   op_launch(e, dtype, vstar_edit_rows_f16, vstar_edit_rows_bf16, (uint16_t*)dev_logits, rows, vocab, ld, d_off, d_tok, d_pen, nullptr);
   return op_result(e, "vstar_vqa_op_edit");
+}
+
+int vstar_vqa_op_logprobs(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* tokens, int n_top,
+                          float* token_logprob, int32_t* token_rank, float* top_logprob, int32_t* top_token) {
+  if (!dev_logits || !tokens || !token_logprob || rows > 65535 || ld < vocab || (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
+    tls_error() = "vstar_vqa_op_logprobs: bad argument";
+    return VSTAR_ERR_INVALID;
+  }
+  if (const char* m = vstar_logprob_check(rows, vocab, tokens, n_top)) {
+    tls_error() = std::string("vstar_vqa_op_logprobs: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
+  if (n_top > 0 ? (!top_logprob || !top_token) : (top_logprob || top_token)) {
+    tls_error() = "vstar_vqa_op_logprobs: top_logprob and top_token are required with n_top > 0 and must be null with n_top == 0";
+    return VSTAR_ERR_INVALID;
+  }
+  hipError_t e = hipSuccess;
+  const size_t nt = (size_t)rows * n_top;
+  OpBuf<int32_t> d_t(e, rows), d_r(e, rows, token_rank != nullptr), d_tt(e, nt, nt != 0);
+  OpBuf<float> d_l(e, rows), d_tl(e, nt, nt != 0);
+  d_t.upload(tokens);
+  op_launch(e, dtype, vstar_logprob_rows_f16, vstar_logprob_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_t, n_top, d_l, d_r,
+            d_tl, d_tt, nullptr);
+  d_l.download(token_logprob);
+  d_r.download(token_rank);
+  d_tl.download(top_logprob);
+  d_tt.download(top_token);
+  return op_result(e, "vstar_vqa_op_logprobs");
 }
 
 int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +19,35 @@ _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF
 
 def _ptr(a: Optional[np.ndarray]):
     return ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+class TokenLogprobs(NamedTuple):
+    """The log-probability record of a call with `logprobs=n` (csrc/logprob.hip), one entry per wanted row: of the
+    token the tail chose its log-probability and rank (0: it is the arg-max), and the n most likely tokens with theirs, sorted by
+    (log-probability descending, token id ascending).  A verify row behind the acceptance holds NaN / -1."""
+    token_logprob: np.ndarray    # float32 [n_want]
+    rank: np.ndarray             # int32 [n_want]
+    top_token: np.ndarray        # int32 [n_want, n]
+    top_logprob: np.ndarray      # float32 [n_want, n]
+
+    @staticmethod
+    def concat(parts: Sequence["TokenLogprobs"], n: int) -> "TokenLogprobs":
+        """The records of consecutive steps as one (an empty record of width n for no steps)."""
+        if not parts:
+            return TokenLogprobs(np.empty(0, np.float32), np.empty(0, np.int32), np.empty((0, n), np.int32), np.empty((0, n), np.float32))
+        return TokenLogprobs(*(np.concatenate([p[k] for p in parts]) for k in range(4)))
+
+    def rows(self, idx) -> "TokenLogprobs":
+        return TokenLogprobs(*(a[idx] for a in self))
+
+
+def check_logprobs(n) -> Optional[int]:
+    """`logprobs=None | n`: None, or the number of alternatives as an int in [0, 32] (ValueError otherwise)."""
+    if n is None:
+        return None
+    if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= _lib.MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be None or an integer in [0, {_lib.MAX_TOP_LOGPROBS}], got {n!r}")
+    return int(n)
 
 
 @dataclass
@@ -148,19 +177,37 @@ class VqaEngine:
         st = _lib.VqaLogitEdits(off.ctypes.data, tok.ctypes.data if tok.size else None, pen.ctypes.data)
         return st, (off, tok, pen)
 
+    @staticmethod
+    def _logprobs_struct(n: int, nw: int):
+        """The vstar_vqa_logprobs record of a call that asks for n alternatives on nw wanted rows, and the host arrays behind it."""
+        m = max(nw, 1)
+        lp, rk = np.empty(m, np.float32), np.empty(m, np.int32)
+        tt, tl = np.empty((m, n), np.int32), np.empty((m, n), np.float32)
+        st = _lib.VqaLogprobs(n, lp.ctypes.data, rk.ctypes.data, tl.ctypes.data if n else None, tt.ctypes.data if n else None)
+        return st, TokenLogprobs(lp[:nw], rk[:nw], tt[:nw], tl[:nw])
+
     def logit_edit_capacity(self) -> int:
         """The most token ids (the three lists of all wanted rows together) one call with edits may carry."""
         return int(self.lib.vstar_vqa_logit_edit_capacity(self.handle))
 
-    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True, edits=None):
+    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True, edits=None, logprobs=None):
         """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
         edits: None, or the packed arrays of `LogitRules.pack` (one plan per wanted row): the logits are edited on the device
         ahead of the arg-max (csrc/edit.hip) and the returned logits are the edited ones (HF's `scores`).
-        Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want])."""
+        logprobs: None, or n in [0, 32]: the arg-max's log-probability and rank and the n best alternatives of every wanted row,
+        computed on the device from the (edited) row the arg-max was taken from (csrc/logprob.hip).
+        Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want]), with logprobs one more value, a `TokenLogprobs`."""
+        n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
         out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if (logits and nw) else None
         out_arg = np.empty((max(nw, 1),), np.int32)
+        if n_lp is not None:
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_logprobs(self.handle, *args, _ptr(out_logits), _ptr(out_arg),
+                                                               ctypes.byref(st) if st is not None else None, ctypes.byref(lp)), self.handle)
+            return out_logits, out_arg[:nw], rec
         if edits is None:
             _lib.check_vqa(self.lib.vstar_vqa_forward(self.handle, *args, _ptr(out_logits), _ptr(out_arg)), self.handle)
         else:
@@ -169,14 +216,23 @@ class VqaEngine:
                            self.handle)
         return out_logits, out_arg[:nw]
 
-    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None) -> np.ndarray:
+    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None, logprobs=None):
         """`forward` with the arg-max replaced by the on-device sampling tail (csrc/sample.hip): `params` holds one
         `_lib.VqaSampling` per wanted row (or one record for all of them); edits as in `forward` (the draw sees the edited
-        logits).  Returns the drawn tokens, int32 [n_want]; the logits never leave the device."""
+        logits).  logprobs as in `forward`, of the drawn token — under the edited, UN-WARPED, temperature-1 distribution (DESIGN.md
+        §8.9).  Returns the drawn tokens, int32 [n_want], with logprobs (tokens, `TokenLogprobs`); the logits never leave the device."""
+        n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
         prm = self._sampling_array(params, nw)
         out = np.empty((max(nw, 1),), np.int32)
+        if n_lp is not None:
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_sample_logprobs(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out),
+                                                                      ctypes.byref(st) if st is not None else None, ctypes.byref(lp)),
+                           self.handle)
+            return out[:nw], rec
         if edits is None:
             _lib.check_vqa(self.lib.vstar_vqa_forward_sample(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out)),
                            self.handle)
@@ -219,13 +275,16 @@ class VqaEngine:
         _lib.check_vqa(self.lib.vstar_vqa_forward_score(self.handle, *args, _ptr(tg), _ptr(nll), _ptr(rk)), self.handle)
         return (nll[:nw], rk[:nw]) if rank else nll[:nw]
 
-    def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None, edits=None):
+    def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None, edits=None,
+                       logprobs=None):
         """`forward` with the arg-max replaced by the on-device verify tail of speculative decoding (csrc/spec.hip, DESIGN.md
         §8.5): wanted rows groups[g] .. groups[g+1]-1 are the rows of one sequence in position order (its current token and the
         drafts fed behind it), draft[j] the token wanted row j's choice is compared with (-1 on a group's last row).  params:
         None = greedy, else one `_lib.VqaSampling` per wanted row (or one record for all).  edits as in `forward`: every row's
         choice sees its edited logits.  Returns (n_accept int32 [n_groups], tokens int32 [n_want]): per group the accepted drafts
-        and one more token, -1 behind them."""
+        and one more token, -1 behind them.  logprobs as in `forward`, of every row's token (NaN / -1 on the -1 rows): one more
+        returned value, a `TokenLogprobs`."""
+        n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(step, wanted)
         nw = args[6]
         go = np.ascontiguousarray(groups, np.int32)
@@ -235,6 +294,12 @@ class VqaEngine:
         acc = np.empty((max(ng, 1),), np.int32)
         tok = np.empty((max(nw, 1),), np.int32)
         tail = (ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None, _ptr(go), ng, _ptr(dr), _ptr(acc), _ptr(tok))
+        if n_lp is not None:
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_verify_logprobs(self.handle, *args, *tail, ctypes.byref(st) if st is not None else None,
+                                                                      ctypes.byref(lp)), self.handle)
+            return acc[:ng], tok[:nw], rec
         if edits is None:
             _lib.check_vqa(self.lib.vstar_vqa_forward_verify(self.handle, *args, *tail), self.handle)
         else:

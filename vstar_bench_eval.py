@@ -44,6 +44,10 @@ def parse_args(argv):
     p.add_argument("--vqa-spec-tokens", dest="vqa_spec_tokens", default=0, type=int, help="d > 0 (<= 15): the free-form pass decodes "
                    "speculatively with up to d prompt-lookup draft tokens per step (DESIGN.md 8.5; 3 keeps every kernel of a one-row "
                    "step at 7B); 0 = the plain greedy decode")
+    p.add_argument("--vqa-logprobs", dest="vqa_logprobs", default=None, type=int, help="N in [0, 32]: the free-form pass also records, per "
+                   "question, the mean log-probability of the answer's tokens and the per-token arrays (log-probability, rank, the N most "
+                   "likely alternatives), computed on the device (DESIGN.md 8.9), as `freeform_logprobs` of the result record; off "
+                   "(default) writes exactly the records without it")
     p.add_argument("--engine-comm", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="world > 1 on GPUs: gather the per-step records with the C-ABI's own RCCL communicator on the engine stream "
                    "(vstar_allgather_results) instead of torch.distributed.  auto (default, round 6): used when the communicator comes up "
