@@ -377,6 +377,45 @@ int64_t vstar_vqa_kv_cache_bytes(const vstar_vqa_handle* h);
  * synchronises. */
 int vstar_vqa_op_kv_quantize(const void* dev_x_f16, int rows, void* dev_codes_u8, void* dev_scales_u8, void* dev_xhat_f16);
 
+/* Op-level doors of the decode-side kernels (decode.hip; tests/test_decode_ops_gpu.py).  fp16 only, null stream, synchronise.  Data
+ * tensors are DEVICE pointers; every index array is a HOST pointer that the door checks against the extents given here and uploads
+ * itself, so no input can make a kernel index outside an allocation.  A violated rule is VSTAR_ERR_INVALID with a message, before
+ * anything is launched or allocated.
+ * vstar_vqa_kv_view: one layer of a KV cache, K and V as [slots][heads][ctx][128] cells (fmt 0 / 2: fp16, fmt 1: e4m3 code bytes with
+ * dev_ks / dev_vs the E8M0 bytes [slots][heads][ctx][4]; vstar_vqa_kv_cache_format above); slot_stride = heads * ctx * 128.
+ * vstar_vqa_kv_rows: the rows of one call (KvRows, kernels.hpp): host row_seq / row_pos / row_slot [R], seq_kv / seq_prefix /
+ * seq_past [n_seq], nullable anc [slots * ctx].  Rules: -1 <= row_pos < min(ctx, table_rows) (-1: a padding row); row_slot, seq_kv,
+ * seq_prefix and every anc entry in [0, slots); row_seq in [0, n_seq); 0 <= seq_past <= row_pos of every row of the sequence. */
+typedef struct vstar_vqa_kv_view {
+  int32_t fmt, heads, ctx, slots;
+  void *dev_k, *dev_v, *dev_ks, *dev_vs;
+} vstar_vqa_kv_view;
+typedef struct vstar_vqa_kv_rows {
+  int32_t R, n_seq;
+  const int32_t *row_seq, *row_pos, *row_slot, *seq_kv, *seq_prefix, *seq_past, *anc;
+} vstar_vqa_kv_rows;
+/* rope_kv_append on dev_qkv [R, 3 * heads * 128] (q | k | v) with the table dev_cos_sin [table_rows, 128] (cos[64] | sin[64]). */
+int vstar_vqa_op_rope_kv_append(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                                const vstar_vqa_kv_rows* rows);
+/* cached_attention -> dev_out [R, heads * 128].  path 0: the rows are already rotated and appended (the un-fused kernel; dev_cos_sin
+ * is not read); path 1: fused, unsplit (no workspace is passed); path 2: fused split-KV, on a workspace the door allocates for R rows
+ * and zero-fills once.  The op is launched `repeat` (>= 1) times back to back on that workspace (the fused writers are idempotent).
+ * *path_ran = what the dispatcher launched.  Further rules: row_pos + 1 <= max_keys <= ctx; paths 1 and 2: no padding rows, exactly
+ * one row per sequence, pairwise distinct seq_kv, row_slot[r] == seq_kv[row_seq[r]]; paths 0 and 1: (128 + max_keys) * 4 <= 40 KiB;
+ * path 2 where the dispatcher would not split (R * heads > 128, max_keys < 256, VSTAR_DECODE_SPLIT_KV=0) is an error, never a
+ * silent fall-back. */
+int vstar_vqa_op_cached_attention(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                                  const vstar_vqa_kv_rows* rows, int max_keys, int path, int repeat, void* dev_out, int* path_ran);
+/* perceiver_attention: dev_q [n * L, H * DH], dev_kv [n * NK, 2 * H * DH] (k | v) -> dev_out [n * L, H * DH]; DH in {32, 64, 96},
+ * 1 <= NK <= 512. */
+int vstar_vqa_op_perceiver_attention(const void* dev_q, const void* dev_kv, void* dev_out, int n, int L, int NK, int H, int DH);
+/* embed_rows: dev_x [R, C] = host_src[r] >= 0 ? dev_table[src] (zero when src >= vocab) : src == INT32_MIN ? 0 :
+ * dev_feats[-(src + 1)] (zero when that is >= n_feat_rows; dev_feats nullable when n_feat_rows == 0); C % 8 == 0. */
+int vstar_vqa_op_embed_rows(const int32_t* host_src, int R, const void* dev_table, int vocab, const void* dev_feats,
+                            int64_t n_feat_rows, void* dev_x, int C);
+/* argmax_rows_lp on dev_x [rows, ld] (ld >= cols) -> host_out [rows]. */
+int vstar_vqa_op_argmax_rows(const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out);
+
 /* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float; "kv:<layer>:<slot>" = the DECODED K then V
  * cache of that layer and slot as floats [2][llm_heads][max_ctx][128], in every kv_cache_format (an index out of range is an error).
  * Returns elements written. */

@@ -44,6 +44,9 @@ EXPORTS_VQA = [
     "vstar_vqa_forward_edits", "vstar_vqa_forward_sample_edits", "vstar_vqa_forward_verify_edits", "vstar_vqa_op_edit",
     "vstar_vqa_logit_edit_capacity",
     "vstar_vqa_forward_logprobs", "vstar_vqa_forward_sample_logprobs", "vstar_vqa_forward_verify_logprobs", "vstar_vqa_op_logprobs",
+    # doors of the decode-side kernels (tests/test_decode_ops_gpu.py)
+    "vstar_vqa_op_rope_kv_append", "vstar_vqa_op_cached_attention", "vstar_vqa_op_perceiver_attention", "vstar_vqa_op_embed_rows",
+    "vstar_vqa_op_argmax_rows",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -98,6 +101,23 @@ class VqaLogprobs(ctypes.Structure):
         ("token_rank", c_void_p),
         ("top_logprob", c_void_p),
         ("top_token", c_void_p),
+    ]
+
+
+class VqaKvView(ctypes.Structure):
+    """vstar_vqa_kv_view (include/vstar_vqa.h): one layer of a KV cache for the decode-side op doors."""
+    _fields_ = [
+        ("fmt", c_int32), ("heads", c_int32), ("ctx", c_int32), ("slots", c_int32),
+        ("dev_k", c_void_p), ("dev_v", c_void_p), ("dev_ks", c_void_p), ("dev_vs", c_void_p),
+    ]
+
+
+class VqaKvRows(ctypes.Structure):
+    """vstar_vqa_kv_rows (include/vstar_vqa.h): the HOST index arrays of one call of the decode-side op doors."""
+    _fields_ = [
+        ("R", c_int32), ("n_seq", c_int32),
+        ("row_seq", c_void_p), ("row_pos", c_void_p), ("row_slot", c_void_p),
+        ("seq_kv", c_void_p), ("seq_prefix", c_void_p), ("seq_past", c_void_p), ("anc", c_void_p),
     ]
 
 
@@ -315,6 +335,17 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_gemm_w4.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int]
     lib.vstar_vqa_op_gemm_w4.restype = c_int
+    lib.vstar_vqa_op_rope_kv_append.argtypes = [c_void_p, c_void_p, c_int, POINTER(VqaKvView), POINTER(VqaKvRows)]
+    lib.vstar_vqa_op_rope_kv_append.restype = c_int
+    lib.vstar_vqa_op_cached_attention.argtypes = [c_void_p, c_void_p, c_int, POINTER(VqaKvView), POINTER(VqaKvRows), c_int, c_int, c_int,
+                                                  c_void_p, POINTER(c_int)]
+    lib.vstar_vqa_op_cached_attention.restype = c_int
+    lib.vstar_vqa_op_perceiver_attention.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]
+    lib.vstar_vqa_op_perceiver_attention.restype = c_int
+    lib.vstar_vqa_op_embed_rows.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int]
+    lib.vstar_vqa_op_embed_rows.restype = c_int
+    lib.vstar_vqa_op_argmax_rows.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p]
+    lib.vstar_vqa_op_argmax_rows.restype = c_int
     lib.vstar_vqa_debug_read.argtypes = [H, c_char_p, c_void_p, c_int64]
     lib.vstar_vqa_debug_read.restype = c_int64
     lib.vstar_vqa_last_forward_ms.argtypes = [H]

@@ -141,6 +141,14 @@ __global__ __launch_bounds__(256) void kv_quantize_rows_kernel(const lp_t* x, in
 }
 
 // ------------------------------------------------ RoPE + KV-cache append ------------------------------------------------
+// One output of rotate-half RoPE with HF's three rounding points: h(h(x * c) + h(y * s)).  Contraction is OFF here: with it the
+// compiler narrows the sum of the two rounded products to fp16 and fuses one product into it (v_pk_fma_f16 / v_fma_f16) — that product
+// is then never rounded on its own, and q / k come out one fp16 step off the reference's in some elements.
+__device__ __forceinline__ lp_t rope_out(float x, float c, float y, float s) {
+#pragma clang fp contract(off)
+  const float xc = rlp(x * c), ys = rlp(y * s);
+  return f2lp(xc + ys);
+}
 // One thread per (row, q|k|v, head, 8-vector of the FIRST half of the head dim); handles d0 and d0 + D/2 together.
 // KVF != 0: a block of 32 is the 8-vectors of 4 neighbouring threads; the round-tripped k AND v also replace the row's k / v in
 // `qkv`, which the prefill attention reads — a position has one value whoever reads it.
@@ -169,8 +177,8 @@ __global__ void rope_kv_append_kernel(lp_t* __restrict__ qkv, const lp_t* __rest
     for (int e = 0; e < 8; ++e) {
       const float a = lp2f((lp_t)x1[e]), b = lp2f((lp_t)x2[e]);
       const float cs = lp2f((lp_t)c[e]), si = lp2f((lp_t)sn[e]);
-      o1[e] = (short)f2lp(rlp(a * cs) + rlp(-b * si));
-      o2[e] = (short)f2lp(rlp(b * cs) + rlp(a * si));
+      o1[e] = (short)rope_out(a, cs, -b, si);
+      o2[e] = (short)rope_out(b, cs, a, si);
     }
     if (KVF == 0 || which == 0) {
       *(lpx8*)(base + d0) = o1;
@@ -251,7 +259,7 @@ __device__ __forceinline__ const T* kv_row(const T* head0, const T* pre, const T
   const lp_t* base = rowp + which * (H * D);                                                           \
   const float x1 = lp2f(base[d]), x2 = lp2f(base[d + 64]);                                             \
   const float cs = lp2f(cos_sin[(int64_t)pos * D + d]), si = lp2f(cos_sin[(int64_t)pos * D + 64 + d]); \
-  const lp_t o1 = f2lp(rlp(x1 * cs) + rlp(-x2 * si)), o2 = f2lp(rlp(x2 * cs) + rlp(x1 * si));          \
+  const lp_t o1 = rope_out(x1, cs, -x2, si), o2 = rope_out(x2, cs, x1, si);                            \
   if (which == 0) {                                                                                    \
     qs[d] = lp2f(o1);                                                                                  \
     qs[d + 64] = lp2f(o2);                                                                             \
@@ -793,14 +801,22 @@ size_t cached_attention_split_ws_bytes(int max_rows, int H, int ctx) {
   return rh * ((size_t)ctx * 4 + SPLIT_P * 2 * 4 + SPLIT_P * 128 * 4 + 4) + 256;
 }
 
+// decode steps of few sequences: P partitions per (row, head) so that the K / V streams of a head run on 8 CUs instead of one
+bool cached_attention_splits(bool fused, bool have_ws, int R, int split_max_rows, int H, int max_keys) {
+  static const bool split_on = [] { const char* v = getenv("VSTAR_DECODE_SPLIT_KV"); return !v || atoi(v) != 0; }();
+  return split_on && fused && have_ws && R <= split_max_rows && R * H <= 128 && max_keys >= 256;
+}
+
+static thread_local int t_last_path = -1;
+int cached_attention_last_path() { return t_last_path; }
+
 template <bool ANC, int KVF>
 static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
                                      int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
-  static const bool split_on = [] { const char* v = getenv("VSTAR_DECODE_SPLIT_KV"); return !v || atoi(v) != 0; }();
   const float inv_scale = sqrtf(128.0f);
   lp_t *kc = (lp_t*)kv.k, *vc = (lp_t*)kv.v;      // (the kernels' cell type is their KVF's)
-  // decode steps of few sequences: P partitions per (row, head) so that the K / V streams of a head run on 8 CUs instead of one
-  if (split_on && fused_cos_sin && split_ws && R <= split_max_rows && R * kv.H <= 128 && max_keys >= 256) {
+  if (cached_attention_splits(fused_cos_sin != nullptr, split_ws != nullptr, R, split_max_rows, kv.H, max_keys)) {
+    t_last_path = 2;
     const SplitWs ws(split_ws, split_max_rows, kv.H, kv.ctx);
     const int span = ((((max_keys + SPLIT_P - 1) / SPLIT_P) + 63) & ~63) + 1;
     hipLaunchKernelGGL((cached_attn_split_scores_kernel<ANC, KVF>), dim3(R, kv.H, SPLIT_P), dim3(256), (size_t)span * sizeof(float), s,
@@ -813,6 +829,7 @@ static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const K
   }
   const size_t lds = (size_t)(128 + max_keys) * sizeof(float);
   if (lds > 40 * 1024) return hipErrorInvalidValue;
+  t_last_path = fused_cos_sin ? 1 : 0;
   hipLaunchKernelGGL((fused_cos_sin ? cached_attn_kernel<true, ANC, KVF> : cached_attn_kernel<false, ANC, KVF>), dim3(R, kv.H), dim3(256),
                      lds, s, qkv, kc, vc, rows.row_seq, rows.row_pos, rows.seq_kv, rows.seq_prefix, rows.seq_past, fused_cos_sin, out, kv.H,
                      kv.ctx, kv.slot_stride, inv_scale, rows.anc, kv.ks, kv.vs);
@@ -821,6 +838,7 @@ static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const K
 
 hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
                             int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
+  t_last_path = -1;
   if (!kv_format_ok(kv)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
   hipError_t e = hipErrorInvalidValue;

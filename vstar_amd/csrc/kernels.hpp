@@ -180,6 +180,12 @@ hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const KvLayer& kv, con
 // its row (RoPE on q,k, K/V appended to the cache) — qkv then holds the raw projection.
 hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
                             int max_keys, hipStream_t s, void* split_ws = nullptr, int split_max_rows = 0);
+// whether cached_attention takes the split-KV pair for such a call (fused: fused_cos_sin given; have_ws: split_ws given) — the ONE
+// place the decision is taken (VSTAR_DECODE_SPLIT_KV=0 turns the path off), for the dispatcher and for the op-level door
+bool cached_attention_splits(bool fused, bool have_ws, int R, int split_max_rows, int H, int max_keys);
+// which kernels the last cached_attention call of THIS thread launched: 0 = un-fused, 1 = fused, 2 = fused split-KV pair, -1 = nothing
+// (observability for the op-level tests, like gemm_last_tile())
+int cached_attention_last_path();
 // KV ancestry table of beam search (anc: [slots, ctx] int32, entry (slot, p) = the slot whose cache holds position p of the
 // sequence in `slot`; cached_attention reads K/V through it when KvRows::anc is given).  mark: entry (row_slot[r], row_pos[r]) =
 // row_slot[r] for every row; fill: slot's entries [lo, hi) = value; reorder: entries [lo, hi) of dst[i] = those of src[i], every
