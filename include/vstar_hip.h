@@ -344,6 +344,50 @@ int vstar_op_gemm_fp8_mxout(void* stream, const uint16_t* dev_A, const uint16_t*
                             int K, int iters, float* gemm_ms);
 int vstar_op_attention_mx(void* stream, const uint16_t* dev_qkv, uint8_t* dev_out8, uint8_t* dev_scales, int B, int S, int H);
 int vstar_w8a8_mx_active(vstar_handle* h);
+/* ---- Doors of the prefill-side GemmParams / attn_* features no other door reaches (tests/test_prefill_ops_gpu.py): row maps,
+ * the RoPE fused into the GEMM epilogue, the LayerNorm sums, grouped attention.  Each makes ONE launch and synchronises.  Every
+ * buffer comes with its extent in ROWS, and a door refuses (VSTAR_ERR_INVALID, message in vstar_last_error(NULL), nothing
+ * launched) when any row a kernel would map or derive — clamped rows of ragged tiles included — leaves an extent. ----
+ *
+ * vstar_op_gemm_ex: C[crow(m), :] = epilogue((A[arow(m), :] . W^T) * row_scale[arow(m)] + bias) (+ residual[crow(m), :]) with
+ *   arow(m) = (m / a_group) * a_gstride + a_off + m % a_group   (a_group <= 0: m), crow likewise from c_group / c_gstride / c_off.
+ *   a_rows: rows of A and of row_scale.  c_rows: rows of C, of residual and of sumsq_out.  w_rows >= ceil(N / 256) * 256.
+ *   sumsq_out [c_rows, sumsq_ld] as in vstar_op_gemm_norm; stats_sum > 0 (>= N / 64, stats_sum + N / 64 <= sumsq_ld): the plain
+ *   sums of the same spans go to sumsq_out[crow * sumsq_ld + stats_sum + n / 64].
+ *   rope_cs [rope_rows, 128] = cos(64) | sin(64) (VSTAR_EPI_NONE, 256 x 256 kernels only, rope_cols % 256 == 0): rotate-half RoPE of
+ *   the columns < rope_cols in heads of 128, each product and the sum rounded to bf16, at position
+ *     plain          m % rope_S
+ *     grouped        (rope_R0 > 0)   q = m % rope_S; q >= rope_R0 ? rope_Lc + ((q - rope_R0) & 31) : q
+ *     shared prefix  (rope_tail > 0) m >= rope_tail ? m - rope_tail : m % rope_S + rope_pos0
+ *   `epilogue` takes the VSTAR_EPI_TILE* bits (not VSTAR_EPI_NOSYNC); VSTAR_GEMM_DEBUG in the environment as in vstar_op_gemm.
+ *   Refused besides the extents: VSTAR_EPI_TILE4W with a row map; rope_cs with VSTAR_EPI_TILE128, with an epilogue other than
+ *   VSTAR_EPI_NONE, with sumsq_out, or outside the 256 x 256 kernels' domain; rope_R0 together with rope_tail; stats_sum without
+ *   sumsq_out; a C row map that sends two rows to one. */
+typedef struct vstar_gemm_ex {
+  const uint16_t* dev_A; int64_t lda; int64_t a_rows; int32_t a_group; int64_t a_gstride, a_off;
+  const uint16_t* dev_W; int64_t w_rows;
+  const uint16_t* dev_bias;
+  const uint16_t* dev_residual; int64_t ldr;
+  uint16_t* dev_C; int64_t ldc; int64_t c_rows; int32_t c_group; int64_t c_gstride, c_off;
+  int32_t M, N, K, epilogue;
+  const float* dev_row_scale; float* dev_sumsq_out; int32_t sumsq_ld, stats_sum;
+  const uint16_t* dev_rope_cs; int32_t rope_rows, rope_S, rope_cols, rope_R0, rope_Lc, rope_pos0, rope_tail;
+} vstar_gemm_ex;
+int vstar_op_gemm_ex(void* stream, const vstar_gemm_ex* g);
+/* In-place rotate-half RoPE on q and k of qkv [qkv_rows >= B * S, 3 * H * D] with the caller's table cos_sin [table_rows, D] =
+ * cos(D / 2) | sin(D / 2); D in {64, 128}; position of row r: q = r % S, grouped (grp_R0 > 0) as above.  The v third is not touched. */
+int vstar_op_rope(void* stream, uint16_t* dev_qkv, int64_t qkv_rows, const uint16_t* dev_cos_sin, int table_rows, int B, int S, int H,
+                  int D, int grp_R0, int grp_Lc);
+/* Causal D = 128 attention (no RoPE) on qkv [qkv_rows >= B * S, 3 * H * 128] -> out [out_rows >= B * S, H * 128] over grouped
+ * sequences: rows [0, grp_Lc) of a sequence are a shared prefix, rows [grp_R0, S) independent 32-row suffix blocks that see the
+ * prefix keys < grp_Lc and, causally, their own rows; rows < grp_R0 are plain causal.  grp_R0 % 128 == 0, 0 < grp_Lc <= grp_R0 <= S,
+ * (S - grp_R0) % 32 == 0 (grp_R0 == 0: plain causal attention).  vstar_op_attention_mx_grouped: the same with the output written
+ * block-scaled like vstar_op_attention_mx (B * S % 128 == 0; out_rows counts rows of dev_out8, the scales hold
+ * vstar_op_mx_scale_bytes(B * S, H * 128) bytes). */
+int vstar_op_attention_grouped(void* stream, const uint16_t* dev_qkv, int64_t qkv_rows, uint16_t* dev_out, int64_t out_rows, int B, int S,
+                               int H, int grp_R0, int grp_Lc);
+int vstar_op_attention_mx_grouped(void* stream, const uint16_t* dev_qkv, int64_t qkv_rows, uint8_t* dev_out8, int64_t out_rows,
+                                  uint8_t* dev_scales, int B, int S, int H, int grp_R0, int grp_Lc);
 /* LayerNorm over the last dim (eps, affine) / LLaMA RMSNorm.  bf16 in/out. */
 int vstar_op_layernorm(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, const uint16_t* dev_beta,
                        uint16_t* dev_y, int rows, int cols, float eps);

@@ -199,6 +199,17 @@ def dots_exact(qh, Kd):
     return bool(np.all(ok | (np.abs(prod).sum(axis=1) == 0)))
 
 
+def tight_gate(o, pv, vabs, u=2.0 ** -11):
+    """TIGHT for a 16-bit format of unit roundoff u (fp16: 2^-11, bf16: 2^-9): 2u |o| (the output's rounding, with slack for the
+    reference's own) + 4u sum p|v| (every probability rounded, the normaliser) + 2^-23 sum |v| (fp32 accumulation)."""
+    return 2 * u * np.abs(o) + 4 * u * pv + 2.0 ** -23 * vabs
+
+
+def loose_gate(tight, delta, pv):
+    """LOOSE = TIGHT + (e^(2 delta) - 1) sum p|v|: every score off by at most delta moves a probability by e^(+-2 delta)."""
+    return tight + np.expm1(2 * delta) * pv
+
+
 def attn_row(qh, Kd, Vd):
     """One (row, head) of cached attention on the decoded operands: qh [128] fp16, Kd / Vd [nk, 128] fp16.
     a_j = sum q k_j; s_j = h(float32(h(a_j)) / float32(sqrt(128))); p_j = h(exp(s_j - max) / sum); o = h(sum p_j v_j).
@@ -210,9 +221,9 @@ def attn_row(qh, Kd, Vd):
     p = h(e / e.sum())
     o = h((p.astype(F64)[:, None] * Vf).sum(axis=0))
     pv = (p.astype(F64)[:, None] * np.abs(Vf)).sum(axis=0)
-    tight = 2.0 ** -10 * np.abs(o.astype(F64)) + 2.0 ** -9 * pv + 2.0 ** -23 * np.abs(Vf).sum(axis=0)
+    tight = tight_gate(o.astype(F64), pv, np.abs(Vf).sum(axis=0))
     delta = (2.0 ** -9 * np.abs(s.astype(F64)) + 2.0 ** -17 * (np.abs(Kf) @ np.abs(q)) / float(SQRT_D)).max()
-    loose = tight + np.expm1(2 * delta) * pv
+    loose = loose_gate(tight, delta, pv)
     s64 = a / np.sqrt(128.0)
     e64 = np.exp(s64 - s64.max())
     f64 = (e64 / e64.sum()) @ Vf

@@ -52,6 +52,14 @@ def test_result_record_layout():
     assert ctypes.sizeof(CVstarConfig) == 4 * (24 + 8)
 
 
+def test_gemm_ex_struct_layout():
+    # vstar_gemm_ex (vstar_op_gemm_ex) crosses the ABI by pointer: natural alignment, 33 fields, 216 bytes
+    g = _lib.GemmEx
+    assert ctypes.sizeof(g) == 216 and len(g._fields_) == 33
+    assert [getattr(g, n).offset for n in ("A", "a_group", "W", "C", "c_group", "M", "row_scale", "sumsq_ld", "rope_cs", "rope_tail")] == \
+        [0, 24, 48, 88, 112, 136, 152, 168, 176, 208]
+
+
 def test_create_without_gpu_fails_loudly(lib):
     import torch
     if torch.cuda.is_available():

@@ -29,6 +29,8 @@ EXPORTS = [
     "vstar_op_add_bcast_repeat", "vstar_op_bcast_rows", "vstar_op_owl_cls_mul", "vstar_op_gather_rows", "vstar_op_argmax_rows",
     "vstar_op_layernorm_ex", "vstar_op_rmsnorm_ex", "vstar_op_ln_rstd", "vstar_op_scale_cols", "vstar_op_fill",
     "vstar_op_quantize_rows_fp8", "vstar_op_rmsnorm_quant_fp8", "vstar_op_small_attention",
+    # doors of the prefill-side GEMM / attention features (tests/test_prefill_ops_gpu.py)
+    "vstar_op_gemm_ex", "vstar_op_rope", "vstar_op_attention_grouped", "vstar_op_attention_mx_grouped",
 ]
 
 # every symbol include/vstar_vqa.h declares
@@ -118,6 +120,21 @@ class VqaKvRows(ctypes.Structure):
         ("R", c_int32), ("n_seq", c_int32),
         ("row_seq", c_void_p), ("row_pos", c_void_p), ("row_slot", c_void_p),
         ("seq_kv", c_void_p), ("seq_prefix", c_void_p), ("seq_past", c_void_p), ("anc", c_void_p),
+    ]
+
+
+class GemmEx(ctypes.Structure):
+    """vstar_gemm_ex (include/vstar_hip.h): one call of vstar_op_gemm_ex, every buffer with its extent in rows."""
+    _fields_ = [
+        ("A", c_void_p), ("lda", c_int64), ("a_rows", c_int64), ("a_group", c_int32), ("a_gstride", c_int64), ("a_off", c_int64),
+        ("W", c_void_p), ("w_rows", c_int64),
+        ("bias", c_void_p),
+        ("residual", c_void_p), ("ldr", c_int64),
+        ("C", c_void_p), ("ldc", c_int64), ("c_rows", c_int64), ("c_group", c_int32), ("c_gstride", c_int64), ("c_off", c_int64),
+        ("M", c_int32), ("N", c_int32), ("K", c_int32), ("epilogue", c_int32),
+        ("row_scale", c_void_p), ("sumsq_out", c_void_p), ("sumsq_ld", c_int32), ("stats_sum", c_int32),
+        ("rope_cs", c_void_p), ("rope_rows", c_int32), ("rope_S", c_int32), ("rope_cols", c_int32), ("rope_R0", c_int32),
+        ("rope_Lc", c_int32), ("rope_pos0", c_int32), ("rope_tail", c_int32),
     ]
 
 
@@ -226,6 +243,14 @@ def load() -> ctypes.CDLL:
     lib.vstar_op_gemm_fp8_mxout.restype = c_int
     lib.vstar_op_attention_mx.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]
     lib.vstar_op_attention_mx.restype = c_int
+    lib.vstar_op_gemm_ex.argtypes = [c_void_p, POINTER(GemmEx)]
+    lib.vstar_op_gemm_ex.restype = c_int
+    lib.vstar_op_rope.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]
+    lib.vstar_op_rope.restype = c_int
+    lib.vstar_op_attention_grouped.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int]
+    lib.vstar_op_attention_grouped.restype = c_int
+    lib.vstar_op_attention_mx_grouped.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int]
+    lib.vstar_op_attention_mx_grouped.restype = c_int
     lib.vstar_w8a8_mx_active.argtypes = [c_void_p]
     lib.vstar_w8a8_mx_active.restype = c_int
     lib.vstar_op_layernorm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]

@@ -4,6 +4,8 @@
 // (SURVEY.md §7 "hard parts"; the lm_head argmax at the verify positions lets the caller prove the collapse is exact).
 #include "llm_cached.hpp"
 #include "mx.hpp"
+#include "gemm_epilogue.hpp"      // gemm_map_row: the op-level doors check extents with the kernels' own row map
+#include <algorithm>
 #include <atomic>
 #include <tuple>
 #include <cstring>
@@ -1712,6 +1714,130 @@ int vstar_op_attention_mx(void* stream, const uint16_t* qkv, uint8_t* out8, uint
   return op_rc(e);
 }
 int vstar_w8a8_mx_active(vstar_handle* h) { return h ? h->last_w8a8_chain : VSTAR_ERR_INVALID; }
+
+// ---- doors of the prefill-side features (row maps, fused RoPE, LayerNorm sums, grouped attention): every extent is checked on the
+// host, with the kernels' own gemm_map_row, before anything is launched ----
+static int op_done(hipError_t e, void* stream);
+static int op_refuse(const char* door, const std::string& why) {
+  tls_error() = std::string(door) + ": " + why;
+  return VSTAR_ERR_INVALID;
+}
+// the RoPE position the three fused-RoPE sites (gemm256.hip, gemm256_direct_epilogue.hpp) and rope_kernel derive for row r
+static int64_t op_rope_pos(int64_t r, int S, int R0, int Lc, int pos0, int tail) {
+  int64_t pos = r % S;
+  if (R0 > 0 && pos >= R0) pos = Lc + ((pos - R0) & 31);
+  if (tail > 0) pos = r >= tail ? r - tail : pos + pos0;
+  return pos;
+}
+// the domain of grouped sequences (attn_forward / attn_forward_mx), as messages; empty = fine
+static std::string op_group_domain(int S, int R0, int Lc) {
+  if (R0 < 0 || Lc < 0) return "grp_R0 / grp_Lc negative";
+  if (R0 == 0) return Lc ? "grp_Lc without grp_R0" : "";
+  if (R0 % 128) return "grp_R0 % 128 != 0 (a suffix region starts on a 128-row query block)";
+  if (Lc <= 0 || Lc > R0) return "0 < grp_Lc <= grp_R0 does not hold";
+  if (R0 > S) return "grp_R0 > S";
+  if ((S - R0) % 32) return "(S - grp_R0) % 32 != 0 (suffix blocks are 32 rows)";
+  return "";
+}
+int vstar_op_gemm_ex(void* stream, const vstar_gemm_ex* g) {
+  static const char* const door = "vstar_op_gemm_ex";
+  if (!g || !g->dev_A || !g->dev_W || !g->dev_C) return op_refuse(door, "null argument");
+  if (g->M <= 0 || g->N <= 0 || g->K <= 0 || g->K % 64) return op_refuse(door, "M, N, K > 0 and K % 64 == 0 required");
+  const int flags = g->epilogue & ~0xff, epi = g->epilogue & 0xff;
+  if (flags & ~(VSTAR_EPI_TILE128 | VSTAR_EPI_TILE256 | VSTAR_EPI_TILE4W)) return op_refuse(door, "unknown bits in `epilogue` (VSTAR_EPI_NOSYNC is not taken)");
+  if (epi > VSTAR_EPI_SILU_MUL) return op_refuse(door, "unknown epilogue");
+  const int forced = (flags & VSTAR_EPI_TILE4W) ? GEMM_TILE_4W : (flags & VSTAR_EPI_TILE256) ? 256 : (flags & VSTAR_EPI_TILE128) ? 128 : 0;
+  if ((flags & (flags - 1)) != 0) return op_refuse(door, "more than one tile override set");
+  const int n_out = epi == VSTAR_EPI_SILU_MUL ? g->N / 2 : g->N;
+  if (epi == VSTAR_EPI_SILU_MUL && g->N % 32) return op_refuse(door, "VSTAR_EPI_SILU_MUL: N % 32 == 0 required");
+  if (g->lda < g->K || g->ldc < n_out || (g->dev_residual && g->ldr < n_out)) return op_refuse(door, "a leading dimension is shorter than its row");
+  if (g->w_rows < ((int64_t)g->N + 255) / 256 * 256) return op_refuse(door, "W needs ceil(N / 256) * 256 rows");
+  GemmParams p{};
+  p.A = g->dev_A; p.lda = g->lda; p.a_group = g->a_group; p.a_gstride = g->a_gstride; p.a_off = g->a_off;
+  p.W = g->dev_W; p.bias = g->dev_bias; p.res = g->dev_residual; p.ldr = g->ldr;
+  p.C = g->dev_C; p.ldc = g->ldc; p.c_group = g->c_group; p.c_gstride = g->c_gstride; p.c_off = g->c_off;
+  p.M = g->M; p.N = g->N; p.K = g->K;
+  p.row_scale = g->dev_row_scale; p.sumsq_out = g->dev_sumsq_out; p.sumsq_ld = g->sumsq_ld; p.stats_sum = g->stats_sum;
+  p.rope_cs = g->dev_rope_cs; p.rope_S = g->rope_S; p.rope_cols = g->rope_cols; p.rope_R0 = g->rope_R0; p.rope_Lc = g->rope_Lc;
+  p.rope_pos0 = g->rope_pos0; p.rope_tail = g->rope_tail;
+  { const char* e = getenv("VSTAR_GEMM_DEBUG"); p.debug_flags = e ? atoi(e) : 0; }
+  p.tile_force = forced;
+  // ---- row maps: every mapped row of the call (rows of a ragged tile are clamped to M - 1 by the kernels, so [0, M) is all of them) ----
+  const bool a_map = p.a_group > 0, c_map = p.c_group > 0;
+  if ((a_map || c_map) && forced == GEMM_TILE_4W) return op_refuse(door, "VSTAR_EPI_TILE4W with a row map (the 4-wave kernel addresses rows by tile)");
+  if (a_map && (p.a_gstride < 0 || p.a_off < 0)) return op_refuse(door, "negative A row map");
+  if (c_map && p.c_off < 0) return op_refuse(door, "negative C row map");
+  if (c_map && p.M > p.c_group && p.c_gstride < p.c_group) return op_refuse(door, "C row map sends two rows to one (c_gstride < c_group)");
+  int64_t a_max = 0, c_max = 0;
+  for (int r = 0; r < p.M; ++r) {
+    a_max = std::max(a_max, gemm_map_row(r, p.a_group, p.a_gstride, p.a_off));
+    c_max = std::max(c_max, gemm_map_row(r, p.c_group, p.c_gstride, p.c_off));
+  }
+  if (a_max >= g->a_rows) return op_refuse(door, "mapped A row " + std::to_string(a_max) + " outside a_rows = " + std::to_string(g->a_rows) + " (A, row_scale)");
+  if (c_max >= g->c_rows) return op_refuse(door, "mapped C row " + std::to_string(c_max) + " outside c_rows = " + std::to_string(g->c_rows) + " (C, residual, sumsq_out)");
+  // ---- statistics ----
+  if (p.stats_sum && !p.sumsq_out) return op_refuse(door, "stats_sum without sumsq_out");
+  if (p.sumsq_out) {
+    if (epi != VSTAR_EPI_NONE || p.N % 64) return op_refuse(door, "sumsq_out: VSTAR_EPI_NONE and N % 64 == 0 only");
+    const int spans = p.N / 64;
+    if (p.stats_sum < 0 || (p.stats_sum && p.stats_sum < spans)) return op_refuse(door, "stats_sum must be 0 or >= N / 64 (the sums would land on the sums of squares)");
+    if (p.sumsq_ld < (p.stats_sum ? p.stats_sum + spans : spans)) return op_refuse(door, "sumsq_ld shorter than the partials of a row");
+  }
+  // ---- fused RoPE ----
+  if (!p.rope_cs && (p.rope_S || p.rope_cols || p.rope_R0 || p.rope_Lc || p.rope_pos0 || p.rope_tail)) return op_refuse(door, "rope_* set without rope_cs");
+  if (p.rope_cs) {
+    if (forced == 128) return op_refuse(door, "rope_cs with VSTAR_EPI_TILE128: the 128-row kernels have no fused RoPE");
+    if (epi != VSTAR_EPI_NONE) return op_refuse(door, "rope_cs with an epilogue other than VSTAR_EPI_NONE");
+    if (p.sumsq_out) return op_refuse(door, "rope_cs with sumsq_out (the in-register epilogue's spans of a RoPE tile are not 64 consecutive columns)");
+    if (((uintptr_t)p.rope_cs & 15)) return op_refuse(door, "rope_cs must be 16-byte aligned");
+    if (p.rope_S <= 0 || p.rope_cols <= 0 || p.rope_cols % 256 || p.rope_cols > p.N) return op_refuse(door, "rope_S > 0 and 0 < rope_cols <= N, rope_cols % 256 == 0 required");
+    if (p.rope_R0 < 0 || p.rope_Lc < 0 || p.rope_pos0 < 0 || p.rope_tail < 0) return op_refuse(door, "negative rope_* argument");
+    if (p.rope_R0 > 0 && p.rope_tail > 0) return op_refuse(door, "rope_R0 together with rope_tail (grouped and shared-prefix positions exclude each other)");
+    if (p.rope_R0 == 0 && p.rope_Lc) return op_refuse(door, "rope_Lc without rope_R0");
+    if (p.rope_tail == 0 && p.rope_pos0) return op_refuse(door, "rope_pos0 without rope_tail");
+    if (p.rope_R0 > 0 && (p.rope_Lc <= 0 || p.rope_Lc > p.rope_R0)) return op_refuse(door, "0 < rope_Lc <= rope_R0 does not hold");
+    if (!gemm256_eligible(p)) return op_refuse(door, "rope_cs: shape outside the 256 x 256 kernels' domain (M >= 1024, N >= 256, K % 128 == 0), the only ones with fused RoPE");
+    int64_t pos_max = 0;
+    for (int r = 0; r < p.M; ++r) pos_max = std::max(pos_max, op_rope_pos(r, p.rope_S, p.rope_R0, p.rope_Lc, p.rope_pos0, p.rope_tail));
+    if (pos_max >= g->rope_rows) return op_refuse(door, "RoPE position " + std::to_string(pos_max) + " outside rope_rows = " + std::to_string(g->rope_rows));
+  }
+  if (forced == 256 && !gemm256_eligible(p)) return op_refuse(door, "VSTAR_EPI_TILE256: shape outside the 256 x 256 kernel's domain (M >= 1024, N >= 256, K % 128 == 0)");
+  if (forced == GEMM_TILE_4W && !(gemm256_eligible(p) && gemm_mx_supported(p, epi))) return op_refuse(door, "VSTAR_EPI_TILE4W: call outside the 4-wave kernel's domain");
+  hipError_t e = gemm_lp(p, epi, false, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return op_refuse(door, "the dispatcher refused the call (alignment of A / W, lda % 8)");
+  return op_done(e, stream);
+}
+int vstar_op_rope(void* stream, uint16_t* qkv, int64_t qkv_rows, const uint16_t* cos_sin, int table_rows, int B, int S, int H, int D,
+                  int grp_R0, int grp_Lc) {
+  static const char* const door = "vstar_op_rope";
+  if (!qkv || !cos_sin || B <= 0 || S <= 0 || H <= 0) return op_refuse(door, "bad argument");
+  if (D != 64 && D != 128) return op_refuse(door, "D must be 64 or 128");
+  if (grp_R0 < 0 || grp_Lc < 0 || (grp_R0 == 0 && grp_Lc) || (grp_R0 > 0 && (grp_Lc <= 0 || grp_Lc > grp_R0))) return op_refuse(door, "0 < grp_Lc <= grp_R0 does not hold");
+  if (qkv_rows < (int64_t)B * S) return op_refuse(door, "qkv_rows < B * S");
+  int64_t pos_max = 0;
+  for (int r = 0; r < S; ++r) pos_max = std::max(pos_max, op_rope_pos(r, S, grp_R0, grp_Lc, 0, 0));
+  if (pos_max >= table_rows) return op_refuse(door, "RoPE position " + std::to_string(pos_max) + " outside table_rows = " + std::to_string(table_rows));
+  return op_done(attn_prepare(qkv, cos_sin, B, S, H, D, (hipStream_t)stream, grp_R0, grp_Lc), stream);
+}
+int vstar_op_attention_grouped(void* stream, const uint16_t* qkv, int64_t qkv_rows, uint16_t* out, int64_t out_rows, int B, int S, int H,
+                               int grp_R0, int grp_Lc) {
+  static const char* const door = "vstar_op_attention_grouped";
+  if (!qkv || !out || B <= 0 || S <= 0 || H <= 0) return op_refuse(door, "bad argument");
+  const std::string why = op_group_domain(S, grp_R0, grp_Lc);
+  if (!why.empty()) return op_refuse(door, why);
+  if (qkv_rows < (int64_t)B * S || out_rows < (int64_t)B * S) return op_refuse(door, "qkv_rows / out_rows < B * S");
+  return op_done(attn_forward(qkv, out, B, S, H, 128, 1, 1.0f / sqrtf(128.0f), (hipStream_t)stream, grp_R0, grp_Lc), stream);
+}
+int vstar_op_attention_mx_grouped(void* stream, const uint16_t* qkv, int64_t qkv_rows, uint8_t* out8, int64_t out_rows, uint8_t* scales, int B,
+                                  int S, int H, int grp_R0, int grp_Lc) {
+  static const char* const door = "vstar_op_attention_mx_grouped";
+  if (!qkv || !out8 || !scales || B <= 0 || S <= 0 || H <= 0) return op_refuse(door, "bad argument");
+  if ((int64_t)B * S % 128) return op_refuse(door, "B * S % 128 != 0 (the scale layout is per 128-row block)");
+  const std::string why = op_group_domain(S, grp_R0, grp_Lc);
+  if (!why.empty()) return op_refuse(door, why);
+  if (qkv_rows < (int64_t)B * S || out_rows < (int64_t)B * S) return op_refuse(door, "qkv_rows / out_rows < B * S");
+  return op_done(attn_forward_mx(qkv, out8, scales, B, S, H, 1.0f / sqrtf(128.0f), (hipStream_t)stream, grp_R0, grp_Lc), stream);
+}
 
 size_t vstar_op_attention_workspace(int B, int S, int H, int D) {
   (void)B; (void)H;

@@ -6,7 +6,7 @@
 
 namespace VS_NS {
 
-__device__ __forceinline__ int64_t gemm_map_row(int r, int group, int64_t gstride, int64_t off) {
+__host__ __device__ __forceinline__ int64_t gemm_map_row(int r, int group, int64_t gstride, int64_t off) {
   if (group <= 0) return (int64_t)r;
   int g = r / group;
   return (int64_t)g * gstride + off + (r - g * group);
