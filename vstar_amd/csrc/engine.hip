@@ -41,11 +41,20 @@ struct vstar_engine : EngineBase {
   uint8_t* lmx = nullptr;                            // W8A8, block-scaled activations (mx.hpp): E8M0 bytes of the o_proj / down_proj inputs
   int make_lin8(const Lin& L, Lin8* out, const lp_t* fold_g = nullptr);
   uint8_t* lmxx = nullptr;                           // ... and of the residual stream (the q|k|v / gate|up inputs of the fully block-scaled chain)
-  int last_w8a8_chain = 0;                           // 0 per token, 1 block-scaled o_proj / down_proj inputs, 2 + q|k|v / gate|up inputs (norms folded)
-  int lin8(const uint8_t* Aq, const float* sa, const Lin& L, const Lin8& L8, void* C, int64_t ldc, int M, int epi,
-           const lp_t* res, int64_t ldr, const lp_t* rope_cs = nullptr, int rope_S = 0, int rope_cols = 0, const uint8_t* a_mx = nullptr,
-           uint8_t* c_mx = nullptr, uint8_t* c8 = nullptr, float* sumsq = nullptr);
-  bool last_w8a8_mx = false;   // whether the last llm_forward ran o_proj / down_proj on block-scaled activations (vstar_w8a8_mx_active)
+  int last_w8a8_chain = 0;                           // W8A8 level of the last llm_forward (vstar_w8a8_mx_active)
+  // The W8A8 level of a pass: how the activations of the four big linears of a block are quantised.
+  enum { W8_TOKEN = 0,      // per token, by stand-alone passes (rmsnorm_quant_fp8 / quantize_rows_fp8)
+         W8_MX = 1,         // + o_proj / down_proj inputs block-scaled by their producers (attention / gate|up epilogue)
+         W8_CHAIN = 2 };    // + the residual stream too: q|k|v / gate|up read it block-scaled, their RMSNorm folded
+  // What describes one LLaMA prefill pass: nseq sequences of S rows, nsel gathered rows for the last block; grouped sequences
+  // (R0 / Lc: shared rows [0, Lc), 32-row suffix blocks from R0; 0 = plain) and the shared-prefix length (VSTAR_F_SHARE_PREFIX; 0 = off)
+  struct LlmPass { int nseq, S, nsel, R0, Lc, Lp; };
+  // The GemmParams of each of those linears over `rows` rows at a level: the ONE place they are assembled — llm_forward's
+  // gemm_mx_supported probes (on llm[0]) and its launches (on llm[i]) both call these.
+  GemmParams w8_params(const void* A8, const Lin& L, const Lin8& L8, void* C, int rows) const;
+  GemmParams w8_qkv(const LlmBlock& b, int level, int rows, const LlmPass& g) const;
+  GemmParams w8_residual(const lp_t* act, const Lin& L, const Lin8& L8, int level, int rows) const;      // o_proj (act = latt) / down_proj (lact)
+  GemmParams w8_gate_up(const LlmBlock& b, int level, int rows) const;
   bool fused_rope = true;      // VSTAR_FUSED_ROPE=0 keeps RoPE as a separate pass (A/B and the bit-identity test)
   // RMSNorms of the LLaMA blocks folded into the linears that consume them (default; VSTAR_FOLD_NORMS=0 before vstar_create keeps
   // the norm kernels): weight folded into W's columns at load, 1/rms applied to the accumulators, statistics from the epilogue
@@ -136,9 +145,8 @@ struct vstar_engine : EngineBase {
                     const int32_t* suffix_ids, int Ls, const int32_t* loc_in_suffix, const int32_t* verify_in_suffix, int n_verify,
                     unsigned flags, vstar_result* out);
   // shared stages of score / score_grouped
-  int grp_R0 = 0, grp_Lc = 0;       // grouped-sequence geometry of the LLaMA pass in flight (0 = plain sequences)
-  int psh_Lp = 0;                   // shared-prefix length of the LLaMA pass in flight (VSTAR_F_SHARE_PREFIX; 0 = off)
-  int llm_forward(int nseq, int S, int nsel);
+  int llm_forward(const LlmPass& pass);
+  int project_clip(int ncrops, lp_t* dst, int64_t ldc, int c_group = 0, int64_t c_gstride = 0, int64_t c_off = 0);
   int llm_heads(int nrec, int n_verify);
   int owl_heads_sam(const lp_t* opix, int Bimg, int nrec, int img_div);
   int owl_features(const lp_t* opix, int Bimg);                   // the part of a9-a11 that does not depend on the LLaMA path
@@ -191,15 +199,41 @@ int vstar_engine::make_lin8(const Lin& L, Lin8* out, const lp_t* fold_g) {
   return 0;
 }
 
-int vstar_engine::lin8(const uint8_t* Aq, const float* sa, const Lin& L, const Lin8& L8, void* C, int64_t ldc, int M, int epi,
-                       const lp_t* res, int64_t ldr, const lp_t* rope_cs, int rope_S, int rope_cols, const uint8_t* a_mx, uint8_t* c_mx,
-                       uint8_t* c8, float* sumsq) {
+// fp8 rows A8 [rows, L.K] against the fp8 twin of L; the scales of A (a_scale and / or a_mx) are the caller's to name
+GemmParams vstar_engine::w8_params(const void* A8, const Lin& L, const Lin8& L8, void* C, int rows) const {
   GemmParams p{};
-  p.A = (const lp_t*)Aq; p.lda = L.K; p.W = (const lp_t*)L8.W; p.res = res; p.ldr = ldr; p.C = C; p.ldc = ldc;
-  p.M = M; p.N = L.N; p.K = L.K; p.a_scale = sa; p.w_scale = L8.s; p.a_mx = a_mx; p.c_mx = c_mx;      // (sa next to a_mx: the folded norm's 1 / rms)
-  p.c8 = c8; p.ldc8 = L.N; p.sumsq_out = c8 ? sumsq : nullptr; p.sumsq_ld = L.N / 64;
-  p.rope_cs = rope_cs; p.rope_S = rope_S; p.rope_cols = rope_cols; p.rope_R0 = grp_R0; p.rope_Lc = grp_Lc;
-  return gemm(p, epi, false);
+  p.A = (const lp_t*)A8; p.lda = L.K; p.W = (const lp_t*)L8.W; p.w_scale = L8.s;
+  p.C = C; p.M = rows; p.N = L.N; p.K = L.K;
+  return p;
+}
+
+GemmParams vstar_engine::w8_qkv(const LlmBlock& b, int level, int rows, const LlmPass& g) const {
+  const bool chain = level == W8_CHAIN;
+  GemmParams p = w8_params(lq8, b.qkv, chain ? b.qkv8f : b.qkv8, lqkv, rows);
+  p.ldc = 3 * cfg.llm_hidden;
+  p.a_scale = chain ? lr : lsa;                  // (lr next to a_mx: the folded norm's 1 / rms)
+  if (chain) p.a_mx = lmxx;
+  if (fused_rope) { p.rope_cs = rope; p.rope_S = g.S; p.rope_cols = 2 * cfg.llm_hidden; p.rope_R0 = g.R0; p.rope_Lc = g.Lc; }
+  return p;
+}
+
+GemmParams vstar_engine::w8_residual(const lp_t* act, const Lin& L, const Lin8& L8, int level, int rows) const {
+  GemmParams p = w8_params(level == W8_TOKEN ? (const void*)lq8 : act, L, L8, lx, rows);
+  p.ldc = p.ldr = cfg.llm_hidden; p.res = lx;
+  if (level == W8_TOKEN) p.a_scale = lsa;
+  else p.a_mx = lmx;
+  if (level == W8_CHAIN) { p.c_mx = lmxx; p.c8 = lq8; p.ldc8 = L.N; p.sumsq_out = lpart; p.sumsq_ld = L.N / 64; }
+  return p;
+}
+
+GemmParams vstar_engine::w8_gate_up(const LlmBlock& b, int level, int rows) const {
+  const bool chain = level == W8_CHAIN;
+  GemmParams p = w8_params(lq8, b.gate_up, chain ? b.gate_up8f : b.gate_up8, lact, rows);
+  p.ldc = cfg.llm_mlp;                           // SiLU(gate) * up: half the columns (bytes per row when c_mx takes the output)
+  p.a_scale = chain ? lr : lsa;
+  if (chain) p.a_mx = lmxx;
+  if (level != W8_TOKEN) p.c_mx = lmx;
+  return p;
 }
 
 int vstar_engine::finalize() {
@@ -547,6 +581,15 @@ __global__ void sam_tokens_kernel(const lp_t* iou, const lp_t* mask_tokens, cons
 }
 }  // namespace
 
+// ---- a3: mm_projector on the patch rows of ncrops CLIP token sequences (the (P, N, 1) row map skips each CLS row), written to
+// dst [.., ldc] — contiguous, or through the C row map (score_body: straight into the spliced LLaMA input; llava_arch.py:93-96,185-208)
+int vstar_engine::project_clip(int ncrops, lp_t* dst, int64_t ldc, int c_group, int64_t c_gstride, int64_t c_off) {
+  GemmParams p = lin_params(clip.x, clip.hidden, projector, dst, ldc, ncrops * clip.P);
+  p.a_group = clip.P; p.a_gstride = clip.N; p.a_off = 1;
+  p.c_group = c_group; p.c_gstride = c_gstride; p.c_off = c_off;
+  return gemm(p, VSTAR_EPI_NONE, false);
+}
+
 // host/device pixel hand-over shared by score / score_grouped
 int vstar_engine::stage_pixels(int B, const lp_t* clip_pix, const lp_t* owl_pix, unsigned flags, bool skip_owl, const lp_t** cpix,
                                const lp_t** opix) {
@@ -568,13 +611,18 @@ int vstar_engine::stage_pixels(int B, const lp_t* clip_pix, const lp_t* owl_pix,
   return 0;
 }
 
+static int w8a8_mx_env() {      // VSTAR_W8A8_MX: the highest W8A8 level a pass may take (default W8_MX); read once per process
+  static const int v = [] { const char* e = getenv("VSTAR_W8A8_MX"); return e ? atoi(e) : 1; }();
+  return v;
+}
+
 // ---- a5: LLaMA prefill (HF LlamaModel via llava_llama.py:93-102) over nseq sequences of S rows in lx; the last block runs on the
-// nsel rows listed in d_rowidx only and leaves them in sel_x.  grp_R0 / grp_Lc describe grouped sequences (shared prefix + 32-row
+// nsel rows listed in d_rowidx only and leaves them in sel_x.  g.R0 / g.Lc describe grouped sequences (shared prefix + 32-row
 // suffix blocks): they only change the RoPE positions and the attention mask — every other op is row-wise.
-int vstar_engine::llm_forward(int nseq, int S, int nsel) {
+int vstar_engine::llm_forward(const LlmPass& g) {
   const vstar_config& c = cfg;
   const int H = c.llm_hidden;
-  const int rows = nseq * S;
+  const int nseq = g.nseq, S = g.S, rows = nseq * S;
   const float att_scale = 1.0f / sqrtf(128.0f);
   // W8A8 (config 5): the four big linears of every block run on the fp8 MFMA when the call has enough rows for the 256^2
   // kernel; activations are quantised per token right where they are produced (inside the RMSNorm for q|k|v and gate|up,
@@ -583,104 +631,75 @@ int vstar_engine::llm_forward(int nseq, int S, int nsel) {
   // Block-scaled activations (mx.hpp, round 6) for the inputs of o_proj and down_proj: quantised by their PRODUCERS (the attention
   // epilogue, the gate|up epilogue) per 32 values, scales applied inside the MFMA — no stand-alone quantisation pass.  Needs the
   // 4-wave kernel's domain (rows % 256 == 0 ...); otherwise the per-token scheme with its two passes.  VSTAR_W8A8_MX=0: A/B runs.
-  static const bool mx_env = [] { const char* e = getenv("VSTAR_W8A8_MX"); return !e || atoi(e) != 0; }();
-  bool mx = false;
-  if (w8 && mx_env && c.llm_layers > 1) {
-    GemmParams q{};
-    LlmBlock& b0 = llm[0];
-    q.A = (const lp_t*)latt; q.lda = H; q.W = (const lp_t*)b0.o8.W; q.C = lx; q.ldc = H; q.res = lx; q.ldr = H; q.M = rows; q.N = H; q.K = H;
-    q.w_scale = b0.o8.s; q.a_mx = lmx;
-    mx = gemm_mx_supported(q, VSTAR_EPI_NONE);
-    q.A = (const lp_t*)lact; q.lda = c.llm_mlp; q.W = (const lp_t*)b0.down8.W; q.K = c.llm_mlp; q.w_scale = b0.down8.s;
-    mx = mx && gemm_mx_supported(q, VSTAR_EPI_NONE);
-    q = GemmParams{};
-    q.A = (const lp_t*)lq8; q.lda = H; q.W = (const lp_t*)b0.gate_up8.W; q.C = lact; q.ldc = c.llm_mlp; q.M = rows; q.N = b0.gate_up.N; q.K = H;
-    q.a_scale = lsa; q.w_scale = b0.gate_up8.s; q.c_mx = lmx;
-    mx = mx && gemm_mx_supported(q, VSTAR_EPI_SILU_MUL);
-  }
+  // The probes ask about the very GemmParams the loop launches (w8_*), on the first block.
+  const LlmBlock* b0 = llm.data();
+  const bool mx = w8 && w8a8_mx_env() != 0 && c.llm_layers > 1 &&
+                  gemm_mx_supported(w8_residual(latt, b0->o, b0->o8, W8_MX, rows), VSTAR_EPI_NONE) &&
+                  gemm_mx_supported(w8_residual(lact, b0->down, b0->down8, W8_MX, rows), VSTAR_EPI_NONE) &&
+                  gemm_mx_supported(w8_gate_up(*b0, W8_MX, rows), VSTAR_EPI_SILU_MUL);
   // Fully block-scaled chain (opt-in: VSTAR_W8A8_MX=2; the default, 1, stops at the step above): the residual stream ALSO leaves o_proj / down_proj
   // as a block-scaled fp8 copy with sum-of-squares partials (mx_none_epilogue), q|k|v and gate|up consume it with the RMSNorm folded
   // (weight into their fp8 W, 1 / rms as the per-row scale) — no rmsnorm_quant pass either.
   // Opt-in because it moves the search: on the config-5 search leg (bench.py, one 341-node tree) levels 0 / 1 / 2 follow the bf16 visit
   // order for 25 / 20 / 3 nodes and level 2 ends in another final box, at +1 % speed over level 1 (profiles/r06_w8a8_levels.txt).
-  static const int mx_level = [] { const char* e = getenv("VSTAR_W8A8_MX"); return e ? atoi(e) : 1; }();
-  bool chain = false;
-  if (mx && mx_level >= 2 && H % 256 == 0) {
-    GemmParams q{};
-    LlmBlock& b0 = llm[0];
-    q.A = (const lp_t*)latt; q.lda = H; q.W = (const lp_t*)b0.o8.W; q.C = lx; q.ldc = H; q.res = lx; q.ldr = H; q.M = rows; q.N = H; q.K = H;
-    q.w_scale = b0.o8.s; q.a_mx = lmx; q.c_mx = lmxx; q.c8 = lq8; q.ldc8 = H; q.sumsq_out = lpart; q.sumsq_ld = H / 64;
-    chain = gemm_mx_supported(q, VSTAR_EPI_NONE);
-    q = GemmParams{};
-    q.A = (const lp_t*)lq8; q.lda = H; q.W = (const lp_t*)b0.qkv8f.W; q.C = lqkv; q.ldc = 3 * H; q.M = rows; q.N = b0.qkv.N; q.K = H;
-    q.a_scale = lr; q.w_scale = b0.qkv8f.s; q.a_mx = lmxx;
-    if (fused_rope) { q.rope_cs = rope; q.rope_S = S; q.rope_cols = 2 * H; }
-    chain = chain && gemm_mx_supported(q, VSTAR_EPI_NONE);
-  }
-  last_w8a8_mx = mx;
-  last_w8a8_chain = chain ? 2 : mx ? 1 : 0;
-  // Shared prefix (VSTAR_F_SHARE_PREFIX, psh_Lp > 0): the first Lp positions of every sequence are the same tokens, so they run
+  const bool chain = mx && w8a8_mx_env() >= 2 && H % 256 == 0 &&
+                     gemm_mx_supported(w8_residual(latt, b0->o, b0->o8, W8_CHAIN, rows), VSTAR_EPI_NONE) &&
+                     gemm_mx_supported(w8_qkv(*b0, W8_CHAIN, rows, g), VSTAR_EPI_NONE);
+  const int level = chain ? W8_CHAIN : mx ? W8_MX : W8_TOKEN;
+  last_w8a8_chain = level;
+  // Shared prefix (VSTAR_F_SHARE_PREFIX, g.Lp > 0): the first Lp positions of every sequence are the same tokens, so they run
   // ONCE, as a sequence of their own in the rows [Lp, 2 Lp) of slot `nseq` of the activation buffers.  The linears see the
   // compact row set {rows [Lp, S) of every sequence} + {the prefix rows} through a periodic row map (group S - Lp, stride S,
   // offset Lp: the partial last group lands exactly on the prefix rows); row-wise kernels simply run over all buffer rows;
   // the attention runs unchanged over the full sequences after the prefix's q|k|v rows were copied to the head of each, plus
   // one small launch for the prefix sequence itself.
-  const int Lp = w8 ? 0 : psh_Lp;
+  const int Lp = w8 ? 0 : g.Lp;
   const bool fold = fold_norms && !w8;
   const int Sr = S - Lp;
   const int M = Lp ? nseq * Sr + Lp : rows;             // rows of the linears
   const int nrows = Lp ? rows + 2 * Lp : rows;          // rows of the row-wise kernels (slot nseq: [0, 2 Lp))
   const size_t pre = (size_t)rows + Lp;                 // first buffer row of the prefix sequence
-  struct MapGuard {                                      // the row map never outlives this call (early error returns included)
-    vstar_engine* e;
-    ~MapGuard() { e->map_group = 0; }
-  } guard{this};
-  auto set_map = [&](bool on) {
-    map_group = (on && Lp) ? Sr : 0;
-    map_gstride = S;
-    map_off = Lp;
+  auto mapped = [&](GemmParams p) {                     // the compact row set on both sides of a linear: row r -> (r / Sr) * S + Lp + r % Sr
+    if (Lp) { p.a_group = p.c_group = Sr; p.a_gstride = p.c_gstride = S; p.a_off = p.c_off = Lp; }
+    return p;
   };
   for (int i = 0; i < c.llm_layers; ++i) {
     LlmBlock& b = llm[i];
-    set_map(true);
-    if (chain) {
-      // rows of lx as block-scaled fp8 (lq8 / lmxx) + their 1 / rms (lr): from the splice for the first block, from the previous
-      // block's down_proj epilogue afterwards
-      if (i == 0) {
-        KCHK(quantize_rows_mx(lx, H, lq8, H, lmxx, rows, H, stream));
-        KCHK(rms_rstd_rows(lx, rows, H, c.llm_rms_eps, lr, stream));
+    if (w8) {
+      if (chain) {
+        // rows of lx as block-scaled fp8 (lq8 / lmxx) + their 1 / rms (lr): from the splice for the first block, from the previous
+        // block's down_proj epilogue afterwards
+        if (i == 0) {
+          KCHK(quantize_rows_mx(lx, H, lq8, H, lmxx, rows, H, stream));
+          KCHK(rms_rstd_rows(lx, rows, H, c.llm_rms_eps, lr, stream));
+        } else {
+          KCHK(rms_rstd_partials(lpart, H / 64, rows, H, c.llm_rms_eps, lr, stream));
+        }
       } else {
-        KCHK(rms_rstd_partials(lpart, H / 64, rows, H, c.llm_rms_eps, lr, stream));
+        KCHK(rmsnorm_quant_fp8(lx, b.in_norm, lq8, lsa, rows, H, c.llm_rms_eps, stream));
       }
-      RC(lin8(lq8, lr, b.qkv, b.qkv8f, lqkv, 3 * H, rows, VSTAR_EPI_NONE, nullptr, 0, fused_rope ? rope : nullptr, S, 2 * H, lmxx));
-      if (!fused_rope) KCHK(attn_prepare(lqkv, rope, nseq, S, c.llm_heads, 128, stream, grp_R0, grp_Lc));
-    } else if (w8) {
-      KCHK(rmsnorm_quant_fp8(lx, b.in_norm, lq8, lsa, rows, H, c.llm_rms_eps, stream));
-      RC(lin8(lq8, lsa, b.qkv, b.qkv8, lqkv, 3 * H, rows, VSTAR_EPI_NONE, nullptr, 0, fused_rope ? rope : nullptr, S, 2 * H));
-      if (!fused_rope) KCHK(attn_prepare(lqkv, rope, nseq, S, c.llm_heads, 128, stream, grp_R0, grp_Lc));
+      RC(gemm(w8_qkv(b, level, rows, g), VSTAR_EPI_NONE, false));
+      if (!fused_rope) KCHK(attn_prepare(lqkv, rope, nseq, S, c.llm_heads, 128, stream, g.R0, g.Lc));
     } else {
       // input RMSNorm: folded (statistics from x for the first block — the spliced embeddings — else from the partial sums the
       // previous block's down_proj epilogue wrote next to the residual stream) or the norm kernel
-      GemmParams p{};
       if (fold) {
         if (i == 0) KCHK(rms_rstd_rows(lx, nrows, H, c.llm_rms_eps, lr, stream));
         else KCHK(rms_rstd_partials(lpart, H / 64, nrows, H, c.llm_rms_eps, lr, stream));
-        p.A = lx; p.row_scale = lr;
       } else {
         KCHK(rmsnorm_lp(lx, b.in_norm, lh, nrows, H, c.llm_rms_eps, nullptr, stream));
-        p.A = lh;
       }
       // q|k|v projection; RoPE rides in the GEMM epilogue when the 256^2 kernel takes the shape (else a separate pass)
-      p.lda = H; p.W = b.qkv.W; p.C = lqkv; p.ldc = 3 * H; p.M = M; p.N = b.qkv.N; p.K = b.qkv.K;
-      if (Lp) { p.a_group = p.c_group = Sr; p.a_gstride = p.c_gstride = S; p.a_off = p.c_off = Lp; }
+      GemmParams p = mapped(lin_params(fold ? lx : lh, H, b.qkv, lqkv, 3 * H, M));
+      if (fold) p.row_scale = lr;
       const bool fused = fused_rope && gemm256_eligible(p);
       if (fused) {
-        p.rope_cs = rope; p.rope_S = Lp ? Sr : S; p.rope_cols = 2 * H; p.rope_R0 = grp_R0; p.rope_Lc = grp_Lc;
+        p.rope_cs = rope; p.rope_S = Lp ? Sr : S; p.rope_cols = 2 * H; p.rope_R0 = g.R0; p.rope_Lc = g.Lc;
         if (Lp) { p.rope_pos0 = Lp; p.rope_tail = nseq * Sr; }
       }
       RC(gemm(p, VSTAR_EPI_NONE, false));
       if (!fused) {
-        KCHK(attn_prepare(lqkv, rope, nseq, S, c.llm_heads, 128, stream, grp_R0, grp_Lc));     // (prefix rows of the sequences: overwritten below)
+        KCHK(attn_prepare(lqkv, rope, nseq, S, c.llm_heads, 128, stream, g.R0, g.Lc));     // (prefix rows of the sequences: overwritten below)
         if (Lp) KCHK(attn_prepare(lqkv + pre * 3 * H, rope, 1, Lp, c.llm_heads, 128, stream, 0, 0));
       }
     }
@@ -688,13 +707,13 @@ int vstar_engine::llm_forward(int nseq, int S, int nsel) {
       KCHK(bcast_rows(lqkv + pre * 3 * H, lqkv, nseq, S, Lp, 3 * H, 3 * H, stream));
       KCHK(attn_forward(lqkv + pre * 3 * H, latt + pre * H, 1, Lp, c.llm_heads, 128, 1, att_scale, stream, 0, 0));
     }
-    if (mx && i + 1 < c.llm_layers) KCHK(attn_forward_mx(lqkv, (uint8_t*)latt, lmx, nseq, S, c.llm_heads, att_scale, stream, grp_R0, grp_Lc));
-    else KCHK(attn_forward(lqkv, latt, nseq, S, c.llm_heads, 128, 1, att_scale, stream, grp_R0, grp_Lc));
+    if (mx && i + 1 < c.llm_layers) KCHK(attn_forward_mx(lqkv, (uint8_t*)latt, lmx, nseq, S, c.llm_heads, att_scale, stream, g.R0, g.Lc));
+    else KCHK(attn_forward(lqkv, latt, nseq, S, c.llm_heads, 128, 1, att_scale, stream, g.R0, g.Lc));
     if (i + 1 == c.llm_layers) {
       // Last block: only the [LOC]-1 row and the verify rows are ever read (VSM.py:465-473), and every op after the
-      // attention is row-wise, so o_proj / MLP run on those gathered rows only (row-wise ops: bit-identical).
+      // attention is row-wise, so o_proj / MLP run on those gathered rows only (row-wise ops: bit-identical; no row map).
       // (W8A8 mode: these few rows stay on the bf16 weights — the weight-bound regime gains nothing from fp8 MFMA.)
-      set_map(false);
+      const int nsel = g.nsel;
       KCHK(gather_rows(latt, d_rowidx, sel_att, nsel, H, stream));
       KCHK(gather_rows(lx, d_rowidx, sel_x, nsel, H, stream));
       RC(lin(sel_att, H, b.o, sel_x, H, nsel, VSTAR_EPI_NONE, sel_x, H));
@@ -703,38 +722,29 @@ int vstar_engine::llm_forward(int nseq, int S, int nsel) {
       RC(lin(sel_act, c.llm_mlp, b.down, sel_x, H, nsel, VSTAR_EPI_NONE, sel_x, H));
       break;
     }
-    if (chain) {
-      RC(lin8((const uint8_t*)latt, nullptr, b.o, b.o8, lx, H, rows, VSTAR_EPI_NONE, lx, H, nullptr, 0, 0, lmx, lmxx, lq8, lpart));
-      KCHK(rms_rstd_partials(lpart, H / 64, rows, H, c.llm_rms_eps, lr, stream));
-      RC(lin8(lq8, lr, b.gate_up, b.gate_up8f, lact, c.llm_mlp, rows, VSTAR_EPI_SILU_MUL, nullptr, 0, nullptr, 0, 0, lmxx, lmx));
-      RC(lin8((const uint8_t*)lact, nullptr, b.down, b.down8, lx, H, rows, VSTAR_EPI_NONE, lx, H, nullptr, 0, 0, lmx, lmxx, lq8, lpart));
-    } else if (mx) {
-      RC(lin8((const uint8_t*)latt, nullptr, b.o, b.o8, lx, H, rows, VSTAR_EPI_NONE, lx, H, nullptr, 0, 0, lmx, nullptr));
-      KCHK(rmsnorm_quant_fp8(lx, b.post_norm, lq8, lsa, rows, H, c.llm_rms_eps, stream));
-      RC(lin8(lq8, lsa, b.gate_up, b.gate_up8, lact, c.llm_mlp, rows, VSTAR_EPI_SILU_MUL, nullptr, 0, nullptr, 0, 0, nullptr, lmx));
-      RC(lin8((const uint8_t*)lact, nullptr, b.down, b.down8, lx, H, rows, VSTAR_EPI_NONE, lx, H, nullptr, 0, 0, lmx, nullptr));
-    } else if (w8) {
-      KCHK(quantize_rows_fp8(latt, H, lq8, H, lsa, rows, H, stream));
-      RC(lin8(lq8, lsa, b.o, b.o8, lx, H, rows, VSTAR_EPI_NONE, lx, H));
-      KCHK(rmsnorm_quant_fp8(lx, b.post_norm, lq8, lsa, rows, H, c.llm_rms_eps, stream));
-      RC(lin8(lq8, lsa, b.gate_up, b.gate_up8, lact, c.llm_mlp, rows, VSTAR_EPI_SILU_MUL, nullptr, 0));
-      KCHK(quantize_rows_fp8(lact, c.llm_mlp, lq8, c.llm_mlp, lsa, rows, c.llm_mlp, stream));
-      RC(lin8(lq8, lsa, b.down, b.down8, lx, H, rows, VSTAR_EPI_NONE, lx, H));
+    if (w8) {
+      // o_proj, post-attention RMSNorm, gate|up, down_proj; a level's stand-alone quantisation passes run where its producers do not quantise
+      if (level == W8_TOKEN) KCHK(quantize_rows_fp8(latt, H, lq8, H, lsa, rows, H, stream));
+      RC(gemm(w8_residual(latt, b.o, b.o8, level, rows), VSTAR_EPI_NONE, false));
+      if (chain) KCHK(rms_rstd_partials(lpart, H / 64, rows, H, c.llm_rms_eps, lr, stream));
+      else KCHK(rmsnorm_quant_fp8(lx, b.post_norm, lq8, lsa, rows, H, c.llm_rms_eps, stream));
+      RC(gemm(w8_gate_up(b, level, rows), VSTAR_EPI_SILU_MUL, false));
+      if (level == W8_TOKEN) KCHK(quantize_rows_fp8(lact, c.llm_mlp, lq8, c.llm_mlp, lsa, rows, c.llm_mlp, stream));
+      RC(gemm(w8_residual(lact, b.down, b.down8, level, rows), VSTAR_EPI_NONE, false));
     } else {
+      // folded post-attention RMSNorm: o_proj and down_proj leave the sum-of-squares partials of the rows they write, gate|up scales by 1 / rms
+      GemmParams o = mapped(lin_params(latt, H, b.o, lx, H, M, lx, H));
+      GemmParams gate_up = mapped(lin_params(fold ? lx : lh, H, b.gate_up, lact, c.llm_mlp, M));
+      GemmParams down = mapped(lin_params(lact, c.llm_mlp, b.down, lx, H, M, lx, H));
       if (fold) {
-        next_sumsq = lpart; next_sumsq_ld = H / 64;
-        RC(lin(latt, H, b.o, lx, H, M, VSTAR_EPI_NONE, lx, H));
-        KCHK(rms_rstd_partials(lpart, H / 64, nrows, H, c.llm_rms_eps, lr, stream));
-        next_row_scale = lr;
-        RC(lin(lx, H, b.gate_up, lact, c.llm_mlp, M, VSTAR_EPI_SILU_MUL));
-        next_sumsq = lpart; next_sumsq_ld = H / 64;
-        RC(lin(lact, c.llm_mlp, b.down, lx, H, M, VSTAR_EPI_NONE, lx, H));
-      } else {
-        RC(lin(latt, H, b.o, lx, H, M, VSTAR_EPI_NONE, lx, H));
-        KCHK(rmsnorm_lp(lx, b.post_norm, lh, nrows, H, c.llm_rms_eps, nullptr, stream));
-        RC(lin(lh, H, b.gate_up, lact, c.llm_mlp, M, VSTAR_EPI_SILU_MUL));
-        RC(lin(lact, c.llm_mlp, b.down, lx, H, M, VSTAR_EPI_NONE, lx, H));
+        o.sumsq_out = down.sumsq_out = lpart; o.sumsq_ld = down.sumsq_ld = H / 64;
+        gate_up.row_scale = lr;
       }
+      RC(gemm(o, VSTAR_EPI_NONE, false));
+      if (fold) KCHK(rms_rstd_partials(lpart, H / 64, nrows, H, c.llm_rms_eps, lr, stream));
+      else KCHK(rmsnorm_lp(lx, b.post_norm, lh, nrows, H, c.llm_rms_eps, nullptr, stream));
+      RC(gemm(gate_up, VSTAR_EPI_SILU_MUL, false));
+      RC(gemm(down, VSTAR_EPI_NONE, false));
     }
   }
   return 0;
@@ -943,7 +953,6 @@ int vstar_engine::score(int B, const lp_t* clip_pix, const lp_t* owl_pix, const 
   last_B = B; last_S = S;
   const bool graphs_on = score_graph_on;
   const bool dev_pix = (flags & (VSTAR_F_INTERNAL_PIXELS | VSTAR_F_DEVICE_INPUTS)) != 0;
-  grp_R0 = grp_Lc = 0;      // host-side state of the pass: reset HERE, not in score_body — a replayed graph never runs that code
   // Not for VSTAR_F_NO_SYNC callers: the graph's H2D nodes read the single pinned staging buffers asynchronously, so a second
   // un-synchronised call would overwrite them before the first graph's copy has run (the eager path stages pageable `ids` at call
   // time and has no such window).
@@ -1002,26 +1011,15 @@ int vstar_engine::score_body(int B, int L, int n_verify, unsigned flags, int img
   const bool forked = !skip_owl && fork_owl(opix, B, &frc_owl);       // OWL-ViT side of the graph on stream2 (small batches)
   OwlJoinGuard join_guard{stream2, forked || frc_owl != 0};
   RC(frc_owl);
-  grp_R0 = grp_Lc = 0;
 
   // ---- a2: CLIP tower (clip_encoder.py:31-60) ----
   RC(run_tower(clip, cpix, B));
-  // ---- a3+a4: mm_projector on the patch rows, written straight into the spliced LLaMA input (llava_arch.py:93-96,185-208)
-  {
-    GemmParams p{};
-    p.A = clip.x; p.lda = clip.hidden; p.a_group = P; p.a_gstride = clip.N; p.a_off = 1;
-    p.W = projector.W; p.bias = projector.b; p.res = nullptr;
-    p.C = lx; p.ldc = H; p.c_group = P; p.c_gstride = S; p.c_off = img_col;
-    p.M = B * P; p.N = projector.N; p.K = projector.K;
-    RC(gemm(p, VSTAR_EPI_NONE, false));
-  }
+  // ---- a3+a4: mm_projector output spliced into the LLaMA input at the image column
+  RC(project_clip(B, lx, H, P, S, img_col));
   KCHK(llm_embed_text(d_ids, L, img_col, P, embed, c.llm_vocab, lx, B, H, stream));
-  psh_Lp = psh;
-  if (psh_Lp)
-    HIPCHK(hipMemcpyAsync(lx + ((size_t)B * S + psh_Lp) * H, lx, (size_t)psh_Lp * H * sizeof(lp_t), hipMemcpyDeviceToDevice, stream));
-  const int frc = llm_forward(B, S, B * (1 + n_verify));
-  psh_Lp = 0;
-  RC(frc);
+  if (psh)
+    HIPCHK(hipMemcpyAsync(lx + ((size_t)B * S + psh) * H, lx, (size_t)psh * H * sizeof(lp_t), hipMemcpyDeviceToDevice, stream));
+  RC(llm_forward(LlmPass{B, S, B * (1 + n_verify), 0, 0, psh}));
   RC(llm_heads(B, n_verify));
   if (!skip_owl) {
     if (forked) {
@@ -1107,17 +1105,9 @@ int vstar_engine::score_grouped(int G, int T, const lp_t* clip_pix, const lp_t* 
   last_B = nrec; last_S = S;
   // ---- a2 + a3: CLIP tower and projector for the G crops -> feature table; a4: splice by row sources ----
   RC(run_tower(clip, cpix, G));
-  {
-    GemmParams p{};
-    p.A = clip.x; p.lda = clip.hidden; p.a_group = P; p.a_gstride = clip.N; p.a_off = 1;
-    p.W = projector.W; p.bias = projector.b; p.C = grp_feats; p.ldc = H; p.M = G * P; p.N = projector.N; p.K = projector.K;
-    RC(gemm(p, VSTAR_EPI_NONE, false));
-  }
+  RC(project_clip(G, grp_feats, H));
   KCHK(embed_rows(d_src, embed, c.llm_vocab, grp_feats, (int64_t)G * P, lx, G * S, H, stream));
-  grp_R0 = R0; grp_Lc = Lc;
-  const int rc = llm_forward(G, S, nrec * (1 + n_verify));
-  grp_R0 = grp_Lc = 0;
-  RC(rc);
+  RC(llm_forward(LlmPass{G, S, nrec * (1 + n_verify), R0, Lc, 0}));
   RC(llm_heads(nrec, n_verify));
   if (forked) {
     HIPCHK(hipStreamWaitEvent(stream, ev_join, 0));
@@ -1161,12 +1151,7 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
     cpix = d_clip_pix;
   }
   RC(run_tower(clip, cpix, 1));
-  {
-    GemmParams p{};
-    p.A = clip.x; p.lda = c.clip_hidden; p.a_group = P; p.a_gstride = clip.N; p.a_off = 1;
-    p.W = projector.W; p.bias = projector.b; p.C = gen_feats; p.ldc = H; p.M = P; p.N = projector.N; p.K = projector.K;
-    RC(gemm(p, VSTAR_EPI_NONE, false));
-  }
+  RC(project_clip(1, gen_feats, H));
   // ---- prefill the spliced prompt, then one decode step per new token ----
   std::vector<int32_t> rows;
   rows.reserve((size_t)L - 1 + P);

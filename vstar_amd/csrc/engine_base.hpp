@@ -212,26 +212,21 @@ struct EngineBase {
     }
     return 0;
   }
+  // The plain launch of a packed Linear: identity row maps and nothing else set.  A call that needs more (folded-norm row scale,
+  // statistics output, a row map, fused RoPE) takes these, sets the named GemmParams fields and calls gemm() itself.
+  static GemmParams lin_params(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, const lp_t* res = nullptr,
+                               int64_t ldr = 0) {
+    GemmParams p{};
+    p.A = A; p.lda = lda;
+    p.W = L.W; p.bias = L.b; p.res = res; p.ldr = ldr;
+    p.C = C; p.ldc = ldc;
+    p.M = M; p.N = L.N; p.K = L.K;
+    return p;
+  }
   int lin(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
           const lp_t* res = nullptr, int64_t ldr = 0, bool f32 = false) {
-    GemmParams p{};
-    p.A = A; p.lda = lda; p.a_group = 0;
-    p.W = L.W; p.bias = L.b; p.res = res; p.ldr = ldr;
-    p.C = C; p.ldc = ldc; p.c_group = 0;
-    p.M = M; p.N = L.N; p.K = L.K;
-    p.row_scale = next_row_scale; p.sumsq_out = next_sumsq; p.sumsq_ld = next_sumsq_ld;     // one-shot (folded norms)
-    p.stats_sum = next_stats_sum;
-    next_row_scale = nullptr; next_sumsq = nullptr; next_sumsq_ld = 0; next_stats_sum = 0;
-    if (map_group > 0) {      // row map in force (shared-prefix LLaMA pass): compact row r -> (r / group) * gstride + off + r % group
-      p.a_group = p.c_group = map_group;
-      p.a_gstride = p.c_gstride = map_gstride;
-      p.a_off = p.c_off = map_off;
-    }
-    return gemm(p, epi, f32);
+    return gemm(lin_params(A, lda, L, C, ldc, M, res, ldr), epi, f32);
   }
-  int map_group = 0; int64_t map_gstride = 0, map_off = 0;
-  const float* next_row_scale = nullptr; float* next_sumsq = nullptr; int next_sumsq_ld = 0;   // consumed by the next lin()
-  int next_stats_sum = 0;
   bool fold_vit_norms = true;          // VSTAR_FOLD_NORMS=0 / VSTAR_FOLD_VIT_NORMS=0: the LayerNorm kernels (the reference's rounding points)
   void collect_profile() {
     if (!profile) return;
@@ -363,16 +358,20 @@ inline int EngineBase::run_tower(VitTower& t, const lp_t* pix, int B) {
       VitBlock& b = t.blocks[i];
       if (i == 0) KCHK(ln_rstd_rows(t.x, rows, C, 1e-5f, t.rstd, stream));
       else KCHK(ln_rstd_partials(t.part, 2 * nsp, rows, C, 1e-5f, t.rstd, stream));
-      next_row_scale = t.rstd;
-      RC(lin(t.x, C, b.qkv, t.qkv, 3 * C, rows));
+      GemmParams qkv = lin_params(t.x, C, b.qkv, t.qkv, 3 * C, rows);
+      qkv.row_scale = t.rstd;
+      RC(gemm(qkv, VSTAR_EPI_NONE, false));
       KCHK(attn_forward(t.qkv, t.att, B, t.N, t.heads, 64, 0, 0.125f, stream));
-      next_sumsq = t.part; next_sumsq_ld = 2 * nsp; next_stats_sum = nsp;
-      RC(lin(t.att, C, b.out, t.x, C, rows, VSTAR_EPI_NONE, t.x, C));
+      GemmParams out = lin_params(t.att, C, b.out, t.x, C, rows, t.x, C);
+      out.sumsq_out = t.part; out.sumsq_ld = 2 * nsp; out.stats_sum = nsp;
+      RC(gemm(out, VSTAR_EPI_NONE, false));
       KCHK(ln_rstd_partials(t.part, 2 * nsp, rows, C, 1e-5f, t.rstd, stream));
-      next_row_scale = t.rstd;
-      RC(lin(t.x, C, b.fc1, t.mlp_buf, t.mlp, rows, VSTAR_EPI_QUICK_GELU));
-      if (i + 1 < t.nblocks) { next_sumsq = t.part; next_sumsq_ld = 2 * nsp; next_stats_sum = nsp; }
-      RC(lin(t.mlp_buf, t.mlp, b.fc2, t.x, C, rows, VSTAR_EPI_NONE, t.x, C));
+      GemmParams fc1 = lin_params(t.x, C, b.fc1, t.mlp_buf, t.mlp, rows);
+      fc1.row_scale = t.rstd;
+      RC(gemm(fc1, VSTAR_EPI_QUICK_GELU, false));
+      GemmParams fc2 = lin_params(t.mlp_buf, t.mlp, b.fc2, t.x, C, rows, t.x, C);
+      if (i + 1 < t.nblocks) { fc2.sumsq_out = t.part; fc2.sumsq_ld = 2 * nsp; fc2.stats_sum = nsp; }
+      RC(gemm(fc2, VSTAR_EPI_NONE, false));
     }
     return 0;
   }
