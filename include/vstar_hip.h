@@ -267,8 +267,16 @@ enum { VSTAR_EPI_NONE = 0, VSTAR_EPI_QUICK_GELU = 1, VSTAR_EPI_GELU = 2, VSTAR_E
        VSTAR_EPI_TILE128 = 0x200, /* OR-ed into `epilogue`: force the 128x128 kernel for this call */
        VSTAR_EPI_TILE256 = 0x400, /* OR-ed into `epilogue`: force the 8-wave 256x256 kernel; VSTAR_ERR_INVALID when the shape is outside
                                      its domain (M >= 1024, N >= 256, K % 128 == 0) — never silently re-routed */
-       VSTAR_EPI_TILE4W = 0x800   /* OR-ed into `epilogue`: force the 4-wave / AGPR 256x256 kernel (gemm4w.hip); error outside its
-                                     domain (M % 256 == 0, N % 256 == 0, K % 128 == 0, 16-byte aligned operands, bf16/fp16 output) */ };
+       VSTAR_EPI_TILE4W = 0x800,  /* OR-ed into `epilogue`: force the 4-wave / AGPR 256x256 kernel (gemm4w.hip); error outside its
+                                     domain (M % 256 == 0, N % 256 == 0, K % 128 == 0, 16-byte aligned operands, bf16/fp16 output) */
+       VSTAR_EPI_VARIANT_MASK = 0x7000 /* a 3-bit field of `epilogue`, VSTAR_EPI_VARIANT(v): run variant v of the 128-row family for this
+                                     call — 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 / 128 x 64 / 128 x 256 tile;
+                                     0 = the dispatcher decides (shape, CU count, VSTAR_GEMM128_STAGES).  Implies VSTAR_EPI_TILE128 and
+                                     keeps the ragged-round split out.  VSTAR_ERR_INVALID, nothing launched, for any other value and
+                                     next to VSTAR_EPI_TILE256, VSTAR_EPI_TILE4W or a fused-RoPE request — never silently re-routed.
+                                     Taken by vstar_op_gemm, vstar_op_gemm_norm, vstar_op_gemm_ex and vstar_op_gemm_plan;
+                                     vstar_op_gemm_last_mode() tells what ran */ };
+#define VSTAR_EPI_VARIANT(v) ((v) << 12)
 
 /* C[M,N] = epi(A[M,K] @ W[N,K]^T + bias) (+ residual).  bf16 in, fp32 accumulate (MFMA), bf16 or fp32 out.
  * Replaces every nn.Linear / conv-as-GEMM on the path (SURVEY.md §8d GEMM shape list).
@@ -299,6 +307,12 @@ int vstar_op_ln_fold(void* stream, uint16_t* dev_W, uint16_t* dev_bias, const ui
  * rounds of 256x256 tiles over the leading rows and the ragged last round's rows as 128x128 tiles — bit-identical to either
  * kernel alone), or 0 (nothing launched).  Lets a test assert that it exercised the kernel it was written for, whatever the dispatcher's heuristics do. */
 int vstar_op_gemm_last_tile(void);
+/* Which variant of the 128-row family the calling thread's last call of the GEMM dispatcher ran (a dry run through
+ * vstar_op_gemm_plan does not count): 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 / 128 x 64 / 128 x 256 tile;
+ * 0 when that call did not reach the family (a 256 x 256 kernel, or the dispatcher refused it).  After a split launch
+ * (vstar_op_gemm_last_tile() == 384) it is the variant of the trailing 128-row part, as in vstar_op_gemm_plan.  With
+ * VSTAR_EPI_VARIANT(v) in `epilogue` it is v, or the call failed. */
+int vstar_op_gemm_last_mode(void);
 /* Dispatcher dry run (host only, no GPU needed, nothing is launched): which kernel vstar_op_gemm / the engine would pick for
  * C[M,N] = A[M,K] · W^T with this epilogue (+ residual, + the fused-RoPE epilogue of the LLaMA qkv projection) on a device with
  * `cus` compute units.  Returns 10 * tile + variant: tile as vstar_op_gemm_last_tile (128, 256, 384 = split launch, 2560 = the
@@ -359,8 +373,8 @@ int vstar_w8a8_mx_active(vstar_handle* h);
  *     plain          m % rope_S
  *     grouped        (rope_R0 > 0)   q = m % rope_S; q >= rope_R0 ? rope_Lc + ((q - rope_R0) & 31) : q
  *     shared prefix  (rope_tail > 0) m >= rope_tail ? m - rope_tail : m % rope_S + rope_pos0
- *   `epilogue` takes the VSTAR_EPI_TILE* bits (not VSTAR_EPI_NOSYNC); VSTAR_GEMM_DEBUG in the environment as in vstar_op_gemm.
- *   Refused besides the extents: VSTAR_EPI_TILE4W with a row map; rope_cs with VSTAR_EPI_TILE128, with an epilogue other than
+ *   `epilogue` takes the VSTAR_EPI_TILE* bits and VSTAR_EPI_VARIANT(v) (not VSTAR_EPI_NOSYNC); VSTAR_GEMM_DEBUG in the environment as in vstar_op_gemm.
+ *   Refused besides the extents: VSTAR_EPI_TILE4W with a row map; rope_cs with VSTAR_EPI_TILE128 or VSTAR_EPI_VARIANT(v), with an epilogue other than
  *   VSTAR_EPI_NONE, with sumsq_out, or outside the 256 x 256 kernels' domain; rope_R0 together with rope_tail; stats_sum without
  *   sumsq_out; a C row map that sends two rows to one. */
 typedef struct vstar_gemm_ex {

@@ -191,19 +191,21 @@ class MapProbe:
     sumsq: Optional[np.ndarray] = None          # [c_rows, N / 64] float64, exact
 
 
-def map_probe(M, N, K, am: RowMap, cm: RowMap, scaled=False) -> MapProbe:
-    """Compact row r of A is one-hot at column r % K, so C[crow(r), n] = W[n, r % K]; W is asymmetric.  Buffer rows no compact row
-    maps to hold 3.0 everywhere (A) / a scale of 3 / a residual of 100: reading one of them changes every output of the row.
+def map_probe(M, N, K, am: RowMap, cm: RowMap, scaled=False, col=None) -> MapProbe:
+    """Compact row r of A is one-hot at column col[r] (default r % K), so C[crow(r), n] = W[n, col[r]]; W is asymmetric.  Buffer rows
+    no compact row maps to hold 3.0 everywhere (A) / a scale of 3 / a residual of 100: reading one of them changes every output of the row.
     scaled: row_scale[arow(r)] = 2^(r % 5 - 2) and res[crow(r), n] = (r + n) % 8, W entries below 13 so that every stored value is
     a multiple of 1/4 below 64 and the sums of squares of 64 of them are exact in fp32 in any order."""
     ar, cr = touched_rows(M, am), touched_rows(M, cm)
     a_rows, c_rows = int(ar.max()) + 1, int(cr.max()) + 1
     A = np.full((a_rows, K), 3.0, F32)
+    col = np.arange(M) % K if col is None else np.asarray(col, np.int64)
+    assert col.shape == (M,) and (0 <= col).all() and (col < K).all()
     A[ar] = 0
-    A[ar, np.arange(M) % K] = 1
+    A[ar, col] = 1
     n, k = np.arange(N)[:, None], np.arange(K)[None, :]
     W = ((n * K + k) % (13 if scaled else 251)).astype(F32)
-    acc = W[:, np.arange(M) % K].T                                   # [M, N], exact
+    acc = W[:, col].T                                                # [M, N], exact
     written = np.zeros(c_rows, bool)
     written[cr] = True
     C = np.zeros((c_rows, N), F32)

@@ -66,3 +66,35 @@ def test_dispatch_rules():
     # the decision depends on the device's CU count (MI300X: 304): same shapes, another table — and no launch, no GPU, either way
     assert plan(lib, 32, "o", cus=304) != plan(lib, 32, "o", cus=256)
     assert lib.vstar_op_gemm_plan(0, 16, 64, 0, 0, 0, 256) < 0
+
+
+@pytest.mark.parametrize("cus", [256, 304])
+@pytest.mark.parametrize("variant", [2, 5, 6, 7])
+def test_forced_variant_is_the_plan(variant, cus):
+    """VSTAR_EPI_VARIANT(v): that kernel of the 128-row family for every shape of the path, whatever the heuristics and the CU count
+    would pick (no 256^2 kernel, no split) — with and without an explicit VSTAR_EPI_TILE128."""
+    lib = _lib.load()
+    for B in sorted(EXPECTED):
+        for name, (rows, N, K, epi, res, _) in SHAPES.items():
+            for flags in (_lib.EPI_VARIANT(variant), _lib.EPI_VARIANT(variant) | _lib.EPI_TILE128):
+                assert lib.vstar_op_gemm_plan(B * rows, N, K, epi | flags, res, 0, cus) == 1280 + variant, (B, name)
+
+
+def test_forced_variant_refusals():
+    """A variant next to a request only the 256^2 kernels serve, or a value that names no kernel: refused, never re-routed."""
+    lib = _lib.load()
+    for name in SHAPES:
+        for v in (2, 5, 6, 7):
+            assert plan(lib, 32, name, flags=_lib.EPI_VARIANT(v) | _lib.EPI_TILE256) == -1
+            assert b"VSTAR_EPI_TILE256" in lib.vstar_last_error(None)
+            assert plan(lib, 32, name, flags=_lib.EPI_VARIANT(v) | _lib.EPI_TILE4W) == -1
+        for v in (1, 3, 4):
+            assert plan(lib, 1, name, flags=_lib.EPI_VARIANT(v)) == -1
+            assert b"2, 5, 6 and 7" in lib.vstar_last_error(None)
+    # the fused-RoPE epilogue exists only in the 256^2 kernels
+    assert lib.vstar_op_gemm_plan(32 * S, 12288, 4096, _lib.EPI_VARIANT(7), 0, 1, 256) == -1
+    assert b"RoPE" in lib.vstar_last_error(None)
+    assert _lib.EPI_VARIANT(7) == _lib.EPI_VARIANT_MASK == 0x7000
+    # a dry run does not count as the thread's last launch
+    before = lib.vstar_op_gemm_last_mode()
+    assert plan(lib, 1, "o") == 1285 and lib.vstar_op_gemm_last_mode() == before

@@ -23,8 +23,9 @@ def _pad_w(w):  # library contract: W allocated to a multiple of 256 rows
     return out
 
 
-def _gemm(lib, a, w, bias=None, res=None, epi=0, f32=False, n=None, tile=0):
-    """tile: 0 = dispatcher's choice, 128 / 256 = force that kernel AND assert it is the one that ran."""
+def _gemm(lib, a, w, bias=None, res=None, epi=0, f32=False, n=None, tile=0, variant=0):
+    """tile: 0 = dispatcher's choice, 128 / 256 = force that kernel AND assert it is the one that ran.
+    variant: 0 = dispatcher's choice, 2 / 5 / 6 / 7 = request that kernel of the 128-row family AND assert it is the one that ran."""
     M, K = a.shape
     N = n if n is not None else w.shape[0]
     n_out = N // 2 if epi == _lib.EPI_SILU_MUL else N
@@ -32,12 +33,15 @@ def _gemm(lib, a, w, bias=None, res=None, epi=0, f32=False, n=None, tile=0):
     wp = _pad_w(w)
     flag = {0: 0, 128: _lib.EPI_TILE128, 256: _lib.EPI_TILE256, _lib.TILE_4W: _lib.EPI_TILE4W}[tile]
     rc = lib.vstar_op_gemm(None, P(a), K, P(wp), P(bias), P(res), n_out if res is not None else 0, P(c), n_out,
-                           1 if f32 else 0, M, N, K, epi | flag)
+                           1 if f32 else 0, M, N, K, epi | flag | _lib.EPI_VARIANT(variant))
     assert rc == 0, lib.vstar_last_error(None)
     ran = lib.vstar_op_gemm_last_tile()
     assert ran in (128, 256, 384, _lib.TILE_4W)
     if tile:
         assert ran == tile, f"asked for the {tile}^2 kernel, the {ran}^2 kernel ran"
+    if variant:
+        mode = lib.vstar_op_gemm_last_mode()
+        assert ran == 128 and mode == variant, f"asked for variant {variant} of the 128-row family, tile {ran} variant {mode} ran"
     torch.cuda.synchronize()
     return c
 
@@ -337,6 +341,10 @@ def test_gemm_ragged_round_split_is_bit_identical(lib, cuda, M, N, K, epi, use_b
         assert ran == (384 if split else 256), ran
 
 
+# test_gemm128_equals_gemm256: (M, N, K) -> the variant of the 128-row family the case is about (the others: dispatcher's choice)
+GEMM128_VARIANT = {(1280, 4096, 4096): 7, (1280, 8192, 2048): 7, (1150, 6912, 2048): 7, (1024, 512, 512): 5, (1100, 320, 384): 6}
+
+
 @pytest.mark.parametrize("M,N,K,epi,use_bias,use_res,f32", [
     (1030, 300, 384, 0, True, False, True),        # M and N tails, fp32 out
     (1500, 768, 256, 1, True, False, False),       # QUICK_GELU + bias (ViT fc1 form)
@@ -348,10 +356,13 @@ def test_gemm_ragged_round_split_is_bit_identical(lib, cuda, M, N, K, epi, use_b
     (1280, 4096, 4096, 0, False, True, False),     # 320 tiles of 128^2, long K: the 128 x 256 loader-wave tile (o_proj, 2 crops)
     (1280, 8192, 2048, 4, False, False, False),    # the same tile with SiLU(gate)*up
     (1150, 6912, 2048, 0, True, False, True),      # ... fp32 output, bias, M tail
+    (1024, 512, 512, 3, True, True, False),        # the 128 x 128 loader-wave tile (variant 5), RELU + bias + residual
+    (1100, 320, 384, 1, True, False, False),       # the 128 x 64 loader-wave tile (variant 6), QUICK_GELU + bias, M and N tails
 ])
 def test_gemm128_equals_gemm256(lib, cuda, M, N, K, epi, use_bias, use_res, f32):
     """Both kernels accumulate K in the same order with the same epilogue arithmetic: forced onto the same operands they
-    must agree BIT FOR BIT (this is what lets the dispatcher pick either by grid fill without changing results)."""
+    must agree BIT FOR BIT (this is what lets the dispatcher pick either by grid fill without changing results).  The cases written
+    for one loader-wave tile request it (GEMM128_VARIANT) instead of relying on the dispatcher and a 256-CU device."""
     g = torch.Generator().manual_seed(M * 3 + N + K + epi)
     a = torch.randn(M, K, generator=g).bfloat16().to(cuda)
     w = (torch.randn(N, K, generator=g) / math.sqrt(K)).bfloat16()
@@ -362,7 +373,7 @@ def test_gemm128_equals_gemm256(lib, cuda, M, N, K, epi, use_bias, use_res, f32)
     bias = torch.randn(N, generator=g).bfloat16().to(cuda) if use_bias else None
     res = torch.randn(M, n_out, generator=g).bfloat16().to(cuda) if use_res else None
     c256 = _gemm(lib, a, w, bias, res, epi=epi, f32=f32, tile=256)
-    c128 = _gemm(lib, a, w, bias, res, epi=epi, f32=f32, tile=128)
+    c128 = _gemm(lib, a, w, bias, res, epi=epi, f32=f32, tile=128, variant=GEMM128_VARIANT.get((M, N, K), 0))
     assert not torch.isnan(c256.float()).any()
     assert torch.equal(c256, c128)
 

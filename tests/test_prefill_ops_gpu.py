@@ -29,6 +29,7 @@ pytestmark = pytest.mark.gpu
 ERR_INVALID = -1
 P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
 FLAG = {128: _lib.EPI_TILE128, 256: _lib.EPI_TILE256, _lib.TILE_4W: _lib.EPI_TILE4W}
+VARIANTS = (2, 5, 6, 7)                 # of the 128-row family: double buffer, loader-wave ring on the 128 x 128 / 128 x 64 / 128 x 256 tile
 
 
 def ok(lib, rc):
@@ -66,10 +67,11 @@ def pad_w(W):
 
 class Gemm:
     """One vstar_op_gemm_ex call over freshly sentinel-filled outputs.  A / row_scale are BUFFERS (a_rows rows), res a buffer of
-    c_rows rows; the C buffer gets `ldc` columns and two rows behind the c_rows the door is told."""
+    c_rows rows; the C buffer gets `ldc` columns and two rows behind the c_rows the door is told.  variant: VSTAR_EPI_VARIANT of the
+    128-row family for this call (tile 128), and vstar_op_gemm_last_mode() must name it."""
 
     def __init__(self, lib, cuda, A, W, M, tile, *, am=R.IDENT, cm=R.IDENT, ldc=None, row_scale=None, res=None, sumsq=False, stats=False,
-                 rope=None):
+                 rope=None, variant=0):
         N, K = W.shape                      # (a device W is already padded: only for N % 256 == 0)
         assert not torch.is_tensor(W) or N % 256 == 0
         self.M, self.N = M, N
@@ -84,7 +86,7 @@ class Gemm:
         keep = [dA, dW, self.C]
         f = dict(A=P(dA), lda=K, a_rows=a_rows, a_group=am.group, a_gstride=am.gstride, a_off=am.off, W=P(dW), w_rows=dW.shape[0],
                  C=P(self.C), ldc=self.ldc, c_rows=self.c_rows, c_group=cm.group, c_gstride=cm.gstride, c_off=cm.off, M=M, N=N, K=K,
-                 epilogue=_lib.EPI_NONE | FLAG[tile])
+                 epilogue=_lib.EPI_NONE | FLAG[tile] | _lib.EPI_VARIANT(variant))
         if row_scale is not None:
             assert len(row_scale) == a_rows
             keep.append(torch.from_numpy(np.ascontiguousarray(row_scale, np.float32)).to(cuda))
@@ -110,6 +112,8 @@ class Gemm:
         g = R.gemm_ex(**f)
         ok(lib, lib.vstar_op_gemm_ex(None, ctypes.byref(g)))
         assert lib.vstar_op_gemm_last_tile() == tile, (lib.vstar_op_gemm_last_tile(), tile)
+        if variant:
+            assert tile == 128 and lib.vstar_op_gemm_last_mode() == variant, (lib.vstar_op_gemm_last_mode(), variant)
 
     def output(self):
         """[M, N] bit patterns of the compact rows, after checking that every gap row, gap column and row behind kept the sentinel."""
@@ -141,20 +145,28 @@ def err_line(name, err, gate, ref, kind):
 # ================================================================ row maps
 @pytest.mark.parametrize("scaled", [False, True], ids=["plain", "scaled"])
 @pytest.mark.parametrize("name", list(R.MAP_CASES))
-def test_row_map_probe(lib, cuda, name, scaled):
+def test_row_map_probe(lib, cuda, name, scaled, variant=0):
     """One-hot compact rows: C[crow(r), n] == W[n, r % K] in bits; with row_scale (by mapped A row), residual and sums of squares (by
     mapped C row) the stored value is still exact.  Gap rows of A / row_scale / residual hold poison."""
     (M, N, K), am, cm, tile = R.MAP_CASES[name]
     p = R.map_probe(M, N, K, am, cm, scaled)
-    g = Gemm(lib, cuda, p.A, p.W, M, tile, am=am, cm=cm, row_scale=p.row_scale, res=p.res, sumsq=p.sumsq is not None)
+    g = Gemm(lib, cuda, p.A, p.W, M, tile, am=am, cm=cm, row_scale=p.row_scale, res=p.res, sumsq=p.sumsq is not None, variant=variant)
     assert np.array_equal(g.output(), R.bits(p.C[g.cr]))
     if p.sumsq is not None:
         sq, _ = g.partials()
         assert np.array_equal(sq.astype(np.float64), p.sumsq[g.cr])
 
 
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("scaled", [False, True], ids=["plain", "scaled"])
+@pytest.mark.parametrize("name", ["g128", "g128_stats"])
+def test_row_map_probe_gemm128_variants(lib, cuda, name, scaled, variant):
+    """test_row_map_probe's 128-row cases on each of the family's four kernels, requested per call."""
+    test_row_map_probe(lib, cuda, name, scaled, variant)
+
+
 @pytest.mark.parametrize("name", list(R.MAP_CASES))
-def test_row_map_random_equals_gathered(lib, cuda, name):
+def test_row_map_random_equals_gathered(lib, cuda, name, variant=0):
     """Random inputs: the mapped call equals, bit for bit, the same forced kernel on the gathered A (row_scale, residual gathered
     likewise) with its output scattered here."""
     (M, N, K), am, cm, tile = R.MAP_CASES[name]
@@ -165,14 +177,20 @@ def test_row_map_random_equals_gathered(lib, cuda, name):
     rs = np.exp(g0.standard_normal(R.extent(M, am))).astype(np.float32)
     res = R.bf(g0.standard_normal((R.extent(M, cm), N)))
     stats = N % 64 == 0
-    mapped = Gemm(lib, cuda, A, W, M, tile, am=am, cm=cm, row_scale=rs, res=res, sumsq=stats, stats=stats)
-    dense = Gemm(lib, cuda, A[ar], W, M, tile, row_scale=rs[ar], res=res[cr], sumsq=stats, stats=stats)
+    mapped = Gemm(lib, cuda, A, W, M, tile, am=am, cm=cm, row_scale=rs, res=res, sumsq=stats, stats=stats, variant=variant)
+    dense = Gemm(lib, cuda, A[ar], W, M, tile, row_scale=rs[ar], res=res[cr], sumsq=stats, stats=stats, variant=variant)
     out = mapped.output()
     assert not np.isnan(as_f32(out)).any()
     assert np.array_equal(out, dense.output())
     if stats:
         for a, b in zip(mapped.partials(), dense.partials()):
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("name", ["g128", "g128_stats"])
+def test_row_map_random_equals_gathered_gemm128_variants(lib, cuda, name, variant):
+    test_row_map_random_equals_gathered(lib, cuda, name, variant)
 
 
 def test_gemm_ex_refusals_launch_nothing(lib, cuda):
@@ -318,7 +336,7 @@ def test_op_rope(lib, cuda, D, S, R0, Lc, B, H):
 # ================================================================ stats_sum
 @pytest.mark.parametrize("name,mapped", [(n, False) for n in R.STATS_CASES] + [(n, True) for n in R.STATS_CMAP],
                          ids=lambda v: v if isinstance(v, str) else ("c_map" if v else "identity"))
-def test_stats_sum_exact(lib, cuda, name, mapped):
+def test_stats_sum_exact(lib, cuda, name, mapped, variant=0):
     """Integer-valued C: sums of squares at [0, N/64), sums at [stats_sum, stats_sum + N/64), both equal to the float64 reference
     exactly, nothing else written (the gap column between them included).  Also through a C row map, for the kernels that take one
     (the door refuses the 4-wave kernel with a map: test_gemm_ex_refusals_launch_nothing)."""
@@ -326,11 +344,18 @@ def test_stats_sum_exact(lib, cuda, name, mapped):
     cm = R.STATS_CMAP[name] if mapped else R.IDENT
     A, W = R.int_operands(M, N, K, 3)
     C = (A.astype(np.float64) @ W.astype(np.float64).T).astype(np.float32)
-    g = Gemm(lib, cuda, A, W, M, tile, cm=cm, sumsq=True, stats=True)
+    g = Gemm(lib, cuda, A, W, M, tile, cm=cm, sumsq=True, stats=True, variant=variant)
     assert np.array_equal(g.output(), R.bits(C))
     sm, sq = R.span_sums(C)
     got_sq, got_sm = g.partials()
     assert np.array_equal(got_sq.astype(np.float64), sq) and np.array_equal(got_sm.astype(np.float64), sm)
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("mapped", [False, True], ids=["identity", "c_map"])
+def test_stats_sum_exact_gemm128_variants(lib, cuda, mapped, variant):
+    """The g128 statistics case on each of the family's four kernels, requested per call."""
+    test_stats_sum_exact(lib, cuda, "g128", mapped, variant)
 
 
 def test_stats_sum_random_kernel_families_agree(lib, cuda, monkeypatch, dv):

@@ -19,7 +19,7 @@ EXPORTS = [
     "vstar_vsm_score_batch", "vstar_upsample_mask", "vstar_debug_read", "vstar_stream", "vstar_profile_enable",
     "vstar_profile_read", "vstar_profile_read_fp8", "vstar_op_gemm", "vstar_op_layernorm", "vstar_op_rmsnorm", "vstar_op_attention",
     "vstar_op_attention_workspace", "vstar_image_set", "vstar_preprocess_crops", "vstar_heatmap_stats", "vstar_heatmap_stats_batch", "vstar_vsm_generate", "vstar_op_gemm_fp8",
-    "vstar_op_gemm_last_tile", "vstar_op_gemm_plan", "vstar_op_gemm_norm", "vstar_op_rms_rstd", "vstar_op_ln_fold", "vstar_upsample_mask_ex", "vstar_vsm_score_grouped",
+    "vstar_op_gemm_last_tile", "vstar_op_gemm_last_mode", "vstar_op_gemm_plan", "vstar_op_gemm_norm", "vstar_op_rms_rstd", "vstar_op_ln_fold", "vstar_upsample_mask_ex", "vstar_vsm_score_grouped",
     "vstar_image_set_slot", "vstar_image_set_slot_async", "vstar_preprocess_crops_slots", "vstar_comm_unique_id", "vstar_comm_init", "vstar_allgather_results",
     "vstar_comm_destroy", "vstar_build_source_hash", "vstar_op_mx_scale_bytes", "vstar_op_mx_scale_offset", "vstar_op_quantize_mx",
     "vstar_op_gemm_mx", "vstar_op_gemm_fp8_mxout", "vstar_op_attention_mx", "vstar_w8a8_mx_active",
@@ -55,6 +55,14 @@ F32, F16, BF16 = 0, 1, 2
 MAX_IMAGE_SLOTS = 64
 EPI_NONE, EPI_QUICK_GELU, EPI_GELU, EPI_RELU, EPI_SILU_MUL = range(5)
 EPI_NOSYNC, EPI_TILE128, EPI_TILE256, EPI_TILE4W = 0x100, 0x200, 0x400, 0x800
+EPI_VARIANT_MASK = 0x7000
+
+
+def EPI_VARIANT(v: int) -> int:
+    """VSTAR_EPI_VARIANT(v): variant v (2, 5, 6 or 7) of the 128-row GEMM family for this call, OR-ed into `epilogue`."""
+    return v << 12
+
+
 TILE_4W = 2564          # vstar_op_gemm_last_tile() value of the 4-wave / AGPR 256 x 256 kernel
 F_SKIP_OWL, F_DEVICE_INPUTS, F_DEVICE_OUTPUT, F_NO_SYNC, F_INTERNAL_PIXELS, F_SHARE_PREFIX = 1, 2, 4, 8, 16, 32
 
@@ -226,6 +234,8 @@ def load() -> ctypes.CDLL:
     lib.vstar_op_ln_fold.restype = c_int
     lib.vstar_op_gemm_last_tile.argtypes = []
     lib.vstar_op_gemm_last_tile.restype = c_int
+    lib.vstar_op_gemm_last_mode.argtypes = []
+    lib.vstar_op_gemm_last_mode.restype = c_int
     lib.vstar_op_gemm_plan.argtypes = [c_int] * 7
     lib.vstar_op_gemm_plan.restype = c_int
     lib.vstar_op_gemm_fp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

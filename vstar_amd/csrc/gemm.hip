@@ -25,9 +25,11 @@ namespace VS_NS {
 static thread_local bool t_plan_only = false;
 static thread_local int t_plan_cus = 0;
 static thread_local int t_last_mode = 0;
+static thread_local int t_launched_mode = 0;      // t_last_mode of the last call that was no dry run
 void gemm_set_plan(bool on, int cus) { t_plan_only = on; t_plan_cus = on ? cus : 0; }
 bool gemm_plan_only() { return t_plan_only; }
 int gemm_last_mode() { return t_last_mode; }
+int gemm_launched_mode() { return t_launched_mode; }
 
 namespace {
 
@@ -294,6 +296,7 @@ template <int EPI, bool OUT_F32, int MODE, int NW = 2>
 hipError_t launch_stages(const GemmParams& p, hipStream_t s) {
   t_last_mode = MODE == 5 ? (NW == 4 ? 7 : (NW == 1 ? 6 : 5)) : MODE;
   if (t_plan_only) return hipSuccess;
+  t_launched_mode = t_last_mode;
   static bool attr_done = false;
   auto kern = gemm128_kernel<EPI, OUT_F32, MODE, NW>;
   constexpr int bn = 64 * NW;
@@ -316,8 +319,10 @@ hipError_t launch(const GemmParams& p, hipStream_t s) {
   // Measured (profiles/r03_gemm_small_batch.txt, M = 640): o_proj 65 -> 40 us, down_proj 169 -> 104 us, CLIP fc2 54 -> 37 us;
   // with more tiles than CUs the double buffer wins by 5-15 %.  What bounds both: a CU pulls operand tiles from L2 at
   // ~65 (one workgroup) to ~88 KB/us (two) whatever the instruction (tools/probes/dma_probe.hip), and a 128^2 tile needs 32 KiB
-  // per K-tile.  VSTAR_GEMM128_STAGES=2|5|6 forces one variant (A/B runs).  Same K order in both: bit-identical results.
-  static const int force = [] { const char* e = getenv("VSTAR_GEMM128_STAGES"); return e ? atoi(e) : 0; }();
+  // per K-tile.  VSTAR_GEMM128_STAGES=2|5|6|7 forces one variant for the process (A/B runs), GemmParams::stages_force for one call
+  // (ahead of the environment; validated by gemm_lp).  Same K order in all: bit-identical results (tests/test_gemm128_gpu.py).
+  static const int env_stages = [] { const char* e = getenv("VSTAR_GEMM128_STAGES"); return e ? atoi(e) : 0; }();
+  const int force = p.stages_force ? p.stages_force : env_stages;
   const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   // 6 = loader-wave ring on the 128 x 64 tile: grids that fill less than HALF the CUs (CLIP / OWL-ViT out-proj and fc2 at small
   // batches: 40 - 114 tiles) — twice the workgroups beats the extra A traffic (12 vs 18 us, 27 vs 37 us at M = 577); between half
@@ -366,11 +371,18 @@ int gemm_device_cus() {
 hipError_t gemm_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
   t_last_tile = 0;
   t_last_mode = 0;
+  if (!t_plan_only) t_launched_mode = 0;
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (p.K % BK != 0 || p.K <= 0 || p.norm_w) return hipErrorInvalidValue;   // fused RMSNorm: skinny kernel only
   if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || (p.lda % 8)) return hipErrorInvalidValue;
   static const int env_force = [] { const char* e = getenv("VSTAR_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  const int force = p.tile_force ? p.tile_force : env_force;
+  // a per-call variant of the 128-row family (stages_force) is a request for that family: it acts as tile_force = 128 (which also
+  // keeps the ragged-round split out), and it is refused — never re-routed — next to anything only the 256^2 kernels do
+  if (p.stages_force != 0) {
+    if (p.stages_force != 2 && p.stages_force != 5 && p.stages_force != 6 && p.stages_force != 7) return hipErrorInvalidValue;
+    if ((p.tile_force != 0 && p.tile_force != 128) || p.rope_cs || p.a_scale || p.a_mx || p.c_mx) return hipErrorInvalidValue;
+  }
+  const int force = p.stages_force ? 128 : (p.tile_force ? p.tile_force : env_force);
   if (force != 0 && force != 128 && force != 256 && force != GEMM_TILE_4W) return hipErrorInvalidValue;
   if (p.a_mx || p.c_mx) {      // block-scaled W8A8 (mx.hpp) exists in the 4-wave kernel only: callers check gemm_mx_supported
     if (out_f32 || (force != 0 && force != GEMM_TILE_4W) || !gemm4w_eligible(p, epilogue, out_f32)) return hipErrorInvalidValue;

@@ -82,6 +82,11 @@ struct GemmParams {
   // kernel choice: 0 = the dispatcher decides, 128 / 256 = force that tile (256 fails with hipErrorInvalidValue when the shape
   // is not gemm256_eligible).  Process-wide default for 0 calls: environment VSTAR_GEMM_TILE (A/B runs).
   int tile_force;
+  // variant of the 128-row family: 0 = the dispatcher decides (shape, CU count, process default VSTAR_GEMM128_STAGES), 2 / 5 / 6 / 7
+  // = that variant for THIS call (gemm_last_mode() values; op-level tests).  Non-zero implies tile_force = 128 (no 256^2 kernel, no
+  // ragged-round split); any other value, or a request next to tile_force 256 / GEMM_TILE_4W, rope_cs, a_scale, a_mx or c_mx, fails
+  // with hipErrorInvalidValue — never re-routed
+  int stages_force;
   // gemm4w only, W8A8 with block-scaled activations (mx.hpp; round 6).  a_mx != null: A holds fp8 bytes whose E8M0
   // block scales (one per row and 32 k, tile-major: mx_scale_offset with m128 = M / 128) are applied inside the MFMA; w_scale as above.
   // c_mx != null (VSTAR_EPI_SILU_MUL): the epilogue writes SiLU(gate) * up as fp8 bytes to (uint8_t*)C (ldc in bytes) and the block
@@ -116,6 +121,8 @@ bool gemm_plan_only();
 // 128-family variant of the last gemm_lp call of this thread: 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 /
 // 128 x 64 / 128 x 256 tile; 0 when the last call did not reach that family
 int gemm_last_mode();
+// the same of the last gemm_lp call of this thread that was no dry run (vstar_op_gemm_last_mode)
+int gemm_launched_mode();
 bool gemm256_eligible(const GemmParams& p);   // true: gemm_lp runs the 256^2 kernel (the only one that honours rope_cs)
 
 // decode-sized GEMM (skinny.hip): M <= 64, identity row maps; same operands/epilogues as gemm_lp
