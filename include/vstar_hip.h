@@ -203,6 +203,26 @@ int vstar_image_set_slot_async(vstar_handle* h, int slot, const uint8_t* rgb, in
 int vstar_vsm_generate(vstar_handle* h, const uint16_t* clip_pix_bf16, const int32_t* ids, int L, int max_new_tokens,
                        int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out);
 
+/* The same greedy decode for n crops at once: the contextual-cue questions of all live searches of a stream round
+ * (vstar_amd/search.py::visual_search_stream) share ONE device-resident decode loop.  A decode step streams the weights once
+ * whatever its row count, so n sequences cost little more than one.  Sequence i is exactly the decode the single-sequence entry
+ * performs for (pixels i, prompt i, max_new_tokens[i], eos_id) and yields the same token list (bf16 engine): the prompts are
+ * prefilled one at a time by the single entry's own call, the n-row step runs the row-count-independent weight-streaming kernels,
+ * and its attention takes the split / unsplit decision of a ONE-row step whatever n is.  A sequence stops at its own cap or at
+ * eos_id (stored as its last id); a finished row stays in the batch, frozen at its position, until the last one ends.
+ *   clip_pix_bf16   [n,3,I,I]: host, device with VSTAR_F_DEVICE_INPUTS; ignored with VSTAR_F_INTERNAL_PIXELS, where the pixels
+ *                   are those the preceding crop preprocessing of n boxes left on the device (n <= max_batch then)
+ *   ids, id_off     prompt i = ids[id_off[i] .. id_off[i+1]), exactly one -200, >= 2 ids
+ *   max_new_tokens  [n], each >= 1;  L_i - 1 + P + max_new_tokens[i] must fit the decode context
+ *   out_ids         [n, max over i of max_new_tokens[i]] (row-major); n_out [n] receives the counts
+ * Bad arguments (n outside [1, VSTAR_GEN_MAX_BATCH], a prompt without or with two -200, a sequence beyond the context, null
+ * arrays) return VSTAR_ERR_INVALID before any device work.  The first call builds the batched runner (KV slots for
+ * VSTAR_GEN_MAX_BATCH sequences: 0.5 GB each at 7B with max_text_len 192); when that fails the call returns VSTAR_ERR_NOMEM, nothing
+ * stays allocated and the single-sequence entry keeps working. */
+#define VSTAR_GEN_MAX_BATCH 16
+int vstar_vsm_generate_batch(vstar_handle* h, int n, const uint16_t* clip_pix_bf16, const int32_t* ids, const int32_t* id_off,
+                             const int32_t* max_new_tokens, int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out);
+
 /* Bilinear (align_corners=False) upsample of a 192x192 low-res mask to h_out x w_out fp32, then clamp(min=0).
  * Replaces F.interpolate(...) + torch.clamp (VSM.py:534-537, visual_search.py:223-224). Host in, host out. */
 int vstar_upsample_mask(vstar_handle* h, const float* lowres, int h_out, int w_out, float* out);
@@ -226,6 +246,8 @@ int vstar_heatmap_stats_batch(vstar_handle* h, int n, const float* lowres, const
 
 /* Debug/parity taps: copy an internal activation of the LAST score_batch call to host as fp32.
  * name in {"clip_features","projector","llm_hidden_loc","embed_det","embed_seg","owl_feats"}.
+ * "gen_attn_path" (one value, no forward needed): the decode-attention path — 0 un-fused, 1 fused, 2 fused split-KV, the codes of
+ * vstar_vqa_op_cached_attention; -1 when no step ran — of the last decode step of the last generate / generate_batch call.
  * Returns the number of floats written (<= cap) or a negative error. */
 int64_t vstar_debug_read(vstar_handle* h, const char* name, float* out, int64_t cap);
 

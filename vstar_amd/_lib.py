@@ -31,6 +31,8 @@ EXPORTS = [
     "vstar_op_quantize_rows_fp8", "vstar_op_rmsnorm_quant_fp8", "vstar_op_small_attention",
     # doors of the prefill-side GEMM / attention features (tests/test_prefill_ops_gpu.py)
     "vstar_op_gemm_ex", "vstar_op_rope", "vstar_op_attention_grouped", "vstar_op_attention_mx_grouped",
+    # the batched contextual-cue decode
+    "vstar_vsm_generate_batch",
 ]
 
 # every symbol include/vstar_vqa.h declares
@@ -64,6 +66,7 @@ def EPI_VARIANT(v: int) -> int:
 
 
 TILE_4W = 2564          # vstar_op_gemm_last_tile() value of the 4-wave / AGPR 256 x 256 kernel
+GEN_MAX_BATCH = 16      # VSTAR_GEN_MAX_BATCH
 F_SKIP_OWL, F_DEVICE_INPUTS, F_DEVICE_OUTPUT, F_NO_SYNC, F_INTERNAL_PIXELS, F_SHARE_PREFIX = 1, 2, 4, 8, 16, 32
 
 
@@ -186,6 +189,8 @@ def load() -> ctypes.CDLL:
     lib.vstar_vsm_score_grouped.restype = c_int
     lib.vstar_vsm_generate.argtypes = [H, c_void_p, c_void_p, c_int, c_int, c_int, c_uint, c_void_p, c_void_p]
     lib.vstar_vsm_generate.restype = c_int
+    lib.vstar_vsm_generate_batch.argtypes = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_uint, c_void_p, c_void_p]
+    lib.vstar_vsm_generate_batch.restype = c_int
     lib.vstar_image_set.argtypes = [H, c_void_p, c_int, c_int]
     lib.vstar_image_set.restype = c_int
     lib.vstar_preprocess_crops.argtypes = [H, c_int, c_void_p]

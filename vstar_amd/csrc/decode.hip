@@ -812,10 +812,12 @@ int cached_attention_last_path() { return t_last_path; }
 
 template <bool ANC, int KVF>
 static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
-                                     int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
+                                     int max_keys, hipStream_t s, void* split_ws, int split_max_rows, int decide_rows) {
   const float inv_scale = sqrtf(128.0f);
   lp_t *kc = (lp_t*)kv.k, *vc = (lp_t*)kv.v;      // (the kernels' cell type is their KVF's)
-  if (cached_attention_splits(fused_cos_sin != nullptr, split_ws != nullptr, R, split_max_rows, kv.H, max_keys)) {
+  // (decide_rows: the decision of a step of that many rows; the workspace bound is R's own either way)
+  if (R <= split_max_rows &&
+      cached_attention_splits(fused_cos_sin != nullptr, split_ws != nullptr, decide_rows > 0 ? decide_rows : R, split_max_rows, kv.H, max_keys)) {
     t_last_path = 2;
     const SplitWs ws(split_ws, split_max_rows, kv.H, kv.ctx);
     const int span = ((((max_keys + SPLIT_P - 1) / SPLIT_P) + 63) & ~63) + 1;
@@ -837,13 +839,13 @@ static hipError_t cached_attention_t(const lp_t* qkv, const KvLayer& kv, const K
 }
 
 hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
-                            int max_keys, hipStream_t s, void* split_ws, int split_max_rows) {
+                            int max_keys, hipStream_t s, void* split_ws, int split_max_rows, int decide_rows) {
   t_last_path = -1;
   if (!kv_format_ok(kv)) return hipErrorInvalidValue;
   if (R <= 0) return hipSuccess;
   hipError_t e = hipErrorInvalidValue;
-  KV_DISPATCH(kv.fmt, e = rows.anc ? cached_attention_t<true, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows)
-                                   : cached_attention_t<false, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows));
+  KV_DISPATCH(kv.fmt, e = rows.anc ? cached_attention_t<true, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows, decide_rows)
+                                   : cached_attention_t<false, KVF>(qkv, kv, rows, fused_cos_sin, out, R, max_keys, s, split_ws, split_max_rows, decide_rows));
   return e;
 }
 

@@ -137,6 +137,16 @@ struct vstar_engine : EngineBase {
   lp_t* gen_feats = nullptr;    // [P, H] projected image features of the crop being decoded
   int generate(const lp_t* clip_pix, const int32_t* ids, int L, int max_new, int eos_id, unsigned flags, int32_t* out_ids,
                int32_t* n_out);
+  // The contextual-cue decodes of several live searches at once (vstar_vsm_generate_batch): a second runner with one KV slot per
+  // sequence, built by the first batched call; it streams gen's tile-major decode weights and takes a one-row step's attention path.
+  LlmCached genb;
+  lp_t* genb_feats = nullptr;   // [VSTAR_GEN_MAX_BATCH * P, H]
+  int gen_ctx() const { return (clip.P + cfg.max_text_len + 255) / 64 * 64; }
+  int ensure_gen();
+  int ensure_genb();
+  int generate_batch(int n, const lp_t* clip_pix, const int32_t* ids, const int32_t* id_off, const int32_t* max_new, int eos_id,
+                     unsigned flags, int32_t* out_ids, int32_t* n_out);
+  int gen_attn_path = -1;       // cached_attention path of the last decode step of the last generate / generate_batch call (-1: none ran)
   int finalize();
   int score(int B, const lp_t* clip_pix, const lp_t* owl_pix, const int32_t* ids, int L, const int32_t* loc_pos,
             const int32_t* verify_pos, int n_verify, unsigned flags, vstar_result* out);
@@ -1127,17 +1137,9 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
   if (!clip_pix || !ids || !out_ids || !n_out || L < 2 || max_new < 1) { set_error("vstar_vsm_generate: bad argument"); return VSTAR_ERR_INVALID; }
   HIPCHK(hipSetDevice(device));
   const int H = c.llm_hidden, P = clip.P;
-  const int ctx = (P + c.max_text_len + 255) / 64 * 64;
-  if (!gen.ready) {
-    LlmCachedCfg rc;
-    rc.hidden = H; rc.heads = c.llm_heads; rc.mlp = c.llm_mlp; rc.layers = c.llm_layers; rc.vocab = c.llm_vocab;
-    rc.rms_eps = c.llm_rms_eps; rc.rope_theta = c.llm_rope_theta;
-    rc.max_slots = 1; rc.max_ctx = ctx; rc.max_rows = ctx;
-    RC(dalloc(&gen_feats, (size_t)P * H));
-    RC(gen.init(this, rc, embed, &llm, final_norm, &lm_head));
-    gen.feats = gen_feats;
-    gen.n_feat_rows = P;
-  }
+  const int ctx = gen_ctx();
+  RC(ensure_gen());
+  gen_attn_path = -1;
   int img = -1;
   for (int i = 0; i < L; ++i)
     if (ids[i] == -200) { if (img >= 0) { set_error("more than one -200 in input_ids"); return VSTAR_ERR_INVALID; } img = i; }
@@ -1168,7 +1170,7 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
     // the decode loop as a replayed hipGraph (llm_cached.hpp): same kernels, no per-token host round trip
     bool used = false;
     RC(gen.decode_greedy_graph(nxt, past, slot, max_new, eos_id, out_ids, &n, &used));
-    if (used) { *n_out = n; return 0; }
+    if (used) { *n_out = n; if (n > 1) gen_attn_path = gen.dec_attn_path; return 0; }
     n = 0;
   }
   for (;;) {
@@ -1176,9 +1178,126 @@ int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int 
     if (nxt == eos_id || n >= max_new) break;
     int32_t one_off[2] = {0, 1}, w0 = 0, tok = nxt;
     RC(gen.forward(LlmRows{1, one_off, &tok, &slot, &slot, &past, 1, &w0}, greedy));
+    gen_attn_path = cached_attention_last_path();
     ++past;
   }
   *n_out = n;
+  return 0;
+}
+
+int vstar_engine::ensure_gen() {
+  if (gen.ready) return 0;
+  const vstar_config& c = cfg;
+  const int H = c.llm_hidden, P = clip.P, ctx = gen_ctx();
+  LlmCachedCfg rc;
+  rc.hidden = H; rc.heads = c.llm_heads; rc.mlp = c.llm_mlp; rc.layers = c.llm_layers; rc.vocab = c.llm_vocab;
+  rc.rms_eps = c.llm_rms_eps; rc.rope_theta = c.llm_rope_theta;
+  rc.max_slots = 1; rc.max_ctx = ctx; rc.max_rows = ctx;
+  RC(dalloc(&gen_feats, (size_t)P * H));
+  RC(gen.init(this, rc, embed, &llm, final_norm, &lm_head));
+  gen.feats = gen_feats;
+  gen.n_feat_rows = P;
+  return 0;
+}
+
+// The batched runner: VSTAR_GEN_MAX_BATCH KV slots of the solo runner's context and a feature table of as many crops.  Everything it
+// allocates is given back when any part fails, so that a failed first batched call leaves the engine, and vstar_vsm_generate, as
+// they were.
+int vstar_engine::ensure_genb() {
+  if (genb.ready) return 0;
+  RC(ensure_gen());
+  const vstar_config& c = cfg;
+  const int H = c.llm_hidden, P = clip.P, ctx = gen_ctx();
+  LlmCachedCfg rc = gen.cfg;
+  rc.max_slots = VSTAR_GEN_MAX_BATCH; rc.max_ctx = ctx; rc.max_rows = ctx;
+  rc.split_rows = VSTAR_GEN_MAX_BATCH;      // the split-KV workspace holds a full batch ...
+  rc.attn_decide_rows = 1;                  // ... and every step takes the decision of a solo step (the sums of a row keep their order)
+  const size_t mark = allocs.size();
+  genb = LlmCached();
+  genb.borrow_dec_w = &gen.dec_w;
+  int rcode = dalloc(&genb_feats, (size_t)VSTAR_GEN_MAX_BATCH * P * H);
+  if (!rcode) rcode = genb.init(this, rc, embed, &llm, final_norm, &lm_head);
+  if (rcode) {
+    const std::string msg = error;
+    (void)hipGetLastError();
+    for (size_t i = mark; i < allocs.size(); ++i) hipFree(allocs[i]);
+    allocs.resize(mark);
+    genb.release();
+    genb = LlmCached();
+    genb_feats = nullptr;
+    set_error("vstar_vsm_generate_batch: building the batched runner failed: " + msg);
+    return rcode == VSTAR_ERR_NOMEM ? VSTAR_ERR_NOMEM : rcode;
+  }
+  genb.feats = genb_feats;
+  genb.n_feat_rows = (int64_t)VSTAR_GEN_MAX_BATCH * P;
+  return 0;
+}
+
+// VSM.generate_boxes / generate_ids_batch: the greedy decodes of n crops, one decode step for all of them (see include/vstar_hip.h)
+int vstar_engine::generate_batch(int n, const lp_t* clip_pix, const int32_t* ids, const int32_t* id_off, const int32_t* max_new,
+                                 int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out) {
+  if (!finalized) { set_error("weights not finalized"); return VSTAR_ERR_STATE; }
+  const vstar_config& c = cfg;
+  const bool internal_pix = flags & VSTAR_F_INTERNAL_PIXELS;
+  if (n < 1 || n > VSTAR_GEN_MAX_BATCH) { set_error("vstar_vsm_generate_batch: n must be in [1, VSTAR_GEN_MAX_BATCH]"); return VSTAR_ERR_INVALID; }
+  if ((!clip_pix && !internal_pix) || !ids || !id_off || !max_new || !out_ids || !n_out) {
+    set_error("vstar_vsm_generate_batch: null argument");
+    return VSTAR_ERR_INVALID;
+  }
+  if (internal_pix && n > c.max_batch) {
+    set_error("vstar_vsm_generate_batch: internal pixels hold at most max_batch crops");
+    return VSTAR_ERR_INVALID;
+  }
+  const int H = c.llm_hidden, P = clip.P, ctx = gen_ctx();
+  int out_ld = 0;
+  std::vector<int> img((size_t)n, -1);
+  for (int i = 0; i < n; ++i) {
+    const int L = id_off[i + 1] - id_off[i];
+    if (id_off[i] < 0 || L < 2 || max_new[i] < 1) { set_error("vstar_vsm_generate_batch: a prompt needs >= 2 ids and max_new_tokens >= 1"); return VSTAR_ERR_INVALID; }
+    for (int j = 0; j < L; ++j)
+      if (ids[id_off[i] + j] == -200) {
+        if (img[i] >= 0) { set_error("more than one -200 in input_ids (sequence " + std::to_string(i) + ")"); return VSTAR_ERR_INVALID; }
+        img[i] = j;
+      }
+    if (img[i] < 0) { set_error("input_ids hold no image token (-200) (sequence " + std::to_string(i) + ")"); return VSTAR_ERR_INVALID; }
+    if ((int64_t)L - 1 + P + max_new[i] > ctx) {
+      set_error("prompt + max_new_tokens exceed the decode context (sequence " + std::to_string(i) + ")");
+      return VSTAR_ERR_INVALID;
+    }
+    out_ld = std::max(out_ld, (int)max_new[i]);
+  }
+  HIPCHK(hipSetDevice(device));
+  RC(ensure_genb());
+  gen_attn_path = -1;
+  // ---- CLIP tower + mm_projector of the n crops -> feature rows [i * P, (i + 1) * P), max_batch crops per pass ----
+  const size_t cn = (size_t)3 * c.clip_image_size * c.clip_image_size;
+  for (int c0 = 0; c0 < n; c0 += c.max_batch) {
+    const int m = std::min(n - c0, (int)c.max_batch);
+    const lp_t* cpix = d_clip_pix;                            // internal pixels: left there by the preceding preprocessing call
+    if (!internal_pix) {
+      if (flags & VSTAR_F_DEVICE_INPUTS) cpix = clip_pix + (size_t)c0 * cn;
+      else HIPCHK(hipMemcpyAsync(d_clip_pix, clip_pix + (size_t)c0 * cn, (size_t)m * cn * 2, hipMemcpyHostToDevice, stream));
+    }
+    RC(run_tower(clip, cpix, m));
+    RC(project_clip(m, genb_feats + (size_t)c0 * P * H, H));
+  }
+  // ---- prefill: one sequence per forward() call, exactly the call the solo decode makes (same rows, same kernels, same bits) ----
+  std::vector<int32_t> first((size_t)n), past((size_t)n), rows;
+  for (int i = 0; i < n; ++i) {
+    const int L = id_off[i + 1] - id_off[i];
+    rows.clear();
+    for (int j = 0; j < L; ++j) {
+      if (j == img[i]) for (int p = 0; p < P; ++p) rows.push_back(-(1 + i * P + p));
+      else rows.push_back(ids[id_off[i] + j]);
+    }
+    int32_t row_off[2] = {0, (int32_t)rows.size()}, slot = i, past0 = 0, want = (int32_t)rows.size() - 1, nxt = 0;
+    RC(genb.forward(LlmRows{1, row_off, rows.data(), &slot, &slot, &past0, 1, &want}, LlmTail::argmax(nullptr, &nxt)));
+    first[i] = nxt;
+    past[i] = (int32_t)rows.size();
+  }
+  RC(genb.decode_greedy_batch(n, first.data(), past.data(), max_new, eos_id, out_ids, out_ld, n_out));
+  for (int i = 0; i < n; ++i)
+    if (n_out[i] > 1) gen_attn_path = genb.dec_attn_path;
   return 0;
 }
 
@@ -1231,6 +1350,7 @@ void vstar_destroy(vstar_handle* h) {
   hipStreamSynchronize(h->stream);
   vstar_comm_destroy(h);
   h->gen.release();
+  h->genb.release();
   h->release_base();
   if (h->d_stats) hipFree(h->d_stats);
   if (h->d_stats_batch) hipFree(h->d_stats_batch);
@@ -1284,6 +1404,12 @@ int vstar_vsm_generate(vstar_handle* h, const uint16_t* clip_pix, const int32_t*
                        unsigned flags, int32_t* out_ids, int32_t* n_out) {
   if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
   return h->generate(clip_pix, ids, L, max_new_tokens, eos_id, flags, out_ids, n_out);
+}
+
+int vstar_vsm_generate_batch(vstar_handle* h, int n, const uint16_t* clip_pix, const int32_t* ids, const int32_t* id_off,
+                             const int32_t* max_new_tokens, int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out) {
+  if (!h) { tls_error() = "null handle"; return VSTAR_ERR_INVALID; }
+  return h->generate_batch(n, clip_pix, ids, id_off, max_new_tokens, eos_id, flags, out_ids, n_out);
 }
 
 int vstar_image_set_slot(vstar_handle* h, int slot, const uint8_t* rgb, int height, int width) {
@@ -1434,7 +1560,12 @@ int64_t vstar_debug_read(vstar_handle* h, const char* name, float* out, int64_t 
     out[0] = (float)h->score_graph_replays; out[1] = (float)captured; out[2] = (float)h->score_graphs.size();
     return 3;
   }
-  const bool pix = !strcmp(name, "clip_pixels") || !strcmp(name, "owl_pixels");
+  if (!strcmp(name, "gen_attn_path")) {             // host value: the decode attention path of the last generate / generate_batch call
+    if (cap < 1) { h->set_error("gen_attn_path needs room for 1 value"); return VSTAR_ERR_INVALID; }
+    out[0] = (float)h->gen_attn_path;
+    return 1;
+  }
+  const bool pix =!strcmp(name, "clip_pixels") || !strcmp(name, "owl_pixels");
   if (!pix && h->last_B == 0) { h->set_error("no forward has run"); return VSTAR_ERR_STATE; }
   const int B = pix ? (int)h->h_jobs.size() / 2 : h->last_B;
   const std::string n(name);

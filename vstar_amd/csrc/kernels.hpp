@@ -185,8 +185,10 @@ hipError_t rope_kv_append(lp_t* qkv, const lp_t* cos_sin, const KvLayer& kv, con
 // (rows.anc given: through the ancestry table).
 // fused_cos_sin != null (only when every sequence has exactly ONE new row): the kernel also does rope_kv_append's work for
 // its row (RoPE on q,k, K/V appended to the cache) — qkv then holds the raw projection.
+// decide_rows > 0: the split-KV decision is the one a step of decide_rows rows would get (the batched cue decode asks for a one-row
+// step's, so that a sequence's sums run in the order of its solo decode whatever R is); the workspace must still hold R rows.
 hipError_t cached_attention(const lp_t* qkv, const KvLayer& kv, const KvRows& rows, const lp_t* fused_cos_sin, lp_t* out, int R,
-                            int max_keys, hipStream_t s, void* split_ws = nullptr, int split_max_rows = 0);
+                            int max_keys, hipStream_t s, void* split_ws = nullptr, int split_max_rows = 0, int decide_rows = 0);
 // whether cached_attention takes the split-KV pair for such a call (fused: fused_cos_sin given; have_ws: split_ws given) — the ONE
 // place the decision is taken (VSTAR_DECODE_SPLIT_KV=0 turns the path off), for the dispatcher and for the op-level door
 bool cached_attention_splits(bool fused, bool have_ws, int R, int split_max_rows, int H, int max_keys);

@@ -115,6 +115,10 @@ struct LlmCachedCfg {
   int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only);
                             // 4: int4 with one fp16 scale per group of 128 (fp16 build only)
   int kv_format = KV_FMT_F16;   // KV_FMT_MXFP8 / KV_FMT_MXFP8_EMU: block-scaled fp8 KV cache (fp16 build only)
+  // Decode attention of a runner whose steps must not depend on their row count (the batched cue decode, decode_greedy_batch):
+  // split_rows > 0 sizes the split-KV workspace for that many rows instead of SPLIT_ROWS, attn_decide_rows > 0 makes every step take
+  // the split / unsplit decision of a step of that many rows (kernels.hpp: cached_attention's decide_rows).
+  int split_rows = 0, attn_decide_rows = 0;
 };
 
 // What the decode GEMV streams for one layer's four block linears (SkinnyWeights, kernels.hpp).  fp16 (cfg.weight_bits == 0):
@@ -246,6 +250,7 @@ struct LlmCached {
   float *d_lp = nullptr, *d_lp_top = nullptr;    // [max_want], [max_want, 32] (row stride: the call's n_top)
   int32_t *d_lp_rank = nullptr, *d_lp_tok = nullptr;
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
+  int split_rows() const { return cfg.split_rows > 0 ? cfg.split_rows : SPLIT_ROWS; }      // rows the workspace holds
   char* split_ws = nullptr;
   // ---- beam search ----
   // KV ancestry table [max_slots, max_ctx]: position p of the sequence in slot s lives in slot d_anc[s * max_ctx + p].  A slot is
@@ -268,6 +273,16 @@ struct LlmCached {
   int dec_keys_bound = 0;                        // context bound the captured attention launch was sized for
   int32_t* d_dec = nullptr;                      // coherent HOST memory: [0] = tokens emitted so far, [1..] = the tokens
   int dec_cap = 0;
+  int dec_attn_path = -1;                        // cached_attention path of the step the graph holds / the last step launched by hand
+  // ---- greedy decode of n sequences, rows 0 .. n - 1, as one replayed hipGraph per n (decode_greedy_batch) ----
+  // The same step over n rows; what differs per call (eos id, per-row caps) lives in DEVICE arrays, so a graph depends on n alone.
+  static constexpr int DEC_BATCH_MAX = 16;
+  hipGraphExec_t decb_exec[DEC_BATCH_MAX + 1] = {};
+  // device: [0] = eos id, [1 + r] = cap of row r (tokens, the prefill's included), [17 + r] = tokens row r has emitted,
+  // [33 + r] = row r finished
+  int32_t* d_decb = nullptr;
+  int32_t* h_decb = nullptr;                     // coherent HOST memory: [0] = steps done, [1] = unfinished rows, [2 + step * n + r] = tokens
+  int decb_cap = 0;                              // steps the log holds
   // ---- the decode GEMV's weight descriptors: empty (row-major fp16 weights only), or one record per layer ----
   // Tile-major copies of the big decode weights (round 5; SKINNY_W_F16): the weight-streaming GEMV gives a workgroup 16 (gate|up: 32)
   // ROWS of the row-major matrix, i.e. 16 - 32 sequential streams 2 K bytes apart and 4096 - 22016 of them over the chip; laid out
@@ -293,9 +308,18 @@ struct LlmCached {
     dec_exec = nullptr;
     if (d_dec) hipHostFree(d_dec);
     d_dec = nullptr;
+    for (hipGraphExec_t& g : decb_exec) { if (g) hipGraphExecDestroy(g); g = nullptr; }
+    if (h_decb) hipHostFree(h_decb);
+    h_decb = nullptr;
   }
   int decode_step_body(int keys_bound);
   int decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids, int* n_out, bool* used);
+  int decode_batch_step_body(int n, int keys_bound);
+  int decode_batch_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id);
+  int decode_greedy_batch(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id, int32_t* out_ids,
+                          int64_t out_ld, int32_t* n_out);
+  // the fp16 tile-major decode weights of another runner over the same blocks (set before init: this runner then builds none)
+  const std::vector<DecodeLayerW>* borrow_dec_w = nullptr;
   int lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
                const lp_t* res = nullptr, int64_t ldr = 0, const SkinnyWeights* dw = nullptr);
   int lin_norm(const lp_t* x, const lp_t* norm_w, lp_t* scratch, const Lin& L, void* C, int64_t ldc, int M, int epi,
@@ -361,7 +385,7 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
   RC(e->dalloc(&d_vtok, (size_t)max_want));
   RC(e->dalloc(&d_vacc, (size_t)max_want));
   {  // split-KV decode attention (decode.hip): scores / partials / tickets for steps of up to SPLIT_ROWS sequences, zeroed once
-    const size_t wb = cached_attention_split_ws_bytes(SPLIT_ROWS, c.heads, c.max_ctx);
+    const size_t wb = cached_attention_split_ws_bytes(split_rows(), c.heads, c.max_ctx);
     RC(e->dalloc(&split_ws, wb));
     if (hipMemset(split_ws, 0, wb) != hipSuccess) { set_error("split-KV workspace memset failed"); return VSTAR_ERR_HIP; }
   }
@@ -399,7 +423,9 @@ inline int LlmCached::init(EngineBase* owner, const LlmCachedCfg& c, const lp_t*
       if (skinny_pack_tiles(L.W, (lp_t*)t, rows, L.K, nt, e->stream) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
       out.tiled = t;
     };
-    if (on && c.hidden >= 512) {
+    if (borrow_dec_w) {
+      dec_w = *borrow_dec_w;                                  // (empty when the lender runs row-major: so does this runner)
+    } else if (on && c.hidden >= 512) {
       size_t need = 0, free_b = 0, total_b = 0;
       for (int i = 0; i < c.layers; ++i) {
         const LlmBlock& b = (*blocks)[i];
@@ -613,7 +639,8 @@ inline int LlmCached::llm_layers_cached(int R, int max_keys, bool single_rows, c
     RC(lin_norm(lx, b.in_norm, lh, b.qkv, lqkv, 3 * H, R, VSTAR_EPI_NONE, &dw.qkv));
     // decode steps (one new row per sequence): RoPE + cache append happen inside the attention kernel
     if (!single_rows) LCHK(rope_kv_append(lqkv, rope, kl, rw, R, e->stream));
-    LCHK(cached_attention(lqkv, kl, rw, single_rows ? rope : nullptr, latt, R, max_keys, e->stream, split_ws, SPLIT_ROWS));
+    LCHK(cached_attention(lqkv, kl, rw, single_rows ? rope : nullptr, latt, R, max_keys, e->stream, split_ws, split_rows(),
+                          c.attn_decide_rows));
     RC(lin_auto(latt, H, b.o, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.o));
     RC(lin_norm(lx, b.post_norm, lh, b.gate_up, lact, c.mlp, R, VSTAR_EPI_SILU_MUL, &dw.gate_up));
     RC(lin_auto(lact, c.mlp, b.down, lx, H, R, VSTAR_EPI_NONE, lx, H, &dw.down));
@@ -978,6 +1005,7 @@ inline int LlmCached::decode_step_body(int keys_bound) {
   const int H = c.hidden;
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, 1, H, e->stream));
   RC(llm_layers_cached(1, keys_bound, true));
+  dec_attn_path = cached_attention_last_path();
   RC(head(0, 1));
   LCHK(argmax_rows_lp(logits, 1, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
   hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_dec, dec_cap);
@@ -1097,6 +1125,193 @@ inline int LlmCached::decode_greedy_graph(int32_t first_token, int past, int slo
   const int timed = launched - launched0;
   if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && timed > 0) last_ms = ms / timed;
   *n_out = n;
+  return 0;
+}
+
+namespace {
+// decode_advance_kernel for rows 0 .. n - 1 (one workgroup, thread r = row r).  ctl: see LlmCached::d_decb.  An unfinished row
+// takes its arg-max as the next input and advances; it finishes when it emitted the eos id or reached its cap.  A FINISHED row is
+// left where it is: the steps it still rides along recompute the same position of its own KV slot, so it can never leave the
+// context however long its companions run, and it touches nobody else's keys.  Every row's token is logged step-major (the host
+// drops what a finished row emits); then, once per step, the number of unfinished rows and — last, with a system-scope release —
+// the step counter are published.
+__global__ void decode_advance_batch_kernel(const int32_t* __restrict__ argmax, int32_t* src, int32_t* row_pos, int32_t* seq_past,
+                                            int32_t* ctl, int32_t* log, int n, int cap_steps) {
+  __shared__ int alive;
+  const int r = threadIdx.x;
+  if (r == 0) alive = 0;
+  __syncthreads();
+  const int32_t step = log[0];
+  if (r < n) {
+    const int32_t t = argmax[r];
+    bool fin = ctl[33 + r] != 0;
+    if (!fin) {
+      src[r] = t;
+      row_pos[r] += 1;
+      seq_past[r] += 1;
+      const int32_t cnt = ctl[17 + r] + 1;
+      ctl[17 + r] = cnt;
+      if (t == ctl[0] || cnt >= ctl[1 + r]) { fin = true; ctl[33 + r] = 1; }
+    }
+    if (step < cap_steps) log[2 + (int64_t)step * n + r] = t;
+    if (!fin) atomicAdd(&alive, 1);
+    __threadfence_system();
+  }
+  __syncthreads();
+  if (r == 0) {
+    log[1] = alive;
+    __threadfence_system();
+    __hip_atomic_store(&log[0], step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+}  // namespace
+
+// one decode step of rows 0 .. n - 1 (one row per sequence), every per-step value read from device memory: what the graph of n captures
+inline int LlmCached::decode_batch_step_body(int n, int keys_bound) {
+  const LlmCachedCfg& c = cfg;
+  LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, n, c.hidden, e->stream));
+  RC(llm_layers_cached(n, keys_bound, true));
+  dec_attn_path = cached_attention_last_path();
+  RC(head(0, n));
+  LCHK(argmax_rows_lp(logits, n, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
+  hipLaunchKernelGGL(decode_advance_batch_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_decb,
+                     h_decb, n, decb_cap);
+  LCHK(hipGetLastError());
+  return 0;
+}
+
+// the per-call state of a batched decode: sequence i is row i and lives in KV slot i with `past[i]` positions cached
+inline int LlmCached::decode_batch_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id) {
+  std::vector<int32_t> seqmeta((size_t)3 * seq_cap(), 0), iota((size_t)n), ctl(1 + 3 * DEC_BATCH_MAX, 0);
+  int alive = 0;
+  ctl[0] = eos_id;
+  for (int i = 0; i < n; ++i) {
+    seq_set(seqmeta, i, i, i, past[i]);
+    iota[i] = i;
+    const bool fin = first[i] == eos_id || caps[i] <= 1;
+    ctl[1 + i] = caps[i]; ctl[17 + i] = 1; ctl[33 + i] = fin;
+    alive += !fin;
+  }
+  LCHK(hipMemcpyAsync(d_src, first, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_row_pos, past, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_row_slot, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_row_seq, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_seq, seqmeta.data(), seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_want, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_decb, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipStreamSynchronize(e->stream));
+  h_decb[0] = 0;
+  h_decb[1] = alive;
+  __atomic_thread_fence(__ATOMIC_SEQ_CST);
+  return 0;
+}
+
+// decode_greedy_graph for n sequences at once: sequence i sits in KV slot i with past[i] positions cached, first[i] is its prefill's
+// arg-max, caps[i] >= 1 the tokens it may emit in all.  Row i of out_ids (row stride out_ld) receives its tokens, n_out[i] their
+// count; it stops at its cap or at eos_id (stored).  One graph per n; VSTAR_DECODE_GRAPH=0, event profiling, a refused capture or a
+// failed warm-up step run the same n-row step launch by launch.  Nothing is launched when no row has a step to take.
+inline int LlmCached::decode_greedy_batch(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id,
+                                          int32_t* out_ids, int64_t out_ld, int32_t* n_out) {
+  const LlmCachedCfg& c = cfg;
+  if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
+  if (n < 1 || n > DEC_BATCH_MAX || n > c.max_slots) { e->set_error("batched decode: row count out of range"); return VSTAR_ERR_INVALID; }
+  static const bool disabled = [] { const char* v = getenv("VSTAR_DECODE_GRAPH"); return v && atoi(v) == 0; }();
+  std::vector<char> fin((size_t)n, 0);
+  int alive = 0, max_steps = 0;
+  for (int i = 0; i < n; ++i) {
+    if (caps[i] < 1 || past[i] < 1 || past[i] + caps[i] - 1 > c.max_ctx || anc_flag[i]) {
+      e->set_error("batched decode: a sequence's cap or cached length is out of range");
+      return VSTAR_ERR_INVALID;
+    }
+    out_ids[(int64_t)i * out_ld] = first[i];
+    n_out[i] = 1;
+    fin[i] = first[i] == eos_id || caps[i] <= 1;
+    if (!fin[i]) { ++alive; max_steps = std::max(max_steps, caps[i] - 1); }
+  }
+  if (alive == 0) return 0;                             // every answer is its prefill's arg-max alone: no decode step at all
+  LCHK(hipSetDevice(e->device));
+  if (!d_decb) RC(e->dalloc(&d_decb, (size_t)1 + 3 * DEC_BATCH_MAX));
+  if (!h_decb) {
+    decb_cap = c.max_ctx;
+    void* hp = nullptr;
+    if (hipHostMalloc(&hp, ((size_t)decb_cap * DEC_BATCH_MAX + 2) * 4, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+      (void)hipGetLastError();
+      e->set_error("batched decode: no pinned host memory for the token log");
+      return VSTAR_ERR_NOMEM;
+    }
+    h_decb = (int32_t*)hp;
+  }
+  const int keys_bound = c.max_ctx;                    // as in decode_greedy_graph: fixed for the graphs' lifetime
+  RC(decode_batch_state(n, first, past, caps, eos_id));
+  int launched = 0;
+  if (!disabled && !e->profile && !decb_exec[n]) {
+    // as in decode_greedy_graph: the first step runs uncaptured (a real step) and takes the one-time attributes out of the capture
+    if (decode_batch_step_body(n, keys_bound) != 0 || hipStreamSynchronize(e->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      e->set_error("");
+      RC(decode_batch_state(n, first, past, caps, eos_id));      // start again, launch by launch (a step rewrites the same K/V rows)
+    } else {
+      launched = 1;
+      hipGraph_t graph = nullptr;
+      if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        const int rc = decode_batch_step_body(n, keys_bound);
+        const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
+        if (rc != 0 || ce != hipSuccess || !graph) {
+          if (graph) hipGraphDestroy(graph);
+          (void)hipGetLastError();
+          e->set_error("");
+        } else {
+          const hipError_t ie = hipGraphInstantiate(&decb_exec[n], graph, nullptr, nullptr, 0);
+          hipGraphDestroy(graph);
+          if (ie != hipSuccess) { decb_exec[n] = nullptr; (void)hipGetLastError(); }
+        }
+      } else {
+        (void)hipGetLastError();
+      }
+    }
+  }
+  const hipGraphExec_t exec = (disabled || e->profile) ? nullptr : decb_exec[n];
+  const int DEPTH = 2;                                  // decode steps queued ahead of the step the host is waiting for
+  int done_steps = 0;
+  LCHK(hipEventRecord(ev0, e->stream));
+  const int launched0 = launched;
+  while (alive > 0 && done_steps < max_steps) {
+    // step k (1-based) produces token k of every row; keep steps done_steps + 1 .. done_steps + DEPTH queued while the device still
+    // reports an unfinished row
+    while (launched < std::min(max_steps, done_steps + DEPTH) && __atomic_load_n(&h_decb[1], __ATOMIC_ACQUIRE) > 0) {
+      if (exec) LCHK(hipGraphLaunch(exec, e->stream));
+      else RC(decode_batch_step_body(n, keys_bound));
+      ++launched;
+    }
+    if (launched <= done_steps) { set_error("batched decode: the device reports no unfinished row, the host has one"); return VSTAR_ERR_HIP; }
+    unsigned spins = 0;
+    while (__atomic_load_n(&h_decb[0], __ATOMIC_ACQUIRE) < done_steps + 1) {
+      if ((++spins & 4095u) == 0) {
+        const hipError_t q = hipStreamQuery(e->stream);
+        if (q == hipSuccess) {
+          if (__atomic_load_n(&h_decb[0], __ATOMIC_ACQUIRE) >= done_steps + 1) break;
+          set_error("batched decode: a step completed without emitting its tokens");
+          return VSTAR_ERR_HIP;
+        }
+        if (q != hipErrorNotReady) { set_error(std::string("batched decode: ") + hipGetErrorString(q)); return VSTAR_ERR_HIP; }
+      }
+      __builtin_ia32_pause();
+    }
+    const volatile int32_t* row = h_decb + 2 + (int64_t)done_steps * n;
+    for (int i = 0; i < n; ++i) {
+      if (fin[i]) continue;
+      const int32_t t = row[i];
+      out_ids[(int64_t)i * out_ld + n_out[i]++] = t;
+      if (t == eos_id || n_out[i] >= caps[i]) { fin[i] = 1; --alive; }
+    }
+    ++done_steps;
+  }
+  LCHK(hipEventRecord(ev1, e->stream));
+  LCHK(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  const int timed = launched - launched0;
+  if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && timed > 0) last_ms = ms / timed;
+  e->collect_profile();
   return 0;
 }
 

@@ -84,6 +84,39 @@ class VstarEngine:
                                                ctypes.byref(n)), self.handle)
         return out[:n.value].tolist()
 
+    def generate_batch(self, clip_pix, prompts, max_new, eos_id: int = 2, internal_pixels: bool = False) -> List[List[int]]:
+        """The greedy decodes of n <= _lib.GEN_MAX_BATCH crops in one device-resident loop (vstar_vsm_generate_batch): sequence i has
+        exactly the tokens `generate(clip_pix[i:i+1], prompts[i], max_new[i], eos_id)` returns.  clip_pix [n,3,I,I] (bf16-castable,
+        CPU or cuda), or None with internal_pixels=True after `preprocess_boxes` of the n crops.  prompts: n id lists, one -200
+        each; max_new: one cap for all or one per sequence."""
+        n = len(prompts)
+        caps = np.full((n,), max_new, np.int32) if np.ndim(max_new) == 0 else np.ascontiguousarray(np.asarray(max_new, np.int32).reshape(-1))
+        assert caps.shape[0] == n
+        off = np.zeros((n + 1,), np.int32)
+        off[1:] = np.cumsum([len(p) for p in prompts])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32).reshape(-1) for p in prompts])) if n else np.zeros((0,), np.int32)
+        flags, cptr = 0, None
+        if internal_pixels:
+            flags |= _lib.F_INTERNAL_PIXELS
+        else:
+            clip_pix = _as_bf16(clip_pix)
+            I = self.cfg.clip_image_size
+            assert tuple(clip_pix.shape) == (n, 3, I, I), clip_pix.shape
+            if clip_pix.is_cuda:
+                flags |= _lib.F_DEVICE_INPUTS
+            cptr = ctypes.c_void_p(clip_pix.data_ptr())
+        ld = max(int(caps.max()), 1) if n else 1
+        out = np.zeros((max(n, 1), ld), np.int32)
+        cnt = np.zeros((max(n, 1),), np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        _lib.check(self.lib.vstar_vsm_generate_batch(self.handle, n, cptr, p(ids), p(off), p(caps), int(eos_id), flags, p(out), p(cnt)),
+                   self.handle)
+        return [out[i, :cnt[i]].tolist() for i in range(n)]
+
+    def gen_attn_path(self) -> int:
+        """Decode-attention path of the last decode step of the last generate / generate_batch call (0 / 1 / 2; -1: no step ran)."""
+        return int(self.debug_read("gen_attn_path", 1)[0])
+
     # ---- the hot path ----
     def score_batch(self, clip_pix, owl_pix, input_ids, loc_pos, verify_pos=None, skip_owl: bool = False,
                     sync: bool = True, raw: bool = False, out_dev: Optional[torch.Tensor] = None, share_prefix: Optional[bool] = None):

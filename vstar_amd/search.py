@@ -305,9 +305,20 @@ def visual_search(vsm, image, target_object_name, target_bbox, smallest_size, co
     try:
         req = next(steps)
         while True:
-            req = steps.send(req[1].score(req[2]) if req[0] == "score" else _serve_stats(vsm, req[1]))
+            req = steps.send(_serve_one(vsm, image, req))
     except StopIteration as done:
         return done.value
+
+
+def _serve_one(vsm, image, req):
+    """One request of a `_visual_search_steps` generator, served alone: what the per-sample loop does."""
+    if req[0] == "score":
+        return req[1].score(req[2])
+    if req[0] == "cue":        # free-text VQA on the crop (one KV-cached greedy decode) ...
+        return vsm.inference(copy.deepcopy(_crop(image, req[1])), req[2], mode="vqa")
+    if req[0] == "seg":        # ... and the crop again with the locate prompt for the phrase it gave
+        return vsm.inference_batch([_crop(image, req[1])], req[2], mode="segmentation", upsample=False)[0]
+    return _serve_stats(vsm, req[1])
 
 
 def _serve_stats(vsm, reqs):
@@ -325,7 +336,9 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
                          _scorer: Optional["_NodeScorer"] = None):
     """The search as a generator: whenever it needs crops scored it yields ("score", scorer, crops) and is sent the engine's
     results for them; whenever it needs heat-map statistics (device reductions) it yields ("stats", [(low_res, h, w, rects), ...])
-    and is sent one statistics vector per item; its return value is visual_search's.  `visual_search` drives one such generator, `visual_search_many` several in lock
+    and is sent one statistics vector per item; in the contextual-cue branch (device reductions) it yields ("cue", bbox, question)
+    and is sent the free-text answer for that crop, then ("seg", bbox, locate question) and is sent the crop's 192x192 low-res
+    map; its return value is visual_search's.  `visual_search` drives one such generator, `visual_search_many` several in lock
     step.  Everything else — the decision math of visual_search.py:390-516 — is unchanged."""
     if visualize:
         assert save_path is not None                         # visual_search.py:485-486
@@ -389,8 +402,9 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
             st, anc_stats = stat_res[0], list(stat_res[1:])
             low = target_cue_heatmap
             if not st[1] > threshold:
-                patch = _crop(image, bbox)
-                vqa_results = vsm.inference(copy.deepcopy(patch), CUE_QUESTION.format(target_object_name), mode="vqa")
+                # contextual-cue branch (visual_search.py:427-443) as two requests, so that a driver of several searches can
+                # decode the cue answers of a round together and score their follow-up crops in one step
+                vqa_results = yield "cue", bbox, CUE_QUESTION.format(target_object_name)
                 phrase = vqa_results.split("most likely to appear")[-1].strip()
                 if phrase.endswith("."):
                     phrase = phrase[:-1]
@@ -400,7 +414,7 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
                     noun_chunker = get_noun_chunker()
                 noun_chunks = noun_chunker(phrase)
                 phrase = noun_chunks[0] if len(noun_chunks) == 1 else "region {}".format(phrase)
-                low = vsm.inference_batch([patch], LOCATE_QUESTION.format(phrase), mode="segmentation", upsample=False)[0]
+                low = yield "seg", bbox, LOCATE_QUESTION.format(phrase)
                 st = (yield "stats", [(low, bbox[3], bbox[2], rel(bbox))])[0]
                 search_path[current_patch_index]["context_cue"] = vqa_results + "#" + phrase
             current_patch["heat_stats"] = {"low_res": low, "min": st[0], "max": st[1], "sum": st[2]}
@@ -659,7 +673,7 @@ def _run_loader_upload(vsm, image, slot):
 
 
 def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: Optional[SpeculationPolicy] = None,
-                         stats: Optional[dict] = None, prefetch: int = 8, **kw):
+                         stats: Optional[dict] = None, prefetch: int = 8, cue_batch: bool = True, **kw):
     """Cross-image lock-step search: `samples` = iterable of (image, target_object_name, target_bbox, smallest_size) — `image` a
     PIL image or a zero-argument loader returning one (called when the sample enters the window; loaders with the same `.key`, or
     the same loader object, share an image slot; `smallest_size` may then be a callable of the loaded image); returns the
@@ -683,7 +697,15 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
     last of them has ended the slot (and the host copy) is released, and a LATER sample with the same key loads the image again.
     Nothing about the results depends on it.
 
-    stats (optional dict) receives: searches, crops_scored (engine records), useful_crops (nodes the best-first order visited),
+    cue_batch (default True): the contextual-cue branch of the live searches is served per round, not per search — every pending
+    cue question in ONE `vsm.generate_boxes` (a batched greedy decode of crops cut on the GPU), then every pending locate follow-up
+    in ONE plain `vsm.inference_boxes(mode="segmentation")` step, repeated until no search asks for either.  False, or a VSM
+    without `generate_boxes`, serves each request alone with the per-sample loop's two calls (the A/B yardstick).  The batched
+    decode emits the solo decode's tokens and plain scoring records do not depend on their batch (bf16 engine; in W8A8 mode a
+    one-crop step and a batched step already differ, because fp8 starts at 1024 rows), so the results are the loop's either way.
+
+    stats (optional dict) receives: cue_requests / cue_calls / cue_batch_max (cue questions, the engine decodes that served them,
+    the largest of those), seg_requests / seg_calls (their locate follow-ups and the scoring steps that served them), searches, crops_scored (engine records), useful_crops (nodes the best-first order visited),
     wasted_crop_frac, engine_steps, per_search = [{crops_scored, path_visited, ...}]."""
     samples = list(samples)
     n = len(samples)
@@ -718,6 +740,10 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
     scorers: Dict[int, _NodeScorer] = {}
     waiting: Dict[int, List[list]] = {}           # search -> the crop(s) it waits for
     want_stats: Dict[int, List] = {}
+    want_cue: Dict[int, Tuple] = {}               # search -> (bbox, cue question) of its contextual-cue branch
+    want_seg: Dict[int, Tuple] = {}               # search -> (bbox, locate question for the cue's phrase)
+    batch_cues = bool(cue_batch) and hasattr(vsm, "generate_boxes") and hasattr(vsm, "inference_boxes")
+    cue_st = dict(cue_requests=0, cue_calls=0, cue_batch_max=0, seg_requests=0, seg_calls=0)
     next_sample = 0
     engine_steps = 0
     n_spec: Dict[int, int] = {}                   # search -> speculative crops scored for it
@@ -815,6 +841,10 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
             req = next(gens[i]) if first else gens[i].send(value)
             if req[0] == "score":
                 waiting[i] = req[2]
+            elif req[0] == "cue":
+                want_cue[i] = (req[1], req[2])
+            elif req[0] == "seg":
+                want_seg[i] = (req[1], req[2])
             else:
                 want_stats[i] = req[1]
         except StopIteration as done:
@@ -838,17 +868,57 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
             next_sample += 1
         prefetch_ahead()
 
+    def serve_round(cur, kind):
+        # the cue questions ("cue") or locate follow-ups ("seg") of a round: one engine call per `cap` requests, or one per request
+        ids = list(cur)
+        cue_st[kind + "_requests"] += len(ids)
+        if not batch_cues:
+            cue_st[kind + "_calls"] += len(ids)
+            return [_serve_one(vsm, scorers[i].image, (kind,) + tuple(cur[i])) for i in ids]
+        out: List = []
+        lim = cap if kind == "seg" else len(ids)           # (generate_boxes chunks by itself: 16 sequences per decode)
+        for c0 in range(0, len(ids), lim):
+            part = ids[c0:c0 + lim]
+            boxes, qs = [list(cur[i][0]) for i in part], [cur[i][1] for i in part]
+            sl_part = [scorers[i].slot for i in part]
+            if kind == "cue":
+                out += list(vsm.generate_boxes(boxes, qs, sl_part))
+                cue_st["cue_batch_max"] = max(cue_st["cue_batch_max"], len(part))
+            else:
+                # the plain entry, as inference_batch uses in the per-sample loop: its records do not depend on the batch
+                gp = getattr(vsm, "group_prompts", False)
+                if gp:
+                    vsm.group_prompts = False
+                try:
+                    out += list(vsm.inference_boxes(boxes, qs, mode="segmentation", upsample=False, slots=sl_part))
+                finally:
+                    if gp:
+                        vsm.group_prompts = gp
+            cue_st[kind + "_calls"] += 1
+        return out
+
     def drain_stats():
-        nonlocal want_stats
-        while want_stats:
-            cur, want_stats = want_stats, {}
-            flat_reqs = [r for i in cur for r in cur[i]]
-            res = _serve_stats(vsm, flat_reqs)
-            k = 0
-            for i in cur:
-                n_i = len(cur[i])
-                advance(i, res[k:k + n_i])
-                k += n_i
+        # everything the live searches ask for between two scoring steps: heat-map statistics, then the round's cue questions, then
+        # their locate follow-ups, until nobody asks for any of them
+        nonlocal want_stats, want_cue, want_seg
+        while want_stats or want_cue or want_seg:
+            if want_stats:
+                cur, want_stats = want_stats, {}
+                flat_reqs = [r for i in cur for r in cur[i]]
+                res = _serve_stats(vsm, flat_reqs)
+                k = 0
+                for i in cur:
+                    n_i = len(cur[i])
+                    advance(i, res[k:k + n_i])
+                    k += n_i
+            elif want_cue:
+                cur, want_cue = want_cue, {}
+                for i, r in zip(list(cur), serve_round(cur, "cue")):
+                    advance(i, r)
+            else:
+                cur, want_seg = want_seg, {}
+                for i, r in zip(list(cur), serve_round(cur, "seg")):
+                    advance(i, r)
 
     grouping = getattr(vsm, "group_prompts", False)
     if grouping:
@@ -938,6 +1008,7 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
         stats["engine_calls"] = int(vsm.timers.get("engine_calls", 0)) - calls0
     if stats is not None:
         stats["async_uploads"] = n_async
+        stats.update(cue_st)
     return results
 
 
@@ -951,6 +1022,8 @@ def _fill_stream_stats(stats: Optional[dict], per_stats: List[dict], engine_step
                  per_search=[{k: v for k, v in p.items() if k != "search_path"} for p in per_stats])
     if stats.get("keep_paths"):              # the visited boxes of every search, in visit order (decision-parity reports)
         stats["visit_orders"] = [[tuple(int(v) for v in p["bbox"]) for p in ps.get("search_path", [])] for ps in per_stats]
+        # ... and what the contextual-cue branch said at each of them (None: the node did not take it)
+        stats["context_cues"] = [[p.get("context_cue") for p in ps.get("search_path", [])] for ps in per_stats]
 
 
 def visual_search_many(vsm, image, target_object_names: Sequence[str], target_bboxes=None, smallest_size: int = 224, *,

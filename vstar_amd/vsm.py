@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._lib import RESULT_FLOATS
+from ._lib import GEN_MAX_BATCH, RESULT_FLOATS
 from .config import VSMConfig
 from .dist import allgather_numpy, allgather_records, pad_count, shard_indices
 from .engine import VstarEngine
@@ -116,7 +116,8 @@ class VSM:
         self.fallback_log: List[dict] = []      # one entry per stepwise-decode fallback (diagnostics / tests)
         import threading
         self._upload_lock = threading.Lock()
-        self.timers = {"preprocess_s": 0.0, "engine_s": 0.0, "gather_s": 0.0, "post_s": 0.0, "crops": 0, "engine_calls": 0}
+        self.timers = {"preprocess_s": 0.0, "engine_s": 0.0, "gather_s": 0.0, "post_s": 0.0, "crops": 0, "engine_calls": 0,
+                       "generate_s": 0.0, "generate_tokens": 0, "generate_calls": 0}      # the batched cue decodes
 
     # ---- cost model of a scoring step (vstar_amd.search.SpeculationPolicy) ----
     step_ms_table = None    # {crops per rank: ms}; None = the policy's built-in MI355X measurements
@@ -236,6 +237,8 @@ class VSM:
         with `defer_mismatch=True` that happens lazily (the slot holds a DeferredMismatch)."""
         assert mode in ("vqa", "segmentation", "detection")
         if mode == "vqa":
+            if len(images) > 1 and hasattr(self.engine, "generate_batch"):      # several crops: one batched decode, the same tokens
+                return [self._gen_text(t) for t in self.generate_ids_batch(images, question)]
             return [self.generate(im, question) for im in images]
         ids, loc_pos, ver_pos, ver_tok = self._ids(question)
         nv = min(len(ver_pos), 8)
@@ -609,11 +612,69 @@ class VSM:
                 break
         return new
 
-    @torch.inference_mode()
-    def generate(self, image: Image.Image, question: str, max_new_tokens: int = 100) -> str:
-        new = self.generate_ids(image, question, max_new_tokens)
+    def _gen_text(self, new: List[int]) -> str:
         text = self.vsm_tokenizer.batch_decode([new], skip_special_tokens=True)[0]
         return text.replace("\n", "").replace("  ", " ").strip()      # visual_search.py:217-219
+
+    @torch.inference_mode()
+    def generate(self, image: Image.Image, question: str, max_new_tokens: int = 100) -> str:
+        return self._gen_text(self.generate_ids(image, question, max_new_tokens))
+
+    # ---- the same decode for several crops at once (vstar_vsm_generate_batch): the cue questions of a stream round ----
+    def _gen_requests(self, questions, n: int, max_new_tokens: int):
+        """Per request the prompt ids and the cap min(max_new_tokens, max_text_len - len(ids)) of generate_ids (<= 0: no room)."""
+        qs = [questions] * n if isinstance(questions, str) else list(questions)
+        assert len(qs) == n
+        per_q = {q: tokenizer_image_token(build_prompt(q, self.use_mm_start_end, conv_type=self.conv_type), self.vsm_tokenizer)
+                 for q in dict.fromkeys(qs)}
+        prompts = [per_q[q] for q in qs]
+        return prompts, [min(max_new_tokens, self.cfg.max_text_len - len(p)) for p in prompts]
+
+    def _generate_chunks(self, n: int, prompts, caps, chunk: int, run) -> List[List[int]]:
+        """run(sel, prompts, caps) -> token lists for the requests `sel` that have room, at most `chunk` per engine call."""
+        out: List[List[int]] = [[] for _ in range(n)]
+        live = [i for i in range(n) if caps[i] > 0]
+        eos = getattr(self.vsm_tokenizer, "eos_token_id", 2)
+        for c0 in range(0, len(live), chunk):
+            sel = live[c0:c0 + chunk]
+            t0 = time.perf_counter()
+            toks = run(sel, [prompts[i] for i in sel], [caps[i] for i in sel], eos)
+            self.timers["generate_s"] = self.timers.get("generate_s", 0.0) + time.perf_counter() - t0
+            self.timers["generate_tokens"] = self.timers.get("generate_tokens", 0) + sum(len(t) for t in toks)
+            self.timers["generate_calls"] = self.timers.get("generate_calls", 0) + 1
+            for i, t in zip(sel, toks):
+                out[i] = t
+        return out
+
+    @torch.inference_mode()
+    def generate_ids_batch(self, images: Sequence[Image.Image], questions, max_new_tokens: int = 100) -> List[List[int]]:
+        """generate_ids for several host crops in one batched decode: entry i is generate_ids(images[i], question i)."""
+        n = len(images)
+        prompts, caps = self._gen_requests(questions, n, max_new_tokens)
+
+        def run(sel, pr, cp, eos):
+            clip = torch.from_numpy(np.stack([clip_preprocess(images[i], self.cfg.clip_image_size) for i in sel])).bfloat16()
+            return self.engine.generate_batch(clip, pr, cp, eos)
+        return self._generate_chunks(n, prompts, caps, GEN_MAX_BATCH, run)
+
+    @torch.inference_mode()
+    def generate_boxes(self, boxes_xywh: Sequence[Sequence[float]], questions, slots: Optional[Sequence[int]] = None,
+                       max_new_tokens: int = 100) -> List[str]:
+        """generate() for crops `image.crop((int(x), int(y), int(x+w), int(y+h)))` of resident images (set_image; `slots`: one
+        image slot per box, None = slot 0), cut and preprocessed on the GPU and decoded together.  `questions`: one string or one
+        per box.  More than min(16, max_batch) requests run in chunks.  With several ranks every rank decodes the whole batch: the
+        tokens are deterministic, so there is nothing to exchange."""
+        n = len(boxes_xywh)
+        prompts, caps = self._gen_requests(questions, n, max_new_tokens)
+        xyxy = np.asarray([[int(b[0]), int(b[1]), int(b[0] + b[2]), int(b[1] + b[3])] for b in boxes_xywh], np.int32).reshape(-1, 4)
+        slot_arr = None if slots is None else np.asarray(list(slots), np.int32).reshape(-1)
+        assert slot_arr is None or len(slot_arr) == n
+
+        def run(sel, pr, cp, eos):
+            self.engine.preprocess_boxes(xyxy[sel], None if slot_arr is None else slot_arr[sel])
+            return self.engine.generate_batch(None, pr, cp, eos, internal_pixels=True)
+        new = self._generate_chunks(n, prompts, caps, min(GEN_MAX_BATCH, int(self.cfg.max_batch)), run)
+        return [self._gen_text(t) if caps[i] > 0 else "" for i, t in enumerate(new)]
 
     @torch.inference_mode()
     def inference(self, image: Image.Image, question: str, mode: str = "segmentation"):
