@@ -197,7 +197,11 @@ int vstar_image_set_slot_async(vstar_handle* h, int slot, const uint8_t* rgb, in
  * generate(max_new_tokens, greedy); called from VSM.inference at visual_search.py:198-219 for the contextual-cue branch,
  * :427-443).  The reference re-runs the whole prefix for every new token (use_cache=False); here the prompt is prefilled
  * once (CLIP tower + projector + LLaMA prefill, K/V kept in HBM) and each new token is one weight-streaming decode step,
- * which yields the same arg-max tokens.  clip_pix: [1,3,I,I] bf16 (host, or device with VSTAR_F_DEVICE_INPUTS); ids[L]:
+ * which yields the same arg-max tokens.  The steps run in the device-resident loop of vstar_vsm_generate_batch below, at n = 1 on
+ * a one-slot runner: the step is captured once as a hipGraph and replayed, a last kernel feeds the arg-max back and logs it to
+ * coherent host memory, the host polls with one step queued ahead.  VSTAR_DECODE_GRAPH=0, event profiling, a refused capture or a
+ * failed warm-up step launch the same step kernel by kernel (same attention path, same bits); without pinned host memory for the
+ * token log the call returns VSTAR_ERR_NOMEM.  clip_pix: [1,3,I,I] bf16 (host, or device with VSTAR_F_DEVICE_INPUTS); ids[L]:
  * the prompt with one -200; generation stops after max_new_tokens or at eos_id (which is stored as the last id).
  * out_ids must hold max_new_tokens entries; *n_out receives the count. */
 int vstar_vsm_generate(vstar_handle* h, const uint16_t* clip_pix_bf16, const int32_t* ids, int L, int max_new_tokens,
@@ -216,7 +220,8 @@ int vstar_vsm_generate(vstar_handle* h, const uint16_t* clip_pix_bf16, const int
  *   max_new_tokens  [n], each >= 1;  L_i - 1 + P + max_new_tokens[i] must fit the decode context
  *   out_ids         [n, max over i of max_new_tokens[i]] (row-major); n_out [n] receives the counts
  * Bad arguments (n outside [1, VSTAR_GEN_MAX_BATCH], a prompt without or with two -200, a sequence beyond the context, null
- * arrays) return VSTAR_ERR_INVALID before any device work.  The first call builds the batched runner (KV slots for
+ * arrays) return VSTAR_ERR_INVALID before any tower or decode work (n and null arrays: before the runner is built).  The first call
+ * with arrays and an n in range builds the batched runner (KV slots for
  * VSTAR_GEN_MAX_BATCH sequences: 0.5 GB each at 7B with max_text_len 192); when that fails the call returns VSTAR_ERR_NOMEM, nothing
  * stays allocated and the single-sequence entry keeps working. */
 #define VSTAR_GEN_MAX_BATCH 16

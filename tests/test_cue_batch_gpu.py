@@ -176,6 +176,35 @@ def test_launch_by_launch_gives_the_same_tokens(kind):
     assert got == want and got_full == want_full and path == 2
 
 
+@pytest.mark.parametrize("kind", ["trained", "random"])
+def test_solo_launch_by_launch_gives_the_graph_tokens(kind):
+    """vstar_vsm_generate under event profiling: the one-row step of the graph, launched by hand with the graph's key bound, so the
+    same attention path and partition span — the tokens of the unprofiled solo decode (the rig's cache), no eos and eos + caps."""
+    r = _rig(kind)
+    n = 3
+    eos = r.an_eos()
+    runs = [(i, CAP, -1) for i in range(n)]
+    runs += [(i, CAPS[(i + k) % 4], eos) for k in (0, 1) for i in range(n)]       # the caps of the two batched tests above
+    want = [r.solo(i, cap=cap, eos=e) for i, cap, e in runs]                      # computed with profiling off
+    r.eng.profile(True)
+    try:
+        got, paths = [], []
+        for i, cap, e in runs:
+            got.append(r.eng.generate(r.clip[i:i + 1], r.prompts[i], cap, e))
+            paths.append(r.eng.gen_attn_path())
+    finally:
+        r.eng.profile(False)
+    assert got == want
+    assert paths == [2 if len(w) > 1 else -1 for w in want] and paths[:n] == [2] * n
+
+
+def test_a_one_token_solo_decode_runs_no_step():
+    r = _rig("random")
+    assert r.eng.generate(r.clip[:1], r.prompts[0], CAP, -1) == r.solo(0) and r.eng.gen_attn_path() == 2
+    assert r.eng.generate(r.clip[:1], r.prompts[0], 1, -1) == r.solo(0)[:1]
+    assert r.eng.gen_attn_path() == -1                      # the prefill's arg-max alone: no decode step ran
+
+
 def test_errors_are_refused_with_a_message_and_leave_the_engine_usable():
     r = _rig("random")
     n = 3

@@ -146,6 +146,8 @@ struct vstar_engine : EngineBase {
   int ensure_genb();
   int generate_batch(int n, const lp_t* clip_pix, const int32_t* ids, const int32_t* id_off, const int32_t* max_new, int eos_id,
                      unsigned flags, int32_t* out_ids, int32_t* n_out);
+  int generate_rows(LlmCached& r, lp_t* feats, const char* door, int n, const lp_t* clip_pix, const int32_t* ids, const int32_t* id_off,
+                    const int32_t* max_new, int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out);
   int gen_attn_path = -1;       // cached_attention path of the last decode step of the last generate / generate_batch call (-1: none ran)
   int finalize();
   int score(int B, const lp_t* clip_pix, const lp_t* owl_pix, const int32_t* ids, int L, const int32_t* loc_pos,
@@ -978,27 +980,17 @@ int vstar_engine::score(int B, const lp_t* clip_pix, const lp_t* owl_pix, const 
       return finish_records(B, n_verify, flags, out);
     }
     if (it != score_graphs.end()) {                       // second call with this signature: capture it
-      hipGraph_t graph = nullptr;
-      if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        const int rc = score_body(B, L, n_verify, flags, img_col, psh, cpix, opix, skip_owl, h_ids_pin, h_rowidx_pin, rowidx.size());
-        const hipError_t ce = hipStreamEndCapture(stream, &graph);
-        hipGraphExec_t exec = nullptr;
-        if (rc == 0 && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess && exec) {
-          hipGraphDestroy(graph);
-          it->second = exec;
-          HIPCHK(hipGraphLaunch(exec, stream));
-          ++score_graph_replays;
-          return finish_records(B, n_verify, flags, out);
-        }
-        if (graph) hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        score_graphs.erase(it);                           // capture refused: this signature stays on the eager path
-        score_graph_max_B = 0;                            // ... and so does everything else (one failure is a property of the runtime)
-        set_error("");
-      } else {
-        (void)hipGetLastError();
-        score_graph_max_B = 0;
+      const hipGraphExec_t exec = capture_exec(stream, [&] {
+        return score_body(B, L, n_verify, flags, img_col, psh, cpix, opix, skip_owl, h_ids_pin, h_rowidx_pin, rowidx.size());
+      });
+      if (exec) {
+        it->second = exec;
+        HIPCHK(hipGraphLaunch(exec, stream));
+        ++score_graph_replays;
+        return finish_records(B, n_verify, flags, out);
       }
+      score_graphs.erase(it);                             // capture refused: this signature stays on the eager path
+      score_graph_max_B = 0;                              // ... and so does everything else (one failure is a property of the runtime)
     } else {
       score_graphs[sig] = nullptr;                        // first call: eager (warm-up), remember the signature
     }
@@ -1129,60 +1121,75 @@ int vstar_engine::score_grouped(int G, int T, const lp_t* clip_pix, const lp_t* 
   return finish_records(nrec, n_verify, flags, out);
 }
 
-// VSM.inference(mode='vqa'): greedy decode of one crop, KV-cached (see include/vstar_hip.h)
+// The greedy decodes of n crops on runner `r` (sequence i in KV slot i, its image features in rows [i * P, (i + 1) * P) of `feats`),
+// for the two entries below: `door` names the caller's in the messages, `out_ids` is [n, max over i of max_new[i]].
+int vstar_engine::generate_rows(LlmCached& r, lp_t* feats, const char* door, int n, const lp_t* clip_pix, const int32_t* ids,
+                                const int32_t* id_off, const int32_t* max_new, int eos_id, unsigned flags, int32_t* out_ids,
+                                int32_t* n_out) {
+  const vstar_config& c = cfg;
+  const int H = c.llm_hidden, P = clip.P, ctx = gen_ctx();
+  const std::string who = std::string(door) + ": ";
+  gen_attn_path = -1;
+  int out_ld = 0;
+  std::vector<int> img((size_t)n, -1);
+  for (int i = 0; i < n; ++i) {
+    const int L = id_off[i + 1] - id_off[i];
+    const std::string seq = " (sequence " + std::to_string(i) + ")";
+    if (id_off[i] < 0 || L < 2 || max_new[i] < 1) { set_error(who + "a prompt needs >= 2 ids and max_new_tokens >= 1"); return VSTAR_ERR_INVALID; }
+    for (int j = 0; j < L; ++j)
+      if (ids[id_off[i] + j] == -200) {
+        if (img[i] >= 0) { set_error(who + "more than one -200 in input_ids" + seq); return VSTAR_ERR_INVALID; }
+        img[i] = j;
+      }
+    if (img[i] < 0) { set_error(who + "input_ids hold no image token (-200)" + seq); return VSTAR_ERR_INVALID; }
+    if ((int64_t)L - 1 + P + max_new[i] > ctx) { set_error(who + "prompt + max_new_tokens exceed the decode context" + seq); return VSTAR_ERR_INVALID; }
+    out_ld = std::max(out_ld, (int)max_new[i]);
+  }
+  // ---- CLIP tower + mm_projector of the n crops -> feature rows [i * P, (i + 1) * P), max_batch crops per pass ----
+  const bool internal_pix = flags & VSTAR_F_INTERNAL_PIXELS;
+  const size_t cn = (size_t)3 * c.clip_image_size * c.clip_image_size;
+  for (int c0 = 0; c0 < n; c0 += c.max_batch) {
+    const int m = std::min(n - c0, (int)c.max_batch);
+    const lp_t* cpix = d_clip_pix;                            // internal pixels: left there by the preceding preprocessing call
+    if (!internal_pix) {
+      if (flags & VSTAR_F_DEVICE_INPUTS) cpix = clip_pix + (size_t)c0 * cn;
+      else HIPCHK(hipMemcpyAsync(d_clip_pix, clip_pix + (size_t)c0 * cn, (size_t)m * cn * 2, hipMemcpyHostToDevice, stream));
+    }
+    RC(run_tower(clip, cpix, m));
+    RC(project_clip(m, feats + (size_t)c0 * P * H, H));
+  }
+  // ---- prefill: one sequence per forward() call, whatever n (same rows, same kernels, same bits) ----
+  std::vector<int32_t> first((size_t)n), past((size_t)n), rows;
+  for (int i = 0; i < n; ++i) {
+    const int L = id_off[i + 1] - id_off[i];
+    rows.clear();
+    for (int j = 0; j < L; ++j) {
+      if (j == img[i]) for (int p = 0; p < P; ++p) rows.push_back(-(1 + i * P + p));
+      else rows.push_back(ids[id_off[i] + j]);
+    }
+    int32_t row_off[2] = {0, (int32_t)rows.size()}, slot = i, past0 = 0, want = (int32_t)rows.size() - 1, nxt = 0;
+    RC(r.forward(LlmRows{1, row_off, rows.data(), &slot, &slot, &past0, 1, &want}, LlmTail::argmax(nullptr, &nxt)));
+    first[i] = nxt;
+    past[i] = (int32_t)rows.size();
+  }
+  // ---- the decode loop on the device (llm_cached.hpp): one step for all n rows, no per-token host round trip ----
+  RC(r.decode_greedy(n, first.data(), past.data(), max_new, eos_id, out_ids, out_ld, n_out));
+  for (int i = 0; i < n; ++i)
+    if (n_out[i] > 1) gen_attn_path = r.dec_attn_path;
+  return 0;
+}
+
+// VSM.inference(mode='vqa'): greedy decode of one crop, KV-cached (see include/vstar_hip.h): generate_rows at n = 1 on the
+// one-slot runner; host or VSTAR_F_DEVICE_INPUTS pixels only
 int vstar_engine::generate(const lp_t* clip_pix, const int32_t* ids, int L, int max_new, int eos_id, unsigned flags,
                            int32_t* out_ids, int32_t* n_out) {
   if (!finalized) { set_error("weights not finalized"); return VSTAR_ERR_STATE; }
-  const vstar_config& c = cfg;
   if (!clip_pix || !ids || !out_ids || !n_out || L < 2 || max_new < 1) { set_error("vstar_vsm_generate: bad argument"); return VSTAR_ERR_INVALID; }
   HIPCHK(hipSetDevice(device));
-  const int H = c.llm_hidden, P = clip.P;
-  const int ctx = gen_ctx();
   RC(ensure_gen());
-  gen_attn_path = -1;
-  int img = -1;
-  for (int i = 0; i < L; ++i)
-    if (ids[i] == -200) { if (img >= 0) { set_error("more than one -200 in input_ids"); return VSTAR_ERR_INVALID; } img = i; }
-  if (img < 0) { set_error("input_ids hold no image token (-200)"); return VSTAR_ERR_INVALID; }
-  if (L - 1 + P + max_new > ctx) { set_error("prompt + max_new_tokens exceed the decode context"); return VSTAR_ERR_INVALID; }
-  // ---- CLIP tower + mm_projector -> feature rows ----
-  const lp_t* cpix = clip_pix;
-  if (!(flags & VSTAR_F_DEVICE_INPUTS)) {
-    const size_t cn = (size_t)3 * c.clip_image_size * c.clip_image_size;
-    HIPCHK(hipMemcpyAsync(d_clip_pix, clip_pix, cn * 2, hipMemcpyHostToDevice, stream));
-    cpix = d_clip_pix;
-  }
-  RC(run_tower(clip, cpix, 1));
-  RC(project_clip(1, gen_feats, H));
-  // ---- prefill the spliced prompt, then one decode step per new token ----
-  std::vector<int32_t> rows;
-  rows.reserve((size_t)L - 1 + P);
-  for (int i = 0; i < L; ++i) {
-    if (i == img) for (int j = 0; j < P; ++j) rows.push_back(-(1 + j));
-    else rows.push_back(ids[i]);
-  }
-  int32_t row_off[2] = {0, (int32_t)rows.size()}, slot = 0, past = 0, want = (int32_t)rows.size() - 1, nxt = 0;
-  const LlmTail greedy = LlmTail::argmax(nullptr, &nxt);
-  RC(gen.forward(LlmRows{1, row_off, rows.data(), &slot, &slot, &past, 1, &want}, greedy));
-  int n = 0;
-  past = (int32_t)rows.size();
-  {
-    // the decode loop as a replayed hipGraph (llm_cached.hpp): same kernels, no per-token host round trip
-    bool used = false;
-    RC(gen.decode_greedy_graph(nxt, past, slot, max_new, eos_id, out_ids, &n, &used));
-    if (used) { *n_out = n; if (n > 1) gen_attn_path = gen.dec_attn_path; return 0; }
-    n = 0;
-  }
-  for (;;) {
-    out_ids[n++] = nxt;
-    if (nxt == eos_id || n >= max_new) break;
-    int32_t one_off[2] = {0, 1}, w0 = 0, tok = nxt;
-    RC(gen.forward(LlmRows{1, one_off, &tok, &slot, &slot, &past, 1, &w0}, greedy));
-    gen_attn_path = cached_attention_last_path();
-    ++past;
-  }
-  *n_out = n;
-  return 0;
+  const int32_t id_off[2] = {0, L}, cap = max_new;
+  return generate_rows(gen, gen_feats, "vstar_vsm_generate", 1, clip_pix, ids, id_off, &cap, eos_id, flags & VSTAR_F_DEVICE_INPUTS,
+                       out_ids, n_out);
 }
 
 int vstar_engine::ensure_gen() {
@@ -1233,74 +1240,25 @@ int vstar_engine::ensure_genb() {
   return 0;
 }
 
-// VSM.generate_boxes / generate_ids_batch: the greedy decodes of n crops, one decode step for all of them (see include/vstar_hip.h)
+// VSM.generate_boxes / generate_ids_batch: the greedy decodes of n crops, one decode step for all of them (see include/vstar_hip.h):
+// generate_rows on the VSTAR_GEN_MAX_BATCH-slot runner
 int vstar_engine::generate_batch(int n, const lp_t* clip_pix, const int32_t* ids, const int32_t* id_off, const int32_t* max_new,
                                  int eos_id, unsigned flags, int32_t* out_ids, int32_t* n_out) {
   if (!finalized) { set_error("weights not finalized"); return VSTAR_ERR_STATE; }
-  const vstar_config& c = cfg;
   const bool internal_pix = flags & VSTAR_F_INTERNAL_PIXELS;
   if (n < 1 || n > VSTAR_GEN_MAX_BATCH) { set_error("vstar_vsm_generate_batch: n must be in [1, VSTAR_GEN_MAX_BATCH]"); return VSTAR_ERR_INVALID; }
   if ((!clip_pix && !internal_pix) || !ids || !id_off || !max_new || !out_ids || !n_out) {
     set_error("vstar_vsm_generate_batch: null argument");
     return VSTAR_ERR_INVALID;
   }
-  if (internal_pix && n > c.max_batch) {
+  if (internal_pix && n > cfg.max_batch) {
     set_error("vstar_vsm_generate_batch: internal pixels hold at most max_batch crops");
     return VSTAR_ERR_INVALID;
   }
-  const int H = c.llm_hidden, P = clip.P, ctx = gen_ctx();
-  int out_ld = 0;
-  std::vector<int> img((size_t)n, -1);
-  for (int i = 0; i < n; ++i) {
-    const int L = id_off[i + 1] - id_off[i];
-    if (id_off[i] < 0 || L < 2 || max_new[i] < 1) { set_error("vstar_vsm_generate_batch: a prompt needs >= 2 ids and max_new_tokens >= 1"); return VSTAR_ERR_INVALID; }
-    for (int j = 0; j < L; ++j)
-      if (ids[id_off[i] + j] == -200) {
-        if (img[i] >= 0) { set_error("more than one -200 in input_ids (sequence " + std::to_string(i) + ")"); return VSTAR_ERR_INVALID; }
-        img[i] = j;
-      }
-    if (img[i] < 0) { set_error("input_ids hold no image token (-200) (sequence " + std::to_string(i) + ")"); return VSTAR_ERR_INVALID; }
-    if ((int64_t)L - 1 + P + max_new[i] > ctx) {
-      set_error("prompt + max_new_tokens exceed the decode context (sequence " + std::to_string(i) + ")");
-      return VSTAR_ERR_INVALID;
-    }
-    out_ld = std::max(out_ld, (int)max_new[i]);
-  }
   HIPCHK(hipSetDevice(device));
   RC(ensure_genb());
-  gen_attn_path = -1;
-  // ---- CLIP tower + mm_projector of the n crops -> feature rows [i * P, (i + 1) * P), max_batch crops per pass ----
-  const size_t cn = (size_t)3 * c.clip_image_size * c.clip_image_size;
-  for (int c0 = 0; c0 < n; c0 += c.max_batch) {
-    const int m = std::min(n - c0, (int)c.max_batch);
-    const lp_t* cpix = d_clip_pix;                            // internal pixels: left there by the preceding preprocessing call
-    if (!internal_pix) {
-      if (flags & VSTAR_F_DEVICE_INPUTS) cpix = clip_pix + (size_t)c0 * cn;
-      else HIPCHK(hipMemcpyAsync(d_clip_pix, clip_pix + (size_t)c0 * cn, (size_t)m * cn * 2, hipMemcpyHostToDevice, stream));
-    }
-    RC(run_tower(clip, cpix, m));
-    RC(project_clip(m, genb_feats + (size_t)c0 * P * H, H));
-  }
-  // ---- prefill: one sequence per forward() call, exactly the call the solo decode makes (same rows, same kernels, same bits) ----
-  std::vector<int32_t> first((size_t)n), past((size_t)n), rows;
-  for (int i = 0; i < n; ++i) {
-    const int L = id_off[i + 1] - id_off[i];
-    rows.clear();
-    for (int j = 0; j < L; ++j) {
-      if (j == img[i]) for (int p = 0; p < P; ++p) rows.push_back(-(1 + i * P + p));
-      else rows.push_back(ids[id_off[i] + j]);
-    }
-    int32_t row_off[2] = {0, (int32_t)rows.size()}, slot = i, past0 = 0, want = (int32_t)rows.size() - 1, nxt = 0;
-    RC(genb.forward(LlmRows{1, row_off, rows.data(), &slot, &slot, &past0, 1, &want}, LlmTail::argmax(nullptr, &nxt)));
-    first[i] = nxt;
-    past[i] = (int32_t)rows.size();
-  }
-  RC(genb.decode_greedy_batch(n, first.data(), past.data(), max_new, eos_id, out_ids, out_ld, n_out));
-  for (int i = 0; i < n; ++i)
-    if (n_out[i] > 1) gen_attn_path = genb.dec_attn_path;
-  return 0;
+  return generate_rows(genb, genb_feats, "vstar_vsm_generate_batch", n, clip_pix, ids, id_off, max_new, eos_id, flags, out_ids, n_out);
 }
-
 
 // =============================================== C ABI ===============================================
 extern "C" {

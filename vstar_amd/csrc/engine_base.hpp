@@ -243,6 +243,22 @@ struct EngineBase {
     ev_used = 0;
   }
 
+  // What `body` enqueues on `s`, as an executable graph: begin capture (thread-local mode), run body, end capture, instantiate,
+  // destroy the graph.  nullptr when the runtime refuses any step or body returns non-zero; no sticky HIP error and no error string
+  // are left behind then, and what runs instead is the caller's business.
+  template <typename F> hipGraphExec_t capture_exec(hipStream_t s, F&& body) {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+      const int rc = body();
+      const hipError_t ce = hipStreamEndCapture(s, &graph);
+      if (rc != 0 || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+      if (graph) hipGraphDestroy(graph);
+    }
+    if (!exec) { (void)hipGetLastError(); set_error(""); }
+    return exec;
+  }
+
   int build_tower(VitTower& t, const std::string& pre, const std::string& preln_name, int image, int patch, int hidden,
                   int heads, int mlp, int nblocks, int maxB);
   int run_tower(VitTower& t, const lp_t* pix, int B);

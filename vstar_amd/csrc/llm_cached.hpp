@@ -115,7 +115,7 @@ struct LlmCachedCfg {
   int weight_bits = 0;      // 8: int8 weight-only decode of the block linears (fp16 build only);
                             // 4: int4 with one fp16 scale per group of 128 (fp16 build only)
   int kv_format = KV_FMT_F16;   // KV_FMT_MXFP8 / KV_FMT_MXFP8_EMU: block-scaled fp8 KV cache (fp16 build only)
-  // Decode attention of a runner whose steps must not depend on their row count (the batched cue decode, decode_greedy_batch):
+  // Decode attention of a runner whose steps must not depend on their row count (the batched cue decode through decode_greedy):
   // split_rows > 0 sizes the split-KV workspace for that many rows instead of SPLIT_ROWS, attn_decide_rows > 0 makes every step take
   // the split / unsplit decision of a step of that many rows (kernels.hpp: cached_attention's decide_rows).
   int split_rows = 0, attn_decide_rows = 0;
@@ -265,24 +265,21 @@ struct LlmCached {
   char* beam_ws = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_ms = 0;
-  // ---- greedy decode of ONE sequence as a replayed hipGraph (decode_greedy_graph) ----
-  // A decode step is ~165 launches of 10-55 us (5 per layer); their arguments never change from token to token — the token id,
-  // position and past length live in DEVICE arrays — so the step is captured once and replayed; a last kernel of the graph feeds
-  // the arg-max back as the next input and advances the position, and the host looks at the emitted tokens every few steps only.
-  hipGraphExec_t dec_exec = nullptr;
-  int dec_keys_bound = 0;                        // context bound the captured attention launch was sized for
-  int32_t* d_dec = nullptr;                      // coherent HOST memory: [0] = tokens emitted so far, [1..] = the tokens
-  int dec_cap = 0;
-  int dec_attn_path = -1;                        // cached_attention path of the step the graph holds / the last step launched by hand
-  // ---- greedy decode of n sequences, rows 0 .. n - 1, as one replayed hipGraph per n (decode_greedy_batch) ----
-  // The same step over n rows; what differs per call (eos id, per-row caps) lives in DEVICE arrays, so a graph depends on n alone.
+  // ---- greedy decode of n sequences, rows 0 .. n - 1, as one replayed hipGraph per n (decode_greedy) ----
+  // A decode step is ~165 launches of 10-55 us (5 per layer); their arguments never change from token to token — token ids,
+  // positions and past lengths live in DEVICE arrays, and so does what differs per call (eos id, per-row caps) — so the step of n
+  // rows is captured once and replayed: a graph depends on n alone.  A last kernel of the step feeds every unfinished row's arg-max
+  // back as its next input, advances its position and logs the tokens to coherent host memory, which the host polls with steps
+  // queued ahead instead of synchronising the stream.  A runner decodes up to dec_rows_max() sequences at once (a one-slot runner: one).
   static constexpr int DEC_BATCH_MAX = 16;
-  hipGraphExec_t decb_exec[DEC_BATCH_MAX + 1] = {};
+  int dec_rows_max() const { return std::min(DEC_BATCH_MAX, cfg.max_slots); }
+  hipGraphExec_t dec_graph[DEC_BATCH_MAX + 1] = {};
+  int dec_attn_path = -1;                        // cached_attention path of the step the graphs hold / the last step launched by hand
   // device: [0] = eos id, [1 + r] = cap of row r (tokens, the prefill's included), [17 + r] = tokens row r has emitted,
   // [33 + r] = row r finished
-  int32_t* d_decb = nullptr;
-  int32_t* h_decb = nullptr;                     // coherent HOST memory: [0] = steps done, [1] = unfinished rows, [2 + step * n + r] = tokens
-  int decb_cap = 0;                              // steps the log holds
+  int32_t* d_dec_ctl = nullptr;
+  int32_t* h_dec_log = nullptr;                  // coherent HOST memory: [0] = steps done, [1] = unfinished rows, [2 + step * n + r] = tokens
+  int dec_log_steps = 0;                         // steps the log holds (of dec_rows_max() rows each)
   // ---- the decode GEMV's weight descriptors: empty (row-major fp16 weights only), or one record per layer ----
   // Tile-major copies of the big decode weights (round 5; SKINNY_W_F16): the weight-streaming GEMV gives a workgroup 16 (gate|up: 32)
   // ROWS of the row-major matrix, i.e. 16 - 32 sequential streams 2 K bytes apart and 4096 - 22016 of them over the chip; laid out
@@ -304,20 +301,14 @@ struct LlmCached {
     if (ev0) hipEventDestroy(ev0);
     if (ev1) hipEventDestroy(ev1);
     ev0 = ev1 = nullptr;
-    if (dec_exec) hipGraphExecDestroy(dec_exec);
-    dec_exec = nullptr;
-    if (d_dec) hipHostFree(d_dec);
-    d_dec = nullptr;
-    for (hipGraphExec_t& g : decb_exec) { if (g) hipGraphExecDestroy(g); g = nullptr; }
-    if (h_decb) hipHostFree(h_decb);
-    h_decb = nullptr;
+    for (hipGraphExec_t& g : dec_graph) { if (g) hipGraphExecDestroy(g); g = nullptr; }
+    if (h_dec_log) hipHostFree(h_dec_log);
+    h_dec_log = nullptr;
   }
-  int decode_step_body(int keys_bound);
-  int decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids, int* n_out, bool* used);
-  int decode_batch_step_body(int n, int keys_bound);
-  int decode_batch_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id);
-  int decode_greedy_batch(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id, int32_t* out_ids,
-                          int64_t out_ld, int32_t* n_out);
+  int decode_step_body(int n, int keys_bound);
+  int decode_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id);
+  int decode_greedy(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id, int32_t* out_ids, int64_t out_ld,
+                    int32_t* n_out);
   // the fp16 tile-major decode weights of another runner over the same blocks (set before init: this runner then builds none)
   const std::vector<DecodeLayerW>* borrow_dec_w = nullptr;
   int lin_auto(const lp_t* A, int64_t lda, const Lin& L, void* C, int64_t ldc, int M, int epi = VSTAR_EPI_NONE,
@@ -982,161 +973,15 @@ inline int LlmCached::kv_copy(int dst, int src, int lo, int hi) {
 }
 
 namespace {
-// last node of the decode graph: the arg-max becomes the next input token, position and past length advance, the token is logged.
-// `log` is coherent HOST memory (hipHostMallocCoherent): the host polls log[0] instead of synchronising the stream, so the next
-// step's graph is already queued while it looks at this step's token.  Token first, counter last, system-scope release.
-__global__ void decode_advance_kernel(const int32_t* __restrict__ argmax, int32_t* src, int32_t* row_pos, int32_t* seq_past, int32_t* log,
-                                      int cap) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const int32_t t = argmax[0];
-  src[0] = t;
-  row_pos[0] += 1;
-  seq_past[0] += 1;
-  const int32_t n = log[0];
-  if (n < cap) log[1 + n] = t;
-  __threadfence_system();
-  __hip_atomic_store(&log[0], n + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-}  // namespace
-
-// one decode step of ONE sequence (row 0) with every per-step value read from device memory: what the graph captures
-inline int LlmCached::decode_step_body(int keys_bound) {
-  const LlmCachedCfg& c = cfg;
-  const int H = c.hidden;
-  LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, 1, H, e->stream));
-  RC(llm_layers_cached(1, keys_bound, true));
-  dec_attn_path = cached_attention_last_path();
-  RC(head(0, 1));
-  LCHK(argmax_rows_lp(logits, 1, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
-  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_dec, dec_cap);
-  LCHK(hipGetLastError());
-  return 0;
-}
-
-// Greedy continuation of the sequence in `slot` whose cache holds `past` positions, starting from `first_token` (already the
-// arg-max of the prefill): emits up to max_new - 1 further tokens, stopping at eos_id.  *used = false when the graph path is
-// not available (event profiling on, a launch of the warm-up step failed): the caller then runs the stepwise loop — same kernels,
-// same tokens (re-running a step rewrites the same K/V rows of the cache, so a half-finished warm-up step does no harm).
-// Round 4: nothing is launched when the prefill's arg-max already is EOS; a failing warm-up step or a refused capture
-// degrades to the stepwise path instead of failing generate(); the emitted tokens are read from coherent host memory with ONE
-// step in flight ahead, so at most one decode step (not up to seven) runs past EOS and the stream is never drained between steps.
-inline int LlmCached::decode_greedy_graph(int32_t first_token, int past, int slot, int max_new, int eos_id, int32_t* out_ids,
-                                          int* n_out, bool* used) {
-  *used = false;
-  const LlmCachedCfg& c = cfg;
-  static const bool disabled = [] { const char* v = getenv("VSTAR_DECODE_GRAPH"); return v && atoi(v) == 0; }();
-  if (disabled || e->profile || max_new < 1) return 0;
-  if (slot < 0 || slot >= c.max_slots || anc_flag[slot]) return 0;     // a beam-reordered slot: the graph's attention reads no ancestry
-  if (first_token == eos_id || max_new < 2) {          // the answer is the prefill's arg-max alone: no decode step at all
-    out_ids[0] = first_token;
-    *n_out = 1;
-    *used = true;
-    return 0;
-  }
-  LCHK(hipSetDevice(e->device));
-  if (!d_dec) {
-    dec_cap = c.max_ctx;
-    void* hp = nullptr;
-    if (hipHostMalloc(&hp, ((size_t)dec_cap + 1) * 4, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;                                         // no pinned memory: the stepwise loop
-    }
-    d_dec = (int32_t*)hp;
-  }
-  volatile int32_t* log = d_dec;
-  const int keys_bound = c.max_ctx;                  // sizes the attention launch's LDS (4 B per key): fixed for the graph's lifetime
-  // ---- per-call state of row 0 ----
-  std::vector<int32_t> seqmeta((size_t)3 * seq_cap(), 0);
-  seq_set(seqmeta, 0, slot, slot, past);
-  const int32_t zero = 0, pos0 = past, slot0 = slot, tok0 = first_token;
-  LCHK(hipMemcpyAsync(d_src, &tok0, 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_row_pos, &pos0, 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_row_slot, &slot0, 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_row_seq, &zero, 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_seq, seqmeta.data(), seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_want, &zero, 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipStreamSynchronize(e->stream));
-  d_dec[0] = 0;
-  __atomic_thread_fence(__ATOMIC_SEQ_CST);
-  int launched = 0;
-  if (!dec_exec || dec_keys_bound != keys_bound) {
-    if (dec_exec) { hipGraphExecDestroy(dec_exec); dec_exec = nullptr; }
-    // the first step runs UNCAPTURED: it is a real decode step (its token is consumed below) and it takes every one-time
-    // hipFuncSetAttribute of the launch helpers out of the capture
-    if (decode_step_body(keys_bound) != 0 || hipStreamSynchronize(e->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      e->set_error("");                                // not an error of generate(): the stepwise loop takes over
-      return 0;
-    }
-    launched = 1;
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      const int rc = decode_step_body(keys_bound);
-      const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
-      if (rc != 0 || ce != hipSuccess || !graph) {
-        if (graph) hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        e->set_error("");
-      } else {
-        const hipError_t ie = hipGraphInstantiate(&dec_exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) { dec_exec = nullptr; (void)hipGetLastError(); }
-        else dec_keys_bound = keys_bound;
-      }
-    } else {
-      (void)hipGetLastError();                          // capture refused: the loop below launches the same step kernel by kernel
-    }
-  }
-  *used = true;                                         // from here on this function owns the sequence's state
-  int n = 0;
-  out_ids[n++] = first_token;
-  const int DEPTH = 2;                                  // decode steps queued ahead of the token the host is waiting for
-  bool done = false;
-  LCHK(hipEventRecord(ev0, e->stream));
-  const int launched0 = launched;
-  while (!done && n < max_new) {
-    // out_ids[k] (k >= 1) = log[k], produced by decode step k; keep steps n .. n + DEPTH - 1 queued
-    while (launched < std::min(max_new - 1, n - 1 + DEPTH)) {
-      if (dec_exec) LCHK(hipGraphLaunch(dec_exec, e->stream));
-      else RC(decode_step_body(keys_bound));
-      ++launched;
-    }
-    if (launched < n) break;                            // max_new reached
-    unsigned spins = 0;
-    while (__atomic_load_n(&d_dec[0], __ATOMIC_ACQUIRE) < n) {
-      if ((++spins & 4095u) == 0) {
-        const hipError_t q = hipStreamQuery(e->stream);
-        if (q == hipSuccess) {
-          if (__atomic_load_n(&d_dec[0], __ATOMIC_ACQUIRE) >= n) break;
-          set_error("decode graph: a step completed without emitting its token");
-          return VSTAR_ERR_HIP;
-        }
-        if (q != hipErrorNotReady) { set_error(std::string("decode graph: ") + hipGetErrorString(q)); return VSTAR_ERR_HIP; }
-      }
-      __builtin_ia32_pause();
-    }
-    const int32_t t = log[n];
-    out_ids[n++] = t;
-    if (t == eos_id) done = true;
-  }
-  LCHK(hipEventRecord(ev1, e->stream));
-  LCHK(hipStreamSynchronize(e->stream));
-  float ms = 0;
-  const int timed = launched - launched0;
-  if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && timed > 0) last_ms = ms / timed;
-  *n_out = n;
-  return 0;
-}
-
-namespace {
-// decode_advance_kernel for rows 0 .. n - 1 (one workgroup, thread r = row r).  ctl: see LlmCached::d_decb.  An unfinished row
-// takes its arg-max as the next input and advances; it finishes when it emitted the eos id or reached its cap.  A FINISHED row is
-// left where it is: the steps it still rides along recompute the same position of its own KV slot, so it can never leave the
+// Last node of a decode step of rows 0 .. n - 1 (one workgroup, thread r = row r).  ctl: see LlmCached::d_dec_ctl.  An unfinished
+// row takes its arg-max as the next input and advances; it finishes when it emitted the eos id or reached its cap.  A FINISHED row
+// is left where it is: the steps it still rides along recompute the same position of its own KV slot, so it can never leave the
 // context however long its companions run, and it touches nobody else's keys.  Every row's token is logged step-major (the host
 // drops what a finished row emits); then, once per step, the number of unfinished rows and — last, with a system-scope release —
-// the step counter are published.
-__global__ void decode_advance_batch_kernel(const int32_t* __restrict__ argmax, int32_t* src, int32_t* row_pos, int32_t* seq_past,
-                                            int32_t* ctl, int32_t* log, int n, int cap_steps) {
+// the step counter are published.  `log` is coherent HOST memory (hipHostMallocCoherent): the host polls log[0] instead of
+// synchronising the stream, so the next step is already queued while it looks at this step's tokens.
+__global__ void decode_advance_kernel(const int32_t* __restrict__ argmax, int32_t* src, int32_t* row_pos, int32_t* seq_past,
+                                      int32_t* ctl, int32_t* log, int n, int cap_steps) {
   __shared__ int alive;
   const int r = threadIdx.x;
   if (r == 0) alive = 0;
@@ -1167,21 +1012,21 @@ __global__ void decode_advance_batch_kernel(const int32_t* __restrict__ argmax, 
 }  // namespace
 
 // one decode step of rows 0 .. n - 1 (one row per sequence), every per-step value read from device memory: what the graph of n captures
-inline int LlmCached::decode_batch_step_body(int n, int keys_bound) {
+inline int LlmCached::decode_step_body(int n, int keys_bound) {
   const LlmCachedCfg& c = cfg;
   LCHK(embed_rows(d_src, embed, c.vocab, feats, n_feat_rows, lx, n, c.hidden, e->stream));
   RC(llm_layers_cached(n, keys_bound, true));
   dec_attn_path = cached_attention_last_path();
   RC(head(0, n));
   LCHK(argmax_rows_lp(logits, n, c.vocab, (int64_t)vpad(), d_argmax, e->stream));
-  hipLaunchKernelGGL(decode_advance_batch_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_decb,
-                     h_decb, n, decb_cap);
+  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, e->stream, d_argmax, d_src, d_row_pos, seq_array(2), d_dec_ctl,
+                     h_dec_log, n, dec_log_steps);
   LCHK(hipGetLastError());
   return 0;
 }
 
-// the per-call state of a batched decode: sequence i is row i and lives in KV slot i with `past[i]` positions cached
-inline int LlmCached::decode_batch_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id) {
+// the per-call state of decode_greedy: sequence i is row i and lives in KV slot i with `past[i]` positions cached
+inline int LlmCached::decode_state(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id) {
   std::vector<int32_t> seqmeta((size_t)3 * seq_cap(), 0), iota((size_t)n), ctl(1 + 3 * DEC_BATCH_MAX, 0);
   int alive = 0;
   ctl[0] = eos_id;
@@ -1198,29 +1043,31 @@ inline int LlmCached::decode_batch_state(int n, const int32_t* first, const int3
   LCHK(hipMemcpyAsync(d_row_seq, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_seq, seqmeta.data(), seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_want, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-  LCHK(hipMemcpyAsync(d_decb, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, e->stream));
+  LCHK(hipMemcpyAsync(d_dec_ctl, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
-  h_decb[0] = 0;
-  h_decb[1] = alive;
+  h_dec_log[0] = 0;
+  h_dec_log[1] = alive;
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
   return 0;
 }
 
-// decode_greedy_graph for n sequences at once: sequence i sits in KV slot i with past[i] positions cached, first[i] is its prefill's
+// Greedy continuation of n sequences at once: sequence i sits in KV slot i with past[i] positions cached, first[i] is its prefill's
 // arg-max, caps[i] >= 1 the tokens it may emit in all.  Row i of out_ids (row stride out_ld) receives its tokens, n_out[i] their
 // count; it stops at its cap or at eos_id (stored).  One graph per n; VSTAR_DECODE_GRAPH=0, event profiling, a refused capture or a
-// failed warm-up step run the same n-row step launch by launch.  Nothing is launched when no row has a step to take.
-inline int LlmCached::decode_greedy_batch(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id,
-                                          int32_t* out_ids, int64_t out_ld, int32_t* n_out) {
+// failed warm-up step run the same n-row step launch by launch, with the same keys_bound — so the same attention path and partition
+// span, the same bits.  Nothing is launched when no row has a step to take.  A beam-reordered (ancestral) slot is refused: the
+// step's attention reads no ancestry.
+inline int LlmCached::decode_greedy(int n, const int32_t* first, const int32_t* past, const int32_t* caps, int eos_id, int32_t* out_ids,
+                                    int64_t out_ld, int32_t* n_out) {
   const LlmCachedCfg& c = cfg;
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
-  if (n < 1 || n > DEC_BATCH_MAX || n > c.max_slots) { e->set_error("batched decode: row count out of range"); return VSTAR_ERR_INVALID; }
+  if (n < 1 || n > dec_rows_max()) { e->set_error("greedy decode: row count out of range"); return VSTAR_ERR_INVALID; }
   static const bool disabled = [] { const char* v = getenv("VSTAR_DECODE_GRAPH"); return v && atoi(v) == 0; }();
   std::vector<char> fin((size_t)n, 0);
   int alive = 0, max_steps = 0;
   for (int i = 0; i < n; ++i) {
     if (caps[i] < 1 || past[i] < 1 || past[i] + caps[i] - 1 > c.max_ctx || anc_flag[i]) {
-      e->set_error("batched decode: a sequence's cap or cached length is out of range");
+      e->set_error("greedy decode: a sequence's cap or cached length is out of range");
       return VSTAR_ERR_INVALID;
     }
     out_ids[(int64_t)i * out_ld] = first[i];
@@ -1230,47 +1077,33 @@ inline int LlmCached::decode_greedy_batch(int n, const int32_t* first, const int
   }
   if (alive == 0) return 0;                             // every answer is its prefill's arg-max alone: no decode step at all
   LCHK(hipSetDevice(e->device));
-  if (!d_decb) RC(e->dalloc(&d_decb, (size_t)1 + 3 * DEC_BATCH_MAX));
-  if (!h_decb) {
-    decb_cap = c.max_ctx;
+  if (!d_dec_ctl) RC(e->dalloc(&d_dec_ctl, (size_t)1 + 3 * DEC_BATCH_MAX));
+  if (!h_dec_log) {
+    dec_log_steps = c.max_ctx;
     void* hp = nullptr;
-    if (hipHostMalloc(&hp, ((size_t)decb_cap * DEC_BATCH_MAX + 2) * 4, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+    if (hipHostMalloc(&hp, ((size_t)dec_log_steps * dec_rows_max() + 2) * 4, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
       (void)hipGetLastError();
-      e->set_error("batched decode: no pinned host memory for the token log");
+      e->set_error("greedy decode: no pinned host memory for the token log");
       return VSTAR_ERR_NOMEM;
     }
-    h_decb = (int32_t*)hp;
+    h_dec_log = (int32_t*)hp;
   }
-  const int keys_bound = c.max_ctx;                    // as in decode_greedy_graph: fixed for the graphs' lifetime
-  RC(decode_batch_state(n, first, past, caps, eos_id));
+  const int keys_bound = c.max_ctx;       // sizes the attention launch (LDS: 4 B per key, split / partition span): fixed for the graphs' lifetime
+  RC(decode_state(n, first, past, caps, eos_id));
   int launched = 0;
-  if (!disabled && !e->profile && !decb_exec[n]) {
-    // as in decode_greedy_graph: the first step runs uncaptured (a real step) and takes the one-time attributes out of the capture
-    if (decode_batch_step_body(n, keys_bound) != 0 || hipStreamSynchronize(e->stream) != hipSuccess) {
+  if (!disabled && !e->profile && !dec_graph[n]) {
+    // the first step runs UNCAPTURED: it is a real decode step (its tokens are consumed below) and it takes every one-time
+    // hipFuncSetAttribute of the launch helpers out of the capture
+    if (decode_step_body(n, keys_bound) != 0 || hipStreamSynchronize(e->stream) != hipSuccess) {
       (void)hipGetLastError();
       e->set_error("");
-      RC(decode_batch_state(n, first, past, caps, eos_id));      // start again, launch by launch (a step rewrites the same K/V rows)
+      RC(decode_state(n, first, past, caps, eos_id));      // start again, launch by launch (a step rewrites the same K/V rows)
     } else {
       launched = 1;
-      hipGraph_t graph = nullptr;
-      if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        const int rc = decode_batch_step_body(n, keys_bound);
-        const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
-        if (rc != 0 || ce != hipSuccess || !graph) {
-          if (graph) hipGraphDestroy(graph);
-          (void)hipGetLastError();
-          e->set_error("");
-        } else {
-          const hipError_t ie = hipGraphInstantiate(&decb_exec[n], graph, nullptr, nullptr, 0);
-          hipGraphDestroy(graph);
-          if (ie != hipSuccess) { decb_exec[n] = nullptr; (void)hipGetLastError(); }
-        }
-      } else {
-        (void)hipGetLastError();
-      }
+      dec_graph[n] = e->capture_exec(e->stream, [&] { return decode_step_body(n, keys_bound); });    // refused: launch by launch
     }
   }
-  const hipGraphExec_t exec = (disabled || e->profile) ? nullptr : decb_exec[n];
+  const hipGraphExec_t exec = (disabled || e->profile) ? nullptr : dec_graph[n];
   const int DEPTH = 2;                                  // decode steps queued ahead of the step the host is waiting for
   int done_steps = 0;
   LCHK(hipEventRecord(ev0, e->stream));
@@ -1278,26 +1111,26 @@ inline int LlmCached::decode_greedy_batch(int n, const int32_t* first, const int
   while (alive > 0 && done_steps < max_steps) {
     // step k (1-based) produces token k of every row; keep steps done_steps + 1 .. done_steps + DEPTH queued while the device still
     // reports an unfinished row
-    while (launched < std::min(max_steps, done_steps + DEPTH) && __atomic_load_n(&h_decb[1], __ATOMIC_ACQUIRE) > 0) {
+    while (launched < std::min(max_steps, done_steps + DEPTH) && __atomic_load_n(&h_dec_log[1], __ATOMIC_ACQUIRE) > 0) {
       if (exec) LCHK(hipGraphLaunch(exec, e->stream));
-      else RC(decode_batch_step_body(n, keys_bound));
+      else RC(decode_step_body(n, keys_bound));
       ++launched;
     }
-    if (launched <= done_steps) { set_error("batched decode: the device reports no unfinished row, the host has one"); return VSTAR_ERR_HIP; }
+    if (launched <= done_steps) { set_error("greedy decode: the device reports no unfinished row, the host has one"); return VSTAR_ERR_HIP; }
     unsigned spins = 0;
-    while (__atomic_load_n(&h_decb[0], __ATOMIC_ACQUIRE) < done_steps + 1) {
+    while (__atomic_load_n(&h_dec_log[0], __ATOMIC_ACQUIRE) < done_steps + 1) {
       if ((++spins & 4095u) == 0) {
         const hipError_t q = hipStreamQuery(e->stream);
         if (q == hipSuccess) {
-          if (__atomic_load_n(&h_decb[0], __ATOMIC_ACQUIRE) >= done_steps + 1) break;
-          set_error("batched decode: a step completed without emitting its tokens");
+          if (__atomic_load_n(&h_dec_log[0], __ATOMIC_ACQUIRE) >= done_steps + 1) break;
+          set_error("greedy decode: a step completed without emitting its tokens");
           return VSTAR_ERR_HIP;
         }
-        if (q != hipErrorNotReady) { set_error(std::string("batched decode: ") + hipGetErrorString(q)); return VSTAR_ERR_HIP; }
+        if (q != hipErrorNotReady) { set_error(std::string("greedy decode: ") + hipGetErrorString(q)); return VSTAR_ERR_HIP; }
       }
       __builtin_ia32_pause();
     }
-    const volatile int32_t* row = h_decb + 2 + (int64_t)done_steps * n;
+    const volatile int32_t* row = h_dec_log + 2 + (int64_t)done_steps * n;
     for (int i = 0; i < n; ++i) {
       if (fin[i]) continue;
       const int32_t t = row[i];
