@@ -290,6 +290,50 @@ int vstar_vqa_forward_verify_logprobs(vstar_vqa_handle* h, int nseq, const int32
                                       const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
                                       int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits,
                                       const vstar_vqa_logprobs* lp);
+/* Further warpers of the sampled decode: the rest of HF 4.31 generate's warper list, on the device, behind
+ * top-k / top-p and ahead of the draw, in HF's order min-p -> typical-p -> epsilon -> eta.  Each stage sees the kept set K the
+ * stage before it left and p_i = m_i / Z_K, with m_i the fixed-point masses of vstar_vqa_sampling (exp(s_i - s_max) in 2^-40 units,
+ * relative to the row's maximum whether or not it is still kept; a token whose mass rounds to 0 takes part in nothing) and
+ * l_i = s_i - s_max in fp32:
+ *   min_p           keep iff p_i >= min_p * max_K p
+ *   typical_p       H = -sum_K p_i ln p_i, d_i = |-ln p_i - H| = |l_i - E_p[l]| (fp32); keep iff the mass of the tokens of K with a
+ *                   strictly smaller d is < typical_p * Z_K: every tie in d is kept, the token of smallest d always stays.  The kept
+ *                   set becomes a band of scores, which may exclude the arg-max
+ *   epsilon_cutoff  keep iff p_i >= epsilon_cutoff
+ *   eta_cutoff      eta = min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)), H the entropy over the current K; keep iff p_i >= eta
+ * The largest score of K always stays (min_tokens_to_keep = 1).  Entropies and softmaxes are exact where HF rounds them to fp16;
+ * E_p[l] is summed in double in a fixed order, every other sum is an exact integer, so a row's result depends on that row and its
+ * records only.  The log-probabilities of vstar_vqa_logprobs stay those of the un-warped row. */
+typedef struct vstar_vqa_warpers {    /* 16 bytes */
+  float min_p;            /* [0, 1]; 0 = off */
+  float typical_p;        /* > 0; >= 1 = off */
+  float epsilon_cutoff;   /* [0, 1); 0 = off */
+  float eta_cutoff;       /* [0, 1); 0 = off */
+} vstar_vqa_warpers;
+
+/* vstar_vqa_forward_sample_logprobs / _forward_verify_logprobs with one vstar_vqa_warpers record per wanted row (host, parallel to
+ * params); edits and lp stay nullable.  warpers == NULL is the _logprobs call, bit for bit and launch for launch; records that are
+ * all off give its bits too.  A greedy verify (params == NULL) checks the records and ignores them, as it has no top-k / top-p.
+ * Errors (VSTAR_ERR_INVALID, before any device work, the engine stays usable): a NaN or negative value, min_p > 1, typical_p <= 0,
+ * a cutoff >= 1; the message names the field.  The device array for the records is allocated by the first call that carries them
+ * (a failed allocation is VSTAR_ERR_NOMEM and leaves the engine usable); a call without them allocates and copies nothing. */
+int vstar_vqa_forward_sample_warp(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src,
+                                  const int32_t* kv_slot, const int32_t* prefix_slot, const int32_t* past_len,
+                                  int n_want, const int32_t* want, const vstar_vqa_sampling* params, int32_t* tokens,
+                                  const vstar_vqa_warpers* warpers, const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp);
+int vstar_vqa_forward_verify_warp(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                  const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                  const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                  int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_warpers* warpers,
+                                  const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp);
+/* Op-level (tests, micro-benchmarks): vstar_vqa_op_sample / vstar_vqa_op_verify with host warpers[rows] (nullable: the plain op).
+ * kept_mask (nullable diagnostic, host, uint8 [rows, vocab]): 1 where the token is in the kept set the draw was made from. */
+int vstar_vqa_op_sample_warp(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
+                             const vstar_vqa_warpers* warpers, int32_t* tokens, float* u_out, int32_t* n_kept, uint8_t* kept_mask);
+int vstar_vqa_op_verify_warp(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off,
+                             int n_groups, const int32_t* draft, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers,
+                             int32_t* n_accept_out, int32_t* tokens_out);
+
 /* Op-level (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22, rows <= 65535, any ld >=
  * vocab); host tokens[rows] (a negative token: the row is not read) and outputs as above with n_want = rows; token_rank nullable,
  * top_logprob / top_token null iff n_top == 0.  n_top outside [0, 32] or a token >= vocab is VSTAR_ERR_INVALID with a message, before

@@ -5,7 +5,8 @@ KV-cached decode steps at several batch sizes, forked option scoring.  Prints on
 --logprobs 0,5 runs `decode_logprobs` alone: greedy decode steps without and with the on-device log-probability stage (logprobs=0 /
 logprobs=5), alternated in blocks of --steps at the --batches sizes, and each mode's tokens/s over the plain one's.
 --sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
-sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio.
+sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio; with --warp a
+third kind of block, the sampled step with min_p 0.05 and typical_p 0.9, and its cost over the plain sampled step.
 --beams 1,2,4,8 adds `decode_beams`: beam-search steps of one prompt with k beams (forward_beam's select tail, the host scorer,
 the KV ancestry reorder) alternated with greedy steps of k copies of the same prompt, and the beam / greedy step-time ratio.
 --score 1,4,8,16 adds `score`: multiple-choice scoring of B questions (~300 cached rows, 4 options x 12 tokens) through
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--batches", default="1,4,16,32")
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--sample", action="store_true", help="add the sampled-decode leg next to greedy")
+    ap.add_argument("--warp", action="store_true", help="--sample: add sampled blocks with min_p=0.05 and typical_p=0.9 (DESIGN.md §8.10)")
     ap.add_argument("--rounds", type=int, default=3, help="--sample / --beams: blocks alternated this many times")
     ap.add_argument("--beams", default="", help="comma-separated beam counts: add the beam-search leg next to greedy")
     ap.add_argument("--score", default="", help="comma-separated batch sizes: add the batched multiple-choice scoring leg")
@@ -166,7 +168,7 @@ def main():
                         "tokens_per_s": round(B / wall * 1e3, 1), "weights_GBps": round(wbytes / d / 1e6, 0)}
     out["decode"] = dec
     if a.sample:
-        out["decode_sample"] = decode_sample(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds)
+        out["decode_sample"] = decode_sample(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds, a.warp)
     if a.beams:
         out["decode_beams"] = decode_beams(eng, plain_rows, [int(x) for x in a.beams.split(",")], a.steps, a.rounds)
     # option scoring: 4 options x 12 tokens forked from one question prefix
@@ -489,18 +491,22 @@ def score_kernels(eng, cfg, n):
     return {"rows": n, "calls": 20}
 
 
-def decode_sample(eng, rows, batches, steps, rounds):
-    """Greedy vs sampled decode steps of B sequences, alternated in blocks of `steps` (same KV positions advance)."""
+def decode_sample(eng, rows, batches, steps, rounds, warp=False):
+    """Greedy vs sampled decode steps of B sequences, alternated in blocks of `steps` (same KV positions advance).  warp: a third
+    kind of block, the sampled step with min_p = 0.05 and typical_p = 0.9 behind top-k / top-p (every added pass of the kernel)."""
+    from vstar_amd.vqa import warper_params
+    modes = ("greedy", "sample", "warp") if warp else ("greedy", "sample")
+    wrec = warper_params(min_p=0.05, typical_p=0.9)
     res = {}
     for B in batches:
         seqs = [Seq(rows, kv_slot=i) for i in range(B)]
         _, nxt = eng.forward(seqs, [(i, -1) for i in range(B)], logits=False)
         pos = len(rows)
         want = [(i, 0) for i in range(B)]
-        dev = {"greedy": [], "sample": []}
-        wall = {"greedy": 0.0, "sample": 0.0}
+        dev = {m: [] for m in modes}
+        wall = {m: 0.0 for m in modes}
         for r in range(rounds):
-            for mode in ("greedy", "sample"):
+            for mode in modes:
                 t0 = time.time()
                 for s in range(steps):
                     step = [Seq([int(nxt[i])], kv_slot=i, past_len=pos) for i in range(B)]
@@ -508,17 +514,20 @@ def decode_sample(eng, rows, batches, steps, rounds):
                         _, nxt = eng.forward(step, want, logits=False)
                     else:
                         nxt = eng.forward_sample(step, want, [sampling_params(0.7, 50, 0.9, seed=i, step=r * steps + s)
-                                                              for i in range(B)])
+                                                              for i in range(B)], **(dict(warpers=wrec) if mode == "warp" else {}))
                     dev[mode].append(eng.last_forward_ms())
                     pos += 1
                 wall[mode] += time.time() - t0
         leg = {}
-        for mode in ("greedy", "sample"):
+        for mode in modes:
             w = wall[mode] / (rounds * steps) * 1e3
             leg[mode] = {"device_ms_per_step": round(float(np.median(dev[mode])), 3), "wall_ms_per_step": round(w, 3),
                          "tokens_per_s": round(B / w * 1e3, 1)}
         leg["sample_over_greedy_tokens_per_s"] = round(leg["sample"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
         leg["sample_minus_greedy_device_ms"] = round(leg["sample"]["device_ms_per_step"] - leg["greedy"]["device_ms_per_step"], 4)
+        if warp:
+            leg["warp_over_sample_tokens_per_s"] = round(leg["warp"]["tokens_per_s"] / leg["sample"]["tokens_per_s"], 4)
+            leg["warp_minus_sample_device_ms"] = round(leg["warp"]["device_ms_per_step"] - leg["sample"]["device_ms_per_step"], 4)
         res[f"B{B}"] = leg
     return res
 

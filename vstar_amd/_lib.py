@@ -48,6 +48,7 @@ EXPORTS_VQA = [
     "vstar_vqa_forward_edits", "vstar_vqa_forward_sample_edits", "vstar_vqa_forward_verify_edits", "vstar_vqa_op_edit",
     "vstar_vqa_logit_edit_capacity",
     "vstar_vqa_forward_logprobs", "vstar_vqa_forward_sample_logprobs", "vstar_vqa_forward_verify_logprobs", "vstar_vqa_op_logprobs",
+    "vstar_vqa_forward_sample_warp", "vstar_vqa_forward_verify_warp", "vstar_vqa_op_sample_warp", "vstar_vqa_op_verify_warp",
     # doors of the decode-side kernels (tests/test_decode_ops_gpu.py)
     "vstar_vqa_op_rope_kv_append", "vstar_vqa_op_cached_attention", "vstar_vqa_op_perceiver_attention", "vstar_vqa_op_embed_rows",
     "vstar_vqa_op_argmax_rows",
@@ -91,6 +92,16 @@ class VqaSampling(ctypes.Structure):
         ("step", ctypes.c_uint32),
         ("seed", ctypes.c_uint64),
         ("stream", ctypes.c_uint64),
+    ]
+
+
+class VqaWarpers(ctypes.Structure):
+    """vstar_vqa_warpers (include/vstar_vqa.h): one row's min-p / typical-p / epsilon / eta values, 16 bytes."""
+    _fields_ = [
+        ("min_p", c_float),             # [0, 1]; 0 = off
+        ("typical_p", c_float),         # > 0; >= 1 = off
+        ("epsilon_cutoff", c_float),    # [0, 1); 0 = off
+        ("eta_cutoff", c_float),        # [0, 1); 0 = off
     ]
 
 
@@ -351,6 +362,17 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_forward_sample_logprobs.restype = c_int
     lib.vstar_vqa_forward_verify_logprobs.argtypes = lib.vstar_vqa_forward_verify_edits.argtypes + [c_void_p]
     lib.vstar_vqa_forward_verify_logprobs.restype = c_int
+    #  params / tokens, then warpers, edits, lp; the verify form: ... tokens_out, then warpers, edits, lp
+    lib.vstar_vqa_forward_sample_warp.argtypes = lib.vstar_vqa_forward_sample.argtypes + [c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_sample_warp.restype = c_int
+    lib.vstar_vqa_forward_verify_warp.argtypes = lib.vstar_vqa_forward_verify.argtypes + [c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_verify_warp.restype = c_int
+    lib.vstar_vqa_op_sample_warp.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]
+    lib.vstar_vqa_op_sample_warp.restype = c_int
+    lib.vstar_vqa_op_verify_warp.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]
+    lib.vstar_vqa_op_verify_warp.restype = c_int
     lib.vstar_vqa_op_logprobs.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p]
     lib.vstar_vqa_op_logprobs.restype = c_int

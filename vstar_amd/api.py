@@ -246,11 +246,13 @@ class LlavaSearchModel:
                  num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None, allowed_tokens_fn=None,
                  prefix_allowed_tokens_fn=None, return_dict_in_generate: bool = False, output_scores: bool = False, top_logprobs=None,
-                 **unused):
+                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
         — the same draws as VQA_LLM.free_form_inference(seed=seed).  Beam sampling is not implemented.
+        min_p, typical_p, epsilon_cutoff, eta_cutoff (do_sample=True; ignored otherwise, as top_p is): HF's warpers of these names
+        behind top-k / top-p, on the device (vqa.warper_params); out-of-range values raise ValueError.
         prompt_lookup_num_tokens = d > 0 (<= 15; num_beams 1): speculative decoding with up to d draft tokens per step from
         `draft_fn` (default: prompt lookup over the text ids, vstar_amd/spec.py — our matching rule, not HF's), greedy or
         sampled; the same ids as VQA_LLM.free_form_inference(speculative=d).
@@ -270,7 +272,7 @@ class LlavaSearchModel:
         `scores` = None: the full vocabulary rows HF returns there deliberately do not cross to the host.  num_beams > 1 with
         output_scores raises NotImplementedError (beam hypotheses carry their own scores; exposing those is a follow-up)."""
         from .logits import BEAM_RULES_MESSAGE, rules_from_kwargs
-        from .vqa import check_spec_tokens, resolve_seed, sampling_params
+        from .vqa import check_spec_tokens, resolve_seed, sampling_params, warper_params
         from .vqa_engine import Seq, check_logprobs
         if allowed_tokens_fn is not None and prefix_allowed_tokens_fn is not None:
             raise ValueError("pass allowed_tokens_fn or prefix_allowed_tokens_fn, not both")
@@ -296,6 +298,8 @@ class LlavaSearchModel:
         if lp is not None and num_beams > 1:
             raise NotImplementedError("output_scores with beam search (num_beams > 1) is not implemented: beam hypotheses carry "
                                       "their own scores, and exposing those is a follow-up")
+        warp = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff) if do_sample else {}
+        warper_params(**warp)                          # (validated before any engine work)
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
         text = [[t for t in ids if t >= 0]]
 
@@ -318,13 +322,13 @@ class LlavaSearchModel:
         if spec:
             p = [sampling_params(temperature, top_k, top_p, resolve_seed(seed))] if do_sample else None
             return result(*one(self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], text, max_new_tokens, spec, p, draft_fn,
-                                                            rules, logprobs=lp)))
+                                                            rules, logprobs=lp, **warp)))
         if num_beams > 1:
             return result(self._llm.beam_decode([Seq(rows, kv_slot=0)], [len(rows)], [len(ids)], max_new_tokens, num_beams, length_penalty,
                                                 early_stopping, num_return_sequences)[0])
         if do_sample:
             p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
-            return result(*one(self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text, logprobs=lp)))
+            return result(*one(self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text, logprobs=lp, **warp)))
         return result(*one(self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text, logprobs=lp)))
 
 

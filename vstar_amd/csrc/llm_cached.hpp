@@ -89,10 +89,10 @@ struct LlmCached;
 struct LlmTail {
   enum Kind { ARGMAX, SAMPLE, BEAM, SCORE, VERIFY };
   static LlmTail argmax(uint16_t* logits_out, int32_t* argmax_out) { LlmTail t; t.logits_out = logits_out; t.tokens_out = argmax_out; return t; }
-  static LlmTail sample(const vstar_vqa_sampling* params, int32_t* tokens) { LlmTail t; t.kind = SAMPLE; t.params = params; t.tokens_out = tokens; return t; }
+  static LlmTail sample(const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_warpers* warpers = nullptr) { LlmTail t; t.kind = SAMPLE; t.params = params; t.tokens_out = tokens; t.warpers = warpers; return t; }
   static LlmTail beam_select(const LlmBeamArgs& b, uint16_t* logits_out) { LlmTail t; t.kind = BEAM; t.beam = b; t.logits_out = logits_out; return t; }
   static LlmTail score_rows(const LlmScoreArgs& sc) { LlmTail t; t.kind = SCORE; t.score = sc; return t; }
-  static LlmTail verify_rows(const LlmVerifyArgs& v, const vstar_vqa_sampling* params) { LlmTail t; t.kind = VERIFY; t.verify = v; t.params = params; return t; }
+  static LlmTail verify_rows(const LlmVerifyArgs& v, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers = nullptr) { LlmTail t; t.kind = VERIFY; t.verify = v; t.params = params; t.warpers = warpers; return t; }
   // the tail with the log-probability stage behind it (null: the tail as it is); refused on BEAM and SCORE by tail_check
   LlmTail with_logprobs(const LlmLogprobArgs* lp) const { LlmTail t = *this; t.has_lp = lp != nullptr; if (lp) t.lp = *lp; return t; }
 
@@ -103,6 +103,7 @@ struct LlmTail {
   uint16_t* logits_out = nullptr;                // ARGMAX, BEAM (nullable): the wanted rows' logits [n_want, vocab]
   int32_t* tokens_out = nullptr;                 // ARGMAX (nullable): the arg-max; SAMPLE: the drawn tokens (sample.hip)
   const vstar_vqa_sampling* params = nullptr;    // SAMPLE; VERIFY (nullable: greedy): one record per wanted row
+  const vstar_vqa_warpers* warpers = nullptr;    // SAMPLE, VERIFY (nullable): the §8.10 stages behind top-p, one record per wanted row
   LlmBeamArgs beam; LlmScoreArgs score; LlmVerifyArgs verify;      // the kind's own host arrays
   bool has_lp = false;                           // ARGMAX, SAMPLE, VERIFY: the log-probability stage runs behind the tail
   LlmLogprobArgs lp;
@@ -238,6 +239,7 @@ struct LlmCached {
     image[seq_index(0, i)] = slot; image[seq_index(1, i)] = prefix; image[seq_index(2, i)] = past;
   }
   vstar_vqa_sampling* d_sparams = nullptr;      // [max_want] per-row sampling records of the SAMPLE and sampled VERIFY tails
+  vstar_vqa_warpers* d_swarp = nullptr;         // [max_want] their §8.10 records: allocated by the first call that carries them
   int max_want = 256;                            // wanted rows of one lm_head call (the scoring tail chunks by it, up to max_rows)
   int32_t *d_starget = nullptr, *d_srank = nullptr;   // [max_rows] the scoring tail's targets / ranks
   float* d_nll = nullptr;                        // [max_rows]
@@ -326,7 +328,7 @@ struct LlmCached {
   int tail_check(const LlmRows& r, const LlmTail& t);
   int edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed);
   int logprobs_check(const LlmRows& r, const LlmTail& t);
-  std::array<TailCopy, 5> tail_copies(const LlmTail& t, int n_want);
+  std::array<TailCopy, 6> tail_copies(const LlmTail& t, int n_want);
   int tail_launch(const LlmTail& t, int w0, int m);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
   int kv_copy(int dst, int src, int lo, int hi);
@@ -655,6 +657,13 @@ inline int LlmCached::tail_check(const LlmRows& r, const LlmTail& t) {
     return VSTAR_ERR_INVALID;
   }
   const char* m = nullptr;
+  if (t.warpers) {             // SAMPLE, VERIFY; the device records are allocated here, by the first call that carries them
+    if ((m = vstar_warpers_check(t.warpers, n_want))) { e->set_error(m); return VSTAR_ERR_INVALID; }
+    if (!d_swarp) {
+      const int rc = e->dalloc(&d_swarp, (size_t)max_want);
+      if (rc) { (void)hipGetLastError(); d_swarp = nullptr; return rc; }
+    }
+  }
   switch (t.kind) {
     default: break;            // ARGMAX, SAMPLE: nothing of their own
     case LlmTail::BEAM:
@@ -752,21 +761,21 @@ inline int LlmCached::logprobs_check(const LlmRows& r, const LlmTail& t) {
 // A tail's copies, in stream order: uploads (`in`, host -> dev) go out with the row metadata before the layers, downloads (dev ->
 // `out`, host) behind the tail.  An entry whose host pointer is null (an output the caller did not ask for, greedy verify's
 // params, the unused entries of the array) or that has zero bytes is no copy.
-inline std::array<LlmCached::TailCopy, 5> LlmCached::tail_copies(const LlmTail& t, int n_want) {
-  const size_t nw4 = (size_t)n_want * 4, np = (size_t)n_want * sizeof(vstar_vqa_sampling);
+inline std::array<LlmCached::TailCopy, 6> LlmCached::tail_copies(const LlmTail& t, int n_want) {
+  const size_t nw4 = (size_t)n_want * 4, np = (size_t)n_want * sizeof(vstar_vqa_sampling), nwp = (size_t)n_want * sizeof(vstar_vqa_warpers);
   const LlmBeamArgs& b = t.beam;
   const LlmVerifyArgs& v = t.verify;
   const size_t nc4 = (size_t)b.n_groups * b.n_cand * 4;
   switch (t.kind) {
     case LlmTail::ARGMAX: return {{{d_argmax, nullptr, t.tokens_out, nw4}}};
-    case LlmTail::SAMPLE: return {{{d_sparams, t.params, nullptr, np}, {d_argmax, nullptr, t.tokens_out, nw4}}};
+    case LlmTail::SAMPLE: return {{{d_sparams, t.params, nullptr, np}, {d_swarp, t.warpers, nullptr, nwp}, {d_argmax, nullptr, t.tokens_out, nw4}}};
     case LlmTail::BEAM:
       return {{{d_bscore, b.scores, nullptr, nw4}, {d_goff, b.goff, nullptr, (size_t)(b.n_groups + 1) * 4},
                {d_cand_s, nullptr, b.cand_s, nc4}, {d_cand_t, nullptr, b.cand_tok, nc4}, {d_cand_r, nullptr, b.cand_row, nc4}}};
     case LlmTail::SCORE: return {{{d_starget, t.score.targets, nullptr, nw4}, {d_nll, nullptr, t.score.nll, nw4}, {d_srank, nullptr, t.score.rank, nw4}}};
     case LlmTail::VERIFY:
       return {{{d_sparams, t.params, nullptr, np}, {d_goff, v.goff, nullptr, (size_t)(v.n_groups + 1) * 4}, {d_vdraft, v.draft, nullptr, nw4},
-               {d_vacc, nullptr, v.n_accept, (size_t)v.n_groups * 4}, {d_vtok, nullptr, v.tokens, nw4}}};
+               {d_vacc, nullptr, v.n_accept, (size_t)v.n_groups * 4}, {d_vtok, nullptr, v.tokens, nw4}, {d_swarp, t.warpers, nullptr, nwp}}};
   }
   return {};
 }
@@ -778,7 +787,7 @@ inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
   switch (t.kind) {
     case LlmTail::ARGMAX: LCHK(argmax_rows_lp(logits, m, V, ld, d_argmax, e->stream)); break;
     case LlmTail::SAMPLE:      // d_argmax receives the drawn tokens
-      LCHK(vstar_sample_rows_lp(logits, m, V, ld, d_sparams, d_argmax, nullptr, nullptr, e->stream));
+      LCHK(vstar_sample_rows_lp(logits, m, V, ld, d_sparams, t.warpers ? d_swarp : nullptr, d_argmax, nullptr, nullptr, e->stream));
       break;
     case LlmTail::BEAM:        // each group's n_cand best candidates
       LCHK(vstar_beam_select_lp(logits, m, V, ld, d_bscore, t.beam.n_groups, d_goff, t.beam.n_cand, beam_ws, d_cand_s, d_cand_t, d_cand_r,
@@ -788,8 +797,8 @@ inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
       LCHK(vstar_score_rows_lp(logits, m, V, ld, d_starget + w0, d_nll + w0, t.score.rank ? d_srank + w0 : nullptr, nullptr, e->stream));
       break;
     case LlmTail::VERIFY:      // per group the accepted count, per row the token; d_argmax / d_vflag are its scratch
-      LCHK(vstar_verify_rows_lp(logits, m, V, ld, d_goff, t.verify.n_groups, d_vdraft, t.params ? d_sparams : nullptr, d_argmax, d_vflag,
-                                d_vacc, d_vtok, e->stream));
+      LCHK(vstar_verify_rows_lp(logits, m, V, ld, d_goff, t.verify.n_groups, d_vdraft, t.params ? d_sparams : nullptr,
+                                t.warpers ? d_swarp : nullptr, d_argmax, d_vflag, d_vacc, d_vtok, e->stream));
       break;
   }
   return 0;
@@ -880,7 +889,7 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   LCHK(hipMemcpyAsync(d_row_seq, h_seq.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_seq, h_seqmeta.data(), h_seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
   if (n_want) LCHK(hipMemcpyAsync(d_want, h_want.data(), (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
-  const std::array<TailCopy, 5> copies = tail_copies(tail, n_want);
+  const std::array<TailCopy, 6> copies = tail_copies(tail, n_want);
   for (const TailCopy& x : copies)
     if (x.in && x.bytes) LCHK(hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, e->stream));
   if (edits) {

@@ -1,7 +1,8 @@
 // sample_core.hpp — the row-level pieces of the sampling tail, shared by the tails that draw from a warped logits row (sample.hip,
 // spec.hip) so that both build the same kept set, the same fixed-point masses and the same draw, bit for bit: the Philox stream,
-// the order-preserving score keys, the 2^-40 masses, the count / mass weighted radix select (top-k, top-p) and the exact block
-// scan behind the inverse-CDF draw.  DESIGN.md §8.1 (1)-(4).  Device code only; one workgroup of 16 waves per row.
+// the order-preserving score keys, the 2^-40 masses, the count / mass weighted radix select (top-k, top-p), the four further
+// warpers of DESIGN.md §8.10 (min-p, typical-p, epsilon, eta) and the exact block scan behind the inverse-CDF draw.  DESIGN.md §8.1
+// (1)-(4).  Device code only; one workgroup of 16 waves per row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,6 +104,25 @@ template <typename Sm> __device__ __forceinline__ uint32_t block_max(Sm& sm, uin
   return m;
 }
 
+// the block totals of an integer (exact) and of a double: per-thread value -> xor butterfly inside the wave (a + b == b + a: every
+// lane holds the same bits) -> the 16 wave sums added in wave order by everyone.  A fixed order: the double is deterministic.
+template <typename Sm> __device__ __forceinline__ void block_sums(Sm& sm, u64& z, double& a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { z += __shfl_xor(z, o, 64); a += __shfl_xor(a, o, 64); }
+  u64 zt = 0;
+  double at = 0.0;
+  if ((threadIdx.x & 63) == 0) sm.wtot[threadIdx.x >> 6] = z;
+  __syncthreads();
+  for (int w = 0; w < WAVES; ++w) zt += sm.wtot[w];
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm.wtot[threadIdx.x >> 6] = (u64)__double_as_longlong(a);
+  __syncthreads();
+  for (int w = 0; w < WAVES; ++w) at += __longlong_as_double((long long)sm.wtot[w]);
+  __syncthreads();
+  z = zt;
+  a = at;
+}
+
 // exclusive prefix of v in thread order, and the block total (exact: integers)
 template <typename Sm> __device__ __forceinline__ void block_scan(Sm& sm, u64 v, u64& excl, u64& total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -152,14 +172,15 @@ __device__ __forceinline__ void select_bin(Sm& sm, u64 need, float frac, int& bi
 
 // The warped row of one workgroup: after keep() every thread knows the key threshold of the kept set (kept = key >= tkeep), the
 // maximal key and its score; the keys of a CACHED row sit in sm.keys.  The caller zeroes sm.hist[0 .. 256) and synchronises
-// before keep() (sample.hip does it together with its Philox word).
-template <bool BF16, bool CACHED>
+// before keep() (sample.hip does it together with its Philox word).  WARP: the row may go on through warp() (§8.10), after which
+// the kept set is the band tkeep <= key <= tcap; without it tcap is never read and the code is the §8.1 code.
+template <bool BF16, bool CACHED, bool WARP = false>
 struct WarpedRow {
   SampleSmem<CACHED>& sm;
   const uint16_t* __restrict__ xr;
   int vocab;
   float t;
-  uint32_t kmax = 0, tkeep = 0;
+  uint32_t kmax = 0, tkeep = 0, tcap = 0xffffu;
   float smax = 0.f;
 
   __device__ __forceinline__ WarpedRow(SampleSmem<CACHED>& sm_, const uint16_t* xr_, int vocab_, float t_)
@@ -177,6 +198,12 @@ struct WarpedRow {
     }
   }
   __device__ __forceinline__ u64 mass(uint32_t key) const { return key_mass<BF16>(key, kmax, smax); }
+  __device__ __forceinline__ bool kept(uint32_t key) const {
+    if constexpr (WARP) return key >= tkeep && key <= tcap;
+    else return key >= tkeep;
+  }
+  // l = s - smax as key_mass takes it (0 at the maximal key, also when the maximum is infinite)
+  __device__ __forceinline__ float ell(uint32_t key) const { return key == kmax ? 0.f : key_score<BF16>(key) - smax; }
 
   // §8.1 (1)-(3): keys, top-k, top-p
   __device__ __forceinline__ void keep(const vstar_vqa_sampling& P) {
@@ -224,6 +251,92 @@ struct WarpedRow {
       tkeep = tp > tk ? tp : tk;
     }
   }
+
+  // ---- §8.10: min-p -> typical-p -> epsilon -> eta on the set keep() left; a stage that is off runs nothing ----
+  // Z = the mass of the kept set (exact), A = sum m * l over it (double, fixed order); tokens of mass 0 take part in nothing
+  __device__ __forceinline__ void sums(u64& Z, double& A) const {
+    u64 z = 0;
+    double a = 0.0;
+    each([&](int, uint32_t key) {
+      if (kept(key)) { const u64 m = mass(key); if (m) { z += m; a += (double)m * (double)ell(key); } }
+    });
+    block_sums(sm, z, a);
+    Z = z;
+    A = a;
+  }
+  // tkeep = max(tkeep, the smallest key whose mass is >= thr), but never above ktop, the largest key of the kept set: mass is
+  // monotone in the key, so this is a bisection of the key space (every thread the same 16 steps, no pass over the row)
+  __device__ __forceinline__ void raise_floor(double thr, uint32_t ktop) {
+    constexpr uint32_t NEG_INF_KEY = BF16 ? 0x007fu : 0x03ffu;       // below it lie NaN patterns only: no element has such a key
+    uint32_t lo = tkeep > NEG_INF_KEY ? tkeep : NEG_INF_KEY, hi = ktop;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if ((double)mass(mid) >= thr) hi = mid; else lo = mid + 1;
+    }
+    tkeep = hi > tkeep ? hi : tkeep;
+  }
+  // d = |l - mu| as a non-negative fp32, complemented: a SMALLER distance is a LARGER word, so select_bin's "from the top" is
+  // "from the smallest distance"
+  __device__ __forceinline__ uint32_t rdist(uint32_t key, double mu) const {
+    return ~__float_as_uint(fabsf((float)((double)ell(key) - mu)));
+  }
+  __device__ __forceinline__ void warp(const vstar_vqa_warpers& W) {
+    static_assert(WARP, "warp() needs the band");
+    uint32_t ktop = kmax;                              // the largest key of the kept set
+    u64 Z = 0;
+    double A = 0.0;
+    bool fresh = false;                                // Z / A are those of the current kept set
+    if (W.min_p > 0.f) raise_floor((double)W.min_p * 0x1p40, ktop);      // p_i >= min_p * max p  <=>  m_i >= min_p * 2^40
+    if (W.typical_p < 1.f) {
+      sums(Z, A);
+      const double mu = A / (double)Z;                 // E_p[l]; Z > 0: the maximal key is kept
+      // the threshold distance D: the largest d whose strictly-smaller mass is < typical_p * Z — a mass-weighted radix select over
+      // the four bytes of the complemented distance word
+      uint32_t pre = 0;
+      u64 need = 0;
+      bool found = true;
+#pragma unroll
+      for (int byte = 3; byte >= 0; --byte) {
+        const int sh = 8 * byte;
+        clear_hist(sm);
+        each([&](int, uint32_t key) {
+          if (!kept(key)) return;
+          const u64 m = mass(key);
+          if (!m) return;
+          const uint32_t r = rdist(key, mu);
+          if (byte == 3 || (r >> (sh + 8)) == pre) atomicAdd(&sm.hist[(r >> sh) & 255u], m);
+        });
+        int b;
+        u64 above, n2;
+        select_bin(sm, need, byte == 3 ? W.typical_p : -1.f, b, above, n2);      // byte 3: need = ceil(typical_p * Z) >= 1
+        found = found && b >= 0;
+        need = n2 - above;
+        pre = (pre << 8) | (uint32_t)(b & 255);
+      }
+      if (found) {                                     // the band: the keys of the kept set with d <= D (all ties in d)
+        uint32_t hi = 0, lo = 0;
+        each([&](int, uint32_t key) {
+          if (kept(key) && rdist(key, mu) >= pre) { hi = key > hi ? key : hi; lo = (0xffffu - key) > lo ? (0xffffu - key) : lo; }
+        });
+        hi = block_max(sm, hi);
+        lo = 0xffffu - block_max(sm, lo);
+        if (lo <= hi) { tkeep = lo; tcap = hi; ktop = hi; }      // (always: the selected token is in it)
+      }
+    }
+    if (W.epsilon_cutoff > 0.f) {
+      if (!fresh) sums(Z, A);
+      const uint32_t t0 = tkeep;
+      raise_floor((double)W.epsilon_cutoff * (double)Z, ktop);           // p_i >= eps  <=>  m_i >= eps * Z
+      fresh = tkeep == t0;
+    }
+    if (W.eta_cutoff > 0.f) {
+      if (!fresh) sums(Z, A);
+      const double eps = (double)W.eta_cutoff, Zd = (double)Z;
+      const double H = log(Zd * 0x1p-40) - A / Zd;     // -sum p ln p with ln m_i = l_i + 40 ln 2
+      const double eta = fmin(eps, sqrt(eps) * exp(-H));
+      raise_floor(eta * Zd, ktop);
+    }
+  }
 };
 
 // §8.1 (4), the inverse CDF in vocabulary order over the kept set: thread-contiguous chunks [c0, c1) of the row, their kept mass
@@ -233,8 +346,8 @@ struct ChunkScan {
   u64 msum, excl, Z, ctot;
 };
 
-template <bool BF16, bool CACHED>
-__device__ __forceinline__ ChunkScan chunk_scan(const WarpedRow<BF16, CACHED>& w) {
+template <bool BF16, bool CACHED, bool WARP>
+__device__ __forceinline__ ChunkScan chunk_scan(const WarpedRow<BF16, CACHED, WARP>& w) {
   ChunkScan c;
   const int tid = threadIdx.x, C = (w.vocab + THREADS - 1) / THREADS;
   c.c0 = tid * C < w.vocab ? tid * C : w.vocab;
@@ -243,7 +356,7 @@ __device__ __forceinline__ ChunkScan chunk_scan(const WarpedRow<BF16, CACHED>& w
   u64 cnt = 0;
   for (int i = c.c0; i < c.c1; ++i) {
     const uint32_t key = w.key_at(i);
-    if (key >= w.tkeep) { c.msum += w.mass(key); ++cnt; }
+    if (w.kept(key)) { c.msum += w.mass(key); ++cnt; }
   }
   u64 cexcl;
   block_scan(w.sm, c.msum, c.excl, c.Z);
@@ -254,8 +367,8 @@ __device__ __forceinline__ ChunkScan chunk_scan(const WarpedRow<BF16, CACHED>& w
 // *out = the smallest kept index whose inclusive prefix mass exceeds `target` (< the total): exactly one thread — the one whose
 // chunk holds the target — walks its chunk and stores.  skip >= 0 takes that index (mass m_skip, 0 if it is not kept) out of the
 // kept set: the prefix masses are those of the remaining tokens, and target < Z - m_skip.
-template <bool BF16, bool CACHED>
-__device__ __forceinline__ void chunk_pick(const WarpedRow<BF16, CACHED>& w, const ChunkScan& c, u64 target, int skip, u64 m_skip,
+template <bool BF16, bool CACHED, bool WARP>
+__device__ __forceinline__ void chunk_pick(const WarpedRow<BF16, CACHED, WARP>& w, const ChunkScan& c, u64 target, int skip, u64 m_skip,
                                            int32_t* __restrict__ out) {
   u64 excl = c.excl, msum = c.msum;
   if (skip >= 0) {
@@ -266,7 +379,7 @@ __device__ __forceinline__ void chunk_pick(const WarpedRow<BF16, CACHED>& w, con
     u64 acc = excl;
     for (int i = c.c0; i < c.c1; ++i) {
       const uint32_t key = w.key_at(i);
-      if (key >= w.tkeep && i != skip) {
+      if (w.kept(key) && i != skip) {
         acc += w.mass(key);
         if (acc > target) { *out = i; break; }
       }

@@ -9,7 +9,8 @@
 //            sum.  No draft (-1): the plain draw, u from Philox (step, stream) — bit-identical to vstar_sample_rows.  Draft x:
 //            accept iff x is kept and floor(u_a * Z) < m_x, u_a from Philox (step, stream + 1); else the residual draw: x is
 //            taken out of the kept set (Z' = Z - m_x, or Z when x is not kept) and the token is the smallest kept index != x
-//            whose inclusive prefix mass, skipping x, exceeds floor(u * Z').  P(row's token = y) = m_y / Z either way.
+//            whose inclusive prefix mass, skipping x, exceeds floor(u * Z').  P(row's token = y) = m_y / Z either way.  With
+//            warpers the kept set is the band they leave: a draft outside it is never accepted.
 // Launch 2, one thread per group: n_accept = the number of leading rows whose flag is set (a group's last row is never
 // compared), tokens = the choices of rows 0 .. n_accept, -1 behind them.
 #include <hip/hip_runtime.h>
@@ -21,10 +22,11 @@ namespace {
 
 using namespace samplecore;
 
-template <bool BF16, bool CACHED>
+template <bool BF16, bool CACHED, bool WARP>
 __global__ __launch_bounds__(THREADS) void verify_sampled_kernel(const uint16_t* __restrict__ x, int vocab, int64_t ld,
                                                                  const int32_t* __restrict__ draft,
                                                                  const vstar_vqa_sampling* __restrict__ params,
+                                                                 const vstar_vqa_warpers* __restrict__ warpers,
                                                                  int32_t* __restrict__ choice, int32_t* __restrict__ flag) {
   __shared__ SampleSmem<CACHED> sm;
   const int row = blockIdx.x, tid = threadIdx.x;
@@ -32,8 +34,9 @@ __global__ __launch_bounds__(THREADS) void verify_sampled_kernel(const uint16_t*
   const int xd = draft[row];                         // -1 or in [0, vocab): checked on the host (vstar_verify_check)
   if (tid < 256) sm.hist[tid] = 0;
   __syncthreads();
-  WarpedRow<BF16, CACHED> w(sm, x + (int64_t)row * ld, vocab, P.temperature);
+  WarpedRow<BF16, CACHED, WARP> w(sm, x + (int64_t)row * ld, vocab, P.temperature);
   w.keep(P);
+  if constexpr (WARP) w.warp(warpers[row]);                  // §8.10: the same kept set (a band) as the draw's
   const ChunkScan c = chunk_scan(w);
   const u64 u = philox_u24(P.seed, P.stream, P.step);        // (every thread: uniform values, no LDS round trip)
   if (xd < 0 || xd >= vocab) {                               // no draft: the plain §8.1 draw
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(THREADS) void verify_sampled_kernel(const uint16_t*
     return;
   }
   const uint32_t kx = w.key_at(xd);
-  const u64 mx = kx >= w.tkeep ? w.mass(kx) : 0;             // 0: not kept (or a kept token whose mass rounds to 0: never accepted)
+  const u64 mx = w.kept(kx) ? w.mass(kx) : 0;                // 0: not kept (or a kept token whose mass rounds to 0: never accepted)
   const u64 ua = philox_u24(P.seed, P.stream + 1, P.step);
   if (scale_u24(c.Z, ua) < mx) {                             // (uniform over the workgroup)
     if (tid == 0) { choice[row] = xd; flag[row] = 1; }
@@ -95,18 +98,23 @@ __global__ void verify_finish_kernel(const int32_t* __restrict__ group_off, int 
 
 template <bool BF16>
 hipError_t verify_rows(const uint16_t* x, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
-                       const int32_t* draft, const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag, int32_t* n_accept,
-                       int32_t* tokens, hipStream_t s) {
+                       const int32_t* draft, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers, int32_t* choice,
+                       int32_t* flag, int32_t* n_accept, int32_t* tokens, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   if (!x || !group_off || !draft || !choice || !flag || !n_accept || !tokens || n_groups <= 0 || n_groups > rows || rows > 65535 ||
       vocab <= 0 || vocab > MAX_VOCAB || ld < vocab)
     return hipErrorInvalidValue;
   if (!params)
     hipLaunchKernelGGL((verify_greedy_kernel<BF16>), dim3(rows), dim3(THREADS), 0, s, x, vocab, ld, draft, choice, flag);
-  else if (vocab <= CACHE)
-    hipLaunchKernelGGL((verify_sampled_kernel<BF16, true>), dim3(rows), dim3(THREADS), 0, s, x, vocab, ld, draft, params, choice, flag);
-  else
-    hipLaunchKernelGGL((verify_sampled_kernel<BF16, false>), dim3(rows), dim3(THREADS), 0, s, x, vocab, ld, draft, params, choice, flag);
+  else {                                             // (greedy ignores the warpers, as it ignores top-k / top-p)
+    const bool cached = vocab <= CACHE;
+#define VSTAR_VERIFY_LAUNCH(C, W)                                                                                                \
+  hipLaunchKernelGGL((verify_sampled_kernel<BF16, C, W>), dim3(rows), dim3(THREADS), 0, s, x, vocab, ld, draft, params, warpers, choice, \
+                     flag)
+    if (warpers) { if (cached) VSTAR_VERIFY_LAUNCH(true, true); else VSTAR_VERIFY_LAUNCH(false, true); }
+    else { if (cached) VSTAR_VERIFY_LAUNCH(true, false); else VSTAR_VERIFY_LAUNCH(false, false); }
+#undef VSTAR_VERIFY_LAUNCH
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(verify_finish_kernel, dim3((n_groups + 63) / 64), dim3(64), 0, s, group_off, n_groups, choice, flag, n_accept, tokens);
@@ -116,15 +124,15 @@ hipError_t verify_rows(const uint16_t* x, int rows, int vocab, int64_t ld, const
 }  // namespace
 
 hipError_t vstar_verify_rows_f16(const uint16_t* x, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
-                                 const int32_t* draft, const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag,
-                                 int32_t* n_accept, int32_t* tokens, hipStream_t s) {
-  return verify_rows<false>(x, rows, vocab, ld, group_off, n_groups, draft, params, choice, flag, n_accept, tokens, s);
+                                 const int32_t* draft, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers, int32_t* choice,
+                                 int32_t* flag, int32_t* n_accept, int32_t* tokens, hipStream_t s) {
+  return verify_rows<false>(x, rows, vocab, ld, group_off, n_groups, draft, params, warpers, choice, flag, n_accept, tokens, s);
 }
 
 hipError_t vstar_verify_rows_bf16(const uint16_t* x, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
-                                  const int32_t* draft, const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag,
-                                  int32_t* n_accept, int32_t* tokens, hipStream_t s) {
-  return verify_rows<true>(x, rows, vocab, ld, group_off, n_groups, draft, params, choice, flag, n_accept, tokens, s);
+                                  const int32_t* draft, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers, int32_t* choice,
+                                  int32_t* flag, int32_t* n_accept, int32_t* tokens, hipStream_t s) {
+  return verify_rows<true>(x, rows, vocab, ld, group_off, n_groups, draft, params, warpers, choice, flag, n_accept, tokens, s);
 }
 
 const char* vstar_verify_check(int rows, int vocab, int n_groups, const int32_t* group_off, const int32_t* draft) {

@@ -16,9 +16,9 @@
 #define VSTAR_TAIL_LP(name) name##_bf16
 #endif
 namespace VS_NS {      // (one definition per instantiation: the two differ)
-inline hipError_t vstar_sample_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* d_params, int32_t* tokens,
-                                       float* u_out, int32_t* n_kept, hipStream_t s) {
-  return VSTAR_TAIL_LP(vstar_sample_rows)(x, rows, vocab, ld, d_params, tokens, u_out, n_kept, s);
+inline hipError_t vstar_sample_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* d_params,
+                                       const vstar_vqa_warpers* d_warpers, int32_t* tokens, float* u_out, int32_t* n_kept, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_sample_rows)(x, rows, vocab, ld, d_params, d_warpers, tokens, u_out, n_kept, nullptr, s);
 }
 inline hipError_t vstar_beam_select_lp(const lp_t* x, int rows, int vocab, int64_t ld, const float* d_scores, int n_groups, const int32_t* d_goff,
                                        int n_cand, void* ws, float* cand_s, int32_t* cand_tok, int32_t* cand_row, float* lp_out, hipStream_t s) {
@@ -29,9 +29,9 @@ inline hipError_t vstar_score_rows_lp(const lp_t* x, int rows, int vocab, int64_
   return VSTAR_TAIL_LP(vstar_score_rows)(x, rows, vocab, ld, d_targets, nll, rank, lse_out, s);
 }
 inline hipError_t vstar_verify_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups, const int32_t* draft,
-                                       const vstar_vqa_sampling* params, int32_t* choice, int32_t* flag, int32_t* n_accept, int32_t* tokens,
-                                       hipStream_t s) {
-  return VSTAR_TAIL_LP(vstar_verify_rows)(x, rows, vocab, ld, group_off, n_groups, draft, params, choice, flag, n_accept, tokens, s);
+                                       const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers, int32_t* choice, int32_t* flag,
+                                       int32_t* n_accept, int32_t* tokens, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_verify_rows)(x, rows, vocab, ld, group_off, n_groups, draft, params, warpers, choice, flag, n_accept, tokens, s);
 }
 inline hipError_t vstar_edit_rows_lp(lp_t* x, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok, const float* penalty,
                                      hipStream_t s) {

@@ -375,12 +375,20 @@ int vstar_vqa_forward_sample_logprobs(vstar_vqa_handle* h, int nseq, const int32
                                       const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                                       const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_logit_edits* edits,
                                       const vstar_vqa_logprobs* lp) {
+  return vstar_vqa_forward_sample_warp(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, tokens, nullptr, edits, lp);
+}
+
+// the two forms with the §8.10 warper records behind top-p; the _logprobs entries pass NULL
+int vstar_vqa_forward_sample_warp(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                  const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                  const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_warpers* warpers,
+                                  const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
   LlmEdits ed;
   LlmLogprobArgs la;
   return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
-                        LlmTail::sample(params, tokens).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
+                        LlmTail::sample(params, tokens, warpers).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
 int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
@@ -426,6 +434,15 @@ int vstar_vqa_forward_verify_logprobs(vstar_vqa_handle* h, int nseq, const int32
                                       const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
                                       int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_logit_edits* edits,
                                       const vstar_vqa_logprobs* lp) {
+  return vstar_vqa_forward_verify_warp(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, group_off, n_groups,
+                                       draft, n_accept_out, tokens_out, nullptr, edits, lp);
+}
+
+int vstar_vqa_forward_verify_warp(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                  const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                  const vstar_vqa_sampling* params, const int32_t* group_off, int n_groups, const int32_t* draft,
+                                  int32_t* n_accept_out, int32_t* tokens_out, const vstar_vqa_warpers* warpers,
+                                  const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   if (!group_off || !draft || !n_accept_out || !tokens_out) {
     h->set_error("forward_verify: group_off, draft and the outputs are required");
@@ -435,7 +452,7 @@ int vstar_vqa_forward_verify_logprobs(vstar_vqa_handle* h, int nseq, const int32
   LlmEdits ed;
   LlmLogprobArgs la;
   return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
-                        LlmTail::verify_rows(v, params).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
+                        LlmTail::verify_rows(v, params, warpers).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
 int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h) { return h ? h->run.edit_capacity() : 0; }
@@ -453,6 +470,11 @@ int vstar_vqa_kv_copy(vstar_vqa_handle* h, int dst, int src, int lo, int hi) {
 // ---- the tails at op level, on device logits the caller owns: checks, scratch (OpBuf), launch + synchronise, copies back ----
 int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
                         int32_t* tokens, float* u_out, int32_t* n_kept) {
+  return vstar_vqa_op_sample_warp(dev_logits, dtype, rows, vocab, ld, params, nullptr, tokens, u_out, n_kept, nullptr);
+}
+
+int vstar_vqa_op_sample_warp(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const vstar_vqa_sampling* params,
+                             const vstar_vqa_warpers* warpers, int32_t* tokens, float* u_out, int32_t* n_kept, uint8_t* kept_mask) {
   if (!dev_logits || !params || !tokens || rows <= 0 || rows > 65535 || vocab <= 0 || vocab > (1 << 22) || ld < vocab ||
       (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
     tls_error() = "vstar_vqa_op_sample: bad argument";
@@ -462,15 +484,24 @@ int vstar_vqa_op_sample(const void* dev_logits, int dtype, int rows, int vocab, 
     tls_error() = "vstar_vqa_op_sample: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
     return VSTAR_ERR_INVALID;
   }
+  if (const char* m = warpers ? vstar_warpers_check(warpers, rows) : nullptr) {
+    tls_error() = std::string("vstar_vqa_op_sample_warp: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
   hipError_t e = hipSuccess;
   OpBuf<vstar_vqa_sampling> d_p(e, rows);
+  OpBuf<vstar_vqa_warpers> d_w(e, rows, warpers != nullptr);
   OpBuf<int32_t> d_tok(e, rows), d_kept(e, rows);
   OpBuf<float> d_u(e, rows);
+  OpBuf<uint8_t> d_mask(e, (size_t)rows * vocab, kept_mask != nullptr);
   d_p.upload(params);
-  op_launch(e, dtype, vstar_sample_rows_f16, vstar_sample_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_tok, d_u, d_kept, nullptr);
+  d_w.upload(warpers);
+  op_launch(e, dtype, vstar_sample_rows_f16, vstar_sample_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_p, d_w, d_tok, d_u, d_kept,
+            d_mask, nullptr);
   d_tok.download(tokens);
   d_u.download(u_out);
   d_kept.download(n_kept);
+  d_mask.download(kept_mask);
   return op_result(e, "vstar_vqa_op_sample");
 }
 
@@ -526,6 +557,12 @@ int vstar_vqa_op_score(const void* dev_logits, int dtype, int rows, int vocab, i
 
 int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
                         const int32_t* draft, const vstar_vqa_sampling* params, int32_t* n_accept_out, int32_t* tokens_out) {
+  return vstar_vqa_op_verify_warp(dev_logits, dtype, rows, vocab, ld, group_off, n_groups, draft, params, nullptr, n_accept_out, tokens_out);
+}
+
+int vstar_vqa_op_verify_warp(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* group_off, int n_groups,
+                             const int32_t* draft, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers,
+                             int32_t* n_accept_out, int32_t* tokens_out) {
   if (!dev_logits || !n_accept_out || !tokens_out || rows > 65535 || ld < vocab || (dtype != VSTAR_F16 && dtype != VSTAR_BF16)) {
     tls_error() = "vstar_vqa_op_verify: bad argument";
     return VSTAR_ERR_INVALID;
@@ -538,14 +575,20 @@ int vstar_vqa_op_verify(const void* dev_logits, int dtype, int rows, int vocab, 
     tls_error() = "vstar_vqa_op_verify: temperature must be > 0 and finite, top_k >= 0, top_p >= 0";
     return VSTAR_ERR_INVALID;
   }
+  if (const char* m = warpers ? vstar_warpers_check(warpers, rows) : nullptr) {
+    tls_error() = std::string("vstar_vqa_op_verify_warp: ") + m;
+    return VSTAR_ERR_INVALID;
+  }
   hipError_t e = hipSuccess;
   OpBuf<int32_t> d_go(e, (size_t)n_groups + 1), d_dr(e, rows), d_ch(e, rows), d_fl(e, rows), d_ac(e, n_groups), d_tok(e, rows);
   OpBuf<vstar_vqa_sampling> d_p(e, rows, params != nullptr);
+  OpBuf<vstar_vqa_warpers> d_w(e, rows, params != nullptr && warpers != nullptr);
   d_go.upload(group_off);
   d_dr.upload(draft);
   d_p.upload(params);
+  d_w.upload(warpers);
   op_launch(e, dtype, vstar_verify_rows_f16, vstar_verify_rows_bf16, (const uint16_t*)dev_logits, rows, vocab, ld, d_go, n_groups, d_dr, d_p,
-            d_ch, d_fl, d_ac, d_tok, nullptr);
+            d_w, d_ch, d_fl, d_ac, d_tok, nullptr);
   d_ac.download(n_accept_out);
   d_tok.download(tokens_out);
   return op_result(e, "vstar_vqa_op_verify");

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._lib import VqaSampling
+from ._lib import VqaSampling, VqaWarpers
 from .config import IMAGE_TOKEN_INDEX, OBJECT_TOKEN_INDEX, VQAConfig
 from .logits import BEAM_RULES_MESSAGE, LogitRules, rules_from_kwargs
 from .preprocess import CLIP_MEAN, CLIP_STD, SyntheticTokenizer, _normalise
@@ -88,11 +88,40 @@ def sampling_params(temperature: float, top_k: Optional[int] = 50, top_p: Option
                        step=step & 0xffffffff, seed=int(seed) & mask, stream=int(stream) & mask)
 
 
+def warper_params(min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                  eta_cutoff: Optional[float] = None) -> Optional[VqaWarpers]:
+    """One row's vstar_vqa_warpers record with HF's conventions and validation: min_p None / 0 = off, else in
+    [0, 1]; typical_p None or >= 1 = off, else > 0; epsilon_cutoff and eta_cutoff None / 0 = off, else in (0, 1).  None when all
+    four are off: the caller then makes the plain call."""
+    min_p = 0.0 if min_p is None else float(min_p)
+    if not 0 <= min_p <= 1:
+        raise ValueError(f"min_p must be in [0, 1] (0 / None = off), got {min_p}")
+    typical_p = 1.0 if typical_p is None else float(typical_p)
+    if not typical_p > 0:
+        raise ValueError(f"typical_p must be > 0 (None or >= 1 = off), got {typical_p}")
+    cut = {}
+    for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        v = 0.0 if v is None else float(v)
+        if not 0 <= v < 1:
+            raise ValueError(f"{name} must be in (0, 1) (0 / None = off), got {v}")
+        cut[name] = v
+    typical_p = min(typical_p, 1.0)
+    if min_p == 0 and typical_p >= 1 and cut["epsilon_cutoff"] == 0 and cut["eta_cutoff"] == 0:
+        return None
+    return VqaWarpers(min_p=min_p, typical_p=typical_p, epsilon_cutoff=cut["epsilon_cutoff"], eta_cutoff=cut["eta_cutoff"])
+
+
 def check_spec_tokens(d) -> int:
     """The draft length of a speculative decode: an integer in [0, 15] (0 = off)."""
     if isinstance(d, bool) or int(d) != d or not 0 <= int(d) <= 15:
         raise ValueError(f"the number of speculative draft tokens must be an integer in [0, 15], got {d!r}")
     return int(d)
+
+
+def _warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff) -> dict:
+    """The `warpers=` keyword of the engine's sampled calls; empty when all four are off (the plain call)."""
+    w = warper_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    return {} if w is None else dict(warpers=w)
 
 
 def _with_step(p: VqaSampling, step: int) -> VqaSampling:
@@ -209,11 +238,14 @@ class VQA_LLM:
     def free_form_inference(self, image, question, temperature=0, top_p=None, num_beams=1, max_new_tokens=200,
                             object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None, speculative=0,
                             draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-                            suppress_tokens=None, allowed_tokens_fn=None, logprobs=None) -> str:
+                            suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
+                            epsilon_cutoff=None, eta_cutoff=None) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
         so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
         4.31 beam search; beam sampling (num_beams > 1 with temperature > 0) is not implemented.
+        min_p, typical_p, epsilon_cutoff, eta_cutoff: HF's warpers of these names, applied on the device behind top-k / top-p in
+        HF's order (`warper_params`); ignored at temperature 0, as top_p is.
         speculative = d > 0: speculative decoding with up to d (<= 15) draft tokens per step from `draft_fn` (default: prompt
         lookup, vstar_amd/spec.py), greedy or sampled; 0 is the plain decode.
         repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, suppress_tokens, allowed_tokens_fn: HF generate's
@@ -226,12 +258,14 @@ class VQA_LLM:
                                     top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn,
                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                     bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                                    allowed_tokens_fn=allowed_tokens_fn, logprobs=logprobs)[0]
+                                    allowed_tokens_fn=allowed_tokens_fn, logprobs=logprobs, min_p=min_p, typical_p=typical_p,
+                                    epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
                         seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, speculative: int = 0,
                         draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-                        suppress_tokens=None, allowed_tokens_fn=None, logprobs=None) -> List[str]:
+                        suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
+                        epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
         single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
@@ -242,7 +276,9 @@ class VQA_LLM:
         logprobs = n in [0, 32] (num_beams 1): self.generated_logprobs becomes a list with one `TokenLogprobs` per sample, aligned
         with self.generated_ids — per generated token its log-probability and rank under the (edited, un-warped) distribution it was
         picked from and the n best alternatives, computed on the device; None (default): self.generated_logprobs is
-        None and the engine calls are the plain ones.  The returned texts are the same either way."""
+        None and the engine calls are the plain ones.  The returned texts are the same either way.
+        min_p, typical_p, epsilon_cutoff, eta_cutoff (temperature > 0; ignored by the greedy decode): the further warpers of
+        DESIGN.md §8.10 for every sample; all off (the default): the engine calls are the plain ones."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if num_beams < 1:
@@ -265,7 +301,9 @@ class VQA_LLM:
         if logprobs is not None and num_beams > 1:
             raise NotImplementedError("logprobs with beam search (num_beams > 1) is not implemented: beam hypotheses carry their "
                                       "own scores, and exposing those is a follow-up")
+        warp = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         if temperature > 0:
+            warper_params(**warp)                      # (validated before any engine work)
             base = resolve_seed(seed)
             params = [sampling_params(temperature, top_k, top_p, s.get("seed", base + i)) for i, s in enumerate(samples)]
         seqs, lens, id_lens, text_ids = [], [], [], []
@@ -281,12 +319,13 @@ class VQA_LLM:
             text_ids.append([t for t in ids if t >= 0])
         if speculative:
             res = self.speculative_decode(seqs, lens, text_ids, max_new_tokens, speculative,
-                                          params if temperature > 0 else None, draft_fn, rules, logprobs=logprobs)
+                                          params if temperature > 0 else None, draft_fn, rules, logprobs=logprobs,
+                                          **(warp if temperature > 0 else {}))
         elif num_beams > 1:
             outs = self.beam_decode(seqs, lens, id_lens, max_new_tokens, num_beams, length_penalty, early_stopping)
             res = [o[0] for o in outs]
         elif temperature > 0:
-            res = self.sample_decode(seqs, lens, max_new_tokens, params, rules, text_ids, logprobs=logprobs)
+            res = self.sample_decode(seqs, lens, max_new_tokens, params, rules, text_ids, logprobs=logprobs, **warp)
         else:
             res = self.greedy_decode(seqs, lens, max_new_tokens, rules, text_ids, logprobs=logprobs)
         self.generated_ids, self.generated_logprobs = res if logprobs is not None else (res, None)
@@ -316,16 +355,20 @@ class VQA_LLM:
                             rules, histories, logprobs)
 
     def sample_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, params, rules: Optional[LogitRules] = None,
-                      histories=None, logprobs=None):
+                      histories=None, logprobs=None, *, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         """model.generate(do_sample=True, use_cache=True): params[i] (`_lib.VqaSampling`) drives sequence i; the Philox step
         of a draw is the index of the token it generates (0 = the token drawn from the prefill's last row).  rules + histories,
-        logprobs: see `_decode`."""
+        logprobs: see `_decode`.  min_p .. eta_cutoff: `warper_params` (DESIGN.md §8.10), the same record for every sequence;
+        all off: the engine calls are the plain ones."""
+        wkw = _warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
         def choose(step, want, idx, t, edits):
-            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx], edits=edits, logprobs=logprobs)
+            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx], edits=edits, logprobs=logprobs, **wkw)
         return self._decode(seqs, lens, max_new_tokens, choose, rules, histories, logprobs)
 
     def speculative_decode(self, seqs: Sequence[Seq], lens: Sequence[int], ids: Sequence[Sequence[int]], max_new_tokens: int,
-                           d: int, params=None, draft_fn=None, rules: Optional[LogitRules] = None, logprobs=None):
+                           d: int, params=None, draft_fn=None, rules: Optional[LogitRules] = None, logprobs=None, *, min_p=None,
+                           typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         """Speculative decoding: greedy (params None) or sampled (params[i] drives sequence i as in
         `sample_decode`).  ids[i]: the un-expanded text ids of sequence i (placeholders left out) — what the drafter sees, with
         the generated tokens appended.  Every engine call feeds each live sequence the rows [cur, draft_0 .. draft_{k-1}] at
@@ -338,6 +381,7 @@ class VQA_LLM:
         = len(out) + r, what a plain decode would see once those drafts are accepted; batch_id = i.
         logprobs = n: returns (ids, records), records[i] a `TokenLogprobs` with one entry per generated token of sequence i — of a
         verify step the entries of the a + 1 tokens that hold (cut at an EOS like the tokens), the -1 rows dropped.
+        min_p .. eta_cutoff (sampled only; greedy ignores them): `warper_params`, the same record for every row.
         self.spec_stats = calls / drafted / accepted / tokens of this run."""
         from .spec import prompt_lookup_draft
         cfg, eng = self.cfg, self.engine
@@ -350,6 +394,8 @@ class VQA_LLM:
         ed0 = self._edits(rules, [(list(ids[i]), 0, i) for i in range(n)])
         logprobs = check_logprobs(logprobs)
         lpkw = {} if logprobs is None else dict(logprobs=logprobs)      # (without: the engine calls are the plain ones)
+        if params is not None:
+            lpkw.update(_warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff))
         if params is None:
             first = eng.forward(seqs, want0, logits=False, edits=ed0, **lpkw)[1:]
         else:

@@ -163,6 +163,15 @@ class VqaEngine:
         return (_lib.VqaSampling * max(nw, 1))(*params)
 
     @staticmethod
+    def _warpers_array(warpers, nw: int):
+        """One `_lib.VqaWarpers` for all wanted rows, or a list of one per row -> the ctypes array behind the C pointer."""
+        if isinstance(warpers, _lib.VqaWarpers):
+            warpers = [warpers] * nw
+        if len(warpers) != nw:
+            raise ValueError(f"{len(warpers)} warper records for {nw} wanted rows")
+        return (_lib.VqaWarpers * max(nw, 1))(*warpers)
+
+    @staticmethod
     def _edits_struct(edits, nw: int):
         """`edits` = the packed arrays (off, tok, penalty) of `LogitRules.pack`, one plan per wanted row -> the
         vstar_vqa_logit_edits record behind the C pointer, and the arrays to keep alive while the call runs."""
@@ -216,16 +225,27 @@ class VqaEngine:
                            self.handle)
         return out_logits, out_arg[:nw]
 
-    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None, logprobs=None):
+    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None, logprobs=None, warpers=None):
         """`forward` with the arg-max replaced by the on-device sampling tail (csrc/sample.hip): `params` holds one
         `_lib.VqaSampling` per wanted row (or one record for all of them); edits as in `forward` (the draw sees the edited
         logits).  logprobs as in `forward`, of the drawn token — under the edited, UN-WARPED, temperature-1 distribution (DESIGN.md
-        §8.9).  Returns the drawn tokens, int32 [n_want], with logprobs (tokens, `TokenLogprobs`); the logits never leave the device."""
+        §8.9).  warpers: None, or one `_lib.VqaWarpers` per wanted row (or one record for all): min-p, typical-p and the epsilon /
+        eta cutoffs between top-p and the draw (`vqa.warper_params`); None is the call without them, launch for
+        launch.  Returns the drawn tokens, int32 [n_want], with logprobs (tokens, `TokenLogprobs`); the logits never leave the device."""
         n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
         prm = self._sampling_array(params, nw)
         out = np.empty((max(nw, 1),), np.int32)
+        if warpers is not None:
+            wrp = self._warpers_array(warpers, nw)
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw) if n_lp is not None else (None, None)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_sample_warp(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out),
+                                                                  ctypes.cast(wrp, ctypes.c_void_p),
+                                                                  ctypes.byref(st) if st is not None else None,
+                                                                  ctypes.byref(lp) if lp is not None else None), self.handle)
+            return (out[:nw], rec) if n_lp is not None else out[:nw]
         if n_lp is not None:
             st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
             lp, rec = self._logprobs_struct(n_lp, nw)
@@ -276,14 +296,15 @@ class VqaEngine:
         return (nll[:nw], rk[:nw]) if rank else nll[:nw]
 
     def forward_verify(self, step: Sequence[Seq], wanted: Sequence[Tuple[int, int]], groups, draft, params=None, edits=None,
-                       logprobs=None):
+                       logprobs=None, warpers=None):
         """`forward` with the arg-max replaced by the on-device verify tail of speculative decoding (csrc/spec.hip, DESIGN.md
         §8.5): wanted rows groups[g] .. groups[g+1]-1 are the rows of one sequence in position order (its current token and the
         drafts fed behind it), draft[j] the token wanted row j's choice is compared with (-1 on a group's last row).  params:
         None = greedy, else one `_lib.VqaSampling` per wanted row (or one record for all).  edits as in `forward`: every row's
         choice sees its edited logits.  Returns (n_accept int32 [n_groups], tokens int32 [n_want]): per group the accepted drafts
         and one more token, -1 behind them.  logprobs as in `forward`, of every row's token (NaN / -1 on the -1 rows): one more
-        returned value, a `TokenLogprobs`."""
+        returned value, a `TokenLogprobs`.  warpers as in `forward_sample` (sampled rows only: a greedy verify ignores them): a draft
+        outside the kept set they leave is never accepted."""
         n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(step, wanted)
         nw = args[6]
@@ -294,6 +315,14 @@ class VqaEngine:
         acc = np.empty((max(ng, 1),), np.int32)
         tok = np.empty((max(nw, 1),), np.int32)
         tail = (ctypes.cast(prm, ctypes.c_void_p) if prm is not None else None, _ptr(go), ng, _ptr(dr), _ptr(acc), _ptr(tok))
+        if warpers is not None:
+            wrp = self._warpers_array(warpers, nw)
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw) if n_lp is not None else (None, None)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_verify_warp(self.handle, *args, *tail, ctypes.cast(wrp, ctypes.c_void_p),
+                                                                  ctypes.byref(st) if st is not None else None,
+                                                                  ctypes.byref(lp) if lp is not None else None), self.handle)
+            return (acc[:ng], tok[:nw], rec) if n_lp is not None else (acc[:ng], tok[:nw])
         if n_lp is not None:
             st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
             lp, rec = self._logprobs_struct(n_lp, nw)
