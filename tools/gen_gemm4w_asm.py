@@ -387,7 +387,13 @@ def main(out_path=None):
     name, name_pf = os.environ.get("G4W_SHAPE", "v2"), os.environ.get("G4W_SHAPE_PF", "v8")
     L = loop_text(SHAPES[name], SHAPES[name].get("pf") is not None)
     Lp = loop_text(SHAPES[name_pf], True)
-    clob = ", ".join(f'"v{i}"' for i in range(NV)) + ", " + ", ".join(f'"a{i}"' for i in range(256))
+    # The register contract of the statements, whole and in one place: the VGPRs a text uses (minus the pinned operands), ALL 256
+    # AGPRs (GEMM4W_AGPRS: also the clobber list of gemm4w.hip's accumulator read statements), memory, scc — and m0, which every
+    # DMA piece rewrites (s_add_u32 m0, ...) and the LDS-DMA builtins behind the statement depend on.
+    def clobbers(name, nv, pinned=()):
+        return "#define " + name + " " + ", ".join(f'"v{i}"' for i in range(nv) if i not in pinned) + ', GEMM4W_AGPRS, "memory", "scc", "m0"\n'
+
+    pinned_f8 = set(range(192, 196)) | set(range(200, 216)) | set(range(218, 222))
     path = out_path or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "vstar_amd", "csrc", "gemm4w_loop.inc")
     with open(path, "w") as f:
         f.write("// GENERATED by tools/gen_gemm4w_asm.py (schedules %s / %s) — do not edit.  The hand-scheduled K loops of gemm4w.hip.\n" % (name, name_pf))
@@ -397,11 +403,10 @@ def main(out_path=None):
         f.write(as_macro("GEMM4W_LOOP_ASM_F8_PF", loop_text_f8(True)))
         f.write(as_macro("GEMM4W_LOOP_ASM_MX", loop_text_f8(False, mx=True)))
         f.write(as_macro("GEMM4W_LOOP_ASM_MX_PF", loop_text_f8(True, mx=True)))
-        f.write("#define GEMM4W_CLOBBERS " + clob + ', "memory", "scc"\n')
-        pinned = set(range(192, 196)) | set(range(200, 216)) | set(range(218, 222))
-        f.write("#define GEMM4W_CLOBBERS_F8 " + ", ".join(f'"v{i}"' for i in range(F8_NV) if i not in pinned) + ", " + ", ".join(f'"a{i}"' for i in range(256)) + ', "memory", "scc"\n')
-        pinned |= {F8_SRD, F8_SOFF}
-        f.write("#define GEMM4W_CLOBBERS_MX " + ", ".join(f'"v{i}"' for i in range(F8_NV_MX) if i not in pinned) + ", " + ", ".join(f'"a{i}"' for i in range(256)) + ', "memory", "scc"\n')
+        f.write("#define GEMM4W_AGPRS " + ", ".join(f'"a{i}"' for i in range(256)) + "\n")
+        f.write(clobbers("GEMM4W_CLOBBERS", NV))
+        f.write(clobbers("GEMM4W_CLOBBERS_F8", F8_NV, pinned_f8))
+        f.write(clobbers("GEMM4W_CLOBBERS_MX", F8_NV_MX, pinned_f8 | {F8_SRD, F8_SOFF}))
     print(os.path.normpath(path), len(L), "+", len(Lp), "instructions,", sum("v_mfma" in x for x in L), "MFMAs per text")
     return L
 

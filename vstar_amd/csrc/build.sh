@@ -1,10 +1,15 @@
 #!/bin/bash
 # Builds libvstar_hip.so (gfx950 only) in-tree next to the Python package.
+#   build.sh                      every object that is out of date, the gemm4w AGPR check, the link
+#   build.sh --objects NAME ...   only build/NAME.o and build/f16_NAME.o, brought up to date by the same recipe; no check, no link
 set -e
 cd "$(dirname "$0")"
 OUT=../libvstar_hip.so
-HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+export HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-unused-value -mllvm -amdgpu-mfma-vgpr-form"
+ONLY=""
+if [ "$1" = --objects ]; then shift; ONLY=" $* "; fi
+wanted() { [ -z "$ONLY" ] || [[ "$ONLY" == *" $1 "* ]]; }
 mkdir -p build
 rm -f build/gemm256a.o build/f16_gemm256a.o     # (round-3 experiment, moved to tools/experiments/gemm256a)
 pids=()
@@ -21,32 +26,36 @@ stale() {  # stale <object> <source>
 # v_accvgpr_read statements in the epilogue): the compiler must never use AGPRs as VGPR spill space there — it did (a2..a9, round 6)
 extra() { [ "$1" = gemm4w ] && echo "-mllvm -amdgpu-spill-vgpr-to-agpr=0"; }
 for f in gemm gemm256 gemm4w norm attention elementwise decode skinny quant heads preprocess engine comm sample beam score spec edit logprob; do
-  if stale build/$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!); fi
+  if wanted $f && stale build/$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!); fi
 done
 # fp16 instantiation (-DVSTAR_LP_F16): the dtype-generic kernel files + the VQA-LLM engine
 for f in gemm gemm256 gemm4w norm attention elementwise decode skinny vqa_engine; do
   [ -f $f.hip ] || continue
-  if stale build/f16_$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -DVSTAR_LP_F16 -c $f.hip -o build/f16_$f.o & pids+=($!); fi
+  if wanted $f && stale build/f16_$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -DVSTAR_LP_F16 -c $f.hip -o build/f16_$f.o & pids+=($!); fi
 done
-# the hash of the kernel sources THIS binary is built from (vstar_amd/provenance.py::kernel_source_hash, same algorithm), compiled
-# into the library and exported as vstar_build_source_hash(): evidence files are stamped with the LOADED library's value, so a
-# .hip edited between building and profiling / summarising shows up as a mismatch instead of a matching stamp.
-SRC_HASH=$(python3 - <<'PY'
-import glob, hashlib, os
-h = hashlib.sha256()
-for path in sorted(glob.glob("*.hip") + glob.glob("*.hpp") + ["build.sh"]):
-    h.update(os.path.basename(path).encode())
-    h.update(open(path, "rb").read())
-print(h.hexdigest()[:16])
-PY
-)
-cat > build/src_hash.cpp.new <<EOF2
+if [ -z "$ONLY" ]; then
+  # the hash of the kernel sources THIS binary is built from (vstar_amd/provenance.py::kernel_source_hash, run as a script: the one
+  # copy of the algorithm), compiled into the library and exported as vstar_build_source_hash(): evidence files are stamped with the
+  # LOADED library's value, so a .hip edited between building and profiling / summarising shows up as a mismatch instead of a
+  # matching stamp.
+  SRC_HASH=$(python3 ../provenance.py)
+  cat > build/src_hash.cpp.new <<EOF2
 extern "C" const char* vstar_build_source_hash(void) { return "$SRC_HASH"; }
 EOF2
-if ! cmp -s build/src_hash.cpp.new build/src_hash.cpp; then mv build/src_hash.cpp.new build/src_hash.cpp; else rm build/src_hash.cpp.new; fi
-if [ ! -f build/src_hash.o ] || [ build/src_hash.cpp -nt build/src_hash.o ]; then g++ -O2 -fPIC -c build/src_hash.cpp -o build/src_hash.o; fi
+  if ! cmp -s build/src_hash.cpp.new build/src_hash.cpp; then mv build/src_hash.cpp.new build/src_hash.cpp; else rm build/src_hash.cpp.new; fi
+  if [ ! -f build/src_hash.o ] || [ build/src_hash.cpp -nt build/src_hash.o ]; then g++ -O2 -fPIC -c build/src_hash.cpp -o build/src_hash.o; fi
+fi
 fail=0
 for p in "${pids[@]}"; do wait $p || fail=1; done
 [ $fail -eq 0 ] || { echo "build failed"; exit 1; }
+[ -z "$ONLY" ] || exit 0
+# the AGPR proof on the two objects that are about to be linked (tools/check_gemm4w_agpr.py: disassembles, compiles nothing): a
+# compiler that parks a value in an unread accumulator fails the build here, not a test somewhere else.  Exit code 2: no llvm-objdump.
+agpr=$(python3 ../../tools/check_gemm4w_agpr.py build/gemm4w.o build/f16_gemm4w.o) && rc=0 || rc=$?
+case $rc in
+  0) echo "gemm4w AGPR check: $(grep -c '^ok ' <<<"$agpr") kernels ok" ;;
+  2) echo "$agpr: check SKIPPED" ;;
+  *) echo "$agpr"; echo "build failed: gemm4w AGPR check"; exit 1 ;;
+esac
 $HIPCC --offload-arch=gfx950 -shared -fPIC build/*.o -o $OUT
 echo "built $(realpath $OUT)"

@@ -42,14 +42,9 @@ constexpr int LDS_TOTAL = 2 * 65536;
 // The accumulators sit in a0..a255 BEHIND the compiler's back: they are clobbers of the K-loop statement, so to the register allocator
 // the AGPRs are free afterwards — and under pressure it parks VGPR values there (round 6: the W piece offsets landed on a2..a9
 // before the epilogue had read them).  Every read statement therefore clobbers the whole AGPR file: no compiler value can live in an
-// AGPR across any of them, i.e. anywhere between the K loop and the last read; tools/check_gemm4w_agpr.py (run by the CPU test suite
-// on the compiler's assembly) proves that no compiler-written AGPR instruction remains in that window.
-#define G4W_A16(b) "a" #b "0", "a" #b "1", "a" #b "2", "a" #b "3", "a" #b "4", "a" #b "5", "a" #b "6", "a" #b "7", "a" #b "8", "a" #b "9"
-#define G4W_ALL_AGPRS                                                                                                              \
-  "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", G4W_A16(1), G4W_A16(2), G4W_A16(3), G4W_A16(4), G4W_A16(5), G4W_A16(6), \
-  G4W_A16(7), G4W_A16(8), G4W_A16(9), G4W_A16(10), G4W_A16(11), G4W_A16(12), G4W_A16(13), G4W_A16(14), G4W_A16(15), G4W_A16(16),     \
-  G4W_A16(17), G4W_A16(18), G4W_A16(19), G4W_A16(20), G4W_A16(21), G4W_A16(22), G4W_A16(23), G4W_A16(24), "a250", "a251", "a252",   \
-  "a253", "a254", "a255"
+// AGPR across any of them, i.e. anywhere between the K loop and the last read; tools/check_gemm4w_agpr.py (run by build.sh on the
+// objects it links, and by the CPU test suite) proves that no compiler-written AGPR instruction touches an unread accumulator in that
+// window.  The list of the 256 names is GEMM4W_AGPRS of the generated file: the one list the loop statements' clobbers are built from.
 #ifdef G4W_TIMELINE   // diagnostic builds only (tools/gemm4w_timeline.py): wall-clock stamps (100 MHz) of the tile phases, wave 0 of WG 0 / 100
 __device__ unsigned long long g4w_timeline[2][64][8];
 #define G4W_STAMP(pt)                                                                                         \
@@ -74,7 +69,7 @@ __device__ __forceinline__ void load_acc_row(f32x4 (&a)[4]) {
                : "=v"(a[0][0]), "=v"(a[0][1]), "=v"(a[0][2]), "=v"(a[0][3]), "=v"(a[1][0]), "=v"(a[1][1]), "=v"(a[1][2]), "=v"(a[1][3]),
                  "=v"(a[2][0]), "=v"(a[2][1]), "=v"(a[2][2]), "=v"(a[2][3]), "=v"(a[3][0]), "=v"(a[3][1]), "=v"(a[3][2]), "=v"(a[3][3])
                : "n"(B)
-               : G4W_ALL_AGPRS);
+               : GEMM4W_AGPRS);
 }
 // The in-register epilogue of the 128 x 64 half H of the wave's tile = ONE virtual wave (wr, wc) of gemm256's 2 x 4 wave grid
 // (gemm256_direct_epilogue.hpp, shared with gemm256.hip).  The accumulators are read from the AGPRs ROW BY ROW where stage 1 consumes
@@ -432,6 +427,12 @@ __global__ __launch_bounds__(256, 1) void gemm4w_kernel(const GemmParams p) {
     const i32x4 srda = {(int)(uint32_t)(uintptr_t)abase, (int)(((uintptr_t)abase >> 32) & 0xffff), a_span(), 0x00020000};
     const i32x4 srdw = {(int)(uint32_t)(uintptr_t)wbase, (int)(((uintptr_t)wbase >> 32) & 0xffff), -1, 0x00020000};
     uint32_t koff = 256;                               // K-tiles 0 and 1 are in flight (issue_head): the loop's first pieces are K-tile 2
+    // The texts rewrite m0 for every DMA piece and say so in their clobber lists: issue_head's LDS-DMA builtins behind the statement
+    // depend on m0, and a compiler that merges or hoists M0 initialisations must see the write.  m0 is a RESERVED register of the
+    // backend, which clang remarks on for every such statement ("may not be preserved across the asm statement": it is not, that is
+    // the point) — silenced for these statements only.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 #define G4W_OPERANDS(CLOB)                                                                                                           \
     : [cnt] "+s"(cnt), [koff] "+s"(koff)                                                                                             \
     : [srda] "s"(srda), [srdw] "s"(srdw), [ldsw] "s"(ldsw), [rd0] "v"(rd[0]), [rd1] "v"(rd[1]), [rd2] "v"(rd[2]),                    \
@@ -481,6 +482,7 @@ __global__ __launch_bounds__(256, 1) void gemm4w_kernel(const GemmParams p) {
       else asm volatile(GEMM4W_LOOP_ASM G4W_OPERANDS(GEMM4W_CLOBBERS));
     }
 #undef G4W_OPERANDS
+#pragma clang diagnostic pop
     G4W_STAMP(1);
     // ---- next tile: its K-tiles 0 and 1 go into the (dead: the loop text ends behind a barrier) LDS buffers NOW, so that the
     // pipeline fill overlaps this tile's epilogue; this tile's coordinates stay in em0 / en0 ----
