@@ -332,7 +332,9 @@ int vstar_op_ln_fold(void* stream, uint16_t* dev_W, uint16_t* dev_bias, const ui
                      int n_rows, int K);
 /* Which GEMM kernel the calling thread's last vstar_op_gemm / vstar_op_gemm_fp8 launched: 128, 256, 384 (= 256 + 128: whole
  * rounds of 256x256 tiles over the leading rows and the ragged last round's rows as 128x128 tiles — bit-identical to either
- * kernel alone), or 0 (nothing launched).  Lets a test assert that it exercised the kernel it was written for, whatever the dispatcher's heuristics do. */
+ * kernel alone), or 0 (nothing launched: an empty call, or the dispatcher refused it).  A dry run through vstar_op_gemm_plan does
+ * not count, here and in vstar_op_gemm_last_mode.  Lets a test assert that it exercised the kernel it was written for, whatever the
+ * dispatcher's heuristics do. */
 int vstar_op_gemm_last_tile(void);
 /* Which variant of the 128-row family the calling thread's last call of the GEMM dispatcher ran (a dry run through
  * vstar_op_gemm_plan does not count): 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 / 128 x 64 / 128 x 256 tile;
@@ -344,7 +346,10 @@ int vstar_op_gemm_last_mode(void);
  * C[M,N] = A[M,K] · W^T with this epilogue (+ residual, + the fused-RoPE epilogue of the LLaMA qkv projection) on a device with
  * `cus` compute units.  Returns 10 * tile + variant: tile as vstar_op_gemm_last_tile (128, 256, 384 = split launch, 2560 = the
  * opt-in hand-scheduled kernel), variant of the 128-row family 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 /
- * 128 x 64 / 128 x 256 tile (0 for the 256^2 kernel; for 384 the variant of the trailing 128-row part); negative = error code. */
+ * 128 x 64 / 128 x 256 tile (0 for the 256^2 kernel; for 384 the variant of the trailing 128-row part); negative = error code.
+ * Takes the same kernel requests in `epilogue` as vstar_op_gemm: with VSTAR_EPI_TILE4W it returns 25640 inside the 4-wave kernel's
+ * domain and an error outside it.  A pure function of its arguments: it changes neither vstar_op_gemm_last_tile() nor
+ * vstar_op_gemm_last_mode(). */
 int vstar_op_gemm_plan(int M, int N, int K, int epilogue, int has_residual, int fused_rope, int cus);
 /* W8A8 GEMM (BASELINE config 5: fp8 weights on the CDNA4 fp8 MFMA), op level, all pointers DEVICE pointers: quantises the
  * rows of A [M,K] (per token) and of W [ceil(N/256)*256, K] (per output channel) to OCP fp8 e4m3 with scale = absmax/448,

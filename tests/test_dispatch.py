@@ -98,3 +98,38 @@ def test_forced_variant_refusals():
     # a dry run does not count as the thread's last launch
     before = lib.vstar_op_gemm_last_mode()
     assert plan(lib, 1, "o") == 1285 and lib.vstar_op_gemm_last_mode() == before
+
+
+def smallest_split(lib, cus, N=1024, K=128):
+    """(M, code) of the smallest M (step 128) that the dispatcher splits on `cus` compute units."""
+    for M in range(128, 1 << 16, 128):
+        code = lib.vstar_op_gemm_plan(M, N, K, 0, 0, 0, cus)
+        if code // 10 == 384:
+            return M, code
+    raise AssertionError("no split launch below 65536 rows")
+
+
+def test_split_reports_the_trailing_variant():
+    """A split launch reports the variant of its trailing 128-row part, planned for those rows alone: K < 256 gives it the double
+    buffer on every CU count, and where a split starts (one full round of 256^2 tiles plus a remainder) moves with the CU count."""
+    lib = _lib.load()
+    (m256, code256), (m304, code304) = smallest_split(lib, 256), smallest_split(lib, 304)
+    assert code256 == 3842 and code304 == 3842
+    assert m256 != m304
+
+
+def test_tile4w_request_is_planned_or_refused():
+    lib = _lib.load()
+    assert lib.vstar_op_gemm_plan(32 * 640, 4096, 4096, _lib.EPI_TILE4W, 0, 0, 256) == 25640
+    assert lib.vstar_op_gemm_plan(640, 4096, 4096, _lib.EPI_TILE4W, 0, 0, 256) < 0            # outside the 256^2 kernels' domain
+    assert lib.vstar_op_gemm_plan(32 * 577, 1024, 1024, _lib.EPI_TILE4W, 0, 0, 256) < 0       # ragged M with K < 4096
+
+
+def test_observers_report_the_last_real_call_only():
+    """vstar_op_gemm_last_tile() / _last_mode(): a dry run changes neither, a refused call leaves both at 0.  K = 65 is refused by the
+    dispatcher's validation, before any HIP call: nothing is launched, with or without a GPU."""
+    lib = _lib.load()
+    assert lib.vstar_op_gemm(None, None, 65, None, None, None, 0, None, 128, 0, 128, 128, 65, 0) != 0
+    assert lib.vstar_op_gemm_last_tile() == 0 and lib.vstar_op_gemm_last_mode() == 0
+    assert plan(lib, 1, "o") == 1285 and plan(lib, 32, "o") == 25640 and plan(lib, 8, "o") == 3845
+    assert lib.vstar_op_gemm_last_tile() == 0 and lib.vstar_op_gemm_last_mode() == 0

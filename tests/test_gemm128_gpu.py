@@ -282,11 +282,12 @@ def _cus():
 F32_OUT_SHAPES = [(128, 128, 64), (256, 384, 128), (200, 130, 192), (1, 514, 768), (777, 1024, 640), (4096, 4096, 1024), (37, 4, 768)]
 
 
-@pytest.mark.parametrize("shape", F32_OUT_SHAPES + ["ring_128x128", "ring_128x256"], ids=str)
+@pytest.mark.parametrize("shape", F32_OUT_SHAPES + ["ring_128x128", "ring_128x256", "split"], ids=str)
 def test_plan_is_what_runs(lib, cuda, shape):
     """After an unforced vstar_op_gemm, last_tile * 10 + last_mode equals vstar_op_gemm_plan at the device's CU count: the host-side
     dispatch table (tests/test_dispatch.py) describes real launches.  Two shapes are searched so that the plan sends them to the
-    128 x 128 and the 128 x 256 loader-wave tile on this device."""
+    128 x 128 and the 128 x 256 loader-wave tile on this device, a third is the smallest M (step 128) the plan splits at N = 1024,
+    K = 128: one full round of 256^2 tiles plus a remainder — 16512 rows on 256 CUs."""
     cus = _cus()
     if shape == "ring_128x128":
         M, K = 1000, 256
@@ -294,12 +295,15 @@ def test_plan_is_what_runs(lib, cuda, shape):
     elif shape == "ring_128x256":
         M, K = 640, 2048
         M, N, K = M, _find(lib, 1287, cus, M, K), K
+    elif shape == "split":
+        N, K = 1024, 128
+        M = next(M for M in range(128, 1 << 16, 128) if lib.vstar_op_gemm_plan(M, N, K, 0, 0, 0, cus) // 10 == 384)
     else:
         M, N, K = shape
     plan = lib.vstar_op_gemm_plan(M, N, K, 0, 0, 0, cus)
     assert plan > 0
     if isinstance(shape, str):
-        assert plan == {"ring_128x128": 1285, "ring_128x256": 1287}[shape]
+        assert plan == {"ring_128x128": 1285, "ring_128x256": 1287, "split": 3842}[shape]
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g).bfloat16().to(cuda)
     w = torch.zeros((N + 255) // 256 * 256, K, dtype=torch.bfloat16, device=cuda)

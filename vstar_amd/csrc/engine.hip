@@ -1593,11 +1593,13 @@ static int op_rc(hipError_t e) {
   return VSTAR_OK;
 }
 
-// The VSTAR_EPI_VARIANT field of `epilogue` -> GemmParams::stages_force.  false (message set, nothing to launch): a value outside
+// The kernel requests of `epilogue`, for every GEMM door: VSTAR_EPI_TILE4W / TILE256 / TILE128 (the first of them that is set) ->
+// GemmParams::tile_force, the VSTAR_EPI_VARIANT field -> stages_force.  false (message set, nothing to launch): a variant outside
 // {0, 2, 5, 6, 7}, or a variant of the 128-row family next to a request for a 256 x 256 kernel.
-static bool op_gemm_variant(int epilogue, int* variant) {
+static bool op_gemm_flags(int epilogue, GemmParams* p) {
+  p->tile_force = (epilogue & VSTAR_EPI_TILE4W) ? GEMM_TILE_4W : (epilogue & VSTAR_EPI_TILE256) ? 256 : (epilogue & VSTAR_EPI_TILE128) ? 128 : 0;
   const int v = (epilogue & VSTAR_EPI_VARIANT_MASK) >> 12;
-  *variant = v;
+  p->stages_force = v;
   if (v == 0) return true;
   if (v != 2 && v != 5 && v != 6 && v != 7) {
     tls_error() = "VSTAR_EPI_VARIANT(" + std::to_string(v) + "): the variants of the 128-row family are 2, 5, 6 and 7";
@@ -1619,8 +1621,7 @@ int vstar_op_gemm(void* stream, const uint16_t* A, int64_t lda, const uint16_t* 
   { const char* e = getenv("VSTAR_GEMM_DEBUG"); p.debug_flags = e ? atoi(e) : 0; }
   const bool nosync = (epilogue & VSTAR_EPI_NOSYNC) != 0;
   if ((epilogue & VSTAR_EPI_TILE128) && (epilogue & VSTAR_EPI_TILE256)) { tls_error() = "both tile overrides set"; return VSTAR_ERR_INVALID; }
-  p.tile_force = (epilogue & VSTAR_EPI_TILE4W) ? GEMM_TILE_4W : (epilogue & VSTAR_EPI_TILE256) ? 256 : (epilogue & VSTAR_EPI_TILE128) ? 128 : 0;
-  if (!op_gemm_variant(epilogue, &p.stages_force)) return VSTAR_ERR_INVALID;
+  if (!op_gemm_flags(epilogue, &p)) return VSTAR_ERR_INVALID;
   if (p.tile_force == 256 && !gemm256_eligible(p)) {
     tls_error() = "VSTAR_EPI_TILE256: shape outside the 256x256 kernel's domain (M >= 1024, N >= 256, K % 128 == 0)";
     return VSTAR_ERR_INVALID;
@@ -1639,8 +1640,7 @@ int vstar_op_gemm_norm(void* stream, const uint16_t* A, int64_t lda, const uint1
   { const char* e = getenv("VSTAR_GEMM_DEBUG"); p.debug_flags = e ? atoi(e) : 0; }
   if ((epilogue & VSTAR_EPI_TILE128) && (epilogue & VSTAR_EPI_TILE256)) { tls_error() = "both tile overrides set"; return VSTAR_ERR_INVALID; }
   if (sumsq_out && ((epilogue & 0xff) != VSTAR_EPI_NONE || N % 64)) { tls_error() = "sumsq_out: VSTAR_EPI_NONE and N % 64 == 0 only"; return VSTAR_ERR_INVALID; }
-  p.tile_force = (epilogue & VSTAR_EPI_TILE4W) ? GEMM_TILE_4W : (epilogue & VSTAR_EPI_TILE256) ? 256 : (epilogue & VSTAR_EPI_TILE128) ? 128 : 0;
-  if (!op_gemm_variant(epilogue, &p.stages_force)) return VSTAR_ERR_INVALID;
+  if (!op_gemm_flags(epilogue, &p)) return VSTAR_ERR_INVALID;
   if (p.tile_force == 256 && !gemm256_eligible(p)) { tls_error() = "VSTAR_EPI_TILE256: shape outside the 256x256 kernel's domain"; return VSTAR_ERR_INVALID; }
   hipError_t e = gemm_lp(p, epilogue & 0xff, false, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
@@ -1661,23 +1661,19 @@ int vstar_op_gemm_last_tile(void) { return gemm_last_tile(); }
 int vstar_op_gemm_last_mode(void) { return gemm_launched_mode(); }
 int vstar_op_gemm_plan(int M, int N, int K, int epilogue, int has_residual, int fused_rope, int cus) {
   if (M <= 0 || N <= 0 || K <= 0 || cus <= 0) { tls_error() = "vstar_op_gemm_plan: bad argument"; return VSTAR_ERR_INVALID; }
-  // nothing is dereferenced in a dry run: the pointers only have to look aligned and non-null
-  static const uintptr_t fake = 0x10000;
+  // gemm_plan dereferences nothing: a residual / a RoPE table only has to be there (non-null, aligned)
+  static const lp_t* const some = (const lp_t*)(uintptr_t)0x10000;
   GemmParams p{};
-  p.A = (const lp_t*)fake; p.lda = K; p.W = (const lp_t*)fake; p.C = (void*)fake;
-  p.M = M; p.N = N; p.K = K;
+  p.lda = K; p.M = M; p.N = N; p.K = K;
   const int n_out = (epilogue & 0xff) == VSTAR_EPI_SILU_MUL ? N / 2 : N;
   p.ldc = n_out;
-  if (has_residual) { p.res = (const lp_t*)fake; p.ldr = n_out; }
-  if (fused_rope) { p.rope_cs = (const lp_t*)fake; p.rope_S = 640; p.rope_cols = N * 2 / 3; }
-  p.tile_force = (epilogue & VSTAR_EPI_TILE256) ? 256 : (epilogue & VSTAR_EPI_TILE128) ? 128 : 0;
-  if (!op_gemm_variant(epilogue, &p.stages_force)) return VSTAR_ERR_INVALID;
+  if (has_residual) { p.res = some; p.ldr = n_out; }
+  if (fused_rope) { p.rope_cs = some; p.rope_S = 640; p.rope_cols = N * 2 / 3; }
+  if (!op_gemm_flags(epilogue, &p)) return VSTAR_ERR_INVALID;
   if (p.stages_force && fused_rope) { tls_error() = "vstar_op_gemm_plan: VSTAR_EPI_VARIANT with fused RoPE (256 x 256 kernels only)"; return VSTAR_ERR_INVALID; }
-  gemm_set_plan(true, cus);
-  const hipError_t e = gemm_lp(p, epilogue & 0xff, false, nullptr);
-  gemm_set_plan(false, 0);
-  if (e != hipSuccess) { tls_error() = std::string("vstar_op_gemm_plan: ") + hipGetErrorString(e); return VSTAR_ERR_INVALID; }
-  return gemm_last_tile() * 10 + gemm_last_mode();
+  const GemmPlan pl = gemm_plan(p, epilogue & 0xff, false, cus);
+  if (pl.status != hipSuccess) { tls_error() = std::string("vstar_op_gemm_plan: ") + hipGetErrorString(pl.status); return VSTAR_ERR_INVALID; }
+  return pl.tile * 10 + pl.mode;
 }
 int vstar_op_layernorm(void* stream, const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y, int rows,
                        int cols, float eps) {
@@ -1842,17 +1838,16 @@ int vstar_op_gemm_ex(void* stream, const vstar_gemm_ex* g) {
   const int flags = g->epilogue & ~0xff, epi = g->epilogue & 0xff;
   if (flags & ~(VSTAR_EPI_TILE128 | VSTAR_EPI_TILE256 | VSTAR_EPI_TILE4W | VSTAR_EPI_VARIANT_MASK)) return op_refuse(door, "unknown bits in `epilogue` (VSTAR_EPI_NOSYNC is not taken)");
   if (epi > VSTAR_EPI_SILU_MUL) return op_refuse(door, "unknown epilogue");
-  const int forced = (flags & VSTAR_EPI_TILE4W) ? GEMM_TILE_4W : (flags & VSTAR_EPI_TILE256) ? 256 : (flags & VSTAR_EPI_TILE128) ? 128 : 0;
   const int tiles = flags & ~VSTAR_EPI_VARIANT_MASK;
   if ((tiles & (tiles - 1)) != 0) return op_refuse(door, "more than one tile override set");
-  int variant = 0;
-  if (!op_gemm_variant(g->epilogue, &variant)) return op_refuse(door, std::string(tls_error()));
-  if (variant && g->dev_rope_cs) return op_refuse(door, "rope_cs with VSTAR_EPI_VARIANT: the 128-row kernels have no fused RoPE");
+  GemmParams p{};
+  if (!op_gemm_flags(g->epilogue, &p)) return op_refuse(door, std::string(tls_error()));
+  const int forced = p.tile_force;
+  if (p.stages_force && g->dev_rope_cs) return op_refuse(door, "rope_cs with VSTAR_EPI_VARIANT: the 128-row kernels have no fused RoPE");
   const int n_out = epi == VSTAR_EPI_SILU_MUL ? g->N / 2 : g->N;
   if (epi == VSTAR_EPI_SILU_MUL && g->N % 32) return op_refuse(door, "VSTAR_EPI_SILU_MUL: N % 32 == 0 required");
   if (g->lda < g->K || g->ldc < n_out || (g->dev_residual && g->ldr < n_out)) return op_refuse(door, "a leading dimension is shorter than its row");
   if (g->w_rows < ((int64_t)g->N + 255) / 256 * 256) return op_refuse(door, "W needs ceil(N / 256) * 256 rows");
-  GemmParams p{};
   p.A = g->dev_A; p.lda = g->lda; p.a_group = g->a_group; p.a_gstride = g->a_gstride; p.a_off = g->a_off;
   p.W = g->dev_W; p.bias = g->dev_bias; p.res = g->dev_residual; p.ldr = g->ldr;
   p.C = g->dev_C; p.ldc = g->ldc; p.c_group = g->c_group; p.c_gstride = g->c_gstride; p.c_off = g->c_off;
@@ -1861,8 +1856,6 @@ int vstar_op_gemm_ex(void* stream, const vstar_gemm_ex* g) {
   p.rope_cs = g->dev_rope_cs; p.rope_S = g->rope_S; p.rope_cols = g->rope_cols; p.rope_R0 = g->rope_R0; p.rope_Lc = g->rope_Lc;
   p.rope_pos0 = g->rope_pos0; p.rope_tail = g->rope_tail;
   { const char* e = getenv("VSTAR_GEMM_DEBUG"); p.debug_flags = e ? atoi(e) : 0; }
-  p.tile_force = forced;
-  p.stages_force = variant;
   // ---- row maps: every mapped row of the call (rows of a ragged tile are clamped to M - 1 by the kernels, so [0, M) is all of them) ----
   const bool a_map = p.a_group > 0, c_map = p.c_group > 0;
   if ((a_map || c_map) && forced == GEMM_TILE_4W) return op_refuse(door, "VSTAR_EPI_TILE4W with a row map (the 4-wave kernel addresses rows by tile)");

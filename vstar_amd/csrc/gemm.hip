@@ -22,15 +22,6 @@
 
 namespace VS_NS {
 
-static thread_local bool t_plan_only = false;
-static thread_local int t_plan_cus = 0;
-static thread_local int t_last_mode = 0;
-static thread_local int t_launched_mode = 0;      // t_last_mode of the last call that was no dry run
-void gemm_set_plan(bool on, int cus) { t_plan_only = on; t_plan_cus = on ? cus : 0; }
-bool gemm_plan_only() { return t_plan_only; }
-int gemm_last_mode() { return t_last_mode; }
-int gemm_launched_mode() { return t_launched_mode; }
-
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
@@ -61,7 +52,7 @@ __device__ __forceinline__ int64_t map_row(int r, int group, int64_t gstride, in
 // always owns whole 64-column spans, so the sumsq epilogue and the gate|up pairing are the same code.
 // NW = 4: a 128 x 256 tile (2 x 4 = EIGHT compute waves of 64 x 64 + the loader wave, 144-KiB ring, one workgroup per CU) for
 // the wide projections of small batches (qkv / gate|up at M = 640: 480 / 860 tiles of 128^2 on 256 CUs): three quarters of the
-// operand bytes per MFMA of the 128^2 tile, which is what bounds this regime (see launch<> below).
+// operand bytes per MFMA of the 128^2 tile, which is what bounds this regime (see gemm128_variant below).
 template <int EPI, bool OUT_F32, int MODE, int NW = 2>
 __global__ __launch_bounds__(MODE == 5 ? (NW == 4 ? 576 : 320) : 256, (NW != 4 && (MODE == 2 || NW == 1)) ? 2 : 1) void gemm128_kernel(const GemmParams p) {
   constexpr bool LDR = MODE == 5;
@@ -288,15 +279,8 @@ __global__ __launch_bounds__(MODE == 5 ? (NW == 4 ? 576 : 320) : 256, (NW != 4 &
   }
 }
 
-}  // namespace
-int gemm_device_cus();
-namespace {
-
 template <int EPI, bool OUT_F32, int MODE, int NW = 2>
 hipError_t launch_stages(const GemmParams& p, hipStream_t s) {
-  t_last_mode = MODE == 5 ? (NW == 4 ? 7 : (NW == 1 ? 6 : 5)) : MODE;
-  if (t_plan_only) return hipSuccess;
-  t_launched_mode = t_last_mode;
   static bool attr_done = false;
   auto kern = gemm128_kernel<EPI, OUT_F32, MODE, NW>;
   constexpr int bn = 64 * NW;
@@ -312,7 +296,43 @@ hipError_t launch_stages(const GemmParams& p, hipStream_t s) {
 }
 
 template <int EPI, bool OUT_F32>
-hipError_t launch(const GemmParams& p, hipStream_t s) {
+hipError_t launch_variant(const GemmParams& p, int mode, hipStream_t s) {
+  if (mode == 7) return launch_stages<EPI, OUT_F32, 5, 4>(p, s);
+  if (mode == 6) return launch_stages<EPI, OUT_F32, 5, 1>(p, s);
+  if (mode == 5) return launch_stages<EPI, OUT_F32, 5, 2>(p, s);
+  return launch_stages<EPI, OUT_F32, 2, 2>(p, s);
+}
+
+// variant `mode` (gemm128_variant) of the 128-row family; the epilogue was validated by gemm_plan
+hipError_t launch128(const GemmParams& p, int epilogue, bool out_f32, int mode, hipStream_t s) {
+#define GEMM_CASE(E)                                                   \
+  case E:                                                              \
+    return out_f32 ? launch_variant<E, true>(p, mode, s) : launch_variant<E, false>(p, mode, s);
+  switch (epilogue) {
+    GEMM_CASE(VSTAR_EPI_NONE)
+    GEMM_CASE(VSTAR_EPI_QUICK_GELU)
+    GEMM_CASE(VSTAR_EPI_GELU)
+    GEMM_CASE(VSTAR_EPI_RELU)
+    GEMM_CASE(VSTAR_EPI_SILU_MUL)
+  }
+#undef GEMM_CASE
+  return hipErrorInvalidValue;
+}
+
+// Process-wide defaults of the dispatcher (A/B runs), read once: VSTAR_GEMM_TILE = the tile_force of calls that set none,
+// VSTAR_GEMM4W = 0 / 1 whether unforced calls inside gemm4w's domain take it, VSTAR_GEMM_SPLIT = 0 turns the ragged-round split
+// off, VSTAR_GEMM128_STAGES = the stages_force of calls that set none.
+struct GemmEnv { int tile, use4w, stages; bool split; };
+const GemmEnv& gemm_env() {
+  static const GemmEnv env = [] {
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    return GemmEnv{num("VSTAR_GEMM_TILE", 0), num("VSTAR_GEMM4W", GEMM4W_DEFAULT), num("VSTAR_GEMM128_STAGES", 0), num("VSTAR_GEMM_SPLIT", 1) != 0};
+  }();
+  return env;
+}
+
+// The variant of the 128-row family for an M x N x K call on `cus` compute units.
+int gemm128_variant(int M, int N, int K, int stages_force, int64_t cus) {
   // Under-filled grids (at most one tile per CU: the small-batch o_proj / down_proj, CLIP out / fc2) take the loader-wave ring
   // (MODE 5): one workgroup per CU anyway, so the 96-KiB ring costs no occupancy.  Fuller grids keep the 64-KiB double buffer,
   // where two co-resident workgroups per CU hide each other's DMA round trips and a ragged last round costs nothing.
@@ -320,43 +340,33 @@ hipError_t launch(const GemmParams& p, hipStream_t s) {
   // with more tiles than CUs the double buffer wins by 5-15 %.  What bounds both: a CU pulls operand tiles from L2 at
   // ~65 (one workgroup) to ~88 KB/us (two) whatever the instruction (tools/probes/dma_probe.hip), and a 128^2 tile needs 32 KiB
   // per K-tile.  VSTAR_GEMM128_STAGES=2|5|6|7 forces one variant for the process (A/B runs), GemmParams::stages_force for one call
-  // (ahead of the environment; validated by gemm_lp).  Same K order in all: bit-identical results (tests/test_gemm128_gpu.py).
-  static const int env_stages = [] { const char* e = getenv("VSTAR_GEMM128_STAGES"); return e ? atoi(e) : 0; }();
-  const int force = p.stages_force ? p.stages_force : env_stages;
-  const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  // 6 = loader-wave ring on the 128 x 64 tile: grids that fill less than HALF the CUs (CLIP / OWL-ViT out-proj and fc2 at small
-  // batches: 40 - 114 tiles) — twice the workgroups beats the extra A traffic (12 vs 18 us, 27 vs 37 us at M = 577); between half
-  // and all CUs (LLaMA o_proj / down_proj at M = 640: 160 tiles, K up to 11008) the 128 x 128 tile moves fewer bytes and wins
-  // (40 vs 44 us, 104 vs 125 us).  5 = loader-wave ring on the 128 x 128 tile.
-  const int64_t cus = gemm_device_cus();
+  // (ahead of the environment; validated by gemm_plan).  Same K order in all: bit-identical results (tests/test_gemm128_gpu.py).
+  const int force = stages_force ? stages_force : gemm_env().stages;
+  if (force == 2 || force == 5 || force == 6 || force == 7) return force;
+  if (K < 4 * BK) return 2;
+  const int64_t tiles = (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   // 7 = loader-wave ring on the 128 x 256 tile (W is padded to 256 rows by contract).
   // More 128^2 tiles than CUs and a long K (the LLaMA linears of 1 - 3 crops: qkv / gate|up at M = 640, o / down at M = 1280 and
   // 1920): whole rounds of 128 x 256 tiles at 1.05 us per K-tile against whole rounds of two co-resident 128^2 tiles at 1.28 us
   // (profiles/r03_gemm_small_batch.txt: qkv 79 -> 68 us, gate|up 144 -> 126 us at M = 640; o 75 -> 65 us, down 183 -> 171 us at
   // M = 1280).  Short-K shapes (the ViT towers) lose on the wide tile's prologue and direct-store epilogue and keep mode 2.
-  const int64_t tiles7 = (int64_t)((p.M + BM - 1) / BM) * ((p.N + 255) / 256);
-  const bool wide = p.K >= 2048 && tiles > cus &&
-                    1.05 * (double)((tiles7 + cus - 1) / cus) <= 1.28 * (double)((tiles + 2 * cus - 1) / (2 * cus));
-  const int mode = force == 2 || force == 5 || force == 6 || force == 7 ? force
-                   : (p.K < 4 * BK ? 2 : (wide ? 7 : (tiles > cus ? 2 : (2 * tiles <= cus ? 6 : 5))));
-  if (mode == 7) return launch_stages<EPI, OUT_F32, 5, 4>(p, s);
-  if (mode == 6) return launch_stages<EPI, OUT_F32, 5, 1>(p, s);
-  if (mode == 5) return launch_stages<EPI, OUT_F32, 5, 2>(p, s);
-  return launch_stages<EPI, OUT_F32, 2, 2>(p, s);
+  const int64_t tiles7 = (int64_t)((M + BM - 1) / BM) * ((N + 255) / 256);
+  if (K >= 2048 && tiles > cus && 1.05 * (double)((tiles7 + cus - 1) / cus) <= 1.28 * (double)((tiles + 2 * cus - 1) / (2 * cus))) return 7;
+  if (tiles > cus) return 2;
+  // 6 = loader-wave ring on the 128 x 64 tile: grids that fill less than HALF the CUs (CLIP / OWL-ViT out-proj and fc2 at small
+  // batches: 40 - 114 tiles) — twice the workgroups beats the extra A traffic (12 vs 18 us, 27 vs 37 us at M = 577); between half
+  // and all CUs (LLaMA o_proj / down_proj at M = 640: 160 tiles, K up to 11008) the 128 x 128 tile moves fewer bytes and wins
+  // (40 vs 44 us, 104 vs 125 us).  5 = loader-wave ring on the 128 x 128 tile.
+  return 2 * tiles <= cus ? 6 : 5;
 }
 
 }  // namespace
 
-bool gemm256_eligible(const GemmParams& p);
 hipError_t gemm256_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s);
 bool gemm4w_eligible(const GemmParams& p, int epilogue, bool out_f32);      // gemm4w.hip: the 4-wave / AGPR 256^2 kernel
 hipError_t gemm4w_lp(const GemmParams& p, int epilogue, hipStream_t s);
 
-static thread_local int t_last_tile = 0;
-int gemm_last_tile() { return t_last_tile; }
-
 int gemm_device_cus() {
-  if (t_plan_only && t_plan_cus > 0) return t_plan_cus;
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -368,53 +378,49 @@ int gemm_device_cus() {
   return n_cu;
 }
 
-hipError_t gemm_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
-  t_last_tile = 0;
-  t_last_mode = 0;
-  if (!t_plan_only) t_launched_mode = 0;
-  if (p.M <= 0 || p.N <= 0) return hipSuccess;
-  if (p.K % BK != 0 || p.K <= 0 || p.norm_w) return hipErrorInvalidValue;   // fused RMSNorm: skinny kernel only
-  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || (p.lda % 8)) return hipErrorInvalidValue;
-  static const int env_force = [] { const char* e = getenv("VSTAR_GEMM_TILE"); return e ? atoi(e) : 0; }();
+GemmPlan gemm_plan(const GemmParams& p, int epilogue, bool out_f32, int cus) {
+  const GemmPlan refused{hipErrorInvalidValue, 0, 0, 0, 0};
+  if (p.M <= 0 || p.N <= 0) return GemmPlan{};
+  if (p.K % BK != 0 || p.K <= 0 || p.norm_w) return refused;   // fused RMSNorm: skinny kernel only
+  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || (p.lda % 8)) return refused;
   // a per-call variant of the 128-row family (stages_force) is a request for that family: it acts as tile_force = 128 (which also
   // keeps the ragged-round split out), and it is refused — never re-routed — next to anything only the 256^2 kernels do
   if (p.stages_force != 0) {
-    if (p.stages_force != 2 && p.stages_force != 5 && p.stages_force != 6 && p.stages_force != 7) return hipErrorInvalidValue;
-    if ((p.tile_force != 0 && p.tile_force != 128) || p.rope_cs || p.a_scale || p.a_mx || p.c_mx) return hipErrorInvalidValue;
+    if (p.stages_force != 2 && p.stages_force != 5 && p.stages_force != 6 && p.stages_force != 7) return refused;
+    if ((p.tile_force != 0 && p.tile_force != 128) || p.rope_cs || p.a_scale || p.a_mx || p.c_mx) return refused;
   }
-  const int force = p.stages_force ? 128 : (p.tile_force ? p.tile_force : env_force);
-  if (force != 0 && force != 128 && force != 256 && force != GEMM_TILE_4W) return hipErrorInvalidValue;
+  const GemmEnv& env = gemm_env();
+  const int force = p.stages_force ? 128 : (p.tile_force ? p.tile_force : env.tile);
+  if (force != 0 && force != 128 && force != 256 && force != GEMM_TILE_4W) return refused;
   if (p.a_mx || p.c_mx) {      // block-scaled W8A8 (mx.hpp) exists in the 4-wave kernel only: callers check gemm_mx_supported
-    if (out_f32 || (force != 0 && force != GEMM_TILE_4W) || !gemm4w_eligible(p, epilogue, out_f32)) return hipErrorInvalidValue;
-    t_last_tile = GEMM_TILE_4W;
-    return gemm4w_lp(p, epilogue, s);
+    if (out_f32 || (force != 0 && force != GEMM_TILE_4W) || !gemm4w_eligible(p, epilogue, out_f32)) return refused;
+    return GemmPlan{hipSuccess, GEMM_TILE_4W, 0, 0, 0};
   }
   const bool elig = gemm256_eligible(p);
-  if (p.tile_force == 256 && !elig) return hipErrorInvalidValue;   // an explicit per-call request must not be silently re-routed
+  if (p.tile_force == 256 && !elig) return refused;   // an explicit per-call request must not be silently re-routed
   // The 4-wave / AGPR kernel (gemm4w.hip) takes the launches made of interior 256^2 tiles with the in-register epilogue — WHERE the
   // dispatcher would run the 256^2 kernel at all (below: under-filled grids still go to the 128^2 family, ragged rounds are still
   // split).  Same k order and epilogue arithmetic as gemm256: bit-identical (tests/test_ops_gpu.py::test_gemm4w_equals_gemm256).
   // tile_force = 256 keeps the 8-wave kernel (A/B, tests), GEMM_TILE_4W demands this one; VSTAR_GEMM4W=0/1 sets the default.
-  static const int env4w = [] { const char* e = getenv("VSTAR_GEMM4W"); return e ? atoi(e) : GEMM4W_DEFAULT; }();
   if (force == GEMM_TILE_4W) {
-    if (!(elig && gemm4w_eligible(p, epilogue, out_f32))) return hipErrorInvalidValue;
-    t_last_tile = GEMM_TILE_4W;
-    return gemm4w_lp(p, epilogue, s);
+    if (!(elig && gemm4w_eligible(p, epilogue, out_f32))) return refused;
+    return GemmPlan{hipSuccess, GEMM_TILE_4W, 0, 0, 0};
   }
-  auto big = [&](const GemmParams& q) -> hipError_t {       // the 256^2 launch of this call (whole, or the leading part of a split)
-    if (force == 0 && env4w != 0 && gemm4w_eligible(q, epilogue, out_f32)) {
-      t_last_tile = GEMM_TILE_4W;
-      return gemm4w_lp(q, epilogue, s);
-    }
-    t_last_tile = 256;
-    return gemm256_lp(q, epilogue, out_f32, s);
+  const bool known_epi = epilogue >= VSTAR_EPI_NONE && epilogue <= VSTAR_EPI_SILU_MUL;
+  // the 256^2 kernel of an M-row launch (whole, or the leading part of a split); 0: gemm256 has no such instantiation (W8A8: the two
+  // epilogues the LLaMA linears use, 16-bit output)
+  auto big = [&](int M) -> int {
+    GemmParams q = p;
+    q.M = M;
+    if (force == 0 && env.use4w != 0 && gemm4w_eligible(q, epilogue, out_f32)) return GEMM_TILE_4W;
+    if (!known_epi || (p.a_scale && (out_f32 || (epilogue != VSTAR_EPI_NONE && epilogue != VSTAR_EPI_SILU_MUL)))) return 0;
+    return 256;
   };
   if (force != 128 && elig) {   // W is padded to 256 rows
     // Under-filled grids (small batches: e.g. o_proj at 1280 rows = 80 tiles of 256^2 on 256 CUs): the 128^2 kernel has four
     // times the tiles; one of its tiles takes ~0.36 of a 256^2 tile (1/4 of the work at ~0.7 of the efficiency), so compare
     // whole rounds over the CUs.  Both kernels accumulate K in the same order: results are bit-identical either way
     // (tests/test_ops_gpu.py::test_gemm128_equals_gemm256).
-    const int64_t cus = gemm_device_cus();
     const int64_t t256 = (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256), t128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
     const bool prefer128 = force != 256 && !p.rope_cs && !p.a_scale && t256 < cus &&
                            0.36 * (double)((t128 + cus - 1) / cus) < (double)((t256 + cus - 1) / cus);
@@ -427,47 +433,52 @@ hipError_t gemm_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t 
       // offset) and without fused RoPE / W8A8 (row-indexed side inputs).
       const int64_t rt = (p.M + 255) / 256, ct = (p.N + 255) / 256;
       const int64_t full = t256 / cus, rem = t256 - full * cus;
-      static const bool env_split = [] { const char* e = getenv("VSTAR_GEMM_SPLIT"); return !e || atoi(e) != 0; }();   // A/B runs
-      const bool split_ok = env_split && force == 0 && p.a_group <= 0 && p.c_group <= 0 && !p.rope_cs && !p.a_scale && !p.debug_flags;
+      const bool split_ok = env.split && force == 0 && p.a_group <= 0 && p.c_group <= 0 && !p.rope_cs && !p.a_scale && !p.debug_flags;
       if (split_ok && full >= 1 && rem > 0) {
         const int64_t rt1 = full * cus / ct;                       // leading row tiles: at most `full` rounds of 256^2 tiles
         const int64_t M1 = rt1 * 256, M2 = p.M - M1;
         const int64_t t128b = ((M2 + 127) / 128) * ((p.N + 127) / 128);
         if (rt1 >= 4 && rt1 < rt && M2 > 0 && t128b <= cus) {      // ONE round of 128^2 tiles (measured: two rounds no longer pay)
-          GemmParams a = p, b = p;
-          a.M = (int)M1;
-          b.M = (int)M2;
-          b.A = p.A + M1 * p.lda;
-          b.C = out_f32 ? (void*)((float*)p.C + M1 * p.ldc) : (void*)((lp_t*)p.C + M1 * p.ldc);
-          if (p.res) b.res = p.res + M1 * p.ldr;
-          if (p.row_scale) b.row_scale = p.row_scale + M1;
-          if (p.sumsq_out) b.sumsq_out = p.sumsq_out + M1 * p.sumsq_ld;      // (stats_sum is an offset inside a partial row: unchanged)
-          b.tile_force = 128;
-          hipError_t e = big(a);
-          if (e != hipSuccess) return e;
-          e = gemm_lp(b, epilogue, out_f32, s);
-          t_last_tile = 256 + 128;                                 // observable: split launch
-          return e;
+          const int lead = big((int)M1);
+          if (lead == 0) return refused;
+          // the trailing rows are a 128-family call of their own: tile 384 is the observable of a split launch
+          return GemmPlan{hipSuccess, 256 + 128, gemm128_variant((int)M2, p.N, p.K, p.stages_force, cus), (int)M1, lead};
         }
       }
-      return big(p);
+      const int tile = big(p.M);
+      return tile ? GemmPlan{hipSuccess, tile, 0, 0, 0} : refused;
     }
   }
-  if (p.rope_cs || p.a_scale) return hipErrorInvalidValue;   // fused RoPE / W8A8 exist only in the 256^2 kernel: callers check gemm256_eligible
-  t_last_tile = 128;
-#define GEMM_CASE(E)                                                   \
-  case E:                                                              \
-    return out_f32 ? launch<E, true>(p, s) : launch<E, false>(p, s);
-  switch (epilogue) {
-    GEMM_CASE(VSTAR_EPI_NONE)
-    GEMM_CASE(VSTAR_EPI_QUICK_GELU)
-    GEMM_CASE(VSTAR_EPI_GELU)
-    GEMM_CASE(VSTAR_EPI_RELU)
-    GEMM_CASE(VSTAR_EPI_SILU_MUL)
+  if (p.rope_cs || p.a_scale || !known_epi) return refused;   // fused RoPE / W8A8 exist only in the 256^2 kernel: callers check gemm256_eligible
+  return GemmPlan{hipSuccess, 128, gemm128_variant(p.M, p.N, p.K, p.stages_force, cus), 0, 0};
+}
+
+static thread_local GemmPlan t_last{};
+int gemm_last_tile() { return t_last.tile; }
+int gemm_launched_mode() { return t_last.mode; }
+
+hipError_t gemm_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
+  const GemmPlan pl = gemm_plan(p, epilogue, out_f32, gemm_device_cus());
+  t_last = pl.status == hipSuccess ? pl : GemmPlan{};
+  if (pl.status != hipSuccess) return pl.status;
+  switch (pl.tile) {
+    case 0: return hipSuccess;
+    case GEMM_TILE_4W: return gemm4w_lp(p, epilogue, s);
+    case 256: return gemm256_lp(p, epilogue, out_f32, s);
+    case 128: return launch128(p, epilogue, out_f32, pl.mode, s);
   }
-#undef GEMM_CASE
-  t_last_tile = 0;
-  return hipErrorInvalidValue;
+  // split: the leading rows on a 256^2 kernel, then the trailing rows (addressed by pointer offset) on the 128-row family
+  const int64_t M1 = pl.split_rows;
+  GemmParams a = p, b = p;
+  a.M = (int)M1;
+  b.M = p.M - (int)M1;
+  b.A = p.A + M1 * p.lda;
+  b.C = out_f32 ? (void*)((float*)p.C + M1 * p.ldc) : (void*)((lp_t*)p.C + M1 * p.ldc);
+  if (p.res) b.res = p.res + M1 * p.ldr;
+  if (p.row_scale) b.row_scale = p.row_scale + M1;
+  if (p.sumsq_out) b.sumsq_out = p.sumsq_out + M1 * p.sumsq_ld;      // (stats_sum is an offset inside a partial row: unchanged)
+  const hipError_t e = pl.lead == GEMM_TILE_4W ? gemm4w_lp(a, epilogue, s) : gemm256_lp(a, epilogue, out_f32, s);
+  return e != hipSuccess ? e : launch128(b, epilogue, out_f32, pl.mode, s);
 }
 
 }  // namespace VS_NS

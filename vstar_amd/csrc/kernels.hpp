@@ -83,7 +83,7 @@ struct GemmParams {
   // is not gemm256_eligible).  Process-wide default for 0 calls: environment VSTAR_GEMM_TILE (A/B runs).
   int tile_force;
   // variant of the 128-row family: 0 = the dispatcher decides (shape, CU count, process default VSTAR_GEMM128_STAGES), 2 / 5 / 6 / 7
-  // = that variant for THIS call (gemm_last_mode() values; op-level tests).  Non-zero implies tile_force = 128 (no 256^2 kernel, no
+  // = that variant for THIS call (GemmPlan::mode values; op-level tests).  Non-zero implies tile_force = 128 (no 256^2 kernel, no
   // ragged-round split); any other value, or a request next to tile_force 256 / GEMM_TILE_4W, rope_cs, a_scale, a_mx or c_mx, fails
   // with hipErrorInvalidValue — never re-routed
   int stages_force;
@@ -108,20 +108,19 @@ constexpr int GEMM_TILE_4W = 2564;
 #ifndef GEMM4W_DEFAULT
 #define GEMM4W_DEFAULT 1
 #endif
-// which kernel the last gemm_lp call of THIS thread launched: 128, 256, or 0 when nothing was launched (observability for the
-// op-level tests: a dispatcher change must not silently move a test onto the other kernel)
-int gemm_last_tile();
 // compute units of the current device, rounded down to a multiple of 8 (>= 8); cached per process
 int gemm_device_cus();
-// Dispatcher dry run (vstar_op_gemm_plan: host-only tests of the kernel choice).  While `on`, gemm_lp takes every decision as
-// usual — with `cus` compute units instead of the device's — but launches nothing; gemm_last_tile() / gemm_last_mode() then
-// tell what it would have launched.  Thread-local, like gemm_last_tile().
-void gemm_set_plan(bool on, int cus);
-bool gemm_plan_only();
-// 128-family variant of the last gemm_lp call of this thread: 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 /
-// 128 x 64 / 128 x 256 tile; 0 when the last call did not reach that family
-int gemm_last_mode();
-// the same of the last gemm_lp call of this thread that was no dry run (vstar_op_gemm_last_mode)
+// What gemm_lp does with a call, as a value.  tile: 0 = nothing to launch, 128 = the 128-row family, 256 = the 8-wave 256^2 kernel,
+// GEMM_TILE_4W, 384 = split launch (the leading split_rows rows on the 256^2 kernel `lead` = 256 / GEMM_TILE_4W, the rest on the
+// 128-row family).  mode: the variant of the 128-row part — 2 = double buffer, 5 / 6 / 7 = loader-wave ring on the 128 x 128 /
+// 128 x 64 / 128 x 256 tile — else 0.  status != hipSuccess: gemm_lp refuses the call, everything else is 0.
+struct GemmPlan { hipError_t status; int tile, mode, split_rows, lead; };
+// The dispatcher's decision for a device with `cus` compute units: a pure function of its arguments and of the process-wide
+// environment defaults — no HIP call, no state, no pointer is dereferenced (vstar_op_gemm_plan: host-only tests of the kernel choice).
+GemmPlan gemm_plan(const GemmParams& p, int epilogue, bool out_f32, int cus);
+// tile / mode of the plan the last gemm_lp call of THIS thread executed, 0 / 0 when it refused the call (observability for the
+// op-level tests: a dispatcher change must not silently move a test onto the other kernel)
+int gemm_last_tile();
 int gemm_launched_mode();
 bool gemm256_eligible(const GemmParams& p);   // true: gemm_lp runs the 256^2 kernel (the only one that honours rope_cs)
 
