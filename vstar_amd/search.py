@@ -13,7 +13,7 @@ from __future__ import annotations
 import copy
 import functools
 from queue import PriorityQueue
-from typing import Sequence,  Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -209,11 +209,6 @@ class _NodeScorer:
                 frontier = nxt
         return todo
 
-    def store(self, todo: List[list], res: List, sizes: List[Tuple[int, int]]) -> None:
-        for b, sz, r in zip(todo, sizes, res):
-            self.cache[tuple(b)] = [r, sz, not self.batched]     # [result, (w, h), heatmap already full-res?]
-        self.n_scored += len(todo)
-
     def missing(self, bbox, queue: PriorityQueue) -> Optional[List[list]]:
         """None when `bbox` is cached, else the crops one engine step should score now (`plan`)."""
         if tuple(bbox) in self.cache:
@@ -268,7 +263,9 @@ class _NodeScorer:
             sizes = [(int(b[0] + b[2]) - int(b[0]), int(b[1] + b[3]) - int(b[1])) for b in todo]
         else:
             sizes = [_crop(self.image, b).size for b in todo]
-        self.store(todo, res, sizes)
+        for b, sz, r in zip(todo, sizes, res):
+            self.cache[tuple(b)] = [r, sz, not self.batched]     # [result, (w, h), heatmap already full-res?]
+        self.n_scored += len(todo)
         self.n_batches += 1
 
     def take(self, bbox):
@@ -282,12 +279,6 @@ class _NodeScorer:
             heat = self.vsm.upsample_heatmap(heat, h, w)        # full-resolution heatmap only for COMMITTED nodes
             self.cache[key] = [(boxes, scores, heat), (w, h), True]
         return boxes, scores, heat
-
-    def get(self, bbox, queue: PriorityQueue):
-        todo = self.missing(bbox, queue)
-        if todo is not None:
-            self.accept(todo, self.score(todo))
-        return self.take(bbox)
 
 
 def visual_search(vsm, image, target_object_name, target_bbox, smallest_size, confidence_high=0.5, confidence_low=0.3,
@@ -310,15 +301,24 @@ def visual_search(vsm, image, target_object_name, target_bbox, smallest_size, co
         return done.value
 
 
+# ---------------- what a `_visual_search_steps` generator asks its driver for, and what it is sent back ----------------
+ScoreReq = NamedTuple("ScoreReq", [("scorer", "_NodeScorer"), ("boxes", List[list])])   # -> the engine's detection records for them
+StatsReq = NamedTuple("StatsReq", [("items", List[Tuple])])      # [(low_res, h, w, rects), ...] -> one statistics vector per item
+CueReq = NamedTuple("CueReq", [("bbox", list), ("question", str)])      # -> the free-text answer to the question on that crop
+SegReq = NamedTuple("SegReq", [("bbox", list), ("question", str)])      # -> the crop's 192x192 low-res map for the locate question
+
+
 def _serve_one(vsm, image, req):
     """One request of a `_visual_search_steps` generator, served alone: what the per-sample loop does."""
-    if req[0] == "score":
-        return req[1].score(req[2])
-    if req[0] == "cue":        # free-text VQA on the crop (one KV-cached greedy decode) ...
-        return vsm.inference(copy.deepcopy(_crop(image, req[1])), req[2], mode="vqa")
-    if req[0] == "seg":        # ... and the crop again with the locate prompt for the phrase it gave
-        return vsm.inference_batch([_crop(image, req[1])], req[2], mode="segmentation", upsample=False)[0]
-    return _serve_stats(vsm, req[1])
+    if isinstance(req, ScoreReq):
+        return req.scorer.score(req.boxes)
+    if isinstance(req, StatsReq):
+        return _serve_stats(vsm, req.items)
+    if isinstance(req, CueReq):        # free-text VQA on the crop (one KV-cached greedy decode) ...
+        return vsm.inference(copy.deepcopy(_crop(image, req.bbox)), req.question, mode="vqa")
+    if isinstance(req, SegReq):        # ... and the crop again with the locate prompt for the phrase it gave
+        return vsm.inference_batch([_crop(image, req.bbox)], req.question, mode="segmentation", upsample=False)[0]
+    raise TypeError(f"not a search request: {req!r}")
 
 
 def _serve_stats(vsm, reqs):
@@ -328,16 +328,34 @@ def _serve_stats(vsm, reqs):
     return [vsm.heatmap_stats(m, h, w, r) for m, h, w, r in reqs]
 
 
+def _cue_threshold(threshold, decay, minimum, level):
+    # the heat-map maximum up to which a node of scale `level` takes the contextual-cue branch (visual_search.py:423)
+    return max(minimum, threshold * decay ** (level - 1))
+
+
+def _cue_phrase(answer: str, target_object_name: str, noun_chunker):
+    """The phrase to locate, from the cue answer (visual_search.py:431-439), and the noun chunker that was used."""
+    phrase = answer.split("most likely to appear")[-1].strip()
+    if phrase.endswith("."):
+        phrase = phrase[:-1]
+    phrase = phrase.split(target_object_name)[-1]
+    if noun_chunker is None:
+        from .noun_chunks import get_noun_chunker
+        noun_chunker = get_noun_chunker()     # spaCy if installed, else the rule-based fallback; only when a search needs it
+    noun_chunks = noun_chunker(phrase)
+    return (noun_chunks[0] if len(noun_chunks) == 1 else "region {}".format(phrase)), noun_chunker
+
+
 def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_size, confidence_high=0.5, confidence_low=0.3,
                          target_cue_threshold=6.0, target_cue_threshold_decay=0.7, target_cue_threshold_minimum=3.0,
                          visualize=False, save_path=None, *, batch_size: Optional[int] = None, speculate: bool = True,
                          noun_chunker: Optional[Callable[[str], List[str]]] = None, stats: Optional[dict] = None,
                          gpu_preprocess: bool = True, device_reductions: Optional[bool] = None,
                          _scorer: Optional["_NodeScorer"] = None):
-    """The search as a generator: whenever it needs crops scored it yields ("score", scorer, crops) and is sent the engine's
-    results for them; whenever it needs heat-map statistics (device reductions) it yields ("stats", [(low_res, h, w, rects), ...])
-    and is sent one statistics vector per item; in the contextual-cue branch (device reductions) it yields ("cue", bbox, question)
-    and is sent the free-text answer for that crop, then ("seg", bbox, locate question) and is sent the crop's 192x192 low-res
+    """The search as a generator: whenever it needs crops scored it yields ScoreReq(scorer, crops) and is sent the engine's
+    results for them; whenever it needs heat-map statistics (device reductions) it yields StatsReq([(low_res, h, w, rects), ...])
+    and is sent one statistics vector per item; in the contextual-cue branch (device reductions) it yields CueReq(bbox, question)
+    and is sent the free-text answer for that crop, then SegReq(bbox, locate question) and is sent the crop's 192x192 low-res
     map; its return value is visual_search's.  `visual_search` drives one such generator, `visual_search_many` several in lock
     step.  Everything else — the decision math of visual_search.py:390-516 — is unchanged."""
     if visualize:
@@ -361,7 +379,7 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
         pw, ph = int(bbox[0] + bbox[2]) - int(bbox[0]), int(bbox[1] + bbox[3]) - int(bbox[1])
         todo = scorer.missing(bbox, queue)
         if todo is not None:
-            scorer.accept(todo, (yield "score", scorer, todo))
+            scorer.accept(todo, (yield ScoreReq(scorer, todo)))
         pred_bboxes, pred_logits, target_cue_heatmap = scorer.take(bbox)
         expand = True
         if len(pred_logits) > 0:
@@ -389,7 +407,7 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
             # float32 with numpy's pairwise order; results agree to ~1e-7 relative, so only exact ties could reorder). ----
             basic_sub_patches, _, _ = get_sub_patches(bbox, *split_4subpatches(bbox))
             current_patch_index = len(search_path) - 1
-            threshold = max(target_cue_threshold_minimum, target_cue_threshold * target_cue_threshold_decay ** (level - 1))
+            threshold = _cue_threshold(target_cue_threshold, target_cue_threshold_decay, target_cue_threshold_minimum, level)
             rel = lambda owner: [[sp[0] - owner[0], sp[1] - owner[1], sp[2], sp[3]] for sp in basic_sub_patches]  # noqa: E731
             # this node's statistics and every ancestor's (over THIS node's child rectangles) in one request
             stat_reqs = [(target_cue_heatmap, bbox[3], bbox[2], rel(bbox))]
@@ -398,24 +416,16 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
                 anc = search_path[anc["parent_index"]]
                 tb = anc["bbox"]
                 stat_reqs.append((anc["heat_stats"]["low_res"], tb[3], tb[2], rel(tb)))
-            stat_res = yield "stats", stat_reqs
+            stat_res = yield StatsReq(stat_reqs)
             st, anc_stats = stat_res[0], list(stat_res[1:])
             low = target_cue_heatmap
             if not st[1] > threshold:
                 # contextual-cue branch (visual_search.py:427-443) as two requests, so that a driver of several searches can
                 # decode the cue answers of a round together and score their follow-up crops in one step
-                vqa_results = yield "cue", bbox, CUE_QUESTION.format(target_object_name)
-                phrase = vqa_results.split("most likely to appear")[-1].strip()
-                if phrase.endswith("."):
-                    phrase = phrase[:-1]
-                phrase = phrase.split(target_object_name)[-1]
-                if noun_chunker is None:
-                    from .noun_chunks import get_noun_chunker
-                    noun_chunker = get_noun_chunker()
-                noun_chunks = noun_chunker(phrase)
-                phrase = noun_chunks[0] if len(noun_chunks) == 1 else "region {}".format(phrase)
-                low = yield "seg", bbox, LOCATE_QUESTION.format(phrase)
-                st = (yield "stats", [(low, bbox[3], bbox[2], rel(bbox))])[0]
+                vqa_results = yield CueReq(bbox, CUE_QUESTION.format(target_object_name))
+                phrase, noun_chunker = _cue_phrase(vqa_results, target_object_name, noun_chunker)
+                low = yield SegReq(bbox, LOCATE_QUESTION.format(phrase))
+                st = (yield StatsReq([(low, bbox[3], bbox[2], rel(bbox))]))[0]
                 search_path[current_patch_index]["context_cue"] = vqa_results + "#" + phrase
             current_patch["heat_stats"] = {"low_res": low, "min": st[0], "max": st[1], "sum": st[2]}
 
@@ -473,7 +483,7 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
         elif expand:
             heat = target_cue_heatmap.view(bbox[3], bbox[2], 1)
             score_max = heat.max().item()
-            threshold = max(target_cue_threshold_minimum, target_cue_threshold * target_cue_threshold_decay ** (level - 1))
+            threshold = _cue_threshold(target_cue_threshold, target_cue_threshold_decay, target_cue_threshold_minimum, level)
             current_patch_index = len(search_path) - 1
             if score_max > threshold:
                 final_heatmap = normalize_score(heat)
@@ -481,15 +491,7 @@ def _visual_search_steps(vsm, image, target_object_name, target_bbox, smallest_s
                 # contextual-cue branch (visual_search.py:427-443): free-text VQA -> noun phrase -> segmentation
                 patch = _crop(image, bbox)
                 vqa_results = vsm.inference(copy.deepcopy(patch), CUE_QUESTION.format(target_object_name), mode="vqa")
-                phrase = vqa_results.split("most likely to appear")[-1].strip()
-                if phrase.endswith("."):
-                    phrase = phrase[:-1]
-                phrase = phrase.split(target_object_name)[-1]
-                if noun_chunker is None:
-                    from .noun_chunks import get_noun_chunker
-                    noun_chunker = get_noun_chunker()     # spaCy if installed, else the rule-based fallback
-                noun_chunks = noun_chunker(phrase)
-                phrase = noun_chunks[0] if len(noun_chunks) == 1 else "region {}".format(phrase)
+                phrase, noun_chunker = _cue_phrase(vqa_results, target_object_name, noun_chunker)
                 ctx = vsm.inference(copy.deepcopy(patch), LOCATE_QUESTION.format(phrase), mode="segmentation")
                 final_heatmap = normalize_score(ctx.view(bbox[3], bbox[2], 1))
                 search_path[current_patch_index]["context_cue"] = vqa_results + "#" + phrase
@@ -672,6 +674,284 @@ def _run_loader_upload(vsm, image, slot):
     return image
 
 
+def _image_key(image):
+    return getattr(image, "key", id(image))
+
+
+class _ImageSlots:
+    """Residency of the stream's images: which image (by `key`) lives in which engine slot, how many live searches use the slot, and
+    what the prefetch workers are preparing ahead of the window.  Slots are handed out from 0 upwards and reused last-freed-first."""
+
+    def __init__(self, vsm, samples, n_slots: int, prefetch: int, want_async: bool):
+        self.vsm, self.samples, self.n_slots, self.prefetch = vsm, samples, n_slots, prefetch
+        self.slot_of: Dict[object, int] = {}          # key -> slot
+        self.key_of: Dict[int, object] = {}           # slot -> key
+        self.refs: Dict[int, int] = {}                # slot -> live searches using it
+        self.free = list(range(n_slots - 1, -1, -1))
+        self.loaded: Dict[object, object] = {}        # key -> the PIL image living in that slot
+        self.pending: Dict[object, Tuple] = {}        # key -> (Future of a loader running ahead, reserved slot or None)
+        self.async_up = bool(getattr(vsm, "supports_async_upload", False)) and want_async
+        self.n_async, self.pool = 0, None
+        if prefetch > 0 and (self.async_up or any(callable(smp[0]) for smp in samples)):
+            from concurrent.futures import ThreadPoolExecutor
+            # several workers: decoding a 4K image takes 40 - 100 ms of host time (PIL releases the GIL) and a step of a full window
+            # consumes 4 - 5 new images; with sharded crops every rank decodes every image while its engine steps shrink with the world
+            # size, so the decode rate is what must scale.  The uploads themselves are serialised inside the VSM
+            self.pool = ThreadPoolExecutor(max_workers=4 if self.async_up else 1, thread_name_prefix="vstar-image-prefetch")
+
+    def prefetch_ahead(self, next_sample: int, limit: Optional[int] = None) -> None:
+        """Hands the next samples' images to the workers, in sample order, at most `limit` (default `prefetch`) in flight or waiting."""
+        if self.pool is None:
+            return
+        limit = self.prefetch if limit is None else limit
+        i = next_sample
+        while i < len(self.samples) and len(self.pending) < limit:
+            image = self.samples[i][0]
+            key = _image_key(image)
+            if key not in self.slot_of and key not in self.pending:
+                if self.async_up and self.free:        # load AND upload, into a slot reserved here
+                    sl = self.free.pop()
+                    self.pending[key] = (self.pool.submit(_run_loader_upload, self.vsm, image, sl), sl)
+                    self.n_async += 1
+                elif callable(image):
+                    self.pending[key] = (self.pool.submit(_run_loader, image), None)
+            i += 1
+
+    def in_flight(self, image) -> bool:
+        """A worker is still preparing this image (and it is not resident already)."""
+        key = _image_key(image)
+        return key not in self.slot_of and key in self.pending and not self.pending[key][0].done()
+
+    def acquire(self, image):
+        """(PIL image, slot) for one more live search on `image` (a PIL image or its loader), or None when every slot is in use.
+        A loader runs once per residency; a prefetched upload's reserved slot becomes the image's slot without a second upload."""
+        key = _image_key(image)
+        if key not in self.slot_of:
+            fut, reserved = self.pending.get(key, (None, None))
+            if reserved is None and not self.free:
+                return None
+            self.pending.pop(key, None)
+            self.loaded[key] = fut.result() if fut is not None else image() if callable(image) else image
+            sl = self.slot_of[key] = self.free.pop() if reserved is None else reserved
+            self.key_of[sl], self.refs[sl] = key, 0
+            if reserved is None:                    # (slot 0 without the argument: the pre-slot signature of set_image)
+                self.vsm.set_image(self.loaded[key]) if sl == 0 else self.vsm.set_image(self.loaded[key], sl)
+        sl = self.slot_of[key]
+        self.refs[sl] += 1
+        return self.loaded[key], sl
+
+    def release(self, slot: int) -> None:
+        """One live search of the slot's image has ended; after the last one the slot (and the host copy) can take another image."""
+        self.refs[slot] -= 1
+        if self.refs[slot] == 0:
+            key = self.key_of.pop(slot)
+            del self.slot_of[key]
+            self.loaded.pop(key, None)
+            self.free.append(slot)
+            self._release_on_engine(slot)
+
+    def _release_on_engine(self, slot: int) -> None:
+        rel = getattr(self.vsm, "release_image", None)
+        if rel is not None:
+            rel(slot)
+
+    def close(self) -> None:
+        if self.pool is not None:
+            for f, _ in self.pending.values():
+                f.cancel()
+            self.pool.shutdown(wait=True)
+        # prefetched-but-unstarted images (an exception unwound the driver): their reserved slots hold host copies too (ADVICE r4)
+        for _, reserved in self.pending.values():
+            if reserved is not None:
+                self._release_on_engine(reserved)
+
+
+def _pack_step(entries: Sequence[Tuple[int, list]], cap: int) -> List[List[int]]:
+    """One scoring round cut into engine calls: `entries` = the round's (slot, box) requests in request order; returns, per call, the
+    indices it scores.  Box-major: requests for the same crop (same image slot, same box) are adjacent, crops in order of first
+    appearance, so that a grouping VSM scores that crop's towers once for all its prompts; a call holds `cap` requests, extended so
+    that one crop's requests are never split."""
+    crops: Dict[Tuple, List[int]] = {}
+    for k, (slot, box) in enumerate(entries):
+        crops.setdefault((slot,) + tuple(box), []).append(k)
+    calls: List[List[int]] = []
+    for ks in crops.values():
+        if not calls or len(calls[-1]) >= cap:
+            calls.append([])
+        calls[-1] += ks
+    return calls
+
+
+class _StreamDriver:
+    """The state of one `visual_search_stream` call: the live searches (generators) with their scorers, what each of them waits
+    for — one mailbox per request kind, {search index: request} — the image slots, and the speculation book-keeping."""
+
+    def __init__(self, vsm, samples, results, per_stats, window, policy, prefetch, cue_batch, kw):
+        self.vsm, self.samples, self.results, self.per_stats = vsm, samples, results, per_stats
+        self.world = world = vsm._dist()[0] if hasattr(vsm, "_dist") else 1
+        self.cap = cap = max(int(getattr(getattr(vsm, "cfg", None), "max_batch", 32)), 1) * world
+        if policy is None:
+            policy = SpeculationPolicy(getattr(vsm, "step_ms_table", None), cap=cap, world=world, enabled=kw.get("speculate", True))
+        self.window = max(1, min(window or cap, len(samples)))
+        # visual_search_many: every search plans its own step (the caller's batch_size / speculate); the stream asks for the node
+        # alone and adds the policy's picks itself
+        self.policy, self.own_plans = policy, bool(getattr(policy, "per_search_plan", False))
+        self.plan = (kw.get("batch_size"), kw.get("speculate", True)) if self.own_plans else (1, False)
+        self.slots = _ImageSlots(vsm, samples, int(getattr(vsm, "max_image_slots", 64)), prefetch, bool(kw.get("async_upload", True)))
+        self.kw = {k: v for k, v in kw.items() if k not in ("batch_size", "speculate", "stats", "async_upload")}
+        # One process: a sample whose image is still being prepared by the prefetch thread does not hold up the searches that are
+        # ready — the engine step runs with what is live and the sample joins a later step (start-up of a job: the first window's
+        # images are decoded and uploaded WHILE the first steps run, instead of all of them before the first step).  With crop sharding
+        # every rank must form identical batches, and "is the future done" is a matter of timing: there the refill blocks.
+        self.nonblocking = world == 1 and self.slots.pool is not None
+        self.batch_cues = bool(cue_batch) and hasattr(vsm, "generate_boxes") and hasattr(vsm, "inference_boxes")
+        self.dkw = {"defer_mismatch": True} if getattr(vsm, "supports_deferred_mismatch", False) else {}
+        self.gens, self.scorers = {}, {}              # search -> its generator / its _NodeScorer
+        self.box: Dict[type, Dict[int, tuple]] = {kind: {} for kind in (ScoreReq, StatsReq, CueReq, SegReq)}
+        self.cue_st = dict(cue_requests=0, cue_calls=0, cue_batch_max=0, seg_requests=0, seg_calls=0)
+        self.next_sample = self.engine_steps = 0
+        self.n_spec: Dict[int, int] = {}              # search -> speculative crops scored for it
+        self.pred_hits: Dict[int, float] = {}         # search -> sum of the (calibrated) visit probabilities of those crops
+
+    def start(self, i: int) -> bool:
+        """Makes sample i a live search and runs it up to its first request; False when no image slot is free."""
+        image, name, gt, smallest = self.samples[i]
+        got = self.slots.acquire(image)
+        if got is None:
+            return False
+        image, sl = got
+        if callable(smallest):
+            smallest = smallest(image)
+        sc = self.scorers[i] = _NodeScorer(self.vsm, image, LOCATE_QUESTION.format(name), smallest, *self.plan, gpu_preprocess=True,
+                                           device_reductions=self.kw.get("device_reductions"), upload_image=False, slot=sl)
+        sc.stream = not self.own_plans
+        self.gens[i] = _visual_search_steps(self.vsm, image, name, gt, smallest, _scorer=sc, stats=self.per_stats[i], **self.kw)
+        self.advance(i, first=True)
+        return True
+
+    def finish(self, i: int, value) -> None:
+        self.results[i] = value
+        st, policy = self.per_stats[i], self.policy
+        if hasattr(policy, "observe"):
+            policy.observe(int(st.get("path_visited", 1)))
+        if hasattr(policy, "observe_speculation") and self.n_spec.get(i):
+            wasted = int(st.get("crops_scored", 0)) - int(st.get("path_visited", 0))
+            policy.observe_speculation(self.pred_hits.get(i, 0.0), max(self.n_spec[i] - max(wasted, 0), 0))
+        self.slots.release(self.scorers[i].slot)
+        self.gens.pop(i).close()
+
+    def advance(self, i: int, value=None, first: bool = False) -> None:
+        """The host decisions of search i up to its next request, which goes to the mailbox of its kind."""
+        try:
+            req = next(self.gens[i]) if first else self.gens[i].send(value)
+        except StopIteration as done:
+            return self.finish(i, done.value)
+        if type(req) not in self.box:
+            raise TypeError(f"not a search request: {req!r}")
+        self.box[type(req)][i] = req
+
+    def refill(self) -> None:
+        while self.next_sample < len(self.samples) and len(self.gens) < self.window:
+            if self.nonblocking and self.gens and self.slots.in_flight(self.samples[self.next_sample][0]):
+                break
+            if not self.start(self.next_sample):
+                break                               # every image slot is in use: wait for a search to end
+            self.next_sample += 1
+        self.slots.prefetch_ahead(self.next_sample)
+
+    def serve_round(self, cur: Dict[int, tuple], kind: str) -> List:
+        """The cue questions ("cue") or locate follow-ups ("seg") of a round: one engine call per `cap` requests, or one per request."""
+        vsm, cue_st, ids = self.vsm, self.cue_st, list(cur)
+        cue_st[kind + "_requests"] += len(ids)
+        if not self.batch_cues:
+            cue_st[kind + "_calls"] += len(ids)
+            return [_serve_one(vsm, self.scorers[i].image, cur[i]) for i in ids]
+        out: List = []
+        lim = self.cap if kind == "seg" else len(ids)      # (generate_boxes chunks by itself: 16 sequences per decode)
+        for c0 in range(0, len(ids), lim):
+            part = ids[c0:c0 + lim]
+            boxes, qs = [list(cur[i].bbox) for i in part], [cur[i].question for i in part]
+            sl_part = [self.scorers[i].slot for i in part]
+            if kind == "cue":
+                out += list(vsm.generate_boxes(boxes, qs, sl_part))
+                cue_st["cue_batch_max"] = max(cue_st["cue_batch_max"], len(part))
+            else:
+                # the plain entry, as inference_batch uses in the per-sample loop: its records do not depend on the batch
+                gp = getattr(vsm, "group_prompts", False)
+                if gp:
+                    vsm.group_prompts = False
+                try:
+                    out += list(vsm.inference_boxes(boxes, qs, mode="segmentation", upsample=False, slots=sl_part))
+                finally:
+                    if gp:
+                        vsm.group_prompts = gp
+            cue_st[kind + "_calls"] += 1
+        return out
+
+    def drain(self) -> None:
+        """Everything the live searches ask for between two scoring steps, until nobody asks for any of it."""
+        while True:
+            # heat-map statistics first, then the round's cue questions, then their locate follow-ups
+            kind = next((k for k in (StatsReq, CueReq, SegReq) if self.box[k]), None)
+            if kind is None:
+                return
+            cur, self.box[kind] = self.box[kind], {}
+            if kind is StatsReq:
+                res = iter(_serve_stats(self.vsm, [r for i in cur for r in cur[i].items]))      # one call for the whole round
+                for i in cur:
+                    self.advance(i, [next(res) for _ in cur[i].items])
+            else:
+                for i, r in zip(list(cur), self.serve_round(cur, "cue" if kind is CueReq else "seg")):
+                    self.advance(i, r)
+
+    def step(self) -> None:
+        """One scoring round: the crop(s) every waiting search MUST have, then the policy's picks among their candidates."""
+        reqs, self.box[ScoreReq] = self.box[ScoreReq], {}
+        scorers, policy = self.scorers, self.policy
+        must = [(i, list(b)) for i, r in reqs.items() for b in r.boxes]
+        cands = [] if self.own_plans else [(p, (i, b)) for i in reqs for p, b in scorers[i].candidates(policy)]
+        extra = policy.select(len(must), cands, len(reqs)) if cands else []
+        for (i, _), pv in zip(extra, getattr(policy, "last_selected_p", []) or [0.0] * len(extra)):
+            self.n_spec[i] = self.n_spec.get(i, 0) + 1
+            self.pred_hits[i] = self.pred_hits.get(i, 0.0) + float(pv)
+        flat = must + [(i, list(b)) for i, b in extra]
+        out: List = [None] * len(flat)
+        for part in _pack_step([(scorers[i].slot, b) for i, b in flat], self.cap):
+            sl_part = [scorers[flat[k][0]].slot for k in part]
+            skw = {"slots": sl_part} if any(sl_part) else {}        # (one image in slot 0: the pre-slot call signature)
+            res = self.vsm.inference_boxes([flat[k][1] for k in part], [scorers[flat[k][0]].question for k in part], mode="detection",
+                                           upsample=False, **skw, **self.dkw)
+            for k, r in zip(part, res):
+                out[k] = r
+            self.engine_steps += 1
+        recs = iter(out)
+        per: Dict[int, List] = {i: [next(recs) for _ in r.boxes] for i, r in reqs.items()}
+        spec: Dict[int, Tuple[List, List]] = {}
+        for (i, b), r in zip(flat[len(must):], recs):
+            bs, rs = spec.setdefault(i, ([], []))
+            bs.append(b)
+            rs.append(r)
+        for i, (bs, rs) in spec.items():       # speculative records go straight into the search's cache
+            scorers[i].accept(bs, rs)
+        for i in reqs:                         # in sample order: host decisions of search i, up to its next request
+            self.advance(i, per[i])
+
+    def run(self) -> None:
+        # the whole first window's images go to the workers at once
+        self.slots.prefetch_ahead(0, limit=max(self.slots.prefetch, min(self.window, self.slots.n_slots // 2)))
+        self.refill()
+        self.drain()
+        self.refill()
+        # between two steps every live search waits for crops: `drain` serves every other request, a search's first request is its
+        # root crop, and with no search live `refill` can always start the next sample
+        while self.box[ScoreReq]:
+            self.step()
+            self.drain()
+            self.refill()
+            self.drain()
+        assert not self.gens and self.next_sample >= len(self.samples)
+
+
 def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: Optional[SpeculationPolicy] = None,
                          stats: Optional[dict] = None, prefetch: int = 8, cue_batch: bool = True, **kw):
     """Cross-image lock-step search: `samples` = iterable of (image, target_object_name, target_bbox, smallest_size) — `image` a
@@ -722,293 +1002,29 @@ def visual_search_stream(vsm, samples, *, window: Optional[int] = None, policy: 
             results[i] = visual_search(vsm, image, name, gt, smallest, stats=per_stats[i], **kw)
         _fill_stream_stats(stats, per_stats, 0)
         return results
-    world = vsm._dist()[0] if hasattr(vsm, "_dist") else 1
-    cap = max(int(getattr(getattr(vsm, "cfg", None), "max_batch", 32)), 1) * world
-    if policy is None:
-        policy = SpeculationPolicy(getattr(vsm, "step_ms_table", None), cap=cap, world=world, enabled=kw.get("speculate", True))
-    n_slots = int(getattr(vsm, "max_image_slots", 64))
-    window = max(1, min(window or cap, n))
-    plan_bs, plan_spec = kw.get("batch_size"), kw.get("speculate", True)
-    want_async = bool(kw.get("async_upload", True))
-    kw = {k: v for k, v in kw.items() if k not in ("batch_size", "speculate", "stats", "async_upload")}
-    own_plans = bool(getattr(policy, "per_search_plan", False))      # visual_search_many: every search plans its own step
-
-    slot_of: Dict[int, int] = {}                  # id(image) -> slot
-    slot_refs: Dict[int, int] = {}                # slot -> live searches using it
-    free_slots = list(range(n_slots - 1, -1, -1))
-    gens: Dict[int, object] = {}
-    scorers: Dict[int, _NodeScorer] = {}
-    waiting: Dict[int, List[list]] = {}           # search -> the crop(s) it waits for
-    want_stats: Dict[int, List] = {}
-    want_cue: Dict[int, Tuple] = {}               # search -> (bbox, cue question) of its contextual-cue branch
-    want_seg: Dict[int, Tuple] = {}               # search -> (bbox, locate question for the cue's phrase)
-    batch_cues = bool(cue_batch) and hasattr(vsm, "generate_boxes") and hasattr(vsm, "inference_boxes")
-    cue_st = dict(cue_requests=0, cue_calls=0, cue_batch_max=0, seg_requests=0, seg_calls=0)
-    next_sample = 0
-    engine_steps = 0
-    n_spec: Dict[int, int] = {}                   # search -> speculative crops scored for it
-    pred_hits: Dict[int, float] = {}              # search -> sum of the (calibrated) visit probabilities of those crops
-
-    loaded: Dict[object, object] = {}             # slot key -> the PIL image living in that slot
-    pending: Dict[object, object] = {}            # slot key -> Future of a loader running ahead (prefetch)
-    pool = None
-    async_up = bool(getattr(vsm, "supports_async_upload", False)) and want_async
-    if prefetch > 0 and (async_up or any(callable(smp[0]) for smp in samples)):
-        from concurrent.futures import ThreadPoolExecutor
-        # several workers: decoding a 4K image takes 40 - 100 ms of host time (PIL releases the GIL) and a step of a full window
-        # consumes 4 - 5 new images; with sharded crops every rank decodes every image while its engine steps shrink with the world
-        # size, so the decode rate is what must scale.  The uploads themselves are serialised inside the VSM
-        pool = ThreadPoolExecutor(max_workers=4 if async_up else 1, thread_name_prefix="vstar-image-prefetch")
-    n_async = 0
-
-    def prefetch_ahead(limit=None):
-        # images of the next samples that are not in the window yet, in sample order, at most `limit` (default: `prefetch`) in
-        # flight or waiting.  pending[key] = (future, reserved slot or None)
-        nonlocal n_async
-        if pool is None:
-            return
-        limit = prefetch if limit is None else limit
-        i = next_sample
-        while i < n and len(pending) < limit:
-            image = samples[i][0]
-            key = getattr(image, "key", id(image))
-            if key not in slot_of and key not in pending:
-                if async_up and free_slots:
-                    sl = free_slots.pop()
-                    pending[key] = (pool.submit(_run_loader_upload, vsm, image, sl), sl)
-                    n_async += 1
-                elif callable(image):
-                    pending[key] = (pool.submit(_run_loader, image), None)
-            i += 1
-
-    def start(i):
-        image, name, gt, smallest = samples[i]
-        key = getattr(image, "key", id(image))
-        if key not in slot_of:
-            fut, reserved = pending.get(key, (None, None))
-            if reserved is None and not free_slots:
-                return False
-            if fut is not None:
-                del pending[key]
-                loaded[key] = fut.result()
-            else:
-                loaded[key] = image() if callable(image) else image
-            if reserved is not None:                # loaded AND already on its way to the slot (prefetch thread)
-                slot_of[key] = reserved
-                slot_refs[reserved] = 0
-            else:
-                slot_of[key] = free_slots.pop()
-                slot_refs[slot_of[key]] = 0
-                vsm.set_image(loaded[key]) if slot_of[key] == 0 else vsm.set_image(loaded[key], slot_of[key])
-        image = loaded[key]
-        if callable(smallest):
-            smallest = smallest(image)
-        sl = slot_of[key]
-        slot_refs[sl] += 1
-        if own_plans:
-            sc = _NodeScorer(vsm, image, LOCATE_QUESTION.format(name), smallest, plan_bs, plan_spec, True, kw.get("device_reductions"),
-                             upload_image=False, slot=sl)
-        else:
-            sc = _NodeScorer(vsm, image, LOCATE_QUESTION.format(name), smallest, 1, False, True, kw.get("device_reductions"),
-                             upload_image=False, slot=sl)
-            sc.stream = True
-        scorers[i] = sc
-        gens[i] = _visual_search_steps(vsm, image, name, gt, smallest, _scorer=sc, stats=per_stats[i], **kw)
-        advance(i, first=True)
-        return True
-
-    def finish(i, value):
-        results[i] = value
-        if hasattr(policy, "observe"):
-            policy.observe(int(per_stats[i].get("path_visited", 1)))
-        if hasattr(policy, "observe_speculation") and n_spec.get(i):
-            wasted = int(per_stats[i].get("crops_scored", 0)) - int(per_stats[i].get("path_visited", 0))
-            policy.observe_speculation(pred_hits.get(i, 0.0), max(n_spec[i] - max(wasted, 0), 0))
-        sl = scorers[i].slot
-        slot_refs[sl] -= 1
-        if slot_refs[sl] == 0:                     # last live search of that image: the slot can take another image
-            key = next(k for k, v in slot_of.items() if v == sl)
-            del slot_of[key]
-            loaded.pop(key, None)
-            free_slots.append(sl)
-            rel = getattr(vsm, "release_image", None)
-            if rel is not None:
-                rel(sl)
-        gens.pop(i).close()
-
-    def advance(i, value=None, first=False):
-        try:
-            req = next(gens[i]) if first else gens[i].send(value)
-            if req[0] == "score":
-                waiting[i] = req[2]
-            elif req[0] == "cue":
-                want_cue[i] = (req[1], req[2])
-            elif req[0] == "seg":
-                want_seg[i] = (req[1], req[2])
-            else:
-                want_stats[i] = req[1]
-        except StopIteration as done:
-            finish(i, done.value)
-
-    # One process: a sample whose image is still being prepared by the prefetch thread does not hold up the searches that are
-    # ready — the engine step runs with what is live and the sample joins a later step (start-up of a job: the first window's
-    # images are decoded and uploaded WHILE the first steps run, instead of all of them before the first step).  With crop sharding
-    # every rank must form identical batches, and "is the future done" is a matter of timing: there the refill blocks.
-    nonblocking = world == 1 and pool is not None
-
-    def refill():
-        nonlocal next_sample
-        while next_sample < n and len(gens) < window:
-            if nonblocking and gens:
-                key = getattr(samples[next_sample][0], "key", id(samples[next_sample][0]))
-                if key not in slot_of and key in pending and not pending[key][0].done():
-                    break
-            if not start(next_sample):
-                break                               # every image slot is in use: wait for a search to end
-            next_sample += 1
-        prefetch_ahead()
-
-    def serve_round(cur, kind):
-        # the cue questions ("cue") or locate follow-ups ("seg") of a round: one engine call per `cap` requests, or one per request
-        ids = list(cur)
-        cue_st[kind + "_requests"] += len(ids)
-        if not batch_cues:
-            cue_st[kind + "_calls"] += len(ids)
-            return [_serve_one(vsm, scorers[i].image, (kind,) + tuple(cur[i])) for i in ids]
-        out: List = []
-        lim = cap if kind == "seg" else len(ids)           # (generate_boxes chunks by itself: 16 sequences per decode)
-        for c0 in range(0, len(ids), lim):
-            part = ids[c0:c0 + lim]
-            boxes, qs = [list(cur[i][0]) for i in part], [cur[i][1] for i in part]
-            sl_part = [scorers[i].slot for i in part]
-            if kind == "cue":
-                out += list(vsm.generate_boxes(boxes, qs, sl_part))
-                cue_st["cue_batch_max"] = max(cue_st["cue_batch_max"], len(part))
-            else:
-                # the plain entry, as inference_batch uses in the per-sample loop: its records do not depend on the batch
-                gp = getattr(vsm, "group_prompts", False)
-                if gp:
-                    vsm.group_prompts = False
-                try:
-                    out += list(vsm.inference_boxes(boxes, qs, mode="segmentation", upsample=False, slots=sl_part))
-                finally:
-                    if gp:
-                        vsm.group_prompts = gp
-            cue_st[kind + "_calls"] += 1
-        return out
-
-    def drain_stats():
-        # everything the live searches ask for between two scoring steps: heat-map statistics, then the round's cue questions, then
-        # their locate follow-ups, until nobody asks for any of them
-        nonlocal want_stats, want_cue, want_seg
-        while want_stats or want_cue or want_seg:
-            if want_stats:
-                cur, want_stats = want_stats, {}
-                flat_reqs = [r for i in cur for r in cur[i]]
-                res = _serve_stats(vsm, flat_reqs)
-                k = 0
-                for i in cur:
-                    n_i = len(cur[i])
-                    advance(i, res[k:k + n_i])
-                    k += n_i
-            elif want_cue:
-                cur, want_cue = want_cue, {}
-                for i, r in zip(list(cur), serve_round(cur, "cue")):
-                    advance(i, r)
-            else:
-                cur, want_seg = want_seg, {}
-                for i, r in zip(list(cur), serve_round(cur, "seg")):
-                    advance(i, r)
-
+    driver = _StreamDriver(vsm, samples, results, per_stats, window, policy, prefetch, cue_batch, kw)
     grouping = getattr(vsm, "group_prompts", False)
     if grouping:
         # a (crop, prompt) record must not depend on its batch companions.  Crops are batched by their NUMBER of prompts
         # (VSM._score_boxes_grouped), so a window of searches for different objects on different images is still one engine call
         vsm.group_prompts = "always"
     calls0 = int(getattr(vsm, "timers", {}).get("engine_calls", 0)) if isinstance(getattr(vsm, "timers", None), dict) else None
-    dkw = {"defer_mismatch": True} if getattr(vsm, "supports_deferred_mismatch", False) else {}
     try:
-        prefetch_ahead(limit=max(prefetch, min(window, n_slots // 2)))      # the whole first window's images go to the workers at once
-        refill()
-        drain_stats()
-        refill()
-        while waiting or gens:
-            if not waiting:                         # every live search ended inside drain_stats / refill
-                refill()
-                drain_stats()
-                if not waiting and not want_stats and next_sample >= n:
-                    break
-                continue
-            reqs, waiting = waiting, {}
-            # MUST crops first, then the policy's picks among every live search's candidates
-            must = [(i, j, b) for i, boxes in reqs.items() for j, b in enumerate(boxes)]
-            cands = [] if own_plans else [(p, (i, b)) for i in reqs for p, b in scorers[i].candidates(policy)]
-            extra = policy.select(len(must), cands, len(reqs)) if cands else []
-            for (i, _), pv in zip(extra, getattr(policy, "last_selected_p", []) or [0.0] * len(extra)):
-                n_spec[i] = n_spec.get(i, 0) + 1
-                pred_hits[i] = pred_hits.get(i, 0.0) + float(pv)
-            flat = [(i, j, list(b)) for i, j, b in must] + [(i, None, list(b)) for i, b in extra]
-            # box-major order inside the step: requests for the same crop (same image slot, same box) next to each other so that
-            # a grouping VSM scores that crop's towers once for all its prompts
-            order: Dict[Tuple, List[int]] = {}
-            for k, (i, _, b) in enumerate(flat):
-                order.setdefault((scorers[i].slot,) + tuple(b), []).append(k)
-            seq = [k for ks in order.values() for k in ks]
-            out: List = [None] * len(flat)
-            c0 = 0
-            while c0 < len(seq):
-                c1 = min(c0 + cap, len(seq))
-                while c1 < len(seq) and flat[seq[c1]][2] == flat[seq[c1 - 1]][2] and \
-                        scorers[flat[seq[c1]][0]].slot == scorers[flat[seq[c1 - 1]][0]].slot:      # keep one crop's requests together
-                    c1 += 1
-                part = seq[c0:c1]
-                sl_part = [scorers[flat[k][0]].slot for k in part]
-                skw = {"slots": sl_part} if any(sl_part) else {}        # (one image in slot 0: the pre-slot call signature)
-                res = vsm.inference_boxes([flat[k][2] for k in part], [scorers[flat[k][0]].question for k in part], mode="detection",
-                                          upsample=False, **skw, **dkw)
-                for k, r in zip(part, res):
-                    out[k] = r
-                engine_steps += 1
-                c0 = c1
-            per: Dict[int, List] = {i: [None] * len(boxes) for i, boxes in reqs.items()}
-            spec: Dict[int, Tuple[List, List]] = {}
-            for (i, j, b), r in zip(flat, out):
-                if j is None:
-                    spec.setdefault(i, ([], []))
-                    spec[i][0].append(b)
-                    spec[i][1].append(r)
-                else:
-                    per[i][j] = r
-            for i, (bs, rs) in spec.items():       # speculative records go straight into the search's cache
-                scorers[i].accept(bs, rs)
-            for i in reqs:                         # in sample order: host decisions of search i, up to its next request
-                advance(i, per[i])
-            drain_stats()
-            refill()
-            drain_stats()
+        driver.run()
     finally:
         if grouping:
             vsm.group_prompts = grouping
-        for g in list(gens.values()):
+        for g in list(driver.gens.values()):
             g.close()
-        if pool is not None:
-            for f, _ in pending.values():
-                f.cancel()
-            pool.shutdown(wait=True)
-        # prefetched-but-unstarted images (an exception unwound the driver): their reserved slots hold host copies too
-        rel = getattr(vsm, "release_image", None)
-        if rel is not None:
-            for _, reserved in pending.values():
-                if reserved is not None:
-                    rel(reserved)
-    _fill_stream_stats(stats, per_stats, engine_steps)
+        driver.slots.close()
+    _fill_stream_stats(stats, per_stats, driver.engine_steps)
     if stats is not None and calls0 is not None:
         # launches of an engine scoring entry point (a step can take several: batch cap, prompt-count buckets); engine_steps counts
         # the driver's scoring rounds
         stats["engine_calls"] = int(vsm.timers.get("engine_calls", 0)) - calls0
     if stats is not None:
-        stats["async_uploads"] = n_async
-        stats.update(cue_st)
+        stats["async_uploads"] = driver.slots.n_async
+        stats.update(driver.cue_st)
     return results
 
 
