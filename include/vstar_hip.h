@@ -79,7 +79,12 @@ typedef struct vstar_config {
   int32_t max_text_len;       /* L_max: input_ids length incl. the single -200 */
   int32_t llm_w8a8;           /* 1: LLaMA linears run W8A8 on the fp8 MFMA (BASELINE config 5) whenever a call has >= 1024 rows;
                                  per-output-channel weight scales, per-token activation scales, OCP e4m3.  0 (default): bf16 */
-  int32_t reserved[7];
+  int32_t vit_w8a8;           /* 1: the qkv / out_proj / fc1 / fc2 linears of every executed CLIP and OWL-ViT encoder block run W8A8 on the
+                                 fp8 MFMA whenever a call has >= 1024 tower rows (same per-token / per-channel e4m3 scheme; LayerNorm1/2
+                                 emit quantised rows).  0 (default): bf16.  Any other value fails at vstar_create.        Independent of
+                                 llm_w8a8.  VSTAR_W8A8_VIT in the environment at vstar_create: 1 turns it on for engines with
+                                 llm_w8a8 = 1, 0 turns it off everywhere.  (Took reserved[0]: the struct's size is unchanged.) */
+  int32_t reserved[6];
 } vstar_config;
 
 typedef struct vstar_engine vstar_handle;
@@ -354,7 +359,8 @@ int vstar_op_gemm_plan(int M, int N, int K, int epilogue, int has_residual, int 
 /* W8A8 GEMM (BASELINE config 5: fp8 weights on the CDNA4 fp8 MFMA), op level, all pointers DEVICE pointers: quantises the
  * rows of A [M,K] (per token) and of W [ceil(N/256)*256, K] (per output channel) to OCP fp8 e4m3 with scale = absmax/448,
  * then C[M,N] = epilogue((A_q . W_q^T) * a_scale[m] * w_scale[n] + bias) (+ residual) with fp32 accumulation on
- * v_mfma_scale_f32_16x16x128_f8f6f4.  Requires M >= 1024, N >= 256, K % 256 == 0; epilogue NONE or SILU_MUL.
+ * v_mfma_scale_f32_16x16x128_f8f6f4.  Requires M >= 1024, N >= 256, K % 256 == 0; epilogue NONE, SILU_MUL or QUICK_GELU (the ViT towers' fc1: the
+ * bf16 kernels' quick-GELU epilogue and rounding points, fed the dequantised accumulators).
  * iters > 0: the GEMM alone is repeated `iters` times between HIP events and *gemm_ms receives the mean (benchmarks). */
 int vstar_op_gemm_fp8(void* stream, const uint16_t* dev_A, const uint16_t* dev_W, const uint16_t* dev_bias,
                       const uint16_t* dev_residual, uint16_t* dev_C, int M, int N, int K, int epilogue, int iters, float* gemm_ms);
@@ -390,6 +396,9 @@ int vstar_op_gemm_fp8_mxout(void* stream, const uint16_t* dev_A, const uint16_t*
                             int K, int iters, float* gemm_ms);
 int vstar_op_attention_mx(void* stream, const uint16_t* dev_qkv, uint8_t* dev_out8, uint8_t* dev_scales, int B, int S, int H);
 int vstar_w8a8_mx_active(vstar_handle* h);
+/* vit_w8a8: which vision towers ran their block linears on the fp8 MFMA in the last scoring step — bit 0 = CLIP, bit 1 = OWL-ViT
+ * (a tower call with fewer than 1024 rows, or widths that are no multiple of 256, runs the bf16 path: its bit is clear). */
+int vstar_w8a8_vit_active(vstar_handle* h);
 /* ---- Doors of the prefill-side GemmParams / attn_* features no other door reaches (tests/test_prefill_ops_gpu.py): row maps,
  * the RoPE fused into the GEMM epilogue, the LayerNorm sums, grouped attention.  Each makes ONE launch and synchronises.  Every
  * buffer comes with its extent in ROWS, and a door refuses (VSTAR_ERR_INVALID, message in vstar_last_error(NULL), nothing
@@ -502,6 +511,9 @@ int vstar_op_quantize_rows_fp8(void* stream, const uint16_t* dev_x, int64_t ldx,
 /* The same bytes and scales as vstar_op_rmsnorm followed by vstar_op_quantize_rows_fp8 (dense, ld = cols); cols <= 4096. */
 int vstar_op_rmsnorm_quant_fp8(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, uint8_t* dev_q, float* dev_scale, int rows,
                                int cols, float eps);
+/* The same bytes and scales as vstar_op_layernorm followed by vstar_op_quantize_rows_fp8 (dense, ld = cols); cols % 8 == 0, cols <= 4096. */
+int vstar_op_layernorm_quant_fp8(void* stream, const uint16_t* dev_x, const uint16_t* dev_gamma, const uint16_t* dev_beta, uint8_t* dev_q,
+                                 float* dev_scale, int rows, int cols, float eps);
 /* SAM-head attention: q [B, Nq, H * D], k / v [B, Nk, H * D] -> out [B, Nq, H * D], scale 1 / sqrt(D); D in {16, 32}, Nk <= 2560. */
 int vstar_op_small_attention(void* stream, const uint16_t* dev_q, const uint16_t* dev_k, const uint16_t* dev_v, uint16_t* dev_out, int B,
                              int Nq, int Nk, int H, int D);

@@ -22,8 +22,8 @@ import sys
 import tempfile
 
 # {NONE, QUICK_GELU, RELU, SILU_MUL} x {plain, prefetch} x {whole tiles, ragged last row tile} (+ eight W8A8 and four block-scaled W8A8
-# kernels in the bf16 build)
-KERNELS = {"gemm4w.o": 22, "f16_gemm4w.o": 12}
+# kernels in the bf16 build); gemm4w_vit8.o: the W8A8 quick-GELU kernels (ViT fc1) x {plain, prefetch, ragged}
+KERNELS = {"gemm4w.o": 22, "f16_gemm4w.o": 12, "gemm4w_vit8.o": 3}
 NAMES_AGPR = re.compile(r"\ba(\d+\b|\[)")
 
 

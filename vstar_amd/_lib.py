@@ -22,7 +22,8 @@ EXPORTS = [
     "vstar_op_gemm_last_tile", "vstar_op_gemm_last_mode", "vstar_op_gemm_plan", "vstar_op_gemm_norm", "vstar_op_rms_rstd", "vstar_op_ln_fold", "vstar_upsample_mask_ex", "vstar_vsm_score_grouped",
     "vstar_image_set_slot", "vstar_image_set_slot_async", "vstar_preprocess_crops_slots", "vstar_comm_unique_id", "vstar_comm_init", "vstar_allgather_results",
     "vstar_comm_destroy", "vstar_build_source_hash", "vstar_op_mx_scale_bytes", "vstar_op_mx_scale_offset", "vstar_op_quantize_mx",
-    "vstar_op_gemm_mx", "vstar_op_gemm_fp8_mxout", "vstar_op_attention_mx", "vstar_w8a8_mx_active",
+    "vstar_op_gemm_mx", "vstar_op_gemm_fp8_mxout", "vstar_op_attention_mx", "vstar_w8a8_mx_active", "vstar_w8a8_vit_active",
+    "vstar_op_layernorm_quant_fp8",
     # doors of the small kernels (tests/test_small_ops_gpu.py)
     "vstar_op_owl_class_logits", "vstar_op_owl_box_finish", "vstar_op_upsample2x_im2col3x3", "vstar_op_hyper_mask",
     "vstar_op_im2col_patch", "vstar_op_vit_assemble_tokens", "vstar_op_llm_embed_text", "vstar_op_add_bcast",
@@ -279,6 +280,8 @@ def load() -> ctypes.CDLL:
     lib.vstar_op_attention_mx_grouped.restype = c_int
     lib.vstar_w8a8_mx_active.argtypes = [c_void_p]
     lib.vstar_w8a8_mx_active.restype = c_int
+    lib.vstar_w8a8_vit_active.argtypes = [c_void_p]
+    lib.vstar_w8a8_vit_active.restype = c_int
     lib.vstar_op_layernorm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]
     lib.vstar_op_layernorm.restype = c_int
     lib.vstar_op_rmsnorm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]
@@ -299,7 +302,8 @@ def load() -> ctypes.CDLL:
         "gather_rows": [V, V, V, I, I], "argmax_rows": [V, I, I, I, V, I],
         "layernorm_ex": [V, V, V, V, I, I, F, V, I], "rmsnorm_ex": [V, V, V, I, I, F, V], "ln_rstd": [V, V, I, I, I, F, V],
         "scale_cols": [V, V, L, I], "fill": [V, L, F], "quantize_rows_fp8": [V, L, V, L, V, I, I],
-        "rmsnorm_quant_fp8": [V, V, V, V, I, I, F], "small_attention": [V, V, V, V, I, I, I, I, I],
+        "rmsnorm_quant_fp8": [V, V, V, V, I, I, F], "layernorm_quant_fp8": [V, V, V, V, V, I, I, F],
+        "small_attention": [V, V, V, V, I, I, I, I, I],
     }.items():
         fn = getattr(lib, "vstar_op_" + name)
         fn.argtypes = [c_void_p] + args

@@ -45,7 +45,8 @@ class CVstarConfig(ctypes.Structure):
         ("max_batch", ctypes.c_int32),
         ("max_text_len", ctypes.c_int32),
         ("llm_w8a8", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 7),
+        ("vit_w8a8", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 6),
     ]
 
 
@@ -75,6 +76,9 @@ class VSMConfig:
     max_batch: int = 32
     max_text_len: int = 192
     llm_w8a8: int = 0               # 1: LLaMA linears on the fp8 MFMA (BASELINE config 5); default bf16
+    # 1: the block linears (qkv / out_proj / fc1 / fc2) of the CLIP and OWL-ViT towers on the fp8 MFMA for tower calls of >= 1024 rows
+    # (DESIGN.md §9); default bf16; independent of llm_w8a8.  VSTAR_W8A8_VIT=1 in the environment turns it on for llm_w8a8 = 1 engines.
+    vit_w8a8: int = 0
 
     # ---- derived ----
     @property

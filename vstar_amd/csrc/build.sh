@@ -24,9 +24,12 @@ stale() {  # stale <object> <source>
 # built once)
 # gemm4w keeps its 256 accumulators in AGPRs BEHIND the compiler's back (they are clobbers of the K-loop asm statement, read back by
 # v_accvgpr_read statements in the epilogue): the compiler must never use AGPRs as VGPR spill space there — it did (a2..a9, round 6)
-extra() { [ "$1" = gemm4w ] && echo "-mllvm -amdgpu-spill-vgpr-to-agpr=0"; }
-for f in gemm gemm256 gemm4w norm attention elementwise decode skinny quant heads preprocess engine comm sample beam score spec edit logprob; do
-  if wanted $f && stale build/$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!); fi
+extra() { [[ "$1" == gemm4w* ]] && echo "-mllvm -amdgpu-spill-vgpr-to-agpr=0"; }
+# (gemm4w_vit8.hip is gemm4w.hip compiled again for the W8A8 quick-GELU kernels: stale with either file)
+for f in gemm gemm256 gemm4w gemm4w_vit8 norm attention elementwise decode skinny quant heads preprocess engine comm sample beam score spec edit logprob; do
+  if wanted $f && { stale build/$f.o $f.hip || { [ $f = gemm4w_vit8 ] && [ gemm4w.hip -nt build/$f.o ]; }; }; then
+    $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!)
+  fi
 done
 # fp16 instantiation (-DVSTAR_LP_F16): the dtype-generic kernel files + the VQA-LLM engine
 for f in gemm gemm256 gemm4w norm attention elementwise decode skinny vqa_engine; do
@@ -49,9 +52,9 @@ fail=0
 for p in "${pids[@]}"; do wait $p || fail=1; done
 [ $fail -eq 0 ] || { echo "build failed"; exit 1; }
 [ -z "$ONLY" ] || exit 0
-# the AGPR proof on the two objects that are about to be linked (tools/check_gemm4w_agpr.py: disassembles, compiles nothing): a
+# the AGPR proof on the three objects that are about to be linked (tools/check_gemm4w_agpr.py: disassembles, compiles nothing): a
 # compiler that parks a value in an unread accumulator fails the build here, not a test somewhere else.  Exit code 2: no llvm-objdump.
-agpr=$(python3 ../../tools/check_gemm4w_agpr.py build/gemm4w.o build/f16_gemm4w.o) && rc=0 || rc=$?
+agpr=$(python3 ../../tools/check_gemm4w_agpr.py build/gemm4w.o build/f16_gemm4w.o build/gemm4w_vit8.o) && rc=0 || rc=$?
 case $rc in
   0) echo "gemm4w AGPR check: $(grep -c '^ok ' <<<"$agpr") kernels ok" ;;
   2) echo "$agpr: check SKIPPED" ;;

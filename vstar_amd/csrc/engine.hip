@@ -1009,6 +1009,7 @@ int vstar_engine::score_body(int B, int L, int n_verify, unsigned flags, int img
   const int P = clip.P, S = L - 1 + P, H = c.llm_hidden;
   HIPCHK(hipMemcpyAsync(d_ids, ids_src, (size_t)B * L * 4, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_rowidx, rowidx_src, n_rowidx * 4, hipMemcpyHostToDevice, stream));
+  clip.last_w8 = owl.last_w8 = 0;                                     // vstar_w8a8_vit_active: what THIS step ran
   int frc_owl = 0;
   const bool forked = !skip_owl && fork_owl(opix, B, &frc_owl);       // OWL-ViT side of the graph on stream2 (small batches)
   OwlJoinGuard join_guard{stream2, forked || frc_owl != 0};
@@ -1054,6 +1055,7 @@ int vstar_engine::score_grouped(int G, int T, const lp_t* clip_pix, const lp_t* 
       (n_verify && !verify_in_suffix)) { set_error("null input"); return VSTAR_ERR_INVALID; }
   if (flags & VSTAR_F_SKIP_OWL) { set_error("grouped scoring always runs the heads"); return VSTAR_ERR_INVALID; }
   HIPCHK(hipSetDevice(device));
+  clip.last_w8 = owl.last_w8 = 0;
   int img_col = -1;
   for (int j = 0; j < Lp; ++j)
     if (prefix_ids[j] == -200) { if (img_col >= 0) { set_error("more than one -200 in the shared prefix"); return VSTAR_ERR_INVALID; } img_col = j; }
@@ -1267,6 +1269,7 @@ int vstar_create(const vstar_config* cfg, int device, vstar_handle** out) {
   if (!cfg || !out) { tls_error() = "null argument"; return VSTAR_ERR_INVALID; }
   if (cfg->abi_version != VSTAR_ABI_VERSION) { tls_error() = "ABI version mismatch"; return VSTAR_ERR_INVALID; }
   if (cfg->max_batch <= 0 || cfg->max_text_len < 2) { tls_error() = "bad limits"; return VSTAR_ERR_INVALID; }
+  if (cfg->vit_w8a8 != 0 && cfg->vit_w8a8 != 1) { tls_error() = "vit_w8a8 must be 0 (bf16 towers) or 1 (W8A8 tower linears)"; return VSTAR_ERR_INVALID; }
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || device < 0 || device >= n) {
@@ -1285,6 +1288,13 @@ int vstar_create(const vstar_config* cfg, int device, vstar_handle** out) {
     return VSTAR_ERR_HIP;
   }
   if (const char* e = getenv("VSTAR_OWL_OVERLAP")) h->owl_overlap = atoi(e) != 0;
+  // W8A8 tower linears: the config decides; VSTAR_W8A8_VIT=1 turns them on for engines created with llm_w8a8 = 1 (config 5 as bench.py
+  // runs it), VSTAR_W8A8_VIT=0 turns them off everywhere
+  h->vit_w8a8 = cfg->vit_w8a8;
+  if (const char* e = getenv("VSTAR_W8A8_VIT")) {
+    if (atoi(e) == 0) h->vit_w8a8 = 0;
+    else if (cfg->llm_w8a8) h->vit_w8a8 = 1;
+  }
   if (hipStreamCreate(&h->stream2) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
     h->stream2 = nullptr;                       // no second stream: everything stays on the main stream
@@ -1806,6 +1816,7 @@ int vstar_op_attention_mx(void* stream, const uint16_t* qkv, uint8_t* out8, uint
   return op_rc(e);
 }
 int vstar_w8a8_mx_active(vstar_handle* h) { return h ? h->last_w8a8_chain : VSTAR_ERR_INVALID; }
+int vstar_w8a8_vit_active(vstar_handle* h) { return h ? (h->clip.last_w8 | (h->owl.last_w8 << 1)) : VSTAR_ERR_INVALID; }
 
 // ---- doors of the prefill-side features (row maps, fused RoPE, LayerNorm sums, grouped attention): every extent is checked on the
 // host, with the kernels' own gemm_map_row, before anything is launched ----
@@ -2032,6 +2043,10 @@ int vstar_op_fill(void* stream, uint16_t* v, int64_t n, float value) {
 int vstar_op_quantize_rows_fp8(void* stream, const uint16_t* x, int64_t ldx, uint8_t* q, int64_t ldq, float* scale, int rows,
                                int cols) {
   return op_done(quantize_rows_fp8(x, ldx, q, ldq, scale, rows, cols, (hipStream_t)stream), stream);
+}
+int vstar_op_layernorm_quant_fp8(void* stream, const uint16_t* x, const uint16_t* gamma, const uint16_t* beta, uint8_t* q, float* scale,
+                                 int rows, int cols, float eps) {
+  return op_done(layernorm_quant_fp8(x, gamma, beta, q, scale, rows, cols, eps, (hipStream_t)stream), stream);
 }
 int vstar_op_rmsnorm_quant_fp8(void* stream, const uint16_t* x, const uint16_t* gamma, uint8_t* q, float* scale, int rows, int cols,
                                float eps) {

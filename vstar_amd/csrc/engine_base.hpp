@@ -29,7 +29,14 @@ struct HostTensor {
 };
 
 struct Lin { lp_t* W = nullptr; lp_t* b = nullptr; int N = 0, K = 0; };
-struct VitBlock { lp_t *ln1_g, *ln1_b, *ln2_g, *ln2_b; Lin qkv, out, fc1, fc2; };
+// fp8 twin of a packed Linear (W8A8 modes): e4m3 rows + per-output-channel scales, same row order/padding as Lin::W
+struct Lin8 { uint8_t* W = nullptr; float* s = nullptr; };
+struct VitBlock {
+  lp_t *ln1_g, *ln1_b, *ln2_g, *ln2_b; Lin qkv, out, fc1, fc2;
+  // vit_w8a8 (bf16 library only): fp8 twins of the UNFOLDED weights, and the qkv / fc1 biases as they were before ln_fold_weights
+  Lin8 qkv8, out8, fc18, fc28;
+  lp_t *qkv_b0 = nullptr, *fc1_b0 = nullptr;
+};
 struct VitTower {
   int image = 0, patch = 0, grid = 0, P = 0, N = 0, hidden = 0, heads = 0, mlp = 0, nblocks = 0, kpad = 0;
   Lin patch_lin; lp_t *cls = nullptr, *pos = nullptr, *pre_g = nullptr, *pre_b = nullptr;
@@ -40,9 +47,13 @@ struct VitTower {
   // epilogues that write it emit 64-column sums of squares and sums — and 1 / sqrt(var + eps) per row; no normalised copy of x
   bool fold = false;
   float *part = nullptr, *rstd = nullptr;
+  // vit_w8a8: the block linears on the fp8 MFMA for calls of >= 1024 rows.  Each tower owns its quantised-row buffer
+  // [rows_max, max(hidden, mlp)] and per-token scales [rows_max] (the OWL-ViT tower may run on a stream of its own).
+  bool w8 = false;
+  uint8_t* q8 = nullptr;
+  float* sa8 = nullptr;
+  int last_w8 = 0;                     // 1: the last run_tower took the fp8 path
 };
-// fp8 twin of a packed Linear (W8A8 mode): e4m3 rows + per-output-channel scales, same row order/padding as Lin::W
-struct Lin8 { uint8_t* W = nullptr; float* s = nullptr; };
 struct LlmBlock {
   lp_t *in_norm, *post_norm; Lin qkv, o, gate_up, down; Lin8 qkv8, o8, gate_up8, down8;
   Lin8 qkv8f, gate_up8f;      // W8A8, fully block-scaled chain: fp8 of W diag(norm weight) (the RMSNorm folded into the linear)
@@ -227,6 +238,20 @@ struct EngineBase {
           const lp_t* res = nullptr, int64_t ldr = 0, bool f32 = false) {
     return gemm(lin_params(A, lda, L, C, ldc, M, res, ldr), epi, f32);
   }
+  int vit_w8a8 = 0;                    // set before build_tower (the VSM engine, from vstar_config::vit_w8a8 / VSTAR_W8A8_VIT); never in the fp16 library
+#ifndef VSTAR_LP_F16
+  int vit_lin8(const Lin& L, Lin8* out, const lp_t* bias, lp_t** bias_copy);
+  static GemmParams vit_w8_params(const VitTower& t, const Lin& L, const Lin8& L8, const lp_t* bias, void* C, int64_t ldc, int rows,
+                                  const lp_t* res = nullptr) {
+    GemmParams p{};
+    p.A = (const lp_t*)t.q8; p.lda = L.K; p.a_scale = t.sa8;
+    p.W = (const lp_t*)L8.W; p.w_scale = L8.s; p.bias = bias;
+    p.C = C; p.ldc = ldc; p.res = res; p.ldr = ldc;
+    p.M = rows; p.N = L.N; p.K = L.K;
+    return p;
+  }
+  int run_tower_w8(VitTower& t, int B);
+#endif
   bool fold_vit_norms = true;          // VSTAR_FOLD_NORMS=0 / VSTAR_FOLD_VIT_NORMS=0: the LayerNorm kernels (the reference's rounding points)
   void collect_profile() {
     if (!profile) return;
@@ -326,6 +351,20 @@ inline int EngineBase::build_tower(VitTower& t, const std::string& pre, const st
     RC(make_lin({lp + "mlp.fc1.weight"}, {lp + "mlp.fc1.bias"}, &b.fc1, hidden));
     RC(make_lin({lp + "mlp.fc2.weight"}, {lp + "mlp.fc2.bias"}, &b.fc2, mlp));
   }
+#ifndef VSTAR_LP_F16
+  // vit_w8a8: fp8 twins of the four block linears, made from the packed weights as loaded — BEFORE the LayerNorm fold below rewrites
+  // the q|k|v / fc1 weights and biases (the fp8 path keeps the reference's scheme: quantised LayerNorm output x unfolded W)
+  t.w8 = vit_w8a8 == 1 && hidden % 256 == 0 && mlp % 256 == 0 && nblocks > 0;
+  if (t.w8) {
+    for (auto& b : t.blocks) {
+      RC(vit_lin8(b.qkv, &b.qkv8, b.qkv.b, &b.qkv_b0));
+      RC(vit_lin8(b.out, &b.out8, nullptr, nullptr));
+      RC(vit_lin8(b.fc1, &b.fc18, b.fc1.b, &b.fc1_b0));
+      RC(vit_lin8(b.fc2, &b.fc28, nullptr, nullptr));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+#endif
   // Linear(LayerNorm(x)) = rstd(x) * (x . W'^T) + (W b_ln + c), W' = W diag(g) with every row centred over k (the mean of x then
   // drops out of the product): one bf16 rounding of W' in place of the reference's rounding of the normalised activations, no
   // normalised copy of x written or read, no LayerNorm launch — the ViT twin of the RMSNorm fold of llm_forward.
@@ -356,8 +395,48 @@ inline int EngineBase::build_tower(VitTower& t, const std::string& pre, const st
     RC(dalloc(&t.part, rows * (size_t)(2 * (hidden / 64))));
     RC(dalloc(&t.rstd, rows));
   }
+  if (t.w8) {
+    RC(dalloc(&t.q8, rows * (size_t)(mlp > hidden ? mlp : hidden)));
+    RC(dalloc(&t.sa8, rows));
+  }
   return 0;
 }
+
+#ifndef VSTAR_LP_F16
+// fp8 twin of a packed tower Linear (per output channel, on the device) + a copy of its bias as loaded
+inline int EngineBase::vit_lin8(const Lin& L, Lin8* out, const lp_t* bias, lp_t** bias_copy) {
+  const int Npad = (L.N + 255) / 256 * 256;
+  if (L.K % 256) { set_error("vit_w8a8 needs K % 256 == 0"); return VSTAR_ERR_INVALID; }
+  RC(dalloc(&out->W, (size_t)Npad * L.K));
+  RC(dalloc(&out->s, (size_t)Npad));
+  KCHK(quantize_rows_fp8(L.W, L.K, out->W, L.K, out->s, Npad, L.K, stream));
+  if (bias && bias_copy) {
+    RC(dalloc(bias_copy, (size_t)Npad));
+    HIPCHK(hipMemcpyAsync(*bias_copy, bias, (size_t)Npad * sizeof(lp_t), hipMemcpyDeviceToDevice, stream));
+  }
+  return 0;
+}
+
+// The encoder blocks of run_tower on the fp8 MFMA (vit_w8a8; the ViT twin of llm_forward's per-token level): LayerNorm1 / LayerNorm2
+// emit quantised rows (layernorm_quant_fp8), the attention output and the quick-GELU output are quantised by stand-alone passes,
+// every linear dequantises its accumulators (per token x per output channel) and then runs the bf16 kernels' epilogue.
+inline int EngineBase::run_tower_w8(VitTower& t, int B) {
+  const int C = t.hidden, rows = B * t.N;
+  for (int i = 0; i < t.nblocks; ++i) {
+    VitBlock& b = t.blocks[i];
+    KCHK(layernorm_quant_fp8(t.x, b.ln1_g, b.ln1_b, t.q8, t.sa8, rows, C, 1e-5f, stream));
+    RC(gemm(vit_w8_params(t, b.qkv, b.qkv8, b.qkv_b0, t.qkv, 3 * C, rows), VSTAR_EPI_NONE, false));
+    KCHK(attn_forward(t.qkv, t.att, B, t.N, t.heads, 64, 0, 0.125f, stream));
+    KCHK(quantize_rows_fp8(t.att, C, t.q8, C, t.sa8, rows, C, stream));
+    RC(gemm(vit_w8_params(t, b.out, b.out8, b.out.b, t.x, C, rows, t.x), VSTAR_EPI_NONE, false));
+    KCHK(layernorm_quant_fp8(t.x, b.ln2_g, b.ln2_b, t.q8, t.sa8, rows, C, 1e-5f, stream));
+    RC(gemm(vit_w8_params(t, b.fc1, b.fc18, b.fc1_b0, t.mlp_buf, t.mlp, rows), VSTAR_EPI_QUICK_GELU, false));
+    KCHK(quantize_rows_fp8(t.mlp_buf, t.mlp, t.q8, t.mlp, t.sa8, rows, t.mlp, stream));
+    RC(gemm(vit_w8_params(t, b.fc2, b.fc28, b.fc2.b, t.x, C, rows, t.x), VSTAR_EPI_NONE, false));
+  }
+  return 0;
+}
+#endif
 
 // HF CLIPVisionTransformer / OwlViTVisionTransformer forward up to the last executed block (pre-LN blocks, quick-GELU)
 inline int EngineBase::run_tower(VitTower& t, const lp_t* pix, int B) {
@@ -366,6 +445,21 @@ inline int EngineBase::run_tower(VitTower& t, const lp_t* pix, int B) {
   RC(lin(t.im2col, t.kpad, t.patch_lin, t.patch_out, C, B * t.P));
   KCHK(vit_assemble_tokens(t.patch_out, t.cls, t.pos, t.h, B, t.P, C, stream));
   KCHK(layernorm_lp(t.h, t.pre_g, t.pre_b, t.x, rows, C, 1e-5f, nullptr, 0, stream));
+  t.last_w8 = 0;
+#ifndef VSTAR_LP_F16
+  // vit_w8a8: calls with enough rows for the 256^2 kernels run the blocks on the fp8 MFMA; the probes ask about the very GemmParams
+  // run_tower_w8 launches (first block).  Every other call runs the bf16 path below, exactly as with the mode off.
+  if (t.w8 && rows >= 1024) {
+    const VitBlock& b0 = t.blocks[0];
+    if (gemm256_eligible(vit_w8_params(t, b0.qkv, b0.qkv8, b0.qkv_b0, t.qkv, 3 * C, rows)) &&
+        gemm256_eligible(vit_w8_params(t, b0.out, b0.out8, b0.out.b, t.x, C, rows, t.x)) &&
+        gemm256_eligible(vit_w8_params(t, b0.fc1, b0.fc18, b0.fc1_b0, t.mlp_buf, t.mlp, rows)) &&
+        gemm256_eligible(vit_w8_params(t, b0.fc2, b0.fc28, b0.fc2.b, t.x, C, rows, t.x))) {
+      t.last_w8 = 1;
+      return run_tower_w8(t, B);
+    }
+  }
+#endif
   if (t.fold) {
     // folded LayerNorms: q|k|v and fc1 read the residual stream itself, scaled per row by 1 / sqrt(var + eps); the statistics come
     // from the rows (first block: the pre-LayerNorm's output) or from the partial sums the epilogue that wrote the stream left

@@ -408,12 +408,12 @@ GemmPlan gemm_plan(const GemmParams& p, int epilogue, bool out_f32, int cus) {
   }
   const bool known_epi = epilogue >= VSTAR_EPI_NONE && epilogue <= VSTAR_EPI_SILU_MUL;
   // the 256^2 kernel of an M-row launch (whole, or the leading part of a split); 0: gemm256 has no such instantiation (W8A8: the two
-  // epilogues the LLaMA linears use, 16-bit output)
+  // epilogues the LLaMA linears use + the ViT towers' quick-GELU, 16-bit output)
   auto big = [&](int M) -> int {
     GemmParams q = p;
     q.M = M;
     if (force == 0 && env.use4w != 0 && gemm4w_eligible(q, epilogue, out_f32)) return GEMM_TILE_4W;
-    if (!known_epi || (p.a_scale && (out_f32 || (epilogue != VSTAR_EPI_NONE && epilogue != VSTAR_EPI_SILU_MUL)))) return 0;
+    if (!known_epi || (p.a_scale && (out_f32 || (epilogue != VSTAR_EPI_NONE && epilogue != VSTAR_EPI_SILU_MUL && epilogue != VSTAR_EPI_QUICK_GELU)))) return 0;
     return 256;
   };
   if (force != 128 && elig) {   // W is padded to 256 rows

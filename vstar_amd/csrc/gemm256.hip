@@ -637,10 +637,11 @@ hipError_t gemm256_lp(const GemmParams& p0, int epilogue, bool out_f32, hipStrea
   if (no_direct) p.debug_flags |= 4;
   static const int stagger = [] { const char* e = getenv("VSTAR_GEMM_XCD_STAGGER"); return e ? atoi(e) & 0xff : 0; }();
   p.debug_flags |= stagger << 8;
-  if (p.a_scale) {       // W8A8 instantiations: the two epilogues the LLaMA linears use
+  if (p.a_scale) {       // W8A8 instantiations: the two epilogues the LLaMA linears use, and the ViT towers' fc1 (quick-GELU)
     if (out_f32) return hipErrorInvalidValue;
     if (epilogue == VSTAR_EPI_NONE) return launch<VSTAR_EPI_NONE, false, true>(p, s);
     if (epilogue == VSTAR_EPI_SILU_MUL) return launch<VSTAR_EPI_SILU_MUL, false, true>(p, s);
+    if (epilogue == VSTAR_EPI_QUICK_GELU) return launch<VSTAR_EPI_QUICK_GELU, false, true>(p, s);
     return hipErrorInvalidValue;
   }
 #define GEMM_CASE(E)                                                   \

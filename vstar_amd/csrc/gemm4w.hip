@@ -14,6 +14,8 @@
 // row tile may be ragged (template parameter RG) —, N % 256 == 0, K % 128 == 0, identity row maps, 16-byte aligned C / residual / bias —
 // i.e. launches whose tiles all take the direct epilogue;
 // epilogues NONE (+bias, +residual, fused RoPE, folded-norm row scale, sum-of-squares / sum statistics), QUICK_GELU, RELU, SILU_MUL.
+// W8A8 (bf16 library): NONE and SILU_MUL (the LLaMA linears; per-token or block-scaled A) and, next to per-token scales only,
+// QUICK_GELU (fc1 of the ViT towers) — those three kernels are built from this file as an object of their own (gemm4w_vit8.hip).
 #include "common.hpp"
 #include "kernels.hpp"
 #include "gemm_epilogue.hpp"
@@ -556,6 +558,17 @@ hipError_t launch(const GemmParams& p, hipStream_t s) {
 
 }  // namespace
 
+#ifdef G4W_TU_VIT8
+// gemm4w_vit8.hip: this file compiled a second time for the W8A8 quick-GELU kernels alone (the ViT towers' fc1) — an object of their
+// own, with its own entry in tools/check_gemm4w_agpr.py; everything public below belongs to the first object.
+hipError_t gemm4w_gelu8_lp(const GemmParams& p, bool pf, hipStream_t s) {
+  return pf ? launch<VSTAR_EPI_QUICK_GELU, true, true>(p, s) : launch<VSTAR_EPI_QUICK_GELU, false, true>(p, s);
+}
+#else
+#ifndef VSTAR_LP_F16
+hipError_t gemm4w_gelu8_lp(const GemmParams& p, bool pf, hipStream_t s);      // gemm4w_vit8.hip
+#endif
+
 #if defined(G4W_TIMELINE) && !defined(VSTAR_LP_F16)
 extern "C" int vstar_debug_gemm4w_timeline(unsigned long long* out) {     // 2 x 64 x 8 stamps
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g4w_timeline), sizeof(g4w_timeline));
@@ -575,8 +588,9 @@ bool gemm4w_eligible(const GemmParams& p, int epilogue, bool out_f32) {
     else if (epilogue == VSTAR_EPI_NONE) { if (!p.c8 || ((uintptr_t)p.c8 & 15) || p.ldc8 % 16 || p.bias || p.rope_cs || p.stats_sum) return false; }
     else return false;
   } else if (p.c8) return false;
-  if (p.a_scale || p.a_mx) {      // W8A8: the two epilogues the LLaMA linears use; K counts fp8 elements, two K-tiles of 128 per loop iteration
-    if (!p.w_scale || (epilogue != VSTAR_EPI_NONE && epilogue != VSTAR_EPI_SILU_MUL) || p.K % 256 || p.row_scale || (p.sumsq_out && !p.c8)) return false;
+  if (p.a_scale || p.a_mx) {      // W8A8: the two epilogues the LLaMA linears use, and quick-GELU (ViT fc1) next to per-token scales only; K counts fp8 elements, two K-tiles of 128 per loop iteration
+    const bool gelu8 = epilogue == VSTAR_EPI_QUICK_GELU && p.a_scale && !p.a_mx && !p.c_mx;
+    if (!p.w_scale || (epilogue != VSTAR_EPI_NONE && epilogue != VSTAR_EPI_SILU_MUL && !gelu8) || p.K % 256 || p.row_scale || (p.sumsq_out && !p.c8)) return false;
     static const bool f8_on = [] { const char* e = getenv("VSTAR_GEMM4W_F8"); return !e || atoi(e) != 0; }();
     if (!f8_on) return false;
   }
@@ -613,6 +627,7 @@ hipError_t gemm4w_lp(const GemmParams& p, int epilogue, hipStream_t s) {
   if (p.a_scale) {
     if (epilogue == VSTAR_EPI_NONE) return pf ? launch<VSTAR_EPI_NONE, true, true>(p, s) : launch<VSTAR_EPI_NONE, false, true>(p, s);
     if (epilogue == VSTAR_EPI_SILU_MUL) return pf ? launch<VSTAR_EPI_SILU_MUL, true, true>(p, s) : launch<VSTAR_EPI_SILU_MUL, false, true>(p, s);
+    if (epilogue == VSTAR_EPI_QUICK_GELU) return gemm4w_gelu8_lp(p, pf, s);
     return hipErrorInvalidValue;
   }
 #endif
@@ -626,5 +641,6 @@ hipError_t gemm4w_lp(const GemmParams& p, int epilogue, hipStream_t s) {
 #undef G4W_CASE
   return hipErrorInvalidValue;
 }
+#endif      // G4W_TU_VIT8
 
 }  // namespace VS_NS

@@ -225,6 +225,10 @@ hipError_t quantize_rows_fp8(const lp_t* x, int64_t ldx, uint8_t* q, int64_t ldq
 // LlamaRMSNorm whose 16-bit output row is quantised on the way out (cols <= 4096)
 hipError_t rmsnorm_quant_fp8(const lp_t* x, const lp_t* gamma, uint8_t* q, float* scale, int rows, int cols, float eps,
                              hipStream_t s);
+// LayerNorm (layernorm_lp with act = 0 and no row index) whose 16-bit output row is quantised on the way out (cols <= 4096): the same
+// bytes and scales as layernorm_lp followed by quantize_rows_fp8 with ld = cols
+hipError_t layernorm_quant_fp8(const lp_t* x, const lp_t* gamma, const lp_t* beta, uint8_t* q, float* scale, int rows, int cols,
+                               float eps, hipStream_t s);
 
 // block-scaled twin (mx.hpp): x [rows, cols] 16-bit -> fp8 bytes q [rows, ldq] + E8M0 scales (tile-major, rows % 128 == 0, cols % 128 == 0)
 hipError_t quantize_rows_mx(const lp_t* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* scales, int rows, int cols, hipStream_t s);

@@ -112,6 +112,84 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_kernel(const lp_t* __restri
   }
 }
 
+// LayerNorm (the statistics, arithmetic and rounding point of norm_kernel<false> with act = 0 and no row index: two-pass variance in
+// fp32, one 16-bit rounding of the result) + per-row fp8 quantisation of that 16-bit output: the ViT twin of rmsnorm_quant_kernel
+// (vit_w8a8: LayerNorm1 / LayerNorm2 of the CLIP and OWL-ViT blocks).  One wave per row, cols <= 4096.
+__global__ __launch_bounds__(256) void layernorm_quant_kernel(const lp_t* __restrict__ x, const lp_t* __restrict__ gamma,
+                                                              const lp_t* __restrict__ beta, uint8_t* __restrict__ q,
+                                                              float* __restrict__ scale, int rows, int cols, float eps) {
+  constexpr int MAXCH = 8;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const lp_t* xr = x + (int64_t)row * cols;
+  const int nvec = cols >> 3;
+  float v[MAXCH][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < MAXCH; ++c) {
+    const int vi = c * 64 + lane;
+    if (vi < nvec) {
+      const lpx8 t = *(const lpx8*)(xr + vi * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        v[c][e] = lp2f((lp_t)t[e]);
+        sum += v[c][e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[c][e] = 0.f;
+    }
+  }
+  sum = wave_sum(sum);
+  const float mean = sum / (float)cols;
+  float sq = 0.f;
+#pragma unroll
+  for (int c = 0; c < MAXCH; ++c) {
+    const int vi = c * 64 + lane;
+    if (vi < nvec) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = v[c][e] - mean;
+        sq += d * d;
+      }
+    }
+  }
+  sq = wave_sum(sq);
+  const float rstd = rsqrtf(sq / (float)cols + eps);
+  float mx = 0.f;
+#pragma unroll
+  for (int c = 0; c < MAXCH; ++c) {
+    const int vi = c * 64 + lane;
+    if (vi < nvec) {
+      const lpx8 g = *(const lpx8*)(gamma + vi * 8);
+      lpx8 b;
+      if (beta) b = *(const lpx8*)(beta + vi * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float r = (v[c][e] - mean) * rstd * lp2f((lp_t)g[e]) + (beta ? lp2f((lp_t)b[e]) : 0.f);
+        v[c][e] = rlp(r);                                            // the 16-bit value the plain norm kernel would store
+        mx = fmaxf(mx, fabsf(v[c][e]));
+      }
+    }
+  }
+  mx = wave_max(mx);
+  const float sc = mx > 0.f ? mx / FP8_MAX : 1.0f;
+  const float inv = 1.0f / sc;
+  if (lane == 0) scale[row] = sc;
+  uint8_t* qr = q + (int64_t)row * cols;
+#pragma unroll
+  for (int c = 0; c < MAXCH; ++c) {
+    const int vi = c * 64 + lane;
+    if (vi < nvec) {
+      uint2 o;
+      o.x = pack4_fp8(v[c][0] * inv, v[c][1] * inv, v[c][2] * inv, v[c][3] * inv);
+      o.y = pack4_fp8(v[c][4] * inv, v[c][5] * inv, v[c][6] * inv, v[c][7] * inv);
+      *(uint2*)(qr + vi * 8) = o;
+    }
+  }
+}
+
 // block-scaled quantisation (mx.hpp): one thread per 8 values, four threads per block of 32
 __global__ __launch_bounds__(256) void quantize_rows_mx_kernel(const lp_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ q, int64_t ldq,
                                                                uint8_t* __restrict__ scales, int rows, int cols) {
@@ -160,6 +238,14 @@ hipError_t rmsnorm_quant_fp8(const lp_t* x, const lp_t* gamma, uint8_t* q, float
   if (rows <= 0) return hipSuccess;
   if (cols % 8 || cols > 4096) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rmsnorm_quant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, q, scale, rows, cols, eps);
+  return hipGetLastError();
+}
+
+hipError_t layernorm_quant_fp8(const lp_t* x, const lp_t* gamma, const lp_t* beta, uint8_t* q, float* scale, int rows, int cols,
+                               float eps, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (cols % 8 || cols > 4096) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(layernorm_quant_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, beta, q, scale, rows, cols, eps);
   return hipGetLastError();
 }
 

@@ -386,6 +386,11 @@ class VstarEngine:
         (q|k|v and gate|up too, RMSNorms folded)."""
         return int(self.lib.vstar_w8a8_mx_active(self.handle))
 
+    def w8a8_vit_active(self) -> int:
+        """Which vision towers ran their block linears on the fp8 MFMA in the last scoring step (VSMConfig.vit_w8a8;
+        vstar_w8a8_vit_active): bit 0 = CLIP, bit 1 = OWL-ViT.  A tower call with fewer than 1024 rows runs the bf16 path."""
+        return int(self.lib.vstar_w8a8_vit_active(self.handle))
+
     @property
     def stream(self) -> int:
         return int(self.lib.vstar_stream(self.handle) or 0)
