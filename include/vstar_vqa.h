@@ -341,6 +341,55 @@ int vstar_vqa_op_verify_warp(const void* dev_logits, int dtype, int rows, int vo
 int vstar_vqa_op_logprobs(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const int32_t* tokens, int n_top,
                           float* token_logprob, int32_t* token_rank, float* top_logprob, int32_t* top_token);
 
+/* Contrastive search: HF 4.31 generate(penalty_alpha = alpha, top_k = k) — contrastive_search + _ranking_fast — with
+ * the degeneration penalty, the pick, the next candidates and the carry-over of the winner on the device.  Per sequence the engine
+ * keeps the hidden history Hs[0 .. L): the final-norm output (LlamaModel.norm, HF's hidden_states[-1]) of every position so far,
+ * spliced image / object rows included, fp16, with the fp32 reciprocal norm of every row; hist_len[slot] = L (host).  T tokens cost
+ * one begin call plus T step calls.  The history ([max_slots][max_ctx][llm_hidden] fp16 + [max_slots][max_ctx] fp32 =
+ * max_slots * max_ctx * (2 * llm_hidden + 4) bytes) and the step's buffers are allocated by the first contrast call (a failed
+ * allocation is VSTAR_ERR_NOMEM and leaves the engine usable); an engine that never asks allocates and launches nothing.  Once the
+ * history exists every other call that writes K/V rows of a slot at position p lowers hist_len[slot] to min(hist_len, p) (host
+ * arithmetic): stale history is never read.
+ * The arithmetic (csrc/contrast.hpp states it in full): hidden rows h(w * h(x * rstd)), one routine for prefill and candidate rows;
+ * cos = dot * rnorm_c * rnorm_j with the dot and the squared norms in fp32 in one fixed order (a result depends on its own inputs
+ * only and repeats bit for bit), a zero-norm row gives cosine 0 (HF: NaN — a stated deviation); pen_c = max_{j < L} cos(h_c, Hs[j]);
+ * score_c = (1 - alpha) * p_c - alpha * pen_c in double from the fp32 p and pen and the fp32 alpha, every operation rounded on its
+ * own, so the pick — the largest score, the lowest c on a tie — is reproducible exactly from the returned p and pen; the top k of a
+ * logits row in vstar_vqa_logprobs' top-n order with p = (float)exp((double)x - lse), lse the scoring tail's double log-sum-exp.
+ * Probabilities and cosines are exact where HF rounds them to fp16.
+ *
+ * begin: a vstar_vqa_forward prefill (the eight row arguments) that writes the hidden row of EVERY new row into the history of its
+ * kv_slot and returns, per wanted row, the k (2 .. 32, <= llm_vocab) best tokens and their probabilities, next_tok / next_prob
+ * [n_want, k] (host).  Rules: prefix_slot == kv_slot; past_len == 0 (a fresh sequence: the history starts again) or == hist_len[kv_slot]
+ * (a chunked prefill continues it); the kv_slots pairwise distinct.  Afterwards hist_len[kv_slot] = past_len + rows. */
+int vstar_vqa_forward_contrast_begin(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                     const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want, int k,
+                                     int32_t* next_tok, float* next_prob);
+/* step: the k candidates of each sequence as one-row continuations.  Every sequence of the call has exactly one row and wanted row j
+ * is row j (n_want == nseq); rows group_off[g] .. group_off[g+1]-1 (1 .. 32 of them) are group g: they share prefix_slot (the owner)
+ * and past_len == hist_len[owner] (>= 1), their kv_slots are pairwise distinct over the whole call (one of a group's may be its owner;
+ * none may be another group's owner); cand_prob[n_want] finite and in [0, 1]; alpha in [0, 1]; k_next in [2, 32], <= llm_vocab.  Per
+ * group g: sel_out[g] = the winner (row in group), next_tok / next_prob [n_groups, k_next] = the top k_next of the winner's logits row,
+ * penalty_out[n_want] (nullable) = pen of every candidate; the winner's hidden row becomes Hs[L] and its K/V row becomes row L of the
+ * owner slot in every layer (copied on the device unless its kv_slot is the owner: 128 code bytes + 4 scale bytes per row in
+ * kv_cache_format 1, else the fp16 row).  Afterwards hist_len[owner] = L + 1, and the history of every other candidate slot is empty.
+ * A violation is VSTAR_ERR_INVALID with a message that names the field, before any launch; the engine stays usable.  Logits edits and
+ * log-probabilities are not available with these two entries (open follow-ups). */
+int vstar_vqa_forward_contrast_step(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                    const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                    const int32_t* group_off, int n_groups, const float* cand_prob, float alpha, int k_next,
+                                    int32_t* sel_out, int32_t* next_tok, float* next_prob, float* penalty_out);
+/* Op-level (tests, micro-benchmarks): the step behind lm_head.  DEVICE: logits [rows, ld] and candidate hidden rows [rows, hidden] of
+ * dtype F16/BF16 (both), the history dev_hist [n_groups, cap, hidden] of that dtype and dev_hist_rnorm [n_groups, cap] fp32, group g's
+ * first hist_len[g] rows valid; the winner's row and reciprocal norm are appended IN PLACE at row hist_len[g].  HOST: hist_len
+ * [n_groups], group_off [n_groups + 1], cand_prob [rows] and the outputs of the step (penalty_out nullable).  Checked before any device
+ * work (VSTAR_ERR_INVALID, the message names the field): a NULL pointer, hidden % 8 != 0, hist_len outside [1, cap), and the step's
+ * rules.  Null stream, synchronises. */
+int vstar_vqa_op_contrast(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const void* dev_cand_hidden, int hidden,
+                          void* dev_hist, float* dev_hist_rnorm, int n_groups, int cap, const int32_t* hist_len, const int32_t* group_off,
+                          const float* cand_prob, float alpha, int k_next, int32_t* sel_out, int32_t* next_tok, float* next_prob,
+                          float* penalty_out);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the
@@ -461,7 +510,9 @@ int vstar_vqa_op_embed_rows(const int32_t* host_src, int R, const void* dev_tabl
 int vstar_vqa_op_argmax_rows(const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out);
 
 /* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float; "kv:<layer>:<slot>" = the DECODED K then V
- * cache of that layer and slot as floats [2][llm_heads][max_ctx][128], in every kv_cache_format (an index out of range is an error).
+ * cache of that layer and slot as floats [2][llm_heads][max_ctx][128], in every kv_cache_format (an index out of range is an error);
+ * "contrast_hist:<slot>" = the hidden history of that slot [hist_len, llm_hidden], "contrast_cand" = the candidate hidden rows of the
+ * last contrast step [rows, llm_hidden] (both VSTAR_ERR_STATE on an engine that ran no contrast call).
  * Returns elements written. */
 int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, int64_t capacity);
 /* Timing of the last forward call in milliseconds (HIP events on the engine stream). */

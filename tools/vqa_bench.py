@@ -4,6 +4,10 @@ KV-cached decode steps at several batch sizes, forked option scoring.  Prints on
   python tools/vqa_bench.py [--out profiles/r01_vqa_bench.json] [--layers 32] [--sample]
 --logprobs 0,5 runs `decode_logprobs` alone: greedy decode steps without and with the on-device log-probability stage (logprobs=0 /
 logprobs=5), alternated in blocks of --steps at the --batches sizes, and each mode's tokens/s over the plain one's.
+--contrast 4,8 runs `decode_contrast` alone: contrastive-search steps of one prompt with k candidates (forward_contrast_step: k forked
+one-row sequences, the penalty / select / adopt kernels) alternated in blocks of --steps with greedy one-row steps of
+the same prompt in the same process; tokens/s of both (one token per step either way) and their ratio.  Written to
+profiles/vqa_contrast_bench.json unless --out says otherwise.
 --sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
 sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio; with --warp a
 third kind of block, the sampled step with min_p 0.05 and typical_p 0.9, and its cost over the plain sampled step.
@@ -77,6 +81,8 @@ def main():
                     "history tokens) against plain ones, alternated blocks (runs alone)")
     ap.add_argument("--logprobs", default="", help="comma-separated n (e.g. '0,5'): greedy decode steps without and with the on-device "
                     "log-probability stage asking for n alternatives, alternated blocks (DESIGN.md 8.9; runs alone)")
+    ap.add_argument("--contrast", default="", help="comma-separated candidate counts (e.g. '4,8'): contrastive-search steps against greedy "
+                    "steps of the same process, alternated blocks (DESIGN.md 8.11; runs alone; default --out profiles/vqa_contrast_bench.json)")
     ap.add_argument("--spec-kernels", type=int, default=0, help="rows: the arg-max and verify tails alone, for a kernel trace")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
@@ -135,6 +141,10 @@ def main():
     if a.logprobs:
         out["decode_logprobs"] = decode_logprobs(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds,
                                                  [int(x) for x in a.logprobs.split(",")])
+        return finish(out, a)
+    if a.contrast:
+        out["decode_contrast"] = decode_contrast(eng, plain_rows, [int(x) for x in a.contrast.split(",")], a.steps, a.rounds)
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vqa_contrast_bench.json")
         return finish(out, a)
     res = {}
     for name, rows in (("plain_296", plain_rows), ("objects_584", short_rows)):
@@ -563,6 +573,51 @@ def decode_logprobs(eng, rows, batches, steps, rounds, ns):
             leg[m]["over_off_tokens_per_s"] = round(leg[m]["tokens_per_s"] / leg["off"]["tokens_per_s"], 4)
             leg[m]["minus_off_device_ms"] = round(leg[m]["device_ms_per_step"] - leg["off"]["device_ms_per_step"], 4)
         res[f"B{B}"] = leg
+    return res
+
+
+def decode_contrast(eng, rows, ks, steps, rounds, alpha=0.6):
+    """Contrastive-search steps of one prompt with k candidates (owner slot k, candidate c in slot k + c: k forked one-row sequences,
+    then the penalty, select and adopt kernels) vs greedy one-row steps of the same prompt (slot 0), alternated in blocks of `steps`.
+    Both emit one token per step; the history grows from len(rows) positions."""
+    res = {}
+    P = len(rows)
+    for k in ks:
+        slots = list(range(k, 2 * k))
+        _, nxt = eng.forward([Seq(rows, kv_slot=0)], [(0, -1)], logits=False)
+        tok, prob = eng.forward_contrast_begin([Seq(rows, kv_slot=slots[0])], [(0, -1)], k)
+        state = {"nxt": nxt, "ct": tok[0].copy(), "cp": prob[0].copy(), "gpos": P, "cpos": P}
+
+        def one(mode):
+            if mode == "greedy":
+                _, state["nxt"] = eng.forward([Seq([int(state["nxt"][0])], kv_slot=0, past_len=state["gpos"])], [(0, 0)], logits=False)
+                state["gpos"] += 1
+            else:
+                step = [Seq([int(state["ct"][c])], kv_slot=slots[c], past_len=state["cpos"], prefix_slot=slots[0]) for c in range(k)]
+                sel, ntok, nprob = eng.forward_contrast_step(step, [0, k], state["cp"], alpha, k)
+                state["ct"], state["cp"] = ntok[0].copy(), nprob[0].copy()
+                state["cpos"] += 1
+
+        for mode in ("greedy", "contrast"):      # warm-up: code objects, the k-row kernels' first launches
+            one(mode)
+            one(mode)
+        dev = {"greedy": [], "contrast": []}
+        wall = {"greedy": 0.0, "contrast": 0.0}
+        for r in range(rounds):
+            for mode in ("greedy", "contrast"):
+                t0 = time.time()
+                for s in range(steps):
+                    one(mode)
+                    dev[mode].append(eng.last_forward_ms())
+                wall[mode] += time.time() - t0
+        leg = {"alpha": alpha, "prompt_rows": P, "steps_per_block": steps, "blocks": rounds}
+        for mode in ("greedy", "contrast"):
+            w = wall[mode] / (rounds * steps) * 1e3
+            leg[mode] = {"device_ms_per_step": round(float(np.median(dev[mode])), 3), "wall_ms_per_step": round(w, 3),
+                         "tokens_per_s": round(1e3 / w, 1)}
+        leg["contrast_over_greedy_tokens_per_s"] = round(leg["contrast"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
+        leg["contrast_over_greedy_device_ms"] = round(leg["contrast"]["device_ms_per_step"] / leg["greedy"]["device_ms_per_step"], 4)
+        res[f"k{k}"] = leg
     return res
 
 

@@ -53,6 +53,8 @@ EXPORTS_VQA = [
     # doors of the decode-side kernels (tests/test_decode_ops_gpu.py)
     "vstar_vqa_op_rope_kv_append", "vstar_vqa_op_cached_attention", "vstar_vqa_op_perceiver_attention", "vstar_vqa_op_embed_rows",
     "vstar_vqa_op_argmax_rows",
+    # contrastive search
+    "vstar_vqa_forward_contrast_begin", "vstar_vqa_forward_contrast_step", "vstar_vqa_op_contrast",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -412,6 +414,14 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_embed_rows.restype = c_int
     lib.vstar_vqa_op_argmax_rows.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p]
     lib.vstar_vqa_op_argmax_rows.restype = c_int
+    _rows8 = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]      # the eight row arguments behind the handle
+    lib.vstar_vqa_forward_contrast_begin.argtypes = _rows8 + [c_int, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_contrast_begin.restype = c_int
+    lib.vstar_vqa_forward_contrast_step.argtypes = _rows8 + [c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_contrast_step.restype = c_int
+    lib.vstar_vqa_op_contrast.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_op_contrast.restype = c_int
     lib.vstar_vqa_debug_read.argtypes = [H, c_char_p, c_void_p, c_int64]
     lib.vstar_vqa_debug_read.restype = c_int64
     lib.vstar_vqa_last_forward_ms.argtypes = [H]

@@ -246,7 +246,7 @@ class LlavaSearchModel:
                  num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None, allowed_tokens_fn=None,
                  prefix_allowed_tokens_fn=None, return_dict_in_generate: bool = False, output_scores: bool = False, top_logprobs=None,
-                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **unused):
+                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None, **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
@@ -270,9 +270,13 @@ class LlavaSearchModel:
         the edited, un-warped, temperature-1 distribution, where HF's are the warped ones — `token_ranks` int32 [1, T] (0: the
         token is the arg-max), `top_tokens` int32 / `top_logprobs` fp32 [1, T, n], the n most likely tokens of each step, and
         `scores` = None: the full vocabulary rows HF returns there deliberately do not cross to the host.  num_beams > 1 with
-        output_scores raises NotImplementedError (beam hypotheses carry their own scores; exposing those is a follow-up)."""
+        output_scores raises NotImplementedError (beam hypotheses carry their own scores; exposing those is a follow-up).
+        penalty_alpha in (0, 1] with top_k in [2, 32] (do_sample=False, num_beams 1): HF 4.31 contrastive search, the penalty and the
+        pick on the device — the same ids as VQA_LLM.free_form_inference(penalty_alpha=, top_k=); it needs top_k KV
+        slots.  Out-of-range values and prompt_lookup_num_tokens > 0 raise ValueError; do_sample, num_beams > 1, an active logits
+        rule or output_scores with it raise NotImplementedError (follow-ups).  None / 0: off."""
         from .logits import BEAM_RULES_MESSAGE, rules_from_kwargs
-        from .vqa import check_spec_tokens, resolve_seed, sampling_params, warper_params
+        from .vqa import check_contrast, check_spec_tokens, resolve_seed, sampling_params, warper_params
         from .vqa_engine import Seq, check_logprobs
         if allowed_tokens_fn is not None and prefix_allowed_tokens_fn is not None:
             raise ValueError("pass allowed_tokens_fn or prefix_allowed_tokens_fn, not both")
@@ -298,6 +302,10 @@ class LlavaSearchModel:
         if lp is not None and num_beams > 1:
             raise NotImplementedError("output_scores with beam search (num_beams > 1) is not implemented: beam hypotheses carry "
                                       "their own scores, and exposing those is a follow-up")
+        alpha = check_contrast(penalty_alpha, top_k, sampled=bool(do_sample), num_beams=num_beams, speculative=spec, rules=rules,
+                               logprobs=lp, sampled_name="do_sample=True")
+        if alpha is not None and int(top_k) > self.cfg.max_slots:
+            raise ValueError(f"top_k={top_k} candidates need {top_k} KV slots; the engine has max_slots={self.cfg.max_slots}")
         warp = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff) if do_sample else {}
         warper_params(**warp)                          # (validated before any engine work)
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
@@ -319,6 +327,8 @@ class LlavaSearchModel:
         def one(res):       # a decode loop's result for the one sequence: (ids, record or None)
             return ([res[0][0]], res[1][0]) if lp is not None else ([res[0]], None)
 
+        if alpha is not None:
+            return result(self._llm.contrastive_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, alpha, int(top_k)))
         if spec:
             p = [sampling_params(temperature, top_k, top_p, resolve_seed(seed))] if do_sample else None
             return result(*one(self._llm.speculative_decode([Seq(rows, kv_slot=0)], [len(rows)], text, max_new_tokens, spec, p, draft_fn,

@@ -158,6 +158,13 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     if n_lp is not None:
         spec_kw["logprobs"] = int(n_lp)
 
+    # `--vqa-penalty-alpha A --vqa-top-k K`: the free-form pass decodes by contrastive search; off = no keyword
+    alpha = getattr(args, "vqa_penalty_alpha", None)
+    slots_per_q = 1
+    if alpha is not None and float(alpha) != 0:
+        spec_kw["penalty_alpha"], spec_kw["top_k"] = float(alpha), getattr(args, "vqa_top_k", None)
+        slots_per_q = max(1, int(spec_kw["top_k"] or 1))            # (a missing / bad K is the decode's ValueError)
+
     def confidence(i):      # sample i of the free-form call just made, as JSON values
         rec = vqa_llm.generated_logprobs[i]
         lp = [float(v) for v in rec.token_logprob]
@@ -179,7 +186,7 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
                             "prediction": prediction, "missing": parse_missing_objects(prediction) if vqa_batch == 1 else None})
     # pass 1, batched: free_form_batch takes one KV slot and one feature slot per question, so its chunks are capped by the engine
     cfg = getattr(vqa_llm, "cfg", None)
-    ff_batch = min(vqa_batch, getattr(cfg, "max_slots", vqa_batch), getattr(cfg, "max_images", vqa_batch))
+    ff_batch = max(1, min(vqa_batch, getattr(cfg, "max_slots", vqa_batch * slots_per_q) // slots_per_q, getattr(cfg, "max_images", vqa_batch)))
     for k in range(0, len(entries) if vqa_batch > 1 else 0, ff_batch):
         chunk = entries[k:k + ff_batch]
         squares = [expand2square_centered(Image.open(e["path"]).convert("RGB"), mean_color)[0] for e in chunk]

@@ -82,17 +82,37 @@ struct LlmLogprobArgs {
   int32_t* top_tok_out = nullptr;
 };
 
+// The contrastive-search tail of forward() (contrast.hip): host arrays.  goff == null: the BEGIN call — a prefill
+// (prefix_slot == kv_slot, past_len == the slot's history length or 0) whose new rows' final-norm hidden rows fill the history of
+// their slot, and per wanted row the k best tokens and their probabilities come back, next_tok / next_prob [n_want, k].  goff given:
+// a STEP — every sequence one row, wanted row j = row j; rows goff[g] .. goff[g+1]-1 are the candidates of group g, continuations of
+// one owner (their common prefix_slot) at past_len == the owner's history length, each into a kv_slot of its own (one may be the
+// owner); cand_prob[n_want] their probabilities.  sel[n_groups], next_tok / next_prob [n_groups, k] and (nullable) pen_out[n_want]
+// come back; the winner's hidden row joins the owner's history and its K/V row becomes the owner's.
+struct LlmContrastArgs {
+  int k = 0;
+  int32_t* next_tok = nullptr;
+  float* next_prob = nullptr;
+  int n_groups = 0;
+  const int32_t* goff = nullptr;
+  const float* cand_prob = nullptr;
+  float alpha = 0.f;
+  int32_t* sel = nullptr;
+  float* pen_out = nullptr;
+};
+
 struct LlmCached;
 
-// What forward() does with the wanted rows' logits: exactly one of the five tails, built by the function of its name — so a call
+// What forward() does with the wanted rows' logits: exactly one of the six tails, built by the function of its name — so a call
 // cannot ask for two tails, or for a tail together with an output that tail does not have.
 struct LlmTail {
-  enum Kind { ARGMAX, SAMPLE, BEAM, SCORE, VERIFY };
+  enum Kind { ARGMAX, SAMPLE, BEAM, SCORE, VERIFY, CONTRAST };
   static LlmTail argmax(uint16_t* logits_out, int32_t* argmax_out) { LlmTail t; t.logits_out = logits_out; t.tokens_out = argmax_out; return t; }
   static LlmTail sample(const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_warpers* warpers = nullptr) { LlmTail t; t.kind = SAMPLE; t.params = params; t.tokens_out = tokens; t.warpers = warpers; return t; }
   static LlmTail beam_select(const LlmBeamArgs& b, uint16_t* logits_out) { LlmTail t; t.kind = BEAM; t.beam = b; t.logits_out = logits_out; return t; }
   static LlmTail score_rows(const LlmScoreArgs& sc) { LlmTail t; t.kind = SCORE; t.score = sc; return t; }
   static LlmTail verify_rows(const LlmVerifyArgs& v, const vstar_vqa_sampling* params, const vstar_vqa_warpers* warpers = nullptr) { LlmTail t; t.kind = VERIFY; t.verify = v; t.params = params; t.warpers = warpers; return t; }
+  static LlmTail contrast(const LlmContrastArgs& c) { LlmTail t; t.kind = CONTRAST; t.con = c; return t; }
   // the tail with the log-probability stage behind it (null: the tail as it is); refused on BEAM and SCORE by tail_check
   LlmTail with_logprobs(const LlmLogprobArgs* lp) const { LlmTail t = *this; t.has_lp = lp != nullptr; if (lp) t.lp = *lp; return t; }
 
@@ -104,7 +124,7 @@ struct LlmTail {
   int32_t* tokens_out = nullptr;                 // ARGMAX (nullable): the arg-max; SAMPLE: the drawn tokens (sample.hip)
   const vstar_vqa_sampling* params = nullptr;    // SAMPLE; VERIFY (nullable: greedy): one record per wanted row
   const vstar_vqa_warpers* warpers = nullptr;    // SAMPLE, VERIFY (nullable): the §8.10 stages behind top-p, one record per wanted row
-  LlmBeamArgs beam; LlmScoreArgs score; LlmVerifyArgs verify;      // the kind's own host arrays
+  LlmBeamArgs beam; LlmScoreArgs score; LlmVerifyArgs verify; LlmContrastArgs con;      // the kind's own host arrays
   bool has_lp = false;                           // ARGMAX, SAMPLE, VERIFY: the log-probability stage runs behind the tail
   LlmLogprobArgs lp;
 };
@@ -251,6 +271,30 @@ struct LlmCached {
   // ---- log-probabilities: allocated by the first forward() that asks for them, never by an engine that does not ----
   float *d_lp = nullptr, *d_lp_top = nullptr;    // [max_want], [max_want, 32] (row stride: the call's n_top)
   int32_t *d_lp_rank = nullptr, *d_lp_tok = nullptr;
+  // ---- contrastive search: allocated by the first forward() with the contrast tail, never by an engine without one ----
+  // The hidden history [max_slots][max_ctx][hidden] and its fp32 reciprocal norms [max_slots][max_ctx]; hist_len[slot] (host) = the
+  // rows of the slot's history that describe the slot's K/V rows.  Once the history exists every other forward() (and whatever else
+  // rewrites K/V rows of a slot) lowers hist_len to the first position it writes: stale history can never be read.
+  lp_t* c_hist = nullptr;
+  float* c_hist_rn = nullptr;
+  std::vector<int32_t> hist_len;
+  lp_t* c_cand = nullptr;                        // [max_want, hidden] the last step's candidate rows
+  float *c_cand_rn = nullptr, *c_prob = nullptr, *c_pen = nullptr, *c_nprob = nullptr;      // [max_want] x 3, [max_want, 32]
+  int32_t *c_sel = nullptr, *c_ntok = nullptr;   // [max_want], [max_want, 32]
+  // the call's metadata, one device block and its host image: int64 dst[max_rows] (fill: history / candidate row of physical row r,
+  // -1: padding) | int64 hbase[max_want] | int32 goff[max_want + 1] | hlen | owner | pos | rowslot [max_want] each
+  char* c_meta = nullptr;
+  std::vector<char> c_meta_host;
+  int c_cand_rows = 0, c_max_group = 0, c_max_len = 0, c_fill_rows = 0;
+  size_t c_meta_bytes() const { return ((size_t)cfg.max_rows + max_want) * 8 + ((size_t)5 * max_want + 1) * 4; }
+  template <typename T> T* c_meta_at(char* base, int which) const {      // which: 0 dst, 1 hbase, 2 goff, 3 hlen, 4 owner, 5 pos, 6 rowslot
+    const size_t W = (size_t)max_want, o8 = ((size_t)cfg.max_rows + W) * 8;
+    const size_t off[7] = {0, (size_t)cfg.max_rows * 8, o8, o8 + (W + 1) * 4, o8 + (2 * W + 1) * 4, o8 + (3 * W + 1) * 4, o8 + (4 * W + 1) * 4};
+    return (T*)(base + off[which]);
+  }
+  int contrast_alloc();
+  int contrast_check(const LlmRows& r, const LlmContrastArgs& a);
+  void hist_lower(int slot, int pos) { if (c_hist && hist_len[(size_t)slot] > pos) hist_len[(size_t)slot] = pos; }
   static constexpr int SPLIT_ROWS = 4;           // decode steps of up to this many sequences take the split-KV attention
   int split_rows() const { return cfg.split_rows > 0 ? cfg.split_rows : SPLIT_ROWS; }      // rows the workspace holds
   char* split_ws = nullptr;
@@ -320,7 +364,7 @@ struct LlmCached {
   int lin_skinny(GemmParams& p, int epi, const SkinnyWeights* dw);
   int llm_layers_prefill(int nseq, int S);
   int llm_layers_cached(int R, int max_keys, bool single_rows, const int32_t* anc = nullptr);
-  // ---- forward(): the head and the tail's stages (one switch over the five tails each) ----
+  // ---- forward(): the head and the tail's stages (one switch over the six tails each) ----
   struct TailCopy { void* dev = nullptr; const void* in = nullptr; void* out = nullptr; size_t bytes = 0; };
   size_t vpad() const { return (size_t)(cfg.vocab + 255) / 256 * 256; }      // row stride of the logits buffer
   int forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits = nullptr);
@@ -329,6 +373,7 @@ struct LlmCached {
   int edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed);
   int logprobs_check(const LlmRows& r, const LlmTail& t);
   std::array<TailCopy, 6> tail_copies(const LlmTail& t, int n_want);
+  void contrast_meta(const LlmRows& r, const LlmTail& t, const std::vector<int32_t>& h_pos, const std::vector<int32_t>& h_slot, int rows);
   int tail_launch(const LlmTail& t, int w0, int m);
   int kv_reorder(int n, const int32_t* dst, const int32_t* src, int lo, int hi);
   int kv_copy(int dst, int src, int lo, int hi);
@@ -648,7 +693,7 @@ inline int LlmCached::head(int w0, int m) {
   return lin_norm(wsel, final_norm, wnorm, *lm_head, logits, (int64_t)vpad(), m, VSTAR_EPI_NONE);
 }
 
-// ---- the five tails, one switch per stage: checks, host <-> device copies, launch ----
+// ---- the six tails, one switch per stage: checks, host <-> device copies, launch ----
 // (forward() validates the rows first, then the tail: of two simultaneous faults the row fault is the one reported)
 inline int LlmCached::tail_check(const LlmRows& r, const LlmTail& t) {
   const int n_want = r.n_want, V = cfg.vocab;
@@ -691,8 +736,117 @@ inline int LlmCached::tail_check(const LlmRows& r, const LlmTail& t) {
       }
       break;
     }
+    case LlmTail::CONTRAST: RC(contrast_check(r, t.con)); break;
   }
   return 0;
+}
+
+// The history and the scratch of the contrast tail, by the first call that carries it: two allocations, the second one's failure
+// frees the first, so a failed allocation leaves nothing behind and the engine as it was.
+inline int LlmCached::contrast_alloc() {
+  if (c_hist) return 0;
+  const size_t S = (size_t)cfg.max_slots * cfg.max_ctx, H = (size_t)cfg.hidden, W = (size_t)max_want;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_hist = up(S * H * 2), b_rn = up(S * 4);
+  const size_t b_cand = up(W * H * 2), b_w4 = up(W * 4), b_top = up(W * VSTAR_CONTRAST_MAX_K * 4), b_meta = up(c_meta_bytes());
+  char *hist = nullptr, *blk = nullptr;
+  if (hipMalloc(&hist, b_hist + b_rn) != hipSuccess) { (void)hipGetLastError(); set_error("contrastive search: no memory for the hidden history (max_slots * max_ctx * (2 * hidden + 4) bytes)"); return VSTAR_ERR_NOMEM; }
+  if (hipMalloc(&blk, b_cand + 4 * b_w4 + 2 * b_top + b_meta) != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(hist);
+    set_error("contrastive search: no memory for the candidate buffers");
+    return VSTAR_ERR_NOMEM;
+  }
+  e->allocs.push_back(hist);
+  e->allocs.push_back(blk);
+  c_hist_rn = (float*)(hist + b_hist);
+  char* q = blk;
+  c_cand = (lp_t*)q; q += b_cand;
+  c_cand_rn = (float*)q; q += b_w4;
+  c_prob = (float*)q; q += b_w4;
+  c_pen = (float*)q; q += b_w4;
+  c_sel = (int32_t*)q; q += b_w4;
+  c_ntok = (int32_t*)q; q += b_top;
+  c_nprob = (float*)q; q += b_top;
+  c_meta = q;
+  c_meta_host.assign(c_meta_bytes(), 0);
+  hist_len.assign((size_t)cfg.max_slots, 0);
+  c_hist = (lp_t*)hist;                          // (last: c_hist != null means all of the above exists)
+  return 0;
+}
+
+// The contrast tail's rules (include/vstar_vqa.h), before any device work; the messages name the field.
+inline int LlmCached::contrast_check(const LlmRows& r, const LlmContrastArgs& a) {
+  auto bad = [&](const std::string& m) { e->set_error(m); return VSTAR_ERR_INVALID; };
+  const bool step = a.goff != nullptr;
+  const char* fn = step ? "forward_contrast_step: " : "forward_contrast_begin: ";
+  if (r.n_want < 1 || !a.next_tok || !a.next_prob) return bad(std::string(fn) + "no wanted rows / next_tok / next_prob");
+  if (a.k < 2 || a.k > VSTAR_CONTRAST_MAX_K || a.k > cfg.vocab) return bad(std::string(fn) + (step ? "k_next" : "k") + " must be in [2, 32] and <= llm_vocab");
+  if (step) {
+    if (!a.sel) return bad(std::string(fn) + "no sel_out");
+    if (r.n_want != r.nseq) return bad(std::string(fn) + "n_want: every sequence has exactly one row and all rows are wanted");
+    for (int i = 0; i < r.nseq; ++i) {
+      if (r.row_off[i + 1] - r.row_off[i] != 1) return bad(std::string(fn) + "row_off: every sequence has exactly one row");
+      if (r.want[i] != i) return bad(std::string(fn) + "want: wanted row j must be row j");
+    }
+    if (const char* m = vstar_contrast_check(r.n_want, cfg.vocab, a.n_groups, a.goff, a.cand_prob, a.alpha, a.k)) return bad(std::string(fn) + m);
+  }
+  RC(contrast_alloc());
+  std::vector<char> used((size_t)cfg.max_slots, 0);      // 1: some row's kv_slot, 2: an owner that no row writes (yet)
+  for (int i = 0; i < r.nseq; ++i) {
+    if (used[r.kv_slot[i]] == 1) return bad(std::string(fn) + "kv_slot: the slots of a call must be pairwise distinct");
+    used[r.kv_slot[i]] = 1;
+  }
+  if (!step) {
+    for (int i = 0; i < r.nseq; ++i) {
+      if (r.prefix_slot[i] != r.kv_slot[i]) return bad(std::string(fn) + "prefix_slot must equal kv_slot");
+      if (r.past_len[i] != 0 && r.past_len[i] != hist_len[r.kv_slot[i]])
+        return bad(std::string(fn) + "past_len must be 0 (a fresh sequence) or the slot's history length " + std::to_string(hist_len[r.kv_slot[i]]));
+      if (r.past_len[i] != 0 && anc_flag[r.kv_slot[i]]) return bad(std::string(fn) + "kv_slot: a beam-reordered slot has no history");
+    }
+    return 0;
+  }
+  for (int g = 0; g < a.n_groups; ++g) {
+    const int own = r.prefix_slot[a.goff[g]], L = r.past_len[a.goff[g]];
+    for (int j = a.goff[g]; j < a.goff[g + 1]; ++j) {
+      if (r.prefix_slot[j] != own) return bad(std::string(fn) + "prefix_slot: the rows of a group share one owner slot");
+      if (r.past_len[j] != L) return bad(std::string(fn) + "past_len: the rows of a group share one past_len");
+    }
+    if (L < 1 || L != hist_len[own])
+      return bad(std::string(fn) + "past_len must equal the owner's history length " + std::to_string(hist_len[own]) +
+                 " (a forward() that rewound the slot invalidated the history behind it; begin again)");
+    if (anc_flag[own]) return bad(std::string(fn) + "prefix_slot: a beam-reordered slot has no history");
+    bool mine = false;
+    for (int j = a.goff[g]; j < a.goff[g + 1]; ++j) mine = mine || r.kv_slot[j] == own;
+    if (!mine) {              // (an owner one of its own rows writes is covered by the distinct kv_slots)
+      if (used[own]) return bad(std::string(fn) + "prefix_slot: an owner slot is another group's owner or candidate slot");
+      used[own] = 2;
+    }
+  }
+  return 0;
+}
+
+// The contrast tail's device metadata (c_meta_host; forward() uploads it with the row metadata), from the physical rows of the call.
+inline void LlmCached::contrast_meta(const LlmRows& r, const LlmTail& t, const std::vector<int32_t>& h_pos, const std::vector<int32_t>& h_slot, int rows) {
+  const LlmContrastArgs& a = t.con;
+  char* hb = c_meta_host.data();
+  int64_t* dst = c_meta_at<int64_t>(hb, 0);
+  if (!a.goff) {
+    for (int q = 0; q < rows; ++q) dst[q] = h_pos[q] >= 0 ? (int64_t)h_slot[q] * cfg.max_ctx + h_pos[q] : -1;
+    return;
+  }
+  int64_t* hbase = c_meta_at<int64_t>(hb, 1);
+  int32_t *goff = c_meta_at<int32_t>(hb, 2), *hlen = c_meta_at<int32_t>(hb, 3), *owner = c_meta_at<int32_t>(hb, 4), *pos = c_meta_at<int32_t>(hb, 5),
+          *rowslot = c_meta_at<int32_t>(hb, 6);
+  for (int j = 0; j < r.n_want; ++j) { dst[j] = j; rowslot[j] = r.kv_slot[j]; }
+  c_max_group = 0; c_max_len = 0;
+  for (int g = 0; g < a.n_groups; ++g) {
+    const int own = r.prefix_slot[a.goff[g]], L = r.past_len[a.goff[g]];
+    goff[g] = a.goff[g]; hbase[g] = (int64_t)own * cfg.max_ctx; hlen[g] = L; owner[g] = own; pos[g] = L;
+    c_max_group = std::max(c_max_group, a.goff[g + 1] - a.goff[g]);
+    c_max_len = std::max(c_max_len, L);
+  }
+  goff[a.n_groups] = a.goff[a.n_groups];
 }
 
 // The edits of a call, validated next to its tail (after the rows: the row fault is the one reported) and before any device work;
@@ -703,6 +857,7 @@ inline int LlmCached::edits_check(const LlmRows& r, const LlmTail& t, const LlmE
                  "log-sum-exp is that of the UNEDITED row; editing the logits ahead of the beam select would compute something else");
     return VSTAR_ERR_INVALID;
   }
+  if (t.kind == LlmTail::CONTRAST) { e->set_error("logits edits with the contrast tail are not supported (open follow-up)"); return VSTAR_ERR_INVALID; }
   if (t.kind == LlmTail::SCORE) {
     e->set_error("logits edits with the scoring tail are not supported: a target's likelihood under edited logits has no reference meaning");
     return VSTAR_ERR_INVALID;
@@ -734,6 +889,7 @@ inline int LlmCached::logprobs_check(const LlmRows& r, const LlmTail& t) {
     e->set_error("log-probabilities with the beam tail are not supported: the beam candidates already carry their scores");
     return VSTAR_ERR_INVALID;
   }
+  if (t.kind == LlmTail::CONTRAST) { e->set_error("log-probabilities with the contrast tail are not supported (open follow-up)"); return VSTAR_ERR_INVALID; }
   if (t.kind == LlmTail::SCORE) {
     e->set_error("log-probabilities with the scoring tail are not supported: it already returns the target's nll and rank");
     return VSTAR_ERR_INVALID;
@@ -776,6 +932,12 @@ inline std::array<LlmCached::TailCopy, 6> LlmCached::tail_copies(const LlmTail& 
     case LlmTail::VERIFY:
       return {{{d_sparams, t.params, nullptr, np}, {d_goff, v.goff, nullptr, (size_t)(v.n_groups + 1) * 4}, {d_vdraft, v.draft, nullptr, nw4},
                {d_vacc, nullptr, v.n_accept, (size_t)v.n_groups * 4}, {d_vtok, nullptr, v.tokens, nw4}, {d_swarp, t.warpers, nullptr, nwp}}};
+    case LlmTail::CONTRAST: {    // (the metadata block goes out with the row metadata: contrast_meta)
+      const LlmContrastArgs& c = t.con;
+      const size_t ng = c.goff ? (size_t)c.n_groups : (size_t)n_want, nk4 = ng * c.k * 4;
+      return {{{c_prob, c.cand_prob, nullptr, nw4}, {c_sel, nullptr, c.sel, ng * 4}, {c_ntok, nullptr, c.next_tok, nk4},
+               {c_nprob, nullptr, c.next_prob, nk4}, {c_pen, nullptr, c.pen_out, nw4}}};
+    }
   }
   return {};
 }
@@ -800,6 +962,28 @@ inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
       LCHK(vstar_verify_rows_lp(logits, m, V, ld, d_goff, t.verify.n_groups, d_vdraft, t.params ? d_sparams : nullptr,
                                 t.warpers ? d_swarp : nullptr, d_argmax, d_vflag, d_vacc, d_vtok, e->stream));
       break;
+    case LlmTail::CONTRAST: {
+      const LlmContrastArgs& c = t.con;
+      const int H = cfg.hidden;
+      const int64_t* dst = c_meta_at<int64_t>(c_meta, 0);
+      if (!c.goff) {           // begin: every new row's final-norm row into its slot's history; the wanted rows' next candidates
+        LCHK(vstar_contrast_fill_lp(lx, nullptr, final_norm, cfg.rms_eps, c_fill_rows, H, dst, c_hist, c_hist_rn, e->stream));
+        LCHK(vstar_contrast_topk_lp(logits, m, V, ld, c.k, c_ntok, c_nprob, e->stream));
+        break;
+      }
+      const vstar_contrast_groups gr{c.n_groups, c_max_group, c_max_len, c_meta_at<int32_t>(c_meta, 2), c_meta_at<int64_t>(c_meta, 1),
+                                     c_meta_at<int32_t>(c_meta, 3)};
+      LCHK(vstar_contrast_fill_lp(lx, d_want, final_norm, cfg.rms_eps, m, H, dst, c_cand, c_cand_rn, e->stream));
+      c_cand_rows = m;
+      LCHK(vstar_contrast_penalty_lp(c_cand, c_cand_rn, m, H, c_hist, c_hist_rn, gr, c_pen, e->stream));
+      LCHK(vstar_contrast_select_lp(logits, m, V, ld, c_cand, c_cand_rn, H, c_prob, c_pen, c.alpha, c.k, c_hist, c_hist_rn, gr, c_sel, c_ntok,
+                                    c_nprob, e->stream));
+      vstar_contrast_kv ck{kv.l0.k, kv.l0.v, kv.l0.ks, kv.l0.vs, kv.l0.fmt == KV_FMT_MXFP8 ? 1 : 2, kv.layers, cfg.heads, cfg.max_ctx,
+                           kv.layer_stride, kv.l0.slot_stride};
+      LCHK(vstar_contrast_adopt(ck, c.n_groups, gr.goff, c_sel, c_meta_at<int32_t>(c_meta, 6), c_meta_at<int32_t>(c_meta, 4),
+                                c_meta_at<int32_t>(c_meta, 5), e->stream));
+      break;
+    }
   }
   return 0;
 }
@@ -889,6 +1073,13 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   LCHK(hipMemcpyAsync(d_row_seq, h_seq.data(), (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipMemcpyAsync(d_seq, h_seqmeta.data(), h_seqmeta.size() * 4, hipMemcpyHostToDevice, e->stream));
   if (n_want) LCHK(hipMemcpyAsync(d_want, h_want.data(), (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+  if (tail.kind == LlmTail::CONTRAST) {
+    contrast_meta(rw, tail, h_pos, h_slot, rows);
+    c_fill_rows = rows;
+    LCHK(hipMemcpyAsync(c_meta, c_meta_host.data(), c_meta_host.size(), hipMemcpyHostToDevice, e->stream));
+  } else if (c_hist) {         // host arithmetic only: the history of a slot ends where this call starts writing its K/V rows
+    for (int i = 0; i < nseq; ++i) hist_lower(kv_slot[i], past_len[i]);
+  }
   const std::array<TailCopy, 6> copies = tail_copies(tail, n_want);
   for (const TailCopy& x : copies)
     if (x.in && x.bytes) LCHK(hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, e->stream));
@@ -932,6 +1123,11 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
     }
   }
   LCHK(hipStreamSynchronize(e->stream));
+  if (tail.kind == LlmTail::CONTRAST) {          // the histories now describe: begin — the slot up to its new rows; step — the owner up to
+    const LlmContrastArgs& a = tail.con;         // the winner's row, and nothing of a candidate slot that is not its group's owner
+    for (int i = 0; i < nseq; ++i) hist_len[kv_slot[i]] = a.goff ? 0 : past_len[i] + (row_off[i + 1] - row_off[i]);
+    for (int g = 0; a.goff && g < a.n_groups; ++g) hist_len[prefix_slot[a.goff[g]]] = past_len[a.goff[g]] + 1;
+  }
   float ms = 0;
   if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) last_ms = ms;
   e->collect_profile();
@@ -960,7 +1156,7 @@ inline int LlmCached::kv_reorder(int n, const int32_t* dst, const int32_t* src, 
   LCHK(hipMemcpyAsync(d_reo, ds.data(), ds.size() * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(kv_anc_reorder(d_anc, d_anc_tmp, d_reo, d_reo + n, n, lo, hi, c.max_ctx, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
-  for (int i = 0; i < n; ++i) anc_flag[dst[i]] = 1;
+  for (int i = 0; i < n; ++i) { anc_flag[dst[i]] = 1; hist_lower(dst[i], lo); }
   return 0;
 }
 
@@ -978,6 +1174,7 @@ inline int LlmCached::kv_copy(int dst, int src, int lo, int hi) {
   LCHK(kv_anc_fill(d_anc, dst, dst, 0, c.max_ctx, c.max_ctx, e->stream));
   LCHK(hipStreamSynchronize(e->stream));
   anc_flag[dst] = 0;
+  hist_lower(dst, lo);
   return 0;
 }
 
@@ -1085,6 +1282,7 @@ inline int LlmCached::decode_greedy(int n, const int32_t* first, const int32_t* 
     if (!fin[i]) { ++alive; max_steps = std::max(max_steps, caps[i] - 1); }
   }
   if (alive == 0) return 0;                             // every answer is its prefill's arg-max alone: no decode step at all
+  for (int i = 0; i < n; ++i) hist_lower(i, past[i]);
   LCHK(hipSetDevice(e->device));
   if (!d_dec_ctl) RC(e->dalloc(&d_dec_ctl, (size_t)1 + 3 * DEC_BATCH_MAX));
   if (!h_dec_log) {

@@ -23,8 +23,7 @@ using rowlse::bits2f;
 using rowlse::CACHE;
 using rowlse::THREADS;
 using rowlse::WAVES;
-using rowsel::block_scan;
-using rowsel::select_bin;
+using rowsel::value_key;
 constexpr int MAX_VOCAB = 1 << 22;
 constexpr int MAX_TOP = VSTAR_LOGPROB_MAX_TOP;
 
@@ -37,14 +36,6 @@ struct LogprobSmem : rowlse::Scratch {
   uint32_t pick_key[MAX_TOP];
   int32_t pick_idx[MAX_TOP];
 };
-
-// order-preserving 16-bit key of the VALUE of logit bits b: NaN -> -inf, -0 -> +0
-template <bool BF16> __device__ __forceinline__ uint32_t value_key(uint32_t b) {
-  constexpr uint32_t NEG_INF = BF16 ? 0xff80u : 0xfc00u;
-  if ((b & 0x7fffu) > (NEG_INF & 0x7fffu)) b = NEG_INF;
-  if (b == 0x8000u) b = 0;
-  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
-}
 
 template <bool BF16, bool CACHED>
 __global__ __launch_bounds__(THREADS) void logprob_rows_kernel(const uint16_t* __restrict__ x, int vocab, int64_t ld,
@@ -95,39 +86,9 @@ __global__ __launch_bounds__(THREADS) void logprob_rows_kernel(const uint16_t* _
     __syncthreads();                                 // (sm.wu is the scans' scratch below)
   }
   if (!n_top) return;
-  // ---- K_T: the n-th largest key (both bins exist: n <= vocab) ----
+  // ---- K_T and the picks (row_select.hpp; both bins exist: n <= vocab) ----
   const uint32_t n = (uint32_t)(n_top < vocab ? n_top : vocab);
-  int hb, lb;
-  uint32_t above, a2;
-  select_bin(sm, n, hb, above);
-  for (int i = tid; i < vocab; i += THREADS) {
-    const uint32_t key = value_key<BF16>(raw(i));
-    if ((int)(key >> 8) == hb) atomicAdd(&sm.hist[key & 255u], 1u);
-  }
-  select_bin(sm, n - above, lb, a2);
-  const uint32_t kt = ((uint32_t)hb << 8) | (uint32_t)lb;
-  // ---- pick: key > K_T, then the lowest-index ties at K_T, in index order over thread-contiguous chunks ----
-  const int C = (vocab + THREADS - 1) / THREADS;
-  const int c0 = tid * C < vocab ? tid * C : vocab, c1 = c0 + C < vocab ? c0 + C : vocab;
-  uint32_t n_gt = 0, n_eq = 0;
-  for (int i = c0; i < c1; ++i) {
-    const uint32_t key = value_key<BF16>(raw(i));
-    n_gt += key > kt;
-    n_eq += key == kt;
-  }
-  uint32_t gt_excl, gt_tot, eq_excl, eq_tot;
-  block_scan(sm, n_gt, gt_excl, gt_tot);
-  block_scan(sm, n_eq, eq_excl, eq_tot);
-  const uint32_t need_eq = n - gt_tot;               // gt_tot < n <= gt_tot + eq_tot
-  if (n_gt || (n_eq && eq_excl < need_eq)) {
-    uint32_t pg = gt_excl, pe = eq_excl;
-    for (int i = c0; i < c1; ++i) {
-      const uint32_t key = value_key<BF16>(raw(i));
-      if (key > kt) { sm.pick_key[pg] = key; sm.pick_idx[pg] = i; ++pg; }
-      else if (key == kt && pe < need_eq) { sm.pick_key[gt_tot + pe] = key; sm.pick_idx[gt_tot + pe] = i; ++pe; }
-    }
-  }
-  __syncthreads();
+  rowsel::pick_top<BF16>(sm, raw, vocab, n);
   // ---- sort: each pick's rank among the n under (key descending, index ascending) ----
   if (tid >= n_top) return;
   float* ol = top_lp + (int64_t)row * n_top;
@@ -137,13 +98,8 @@ __global__ __launch_bounds__(THREADS) void logprob_rows_kernel(const uint16_t* _
     ot[tid] = -1;
     return;
   }
-  const uint32_t ki = sm.pick_key[tid];
   const int32_t ii = sm.pick_idx[tid];
-  uint32_t r = 0;
-  for (uint32_t j = 0; j < n; ++j) {
-    const uint32_t kj = sm.pick_key[j];
-    r += (kj > ki) || (kj == ki && sm.pick_idx[j] < ii);
-  }
+  const uint32_t r = rowsel::pick_rank(sm, n, (uint32_t)tid);
   ot[r] = ii;
   ol[r] = (float)((double)bits2f<BF16>(raw(ii)) - lse);
 }

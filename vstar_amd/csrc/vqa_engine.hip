@@ -455,6 +455,76 @@ int vstar_vqa_forward_verify_warp(vstar_vqa_handle* h, int nseq, const int32_t* 
                         LlmTail::verify_rows(v, params, warpers).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
 }
 
+// contrastive search: the prefill that fills the hidden history, and the candidate step
+int vstar_vqa_forward_contrast_begin(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                     const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want, int k,
+                                     int32_t* next_tok, float* next_prob) {
+  if (int rc = vqa_ready(h)) return rc;
+  LlmContrastArgs a;
+  a.k = k; a.next_tok = next_tok; a.next_prob = next_prob;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::contrast(a));
+}
+
+int vstar_vqa_forward_contrast_step(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                    const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                    const int32_t* group_off, int n_groups, const float* cand_prob, float alpha, int k_next,
+                                    int32_t* sel_out, int32_t* next_tok, float* next_prob, float* penalty_out) {
+  if (int rc = vqa_ready(h)) return rc;
+  if (!group_off) { h->set_error("forward_contrast_step: no group_off"); return VSTAR_ERR_INVALID; }
+  LlmContrastArgs a;
+  a.k = k_next; a.next_tok = next_tok; a.next_prob = next_prob; a.n_groups = n_groups; a.goff = group_off; a.cand_prob = cand_prob;
+  a.alpha = alpha; a.sel = sel_out; a.pen_out = penalty_out;
+  return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want}, LlmTail::contrast(a));
+}
+
+int vstar_vqa_op_contrast(const void* dev_logits, int dtype, int rows, int vocab, int64_t ld, const void* dev_cand_hidden, int hidden,
+                          void* dev_hist, float* dev_hist_rnorm, int n_groups, int cap, const int32_t* hist_len, const int32_t* group_off,
+                          const float* cand_prob, float alpha, int k_next, int32_t* sel_out, int32_t* next_tok, float* next_prob,
+                          float* penalty_out) {
+  const char* m = nullptr;
+  if (!dev_logits) m = "dev_logits is NULL";
+  else if (!dev_cand_hidden) m = "dev_cand_hidden is NULL";
+  else if (!dev_hist || !dev_hist_rnorm) m = "dev_hist / dev_hist_rnorm is NULL";
+  else if (!hist_len) m = "hist_len is NULL";
+  else if (!sel_out || !next_tok || !next_prob) m = "sel_out / next_tok / next_prob is NULL";
+  else if (dtype != VSTAR_F16 && dtype != VSTAR_BF16) m = "dtype must be F16 or BF16";
+  else if (ld < vocab) m = "ld must be >= vocab";
+  else if (hidden <= 0 || hidden % 8) m = "hidden must be a positive multiple of 8";
+  else m = vstar_contrast_check(rows, vocab, n_groups, group_off, cand_prob, alpha, k_next);
+  int max_len = 0, max_group = 0;
+  for (int g = 0; !m && g < n_groups; ++g) {
+    if (hist_len[g] < 1 || hist_len[g] >= cap) m = "hist_len must be in [1, cap)";
+    max_len = std::max(max_len, hist_len[g]);
+    max_group = std::max(max_group, group_off[g + 1] - group_off[g]);
+  }
+  if (m) { tls_error() = std::string("vstar_vqa_op_contrast: ") + m; return VSTAR_ERR_INVALID; }
+  hipError_t e = hipSuccess;
+  std::vector<int64_t> hbase((size_t)n_groups);
+  for (int g = 0; g < n_groups; ++g) hbase[(size_t)g] = (int64_t)g * cap;
+  const size_t nk = (size_t)n_groups * k_next;
+  OpBuf<int32_t> d_goff(e, (size_t)n_groups + 1), d_hlen(e, n_groups), d_sel(e, n_groups), d_nt(e, nk);
+  OpBuf<int64_t> d_hbase(e, n_groups);
+  OpBuf<float> d_rn(e, rows), d_prob(e, rows), d_pen(e, rows), d_np(e, nk);
+  d_goff.upload(group_off);
+  d_hlen.upload(hist_len);
+  d_hbase.upload(hbase.data());
+  d_prob.upload(cand_prob);
+  const vstar_contrast_groups gr{n_groups, max_group, max_len, d_goff, d_hbase, d_hlen};
+  const bool bf = dtype == VSTAR_BF16;
+  const uint16_t* cand = (const uint16_t*)dev_cand_hidden;
+  if (e == hipSuccess) e = (bf ? vstar_contrast_rnorm_bf16 : vstar_contrast_rnorm_f16)(cand, rows, hidden, d_rn, nullptr);
+  if (e == hipSuccess) e = (bf ? vstar_contrast_penalty_bf16 : vstar_contrast_penalty_f16)(cand, d_rn, rows, hidden, (const uint16_t*)dev_hist, dev_hist_rnorm, gr, d_pen, nullptr);
+  if (e == hipSuccess)
+    e = (bf ? vstar_contrast_select_bf16 : vstar_contrast_select_f16)((const uint16_t*)dev_logits, rows, vocab, ld, cand, d_rn, hidden, d_prob, d_pen, alpha, k_next,
+                                                                      (uint16_t*)dev_hist, dev_hist_rnorm, gr, d_sel, d_nt, d_np, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  d_sel.download(sel_out);
+  d_nt.download(next_tok);
+  d_np.download(next_prob);
+  d_pen.download(penalty_out);
+  return op_result(e, "vstar_vqa_op_contrast");
+}
+
 int64_t vstar_vqa_logit_edit_capacity(const vstar_vqa_handle* h) { return h ? h->run.edit_capacity() : 0; }
 
 int vstar_vqa_kv_reorder(vstar_vqa_handle* h, int n, const int32_t* dst_slot, const int32_t* src_slot, int lo, int hi) {
@@ -912,7 +982,17 @@ int64_t vstar_vqa_debug_read(vstar_vqa_handle* h, const char* name, float* out, 
   if (n.rfind("kv:", 0) == 0) return debug_read_kv(h, n, out, cap);
   const lp_t* src = nullptr;
   int64_t cnt = 0;
-  if (n == "features") { src = h->feats; cnt = (int64_t)h->cfg.max_images * (h->clip.P + h->cfg.pcv_latents) * h->cfg.llm_hidden; }
+  if (n.rfind("contrast_", 0) == 0) {      // the hidden history of a slot [hist_len, hidden] / the last step's candidate rows [rows, hidden]
+    int slot = -1;
+    char tail = 0;
+    if (!h->run.c_hist) { h->set_error("debug_read: " + n + ": no contrast call has run on this engine"); return VSTAR_ERR_STATE; }
+    if (n == "contrast_cand") { src = h->run.c_cand; cnt = (int64_t)h->run.c_cand_rows * h->cfg.llm_hidden; }
+    else if (sscanf(n.c_str(), "contrast_hist:%d%c", &slot, &tail) == 1 && slot >= 0 && slot < h->cfg.max_slots) {
+      src = h->run.c_hist + (int64_t)slot * h->cfg.max_ctx * h->cfg.llm_hidden;
+      cnt = (int64_t)h->run.hist_len[(size_t)slot] * h->cfg.llm_hidden;
+    } else { h->set_error("debug_read: bad contrast tensor name (contrast_hist:<slot>, contrast_cand): " + n); return VSTAR_ERR_INVALID; }
+  }
+  else if (n == "features") { src = h->feats; cnt = (int64_t)h->cfg.max_images * (h->clip.P + h->cfg.pcv_latents) * h->cfg.llm_hidden; }
   else if (n == "clip_hidden") { src = h->clip.x; cnt = (int64_t)h->enc_batch * h->clip.N * h->clip.hidden; }
   else { h->set_error("unknown debug tensor: " + n); return VSTAR_ERR_INVALID; }
   if (cnt > cap) cnt = cap;

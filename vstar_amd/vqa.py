@@ -118,6 +118,39 @@ def check_spec_tokens(d) -> int:
     return int(d)
 
 
+CONTRAST_MAX_K = 32      # VSTAR_VQA_MAX_TOP_LOGPROBS: the candidates of one contrastive-search step
+
+
+def check_contrast(penalty_alpha, top_k, *, sampled: bool, num_beams: int, speculative: int, rules, logprobs,
+                   sampled_name: str = "temperature > 0") -> Optional[float]:
+    """The contrastive-search arguments of free_form_batch / generate (HF: penalty_alpha > 0, top_k > 1, greedy, one beam): None when
+    the mode is off (penalty_alpha None or 0), else alpha.  ValueError for a value out of range or a combination that contradicts
+    itself, NotImplementedError for the combinations that are follow-ups."""
+    if penalty_alpha is None:
+        return None
+    alpha = float(penalty_alpha)
+    if not 0 <= alpha <= 1:
+        raise ValueError(f"penalty_alpha must be in [0, 1] (None / 0 = off), got {penalty_alpha!r}")
+    if alpha == 0:
+        return None
+    if top_k is None or isinstance(top_k, bool) or int(top_k) != top_k or not 2 <= int(top_k) <= CONTRAST_MAX_K:
+        raise ValueError(f"top_k is the number of candidates of contrastive search (penalty_alpha > 0) and must be an integer in "
+                         f"[2, {CONTRAST_MAX_K}], got {top_k!r} (the sampling default 50 has to be overridden, as with HF generate)")
+    if speculative:
+        raise ValueError("speculative decoding (speculative > 0) cannot be combined with contrastive search (penalty_alpha > 0)")
+    if sampled:
+        raise NotImplementedError(f"contrastive search (penalty_alpha > 0) with {sampled_name} is not implemented: HF's contrastive "
+                                  "search is a greedy mode")
+    if num_beams > 1:
+        raise NotImplementedError("contrastive search (penalty_alpha > 0) with num_beams > 1 is not implemented")
+    if rules is not None and rules.active:
+        raise NotImplementedError("contrastive search (penalty_alpha > 0) with logits rules (repetition_penalty, no_repeat_ngram_size, "
+                                  "bad_words_ids, min_new_tokens, suppress_tokens, allowed_tokens_fn) is not implemented: a follow-up")
+    if logprobs is not None:
+        raise NotImplementedError("contrastive search (penalty_alpha > 0) with logprobs is not implemented: a follow-up")
+    return alpha
+
+
 def _warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff) -> dict:
     """The `warpers=` keyword of the engine's sampled calls; empty when all four are off (the plain call)."""
     w = warper_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
@@ -239,7 +272,7 @@ class VQA_LLM:
                             object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None, speculative=0,
                             draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
                             suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
-                            epsilon_cutoff=None, eta_cutoff=None) -> str:
+                            epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
         so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
@@ -252,20 +285,22 @@ class VQA_LLM:
         logits processors of these names (allowed_tokens_fn = prefix_allowed_tokens_fn), applied to the logits on the device ahead
         of the pick (vstar_amd/logits.py); the defaults mean no rules, and num_beams > 1 with a rule raises.
         logprobs = n in [0, 32]: self.generated_logprobs[0] then holds, per generated token, its log-probability and rank and the n
-        best alternatives (`TokenLogprobs`), aligned with self.generated_ids[0]; the returned text is unchanged."""
+        best alternatives (`TokenLogprobs`), aligned with self.generated_ids[0]; the returned text is unchanged.
+        penalty_alpha in (0, 1] (temperature 0, num_beams 1): HF 4.31 contrastive search with top_k (2 .. 32, to be given) candidates
+        per step, the degeneration penalty and the pick on the device (`contrastive_decode`); None / 0: off."""
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
                                           objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
                                     top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn,
                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                     bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                                     allowed_tokens_fn=allowed_tokens_fn, logprobs=logprobs, min_p=min_p, typical_p=typical_p,
-                                    epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)[0]
+                                    epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, penalty_alpha=penalty_alpha)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
                         seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, speculative: int = 0,
                         draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
                         suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
-                        epsilon_cutoff=None, eta_cutoff=None) -> List[str]:
+                        epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
         single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
@@ -278,7 +313,10 @@ class VQA_LLM:
         picked from and the n best alternatives, computed on the device; None (default): self.generated_logprobs is
         None and the engine calls are the plain ones.  The returned texts are the same either way.
         min_p, typical_p, epsilon_cutoff, eta_cutoff (temperature > 0; ignored by the greedy decode): the further warpers of
-        DESIGN.md §8.10 for every sample; all off (the default): the engine calls are the plain ones."""
+        DESIGN.md §8.10 for every sample; all off (the default): the engine calls are the plain ones.
+        penalty_alpha in (0, 1] (temperature 0, num_beams 1, no rules, no logprobs, not speculative): contrastive search with
+        top_k (2 .. 32) candidates, the k candidate slots of sample i in KV slots i*k .. i*k+k-1 (n*k <= max_slots), one group per
+        sample in every step's forward (`contrastive_decode`); None / 0 (default): off, every call is as before."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if num_beams < 1:
@@ -301,6 +339,12 @@ class VQA_LLM:
         if logprobs is not None and num_beams > 1:
             raise NotImplementedError("logprobs with beam search (num_beams > 1) is not implemented: beam hypotheses carry their "
                                       "own scores, and exposing those is a follow-up")
+        alpha = check_contrast(penalty_alpha, top_k, sampled=temperature > 0, num_beams=num_beams, speculative=speculative,
+                               rules=rules, logprobs=logprobs)
+        k_slots = int(top_k) if alpha is not None else num_beams      # KV slots per sample
+        if alpha is not None and n * k_slots > cfg.max_slots:
+            raise ValueError(f"{n} samples x {k_slots} candidates need {n * k_slots} KV slots; the engine has max_slots="
+                             f"{cfg.max_slots} (build it with a larger VQAConfig.max_slots)")
         warp = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         if temperature > 0:
             warper_params(**warp)                      # (validated before any engine work)
@@ -313,11 +357,13 @@ class VQA_LLM:
             img_slots, obj_slots = self._encode(s["image"], crops, fslot)
             fslot += 1 + len(obj_slots)
             ids, rows = self._question_rows(s["question"], img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))
-            seqs.append(Seq(rows, kv_slot=i * num_beams))
+            seqs.append(Seq(rows, kv_slot=i * k_slots))
             lens.append(len(rows))
             id_lens.append(len(ids))
             text_ids.append([t for t in ids if t >= 0])
-        if speculative:
+        if alpha is not None:
+            res = self.contrastive_decode(seqs, lens, max_new_tokens, alpha, k_slots)
+        elif speculative:
             res = self.speculative_decode(seqs, lens, text_ids, max_new_tokens, speculative,
                                           params if temperature > 0 else None, draft_fn, rules, logprobs=logprobs,
                                           **(warp if temperature > 0 else {}))
@@ -496,6 +542,40 @@ class VQA_LLM:
             for i in live:
                 pos[i] += 1
         return [b.finalize(num_return_sequences) for b in bs]
+
+    def contrastive_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, alpha: float, k: int) -> List[List[int]]:
+        """model.generate(penalty_alpha=alpha, top_k=k, do_sample=False) (HF 4.31 contrastive_search) for every
+        sequence: seqs[i] (the prompt rows) is prefilled into its slot seqs[i].kv_slot, the OWNER, and owns the slots kv_slot ..
+        kv_slot+k-1.  The begin call fills the owner's hidden history and returns the k most probable first tokens; every further
+        engine call feeds the k candidates of every unfinished sequence as k one-row forks of its owner — candidate c writes slot
+        kv_slot+c — and on the device takes their degeneration penalty against the history, picks the winner, appends its hidden
+        row, moves its K/V row into the owner and returns the winner's index and its k next candidates: one engine call per
+        generated position, T tokens = one prefill + T steps.  alpha = 0 is the greedy decode.  A sequence stops at EOS, at
+        max_new_tokens or when its context is full."""
+        cfg, eng, k = self.cfg, self.engine, int(k)
+        n = len(seqs)
+        if not 0 <= alpha <= 1:
+            raise ValueError(f"alpha must be in [0, 1], got {alpha!r}")
+        if not 2 <= k <= CONTRAST_MAX_K:
+            raise ValueError(f"k must be in [2, {CONTRAST_MAX_K}], got {k}")
+        slots = [[s.kv_slot + c for c in range(k)] for s in seqs]
+        if any(sl[-1] >= cfg.max_slots for sl in slots) or len({x for sl in slots for x in sl}) != n * k:
+            raise ValueError(f"{n} sequences x {k} candidates need {n * k} distinct KV slots below max_slots={cfg.max_slots}")
+        tok, prob = eng.forward_contrast_begin([Seq(list(s.rows), kv_slot=s.kv_slot) for s in seqs], [(i, -1) for i in range(n)], k)
+        cand = {i: (tok[i].copy(), prob[i].copy()) for i in range(n)}
+        out: List[List[int]] = [[] for _ in range(n)]
+        pos = list(lens)
+        live = [i for i in range(n) if max_new_tokens > 0 and pos[i] < cfg.max_ctx]
+        while live:
+            step = [Seq([int(cand[i][0][c])], kv_slot=slots[i][c], past_len=pos[i], prefix_slot=slots[i][0]) for i in live for c in range(k)]
+            sel, ntok, nprob = eng.forward_contrast_step(step, np.arange(len(live) + 1, dtype=np.int32) * k,
+                                                         np.concatenate([cand[i][1] for i in live]), alpha, k)
+            for j, i in enumerate(live):
+                out[i].append(int(cand[i][0][int(sel[j])]))
+                cand[i] = (ntok[j].copy(), nprob[j].copy())
+                pos[i] += 1
+            live = [i for i in live if out[i][-1] != self.eos_token_id and len(out[i]) < max_new_tokens and pos[i] < cfg.max_ctx]
+        return out
 
     def _decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, choose, rules: Optional[LogitRules] = None,
                 histories=None, logprobs=None):

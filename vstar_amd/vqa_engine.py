@@ -336,6 +336,49 @@ class VqaEngine:
             _lib.check_vqa(self.lib.vstar_vqa_forward_verify_edits(self.handle, *args, *tail, ctypes.byref(st)), self.handle)
         return acc[:ng], tok[:nw]
 
+    def forward_contrast_begin(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], k: int):
+        """The prefill of contrastive search (csrc/contrast.hip): `forward` that also writes the final-norm hidden
+        row of every new row into its slot's history (prefix_slot == kv_slot; past_len 0, or the slot's history length for a chunked
+        prefill).  Returns (next_tok int32 [n_want, k], next_prob float32 [n_want, k]): per wanted row the k most probable tokens,
+        sorted by (probability descending, token id ascending)."""
+        args, _keep = self._rows_args(seqs, want)
+        nw, k = args[6], int(k)
+        nt = np.empty((max(nw, 1), max(k, 1)), np.int32)
+        npb = np.empty((max(nw, 1), max(k, 1)), np.float32)
+        _lib.check_vqa(self.lib.vstar_vqa_forward_contrast_begin(self.handle, *args, k, _ptr(nt), _ptr(npb)), self.handle)
+        return nt[:nw, :k], npb[:nw, :k]
+
+    def forward_contrast_step(self, seqs: Sequence[Seq], group_off, cand_prob, alpha: float, k_next: int, penalties: bool = False):
+        """One step of contrastive search: every Seq is ONE candidate row (all rows are wanted), rows group_off[g] ..
+        group_off[g+1]-1 the candidates of group g — continuations of one owner slot (their prefix_slot) at past_len == the owner's
+        history length, each into a kv_slot of its own.  cand_prob[j]: candidate j's probability.  On the device: the degeneration
+        penalty against the owner's hidden history, score = (1 - alpha) p - alpha pen, the pick, the winner's hidden row appended,
+        its K/V row adopted by the owner slot.  Returns (sel int32 [n_groups] — the winner's row in its group, next_tok int32
+        [n_groups, k_next], next_prob float32 [n_groups, k_next]), with penalties=True one more value, pen float32 [n_rows]."""
+        args, _keep = self._rows_args(seqs, [(i, 0) for i in range(len(seqs))])
+        nw, k = args[6], int(k_next)
+        go = np.ascontiguousarray(group_off, np.int32)
+        ng = max(len(go) - 1, 0)
+        cp = self._per_row(cand_prob, np.float32, nw, "candidate probabilities")
+        sel = np.empty((max(ng, 1),), np.int32)
+        nt = np.empty((max(ng, 1), max(k, 1)), np.int32)
+        npb = np.empty((max(ng, 1), max(k, 1)), np.float32)
+        pen = np.empty((max(nw, 1),), np.float32) if penalties else None
+        _lib.check_vqa(self.lib.vstar_vqa_forward_contrast_step(self.handle, *args, _ptr(go), ng, _ptr(cp), float(alpha), k, _ptr(sel),
+                                                                _ptr(nt), _ptr(npb), _ptr(pen)), self.handle)
+        out = (sel[:ng], nt[:ng, :k], npb[:ng, :k])
+        return out + (pen[:nw],) if penalties else out
+
+    def contrast_hist(self, slot: int) -> np.ndarray:
+        """The hidden history of a slot, float32 [hist_len, hidden] (parity tests)."""
+        H = self.cfg.llm_hidden
+        return self.debug_read(f"contrast_hist:{int(slot)}", self.cfg.max_ctx * H).reshape(-1, H)
+
+    def contrast_cand(self) -> np.ndarray:
+        """The candidate hidden rows of the last contrast step, float32 [rows, hidden] (parity tests)."""
+        H = self.cfg.llm_hidden
+        return self.debug_read("contrast_cand", 256 * H).reshape(-1, H)
+
     def kv_reorder(self, dst_slots: Sequence[int], src_slots: Sequence[int], lo: int, hi: int) -> None:
         """Beam reorder without moving K/V: ancestry entries [lo, hi) of dst_slots[i] = those of src_slots[i], all sources read
         before any destination is written (include/vstar_vqa.h)."""

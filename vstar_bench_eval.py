@@ -48,6 +48,11 @@ def parse_args(argv):
                    "question, the mean log-probability of the answer's tokens and the per-token arrays (log-probability, rank, the N most "
                    "likely alternatives), computed on the device (DESIGN.md 8.9), as `freeform_logprobs` of the result record; off "
                    "(default) writes exactly the records without it")
+    p.add_argument("--vqa-penalty-alpha", dest="vqa_penalty_alpha", default=None, type=float, help="alpha in (0, 1]: the free-form pass "
+                   "decodes by contrastive search (HF's penalty_alpha) with --vqa-top-k candidates per step, the degeneration penalty and "
+                   "the pick on the device (DESIGN.md 8.11); off (default) is the greedy decode")
+    p.add_argument("--vqa-top-k", dest="vqa_top_k", default=None, type=int, help="K in [2, 32]: the candidates per step of "
+                   "--vqa-penalty-alpha (each question then takes K KV slots); required with it, ignored without")
     p.add_argument("--engine-comm", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="world > 1 on GPUs: gather the per-step records with the C-ABI's own RCCL communicator on the engine stream "
                    "(vstar_allgather_results) instead of torch.distributed.  auto (default, round 6): used when the communicator comes up "
