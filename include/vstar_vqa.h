@@ -509,6 +509,27 @@ int vstar_vqa_op_embed_rows(const int32_t* host_src, int R, const void* dev_tabl
 /* argmax_rows_lp on dev_x [rows, ld] (ld >= cols) -> host_out [rows]. */
 int vstar_vqa_op_argmax_rows(const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out);
 
+/* Op-level doors of the fp16 PREFILL kernels — the -DVSTAR_LP_F16 build of attention.hip, norm.hip and elementwise.hip that every VQA
+ * prefill, the fp16 CLIP tower and the Perceiver run (tests/test_f16_prefill_gpu.py).  fp16 only, null stream, one launch, synchronise.
+ * Data tensors are DEVICE pointers and every buffer comes with its extent in rows; a violated rule is VSTAR_ERR_INVALID with a message,
+ * before anything is allocated or launched.  The doors do no arithmetic of their own.
+ * attention: attn_forward alone (no RoPE, no grouped sequences) on dev_qkv [qkv_rows >= B * S, 3 * H * D] (q | k | v) -> dev_out
+ * [out_rows >= B * S, H * D], scale 1 / sqrtf(D); D in {64, 128}, causal 0 or 1, 1 <= H <= 256, B * S <= 2^24, S * 3 * H * D * 2 < 2^31. */
+int vstar_vqa_op_attention(const void* dev_qkv, int64_t qkv_rows, void* dev_out, int64_t out_rows, int B, int S, int H, int D, int causal);
+/* layernorm_lp: dev_y [rows, cols] = LN(dev_x[host_row_index ? host_row_index[r] : r]) * dev_gamma [cols] + dev_beta [cols] (nullable);
+ * act 1: exact-erf GELU of the fp16-rounded affine result.  dev_x [x_rows, cols]; host_row_index (nullable, HOST, [rows]) is checked
+ * against x_rows and uploaded by the door; without it x_rows >= rows.  cols % 8 == 0, 8 <= cols <= 4096, 1 <= rows <= 2^20. */
+int vstar_vqa_op_layernorm(const void* dev_x, int64_t x_rows, const void* dev_gamma, const void* dev_beta, void* dev_y, int rows, int cols,
+                           float eps, const int32_t* host_row_index, int act);
+/* rmsnorm_lp (LlamaRMSNorm: gamma * fp16(x * rstd)); arguments and rules as vstar_vqa_op_layernorm. */
+int vstar_vqa_op_rmsnorm(const void* dev_x, int64_t x_rows, const void* dev_gamma, void* dev_y, int rows, int cols, float eps,
+                         const int32_t* host_row_index);
+/* add_bcast: dev_out [rows, cols] = dev_a [rows, cols] + dev_b [b_rows, cols][r % b_rows], one fp32 add rounded once; cols % 8 == 0,
+ * 1 <= b_rows <= rows <= 2^24. */
+int vstar_vqa_op_add_bcast(const void* dev_a, const void* dev_b, void* dev_out, int64_t rows, int cols, int64_t b_rows);
+/* vit_assemble_tokens: dev_tokens [B * (P + 1), C] = cat([dev_cls [C], dev_patch [B, P, C]]) + dev_pos [P + 1, C]; C % 8 == 0. */
+int vstar_vqa_op_vit_assemble_tokens(const void* dev_patch, const void* dev_cls, const void* dev_pos, void* dev_tokens, int B, int P, int C);
+
 /* Diagnostics for the parity tests: "features" = the whole feature table, fp16 -> float; "kv:<layer>:<slot>" = the DECODED K then V
  * cache of that layer and slot as floats [2][llm_heads][max_ctx][128], in every kv_cache_format (an index out of range is an error);
  * "contrast_hist:<slot>" = the hidden history of that slot [hist_len, llm_hidden], "contrast_cand" = the candidate hidden rows of the

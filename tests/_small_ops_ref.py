@@ -94,9 +94,15 @@ def fill(n, value):
 
 
 # ---------------------------------------------------------------- norms
-def layernorm_ex(x, gamma, beta, eps, row_index=None, act=0):
+def rf16(t):
+    """Round through fp16 storage (nearest even, ONE rounding from float64: numpy's conversion); float64 out."""
+    return torch.from_numpy(t.double().numpy().astype("float16")).double()
+
+
+def layernorm_ex(x, gamma, beta, eps, row_index=None, act=0, rnd=rbf):
     """nn.LayerNorm over the last dim of x[row_index] (biased variance); act 1: exact-erf GELU of the bf16-rounded affine result
-    (LayerNorm2d + GELU of the mask head).  float64, before the store rounding."""
+    (LayerNorm2d + GELU of the mask head).  float64, before the store rounding.  rnd: the storage type's rounding (rbf: the bf16
+    build, rf16: the fp16 build of the same kernel)."""
     xs = x.double() if row_index is None else x.double()[row_index.long()]
     mean = xs.mean(-1, keepdim=True)
     var = ((xs - mean) ** 2).mean(-1, keepdim=True)
@@ -104,15 +110,15 @@ def layernorm_ex(x, gamma, beta, eps, row_index=None, act=0):
     if beta is not None:
         y = y + beta.double()
     if act == 1:
-        t = rbf(y)
+        t = rnd(y)
         y = 0.5 * t * (1.0 + torch.erf(t / math.sqrt(2.0)))
     return y
 
 
-def rmsnorm_ex(x, gamma, eps, row_index=None):
-    """LlamaRMSNorm: weight * (x * rsqrt(mean(x^2) + eps)).to(bf16).  float64, before the store rounding."""
+def rmsnorm_ex(x, gamma, eps, row_index=None, rnd=rbf):
+    """LlamaRMSNorm: weight * (x * rsqrt(mean(x^2) + eps)).to(bf16).  float64, before the store rounding.  rnd as in layernorm_ex."""
     xs = x.double() if row_index is None else x.double()[row_index.long()]
-    return gamma.double() * rbf(xs / torch.sqrt((xs ** 2).mean(-1, keepdim=True) + eps))
+    return gamma.double() * rnd(xs / torch.sqrt((xs ** 2).mean(-1, keepdim=True) + eps))
 
 
 def ln_rstd(x, eps):

@@ -53,6 +53,9 @@ EXPORTS_VQA = [
     # doors of the decode-side kernels (tests/test_decode_ops_gpu.py)
     "vstar_vqa_op_rope_kv_append", "vstar_vqa_op_cached_attention", "vstar_vqa_op_perceiver_attention", "vstar_vqa_op_embed_rows",
     "vstar_vqa_op_argmax_rows",
+    # doors of the fp16 prefill kernels (tests/test_f16_prefill_gpu.py)
+    "vstar_vqa_op_attention", "vstar_vqa_op_layernorm", "vstar_vqa_op_rmsnorm", "vstar_vqa_op_add_bcast",
+    "vstar_vqa_op_vit_assemble_tokens",
     # contrastive search
     "vstar_vqa_forward_contrast_begin", "vstar_vqa_forward_contrast_step", "vstar_vqa_op_contrast",
 ]
@@ -414,6 +417,16 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_embed_rows.restype = c_int
     lib.vstar_vqa_op_argmax_rows.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p]
     lib.vstar_vqa_op_argmax_rows.restype = c_int
+    lib.vstar_vqa_op_attention.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int]
+    lib.vstar_vqa_op_attention.restype = c_int
+    lib.vstar_vqa_op_layernorm.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_int]
+    lib.vstar_vqa_op_layernorm.restype = c_int
+    lib.vstar_vqa_op_rmsnorm.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]
+    lib.vstar_vqa_op_rmsnorm.restype = c_int
+    lib.vstar_vqa_op_add_bcast.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64]
+    lib.vstar_vqa_op_add_bcast.restype = c_int
+    lib.vstar_vqa_op_vit_assemble_tokens.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]
+    lib.vstar_vqa_op_vit_assemble_tokens.restype = c_int
     _rows8 = [H, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]      # the eight row arguments behind the handle
     lib.vstar_vqa_forward_contrast_begin.argtypes = _rows8 + [c_int, c_void_p, c_void_p]
     lib.vstar_vqa_forward_contrast_begin.restype = c_int

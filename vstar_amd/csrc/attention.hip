@@ -269,10 +269,16 @@ __global__ __launch_bounds__(256) void attn2_kernel(const lp_t* __restrict__ qkv
       }
     }
     // ---- online softmax against the STALE reference m: p = exp2(s - m) straight from the accumulator.  m is only touched on
-    // the slow path: the wave's first sub-tile (m := true row max, so the final row sum is >= 1) and whenever some row's
-    // probabilities outgrow 2^16 (m := new row max, history rescaled).  exp2 stays finite below that, P is bf16 (relative
-    // precision) and l / O are fp32, so nothing else depends on how stale m is.
+    // the slow path: the wave's first sub-tile (m := true row max, so the final row sum is >= 1) and whenever some lane's partial row
+    // sum outgrows BIG (m := new row max, history rescaled).  Every p <= rs <= BIG must round to a FINITE value of the storage type:
+    // bf16 has fp32's exponent range (BIG = 2^16 is a choice), but fp16 rounds p >= 65520 to +inf — there BIG is the largest finite
+    // fp16, 65504.  Below BIG exp2 stays finite, P keeps its relative precision and l / O are fp32, so nothing else depends on how
+    // stale m is.
+#ifdef VSTAR_LP_F16
+    constexpr float BIG = 65504.0f;
+#else
     constexpr float BIG = 65536.0f;
+#endif
     float p[16];
     float rs = 0.f;
 #pragma unroll

@@ -960,6 +960,85 @@ int vstar_vqa_op_argmax_rows(const void* dev_x, int rows, int cols, int64_t ld, 
   return op_result(e, "vstar_vqa_op_argmax_rows");
 }
 
+// ---- op-level doors of the fp16 PREFILL kernels (attention.hip, norm.hip, elementwise.hip built with -DVSTAR_LP_F16;
+// tests/test_f16_prefill_gpu.py): every buffer comes with its extent in rows, a violated rule is VSTAR_ERR_INVALID with a message before
+// anything is allocated or launched; no arithmetic here ----
+static int op_refuse(const char* fn, const char* why) {
+  tls_error() = std::string(fn) + ": " + why;
+  return VSTAR_ERR_INVALID;
+}
+
+int vstar_vqa_op_attention(const void* dev_qkv, int64_t qkv_rows, void* dev_out, int64_t out_rows, int B, int S, int H, int D, int causal) {
+  const char* fn = "vstar_vqa_op_attention";
+  if (!dev_qkv || !dev_out) return op_refuse(fn, "qkv and out are required");
+  if (D != 64 && D != 128) return op_refuse(fn, "D must be 64 or 128");
+  if (B < 1 || S < 1 || H < 1 || H > 256 || (causal != 0 && causal != 1)) return op_refuse(fn, "B, S >= 1, H in [1, 256], causal 0 or 1");
+  if ((int64_t)B * S > (1 << 24) || (int64_t)S * 3 * H * D * 2 >= ((int64_t)1 << 31))
+    return op_refuse(fn, "B * S <= 2^24 and one sequence's qkv rows below 2^31 bytes");
+  if (qkv_rows < (int64_t)B * S || out_rows < (int64_t)B * S) return op_refuse(fn, "qkv_rows / out_rows < B * S");
+  hipError_t e = attn_forward((const lp_t*)dev_qkv, (lp_t*)dev_out, B, S, H, D, causal, 1.0f / sqrtf((float)D), nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
+// the shared rules of the two norm doors; returns the violated rule, or null
+static const char* norm_op_check(const void* x, int64_t x_rows, const void* gamma, const void* y, int rows, int cols, const int32_t* row_index) {
+  if (!x || !gamma || !y) return "x, gamma and y are required";
+  if (rows < 1 || rows > (1 << 20)) return "rows in [1, 2^20]";
+  if (cols < 8 || cols > 4096 || cols % 8) return "cols % 8 == 0, 8 <= cols <= 4096";
+  if (!row_index) return x_rows < rows ? "x_rows < rows" : nullptr;
+  for (int r = 0; r < rows; ++r)
+    if (row_index[r] < 0 || row_index[r] >= x_rows) return "row_index entries must lie in [0, x_rows)";
+  return nullptr;
+}
+
+int vstar_vqa_op_layernorm(const void* dev_x, int64_t x_rows, const void* dev_gamma, const void* dev_beta, void* dev_y, int rows, int cols,
+                           float eps, const int32_t* host_row_index, int act) {
+  const char* fn = "vstar_vqa_op_layernorm";
+  const char* bad = (act != 0 && act != 1) ? "act must be 0 or 1" : norm_op_check(dev_x, x_rows, dev_gamma, dev_y, rows, cols, host_row_index);
+  if (bad) return op_refuse(fn, bad);
+  hipError_t e = hipSuccess;
+  OpBuf<int32_t> d_idx(e, rows, host_row_index != nullptr);
+  d_idx.upload(host_row_index);
+  if (e == hipSuccess)
+    e = layernorm_lp((const lp_t*)dev_x, (const lp_t*)dev_gamma, (const lp_t*)dev_beta, (lp_t*)dev_y, rows, cols, eps, d_idx, act, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
+int vstar_vqa_op_rmsnorm(const void* dev_x, int64_t x_rows, const void* dev_gamma, void* dev_y, int rows, int cols, float eps,
+                         const int32_t* host_row_index) {
+  const char* fn = "vstar_vqa_op_rmsnorm";
+  const char* bad = norm_op_check(dev_x, x_rows, dev_gamma, dev_y, rows, cols, host_row_index);
+  if (bad) return op_refuse(fn, bad);
+  hipError_t e = hipSuccess;
+  OpBuf<int32_t> d_idx(e, rows, host_row_index != nullptr);
+  d_idx.upload(host_row_index);
+  if (e == hipSuccess) e = rmsnorm_lp((const lp_t*)dev_x, (const lp_t*)dev_gamma, (lp_t*)dev_y, rows, cols, eps, d_idx, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
+int vstar_vqa_op_add_bcast(const void* dev_a, const void* dev_b, void* dev_out, int64_t rows, int cols, int64_t b_rows) {
+  const char* fn = "vstar_vqa_op_add_bcast";
+  if (!dev_a || !dev_b || !dev_out) return op_refuse(fn, "a, b and out are required");
+  if (rows < 1 || rows > (1 << 24) || b_rows < 1 || b_rows > rows) return op_refuse(fn, "rows in [1, 2^24], b_rows in [1, rows]");
+  if (cols < 8 || cols > 65536 || cols % 8) return op_refuse(fn, "cols % 8 == 0, 8 <= cols <= 65536");
+  hipError_t e = add_bcast((const lp_t*)dev_a, (const lp_t*)dev_b, (lp_t*)dev_out, rows, cols, b_rows, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
+int vstar_vqa_op_vit_assemble_tokens(const void* dev_patch, const void* dev_cls, const void* dev_pos, void* dev_tokens, int B, int P, int C) {
+  const char* fn = "vstar_vqa_op_vit_assemble_tokens";
+  if (!dev_patch || !dev_cls || !dev_pos || !dev_tokens) return op_refuse(fn, "patch, cls, pos and tokens are required");
+  if (B < 1 || P < 1 || (int64_t)B * (P + 1) > (1 << 24)) return op_refuse(fn, "B, P >= 1, B * (P + 1) <= 2^24");
+  if (C < 8 || C > 65536 || C % 8) return op_refuse(fn, "C % 8 == 0, 8 <= C <= 65536");
+  hipError_t e = vit_assemble_tokens((const lp_t*)dev_patch, (const lp_t*)dev_cls, (const lp_t*)dev_pos, (lp_t*)dev_tokens, B, P, C, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
 // "kv:<layer>:<slot>": the decoded K then V cache of one layer and slot, [2][heads][ctx][128]
 static int64_t debug_read_kv(vstar_vqa_handle* h, const std::string& n, float* out, int64_t cap) {
   int layer = -1, slot = -1;
