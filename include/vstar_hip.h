@@ -518,6 +518,49 @@ int vstar_op_layernorm_quant_fp8(void* stream, const uint16_t* dev_x, const uint
 int vstar_op_small_attention(void* stream, const uint16_t* dev_q, const uint16_t* dev_k, const uint16_t* dev_v, uint16_t* dev_out, int B,
                              int Nq, int Nk, int H, int D);
 
+/* ---- Op-level doors of the bf16 DECODE kernels — the bf16 build of decode.hip and skinny.hip that vstar_vsm_generate and the batched
+ * contextual-cue decode run (tests/test_bf16_decode_gpu.py).  Null stream, synchronise.  Data tensors are DEVICE pointers of bf16
+ * bits; every index array is a HOST pointer that the door checks against the extents given here and uploads itself, so no input can
+ * make a kernel index outside an allocation.  A violated rule is VSTAR_ERR_INVALID with a message in vstar_last_error(NULL), before
+ * anything is allocated or launched.  The first four are the twins of the fp16 doors vstar_vqa_op_rope_kv_append / _cached_attention /
+ * _embed_rows / _argmax_rows (vstar_vqa.h: same parameter lists, same rules, the same checks instantiated for the other storage
+ * type), with one rule more: fmt != 0 is refused, the bf16 build has KV format 0 only. ----
+ * vstar_vqa_kv_view: one layer of a KV cache, K and V as [slots][heads][ctx][128] cells (fmt 0 / 2: 16-bit cells, fmt 1: e4m3 code
+ * bytes with dev_ks / dev_vs the E8M0 bytes [slots][heads][ctx][4]; formats 1 and 2: fp16 build only); slot_stride = heads * ctx * 128.
+ * vstar_vqa_kv_rows: the rows of one call (KvRows, kernels.hpp): host row_seq / row_pos / row_slot [R], seq_kv / seq_prefix /
+ * seq_past [n_seq], nullable anc [slots * ctx].  Rules: -1 <= row_pos < min(ctx, table_rows) (-1: a padding row); row_slot, seq_kv,
+ * seq_prefix and every anc entry in [0, slots); row_seq in [0, n_seq); 0 <= seq_past <= row_pos of every row of the sequence. */
+typedef struct vstar_vqa_kv_view {
+  int32_t fmt, heads, ctx, slots;
+  void *dev_k, *dev_v, *dev_ks, *dev_vs;
+} vstar_vqa_kv_view;
+typedef struct vstar_vqa_kv_rows {
+  int32_t R, n_seq;
+  const int32_t *row_seq, *row_pos, *row_slot, *seq_kv, *seq_prefix, *seq_past, *anc;
+} vstar_vqa_kv_rows;
+int vstar_op_rope_kv_append(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                            const vstar_vqa_kv_rows* rows);
+/* *path_ran = what the dispatcher launched (0 un-fused, 1 fused, 2 fused split-KV pair); another path than the one asked for is
+ * VSTAR_ERR_STATE, never a re-route. */
+int vstar_op_cached_attention(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                              const vstar_vqa_kv_rows* rows, int max_keys, int path, int repeat, void* dev_out, int* path_ran);
+int vstar_op_embed_rows(const int32_t* host_src, int R, const void* dev_table, int vocab, const void* dev_feats, int64_t n_feat_rows,
+                        void* dev_x, int C);
+/* argmax_rows_lp on bf16 dev_x [rows, ld] (ld >= cols) -> host_out [rows]: the first column holding the largest number above -3e38;
+ * NaN never wins; a row with no such column returns 0. */
+int vstar_op_argmax_rows_lp(const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out);
+/* The weight-streaming GEMV of the decode path (gemm_skinny_lp): C [M, n_out] = epilogue(A [M, K] . W^T + bias) (+ residual [M, n_out]),
+ * dense rows (lda = K, ldc = ldr = n_out; n_out = N / 2 under VSTAR_EPI_SILU_MUL, else N).  W [ceil(N / 256) * 256, K], zero padded.
+ * kernel: 1 = the dispatch (the LDS-ring kernel for M <= 8, M <= 7 with the norm, and K >= 512, else the register kernel), 3 = the
+ * register kernel everywhere.  out_f32 1: C is fp32 (the OUT_F32 instantiations).  dev_norm_w (nullable) [K]: the rows of A are
+ * RMS-normalised on the fly.  layout 1: the door packs a temporary tile-major image of W (skinny_pack_tiles) that the ring kernel
+ * streams instead of W; needs N % 16 == 0 (SiLU-mul: N % 32 == 0).  *kernel_ran: 1 = the register kernel, 2 = the ring kernel.
+ * Refused: null A / W / C / kernel_ran, M outside [1, 64], N < 1, K < 64 or K % 64 != 0, an odd N under SiLU-mul, an epilogue that
+ * is none of the five, kernel not 1 or 3, out_f32 or layout not 0 or 1. */
+int vstar_op_gemm_skinny(const void* dev_A, const void* dev_W, const void* dev_bias, const void* dev_residual, void* dev_C, int M, int N,
+                         int K, int epilogue, int kernel, int out_f32, const void* dev_norm_w, float norm_eps, int layout,
+                         int* kernel_ran);
+
 #ifdef __cplusplus
 }
 #endif

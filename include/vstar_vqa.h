@@ -474,19 +474,9 @@ int vstar_vqa_op_kv_quantize(const void* dev_x_f16, int rows, void* dev_codes_u8
  * tensors are DEVICE pointers; every index array is a HOST pointer that the door checks against the extents given here and uploads
  * itself, so no input can make a kernel index outside an allocation.  A violated rule is VSTAR_ERR_INVALID with a message, before
  * anything is launched or allocated.
- * vstar_vqa_kv_view: one layer of a KV cache, K and V as [slots][heads][ctx][128] cells (fmt 0 / 2: fp16, fmt 1: e4m3 code bytes with
- * dev_ks / dev_vs the E8M0 bytes [slots][heads][ctx][4]; vstar_vqa_kv_cache_format above); slot_stride = heads * ctx * 128.
- * vstar_vqa_kv_rows: the rows of one call (KvRows, kernels.hpp): host row_seq / row_pos / row_slot [R], seq_kv / seq_prefix /
- * seq_past [n_seq], nullable anc [slots * ctx].  Rules: -1 <= row_pos < min(ctx, table_rows) (-1: a padding row); row_slot, seq_kv,
- * seq_prefix and every anc entry in [0, slots); row_seq in [0, n_seq); 0 <= seq_past <= row_pos of every row of the sequence. */
-typedef struct vstar_vqa_kv_view {
-  int32_t fmt, heads, ctx, slots;
-  void *dev_k, *dev_v, *dev_ks, *dev_vs;
-} vstar_vqa_kv_view;
-typedef struct vstar_vqa_kv_rows {
-  int32_t R, n_seq;
-  const int32_t *row_seq, *row_pos, *row_slot, *seq_kv, *seq_prefix, *seq_past, *anc;
-} vstar_vqa_kv_rows;
+ * vstar_vqa_kv_view / vstar_vqa_kv_rows — one layer of a KV cache and the host index arrays of one call — are declared, with their
+ * rules, in vstar_hip.h (which this header includes): the bf16 doors vstar_op_rope_kv_append / vstar_op_cached_attention take the same
+ * structs.  Here fmt is 0, 1 or 2 (vstar_vqa_kv_cache_format above). */
 /* rope_kv_append on dev_qkv [R, 3 * heads * 128] (q | k | v) with the table dev_cos_sin [table_rows, 128] (cos[64] | sin[64]). */
 int vstar_vqa_op_rope_kv_append(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
                                 const vstar_vqa_kv_rows* rows);

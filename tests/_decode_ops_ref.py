@@ -1,11 +1,14 @@
 """References, input builders and gates of the decode-side op tests (tests/test_decode_ops_gpu.py; pinned on the CPU by
 tests/test_decode_ops_ref.py).  Plain numpy: h(x) is round-to-nearest-even to fp16, everything else float64 unless said otherwise.
 
+The pieces the bf16 tests reuse (tests/_bf16_decode_ref.py) take a storage type `st` (a Storage, default FP16): how a value is rounded
+to the 16-bit format, which numpy dtype carries it, its unit roundoff and its bit patterns.  A Case carries its own.
+
 Layouts (decode.hip): qkv [R, 3 * H * 128] = q | k | v; the RoPE table [rows, 128] = cos[64] | sin[64]; a cache K / V as
 [slots][H][ctx][128] LOGICAL values (what a reader decodes), packed for the device by `pack_cache`.
 """
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import numpy as np
 import torch
@@ -27,21 +30,37 @@ def bits(x):
     return np.ascontiguousarray(x).view({1: np.uint8, 2: np.uint16, 4: np.uint32}[np.asarray(x).dtype.itemsize])
 
 
-def rt(x, fmt):
-    """What the cache of format `fmt` holds for the fp16 rows x [..., 128]."""
+@dataclass(frozen=True)
+class Storage:
+    """A 16-bit storage type: r rounds to nearest even into arrays of `dtype`, bits gives the 16-bit patterns, u is the unit roundoff,
+    codes(n, seed[, emin, emax]) a pool of finite, normal, non-zero values with distinct bit patterns."""
+    name: str
+    dtype: type
+    u: float
+    torch_dtype: object
+    r: Callable
+    bits: Callable
+    codes: Callable
+
+
+def rt(x, fmt, st=None):
+    """What the cache of format `fmt` holds for the 16-bit rows x [..., 128]."""
+    st = st or FP16
     if fmt == 0:
-        return h(x)
+        return st.r(x)
+    assert st is FP16, "formats 1 and 2 exist in the fp16 build only"
     return kv8_round_trip(torch.from_numpy(np.ascontiguousarray(h(x)))).numpy().astype(F16)
 
 
 # ---------------------------------------------------------------- RoPE
-def llama_table(rows, theta=1e4):
-    cos, sin = rope_tables(rows, D, theta, torch.float16)
-    return np.concatenate([cos[:, :64].numpy(), sin[:, :64].numpy()], axis=1)
+def llama_table(rows, theta=1e4, st=None):
+    st = st or FP16
+    cos, sin = rope_tables(rows, D, theta, st.torch_dtype)
+    return st.r(np.concatenate([cos[:, :64].float().numpy(), sin[:, :64].float().numpy()], axis=1))
 
 
-def identity_table(rows):
-    t = np.zeros((rows, D), F16)
+def identity_table(rows, st=None):
+    t = np.zeros((rows, D), (st or FP16).dtype)
     t[:, :64] = 1
     return t
 
@@ -51,17 +70,19 @@ _GRID_PAIRS = np.array([(1, 0), (0, 1), (-1, 0), (0, -1), (1, 0), (0, -1), (.5, 
                         (-.5, .5), (-.5, -.5), (0, 1), (-1, 0)], F16)
 
 
-def grid_table(rows):
+def grid_table(rows, st=None):
     """A synthetic table whose entries lie in {0, +-0.5, +-1} and vary with the position and the dimension."""
     p, d = np.arange(rows)[:, None], np.arange(64)[None, :]
     pair = _GRID_PAIRS[(p * 7 + d * 3 + (p * d) % 5 + (p // 16) * (1 + d % 3)) % 16]
-    return np.concatenate([pair[..., 0], pair[..., 1]], axis=1).astype(F16)
+    return np.concatenate([pair[..., 0], pair[..., 1]], axis=1).astype((st or FP16).dtype)
 
 
-def rope_rows(x, cs):
-    """x [..., 128] fp16 rotated with cs [..., 128] (cos | sin): o1 = h(h(a c) + h(-b s)), o2 = h(h(b c) + h(a s)), products and
-    sums in float32 — every step of the kernel, so the result is the kernel's bit for bit."""
-    x, cs = np.asarray(x, F16), np.asarray(cs, F16)
+def rope_rows(x, cs, st=None):
+    """x [..., 128] rotated with cs [..., 128] (cos | sin): o1 = h(h(a c) + h(-b s)), o2 = h(h(b c) + h(a s)), products and
+    sums in float32 — every step of the kernel, so the result is the kernel's bit for bit (h = st.r, default fp16)."""
+    st = st or FP16
+    h = st.r
+    x, cs = np.asarray(x, st.dtype), np.asarray(cs, st.dtype)
     a, b = x[..., :64].astype(F32), x[..., 64:].astype(F32)
     c, s = cs[..., :64].astype(F32), cs[..., 64:].astype(F32)
     o1 = h(h(a * c).astype(F32) + h(-b * s).astype(F32))
@@ -91,6 +112,10 @@ class Case:
     anc: Optional[np.ndarray] = None
     targets: Optional[np.ndarray] = None      # probes: [R, H] the key that must win (-1: padding row)
     name: str = ""
+    st: Optional[Storage] = None              # the storage type of table, qkv, K and V (None: fp16)
+
+    def __post_init__(self):
+        self.st = self.st or FP16
 
     @property
     def R(self):
@@ -109,10 +134,10 @@ class Case:
         return np.where(np.arange(nk) < self.seq_past[seq], self.seq_prefix[seq], self.seq_kv[seq])
 
 
-def pack_cache(x, fmt):
-    """Logical rows -> the device image: fp16 cells (formats 0, 2) or (code bytes, E8M0 bytes [..., 4]) (format 1)."""
+def pack_cache(x, fmt, st=None):
+    """Logical rows -> the device image: 16-bit cells (formats 0, 2) or (code bytes, E8M0 bytes [..., 4]) (format 1)."""
     if fmt != 1:
-        return np.ascontiguousarray(x, F16), None
+        return np.ascontiguousarray(x, (st or FP16).dtype), None
     codes, e, dec = kv8_quantize(np.ascontiguousarray(x, F16).reshape(-1, D))
     assert np.array_equal(bits(dec), bits(x.reshape(-1, D))), "format 1 caches are built from fixed points of the round trip"
     return codes.reshape(x.shape), e.reshape(x.shape[:-1] + (4,))
@@ -139,9 +164,9 @@ def append_ref(c: Case, rows=None) -> AppendRef:
         if pos < 0:
             continue
         cs = c.table[pos]
-        qkv[r, 0] = rope_rows(qkv[r, 0], cs)
-        k, v = rope_rows(qkv[r, 1], cs), qkv[r, 2].copy()
-        qkv[r, 1], qkv[r, 2] = rt(k, c.fmt), rt(v, c.fmt)
+        qkv[r, 0] = rope_rows(qkv[r, 0], cs, c.st)
+        k, v = rope_rows(qkv[r, 1], cs, c.st), qkv[r, 2].copy()
+        qkv[r, 1], qkv[r, 2] = rt(k, c.fmt, c.st), rt(v, c.fmt, c.st)
         s = c.row_slot[r]
         assert not written[s, :, pos].any(), "two rows of a call write the same cache row"
         Kr[s, :, pos], Vr[s, :, pos] = k, v
@@ -150,12 +175,12 @@ def append_ref(c: Case, rows=None) -> AppendRef:
     return AppendRef(qkv.reshape(c.R, 3 * H * D), K, V, Kr, Vr, written)
 
 
-def cache_image_after(before_cells, before_scales, raw, written, fmt):
+def cache_image_after(before_cells, before_scales, raw, written, fmt, st=None):
     """Device image after a call: `before` everywhere but on the written rows, which hold pack(raw row)."""
     cells = before_cells.copy()
     scales = None if before_scales is None else before_scales.copy()
     idx = np.nonzero(written)
-    rows = np.ascontiguousarray(raw[idx], F16)                       # [n, 128]
+    rows = np.ascontiguousarray(raw[idx], (st or FP16).dtype)        # [n, 128]
     if len(rows) == 0:
         return cells, scales
     if fmt == 0:
@@ -200,7 +225,7 @@ def dots_exact(qh, Kd):
 
 
 def tight_gate(o, pv, vabs, u=2.0 ** -11):
-    """TIGHT for a 16-bit format of unit roundoff u (fp16: 2^-11, bf16: 2^-9): 2u |o| (the output's rounding, with slack for the
+    """TIGHT for a 16-bit format of unit roundoff u (fp16: 2^-11, bf16: 2^-8): 2u |o| (the output's rounding, with slack for the
     reference's own) + 4u sum p|v| (every probability rounded, the normaliser) + 2^-23 sum |v| (fp32 accumulation)."""
     return 2 * u * np.abs(o) + 4 * u * pv + 2.0 ** -23 * vabs
 
@@ -210,10 +235,13 @@ def loose_gate(tight, delta, pv):
     return tight + np.expm1(2 * delta) * pv
 
 
-def attn_row(qh, Kd, Vd):
-    """One (row, head) of cached attention on the decoded operands: qh [128] fp16, Kd / Vd [nk, 128] fp16.
-    a_j = sum q k_j; s_j = h(float32(h(a_j)) / float32(sqrt(128))); p_j = h(exp(s_j - max) / sum); o = h(sum p_j v_j).
+def attn_row(qh, Kd, Vd, st=None):
+    """One (row, head) of cached attention on the decoded operands: qh [128], Kd / Vd [nk, 128] in the storage type st (default fp16,
+    h = st.r, u = st.u).  a_j = sum q k_j; s_j = h(float32(h(a_j)) / float32(sqrt(128))); p_j = h(exp(s_j - max) / sum);
+    o = h(sum p_j v_j).  delta = 4u |s| + 2^-17 sum |q||k| / sqrt(128).
     Returns o, p, the TIGHT and LOOSE gates [128] and the plain float64 attention."""
+    st = st or FP16
+    h = st.r
     q, Kf, Vf = qh.astype(F64), Kd.astype(F64), Vd.astype(F64)
     a = Kf @ q
     s = h(h(a).astype(F32) / SQRT_D)
@@ -221,8 +249,8 @@ def attn_row(qh, Kd, Vd):
     p = h(e / e.sum())
     o = h((p.astype(F64)[:, None] * Vf).sum(axis=0))
     pv = (p.astype(F64)[:, None] * np.abs(Vf)).sum(axis=0)
-    tight = tight_gate(o.astype(F64), pv, np.abs(Vf).sum(axis=0))
-    delta = (2.0 ** -9 * np.abs(s.astype(F64)) + 2.0 ** -17 * (np.abs(Kf) @ np.abs(q)) / float(SQRT_D)).max()
+    tight = tight_gate(o.astype(F64), pv, np.abs(Vf).sum(axis=0), st.u)
+    delta = (4 * st.u * np.abs(s.astype(F64)) + 2.0 ** -17 * (np.abs(Kf) @ np.abs(q)) / float(SQRT_D)).max()
     loose = loose_gate(tight, delta, pv)
     s64 = a / np.sqrt(128.0)
     e64 = np.exp(s64 - s64.max())
@@ -238,7 +266,7 @@ def attention_ref(c: Case) -> AttnRef:
     if c.path >= 1:                 # fused: the row is rotated and appended first, then read like any other key
         app = append_ref(c)
         K, V, qkv = app.K, app.V, app.qkv.reshape(c.R, 3, H, D)
-    out = np.zeros((c.R, H, D), F16)
+    out = np.zeros((c.R, H, D), c.st.dtype)
     tight, loose, f64 = np.zeros((c.R, H, D)), np.zeros((c.R, H, D)), np.zeros((c.R, H, D))
     ps, exact = [], True
     for r in range(c.R):
@@ -249,7 +277,7 @@ def attention_ref(c: Case) -> AttnRef:
         j = np.arange(len(ks))
         for hh in range(H):
             Kd, Vd = K[ks, hh, j], V[ks, hh, j]
-            o, p, t, lo, f = attn_row(qkv[r, 0, hh], Kd, Vd)
+            o, p, t, lo, f = attn_row(qkv[r, 0, hh], Kd, Vd, c.st)
             out[r, hh], tight[r, hh], loose[r, hh], f64[r, hh] = o, t, lo, f
             ps[r].append(p)
             exact = exact and dots_exact(qkv[r, 0, hh], Kd)
@@ -283,12 +311,15 @@ def f16_codes(n, seed, emin=1, emax=30):
     return out.astype(np.uint16).view(F16)
 
 
-def cache_values(shape, seed, fmt):
+FP16 = Storage("fp16", F16, 2.0 ** -11, torch.float16, h, bits, f16_codes)
+
+
+def cache_values(shape, seed, fmt, st=None):
     """A cache full of distinct codes; formats 1 / 2: of round-trip fixed points none of which is zero (magnitudes in [2^-4, 4): no
     element of a block lies 2^17 below its largest)."""
     n = int(np.prod(shape))
     if fmt == 0:
-        return f16_codes(n, seed).reshape(shape)
+        return (st or FP16).codes(n, seed).reshape(shape)
     return rt(f16_codes(n, seed, 11, 16).reshape(shape), fmt)
 
 
@@ -387,16 +418,17 @@ def probe_dq(r, hh, t):
     return 8 * ((r * 5 + hh * 3 + t) % 16) + (r + 2 * hh + t) % 8
 
 
-def probe_case(path, fmt, g, t, H=2, seed=0) -> Case:
-    """Round t of the one-hot probes on the geometry g: row r aims at its (t mod n)-th target.  q = 16 e_dq; the target key holds
-    16 at dq, every other key of the row 0; identity table.  Scores: 256 -> h(256 / sqrt(128)) = 22.625 against 0."""
+def probe_case(path, fmt, g, t, H=2, seed=0, st=None, mag=(16, 16)) -> Case:
+    """Round t of the one-hot probes on the geometry g: row r aims at its (t mod n)-th target.  q = mag[0] e_dq; the target key holds
+    mag[1] at dq, every other key of the row 0; identity table.  fp16 (16, 16): scores 256 -> h(256 / sqrt(128)) = 22.625 against 0."""
+    st = st or FP16
     ctx, slots = g["ctx"], g["slots"]
     R = len(g["row_pos"])
-    K = cache_values((slots, H, ctx, D), 100 + seed, fmt)
-    V = cache_values((slots, H, ctx, D), 200 + seed, fmt)
-    qkv = f16_codes(R * 3 * H * D, 300 + seed, *((1, 30) if fmt == 0 else (11, 16))).reshape(R, 3, H, D).copy()
+    K = cache_values((slots, H, ctx, D), 100 + seed, fmt, st)
+    V = cache_values((slots, H, ctx, D), 200 + seed, fmt, st)
+    qkv = (st.codes(R * 3 * H * D, 300 + seed) if fmt == 0 else f16_codes(R * 3 * H * D, 300 + seed, 11, 16)).reshape(R, 3, H, D).copy()
     qkv[:, 0] = 0
-    c = own_anc(Case(path, fmt, H, table=identity_table(ctx), qkv=qkv.reshape(R, -1), K=K, V=V, **g))
+    c = own_anc(Case(path, fmt, H, table=identity_table(ctx, st), qkv=qkv.reshape(R, -1), K=K, V=V, st=st, **g))
     c.max_keys = int(max(c.row_pos.max() + 1, 256 if path == 2 else 1))
     qkv = c.qkv.reshape(R, 3, H, D)
     targets = np.full((R, H), -1, np.int64)
@@ -411,13 +443,13 @@ def probe_case(path, fmt, g, t, H=2, seed=0) -> Case:
             dq = probe_dq(r, hh, t)
             jt = tl[(t + hh) % len(tl)]
             targets[r, hh] = jt
-            qkv[r, 0, hh, dq] = 16
+            qkv[r, 0, hh, dq] = mag[0]
             K[ks, hh, j, dq] = 0
             if path >= 1:
-                qkv[r, 1, hh, dq] = 16 if jt == pos else 0
+                qkv[r, 1, hh, dq] = mag[1] if jt == pos else 0
             if not (path >= 1 and jt == pos):
-                K[ks[jt], hh, jt, dq] = 16
-    c.K = rt(K, fmt)                                    # (formats 1 / 2: the edited blocks, made fixed points again)
+                K[ks[jt], hh, jt, dq] = mag[1]
+    c.K = rt(K, fmt, st)                                # (formats 1 / 2: the edited blocks, made fixed points again)
     c.targets = targets
     c.name = f"probe path {path} fmt {fmt} round {t}"
     return c
@@ -427,25 +459,27 @@ def probe_rounds(path, g):
     return max(len(probe_targets(path, int(p), int(g["seq_past"][s]))) for p, s in zip(g["row_pos"], g["row_seq"]))
 
 
-def _grid(g, shape, lo=1):
+def _grid(g, shape, lo=1, st=None):
     """Random non-zero multiples of 1/8 in [-1, 1] with |x| >= lo / 8."""
-    return (g.integers(lo, 9, shape) * g.choice([-1, 1], shape) / 8.0).astype(F16)
+    return (g.integers(lo, 9, shape) * g.choice([-1, 1], shape) / 8.0).astype((st or FP16).dtype)
 
 
-def exact_dot_case(path, fmt, g, H=2, seed=0) -> Case:
+def exact_dot_case(path, fmt, g, H=2, seed=0, st=None) -> Case:
     """Exact-dot inputs: q, k multiples of 1/8 in [-1, 1], table entries in {0, +-0.5, +-1}, so the rotated rows lie on a grid of
     1/16 and every dot product is exact in fp32 in any order.  Lumpy probabilities: the keys at the edges of every mechanism (0,
     past - 1, past, the partition edges, pos - 1 and the rows' own keys) are aligned with the sign of the (rotated) query, everything
     else is random."""
+    st = st or FP16
+    h = st.r
     rng = np.random.default_rng(seed)
     ctx, slots = g["ctx"], g["slots"]
     R = len(g["row_pos"])
-    table = grid_table(ctx)
-    K = _grid(rng, (slots, H, ctx, D))
-    V = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt)
-    qkv = np.zeros((R, 3, H, D), F16)
+    table = grid_table(ctx, st)
+    K = _grid(rng, (slots, H, ctx, D), st=st)
+    V = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt, st)
+    qkv = np.zeros((R, 3, H, D), st.dtype)
     qkv[:, 2] = h(0.5 * rng.standard_normal((R, H, D)))
-    c = own_anc(Case(path, fmt, H, table=table, qkv=qkv.reshape(R, -1), K=K, V=V, **g))
+    c = own_anc(Case(path, fmt, H, table=table, qkv=qkv.reshape(R, -1), K=K, V=V, st=st, **g))
     c.max_keys = int(max(c.row_pos.max() + 1, 256 if path == 2 else 1))
     qkv = c.qkv.reshape(R, 3, H, D)
     for s in range(c.n_seq):
@@ -466,24 +500,26 @@ def exact_dot_case(path, fmt, g, H=2, seed=0) -> Case:
             hot = [j for j in probe_targets(path, pos, past) if not (path >= 1 and j == pos)]
             if path == 0:
                 hot += [int(c.row_pos[r2]) for r2 in rows if c.row_pos[r2] <= pos]
-            qh = sign if path == 0 else np.sign(rope_rows(qkv[r, 0], table[pos]).astype(F64))
+            qh = sign if path == 0 else np.sign(rope_rows(qkv[r, 0], table[pos], st).astype(F64))
             for j in set(hot):
                 al = np.where(qh != 0, qh, 1.0) * rng.integers(6, 9, (H, D)) / 8.0
                 K[ks[j], :, j] = h(al)
-    c.K = rt(K, fmt)
+    c.K = rt(K, fmt, st)
     c.name = f"exact-dot path {path} fmt {fmt}"
     return c
 
 
-def random_case(path, fmt, g, H=2, seed=0) -> Case:
+def random_case(path, fmt, g, H=2, seed=0, st=None) -> Case:
     """The real LLaMA table; qkv and the caches 0.5 x normal."""
+    st = st or FP16
+    h = st.r
     rng = np.random.default_rng(1000 + seed)
     ctx, slots = g["ctx"], g["slots"]
     R = len(g["row_pos"])
-    K = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt)
-    V = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt)
+    K = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt, st)
+    V = rt(h(0.5 * rng.standard_normal((slots, H, ctx, D))), fmt, st)
     qkv = h(0.5 * rng.standard_normal((R, 3 * H * D)))
-    c = own_anc(Case(path, fmt, H, table=llama_table(ctx), qkv=qkv, K=K, V=V, **g))
+    c = own_anc(Case(path, fmt, H, table=llama_table(ctx, st=st), qkv=qkv, K=K, V=V, st=st, **g))
     c.max_keys = int(max(c.row_pos.max() + 1, 256 if path == 2 else 1))
     c.name = f"random path {path} fmt {fmt}"
     return c
@@ -498,9 +534,9 @@ def one_hot(c: Case, ref: AttnRef) -> bool:
     """Every probability vector is exactly one-hot at the target."""
     for r in range(c.R):
         for hh, p in enumerate(ref.p[r]):
-            want = np.zeros(len(p), F16)
+            want = np.zeros(len(p), c.st.dtype)
             want[c.targets[r, hh]] = 1
-            if not np.array_equal(bits(p), bits(want)):
+            if not np.array_equal(c.st.bits(p), c.st.bits(want)):
                 return False
     return True
 
@@ -631,7 +667,7 @@ def perceiver_random(n, H, L, NK, DH, seed):
 # ---------------------------------------------------------------- embed_rows / argmax_rows_lp (contracts: kernels.hpp)
 def embed_rows(src, table, feats):
     """x[r] = table[src] for 0 <= src < vocab, feats[-(src + 1)] for a feature index in range, zero for INT32_MIN and out-of-range."""
-    out = np.zeros((len(src), table.shape[1]), F16)
+    out = np.zeros((len(src), table.shape[1]), table.dtype)          # (the storage type's carrier: float16, or float32 for bf16)
     for r, s in enumerate(np.asarray(src, np.int64)):
         if 0 <= s < len(table):
             out[r] = table[s]
@@ -653,7 +689,7 @@ def argmax_rows(x):
 
 
 # ---------------------------------------------------------------- builders of the remaining cases
-def append_case(H, fmt, seed=0) -> Case:
+def append_case(H, fmt, seed=0, st=None, table=None) -> Case:
     """rope_kv_append: 37 rows over 3 sequences, 5 of them padding, positions in no order, slots (2, 0, 3) for sequences (0, 1, 2);
     the real LLaMA table, random qkv; the caches full of distinct codes (the sentinel of every row the call does not write)."""
     rng = np.random.default_rng(50 + seed)
@@ -665,16 +701,17 @@ def append_case(H, fmt, seed=0) -> Case:
         idx = np.nonzero(row_seq == s)[0]
         row_pos[idx] = rng.permutation(ctx)[: len(idx)]
     row_pos[[4, 11, 12, 30, 36]] = -1
-    qkv = h(rng.standard_normal((R, 3 * H * D)))
+    st = st or FP16
+    qkv = st.r(rng.standard_normal((R, 3 * H * D)))
     return Case(-1, fmt, H, ctx, slots, row_seq, row_pos, seq_kv[row_seq].copy(), seq_kv, seq_kv.copy(), np.zeros(3, np.int32),
-                llama_table(ctx), qkv, cache_values((slots, H, ctx, D), 7, fmt), cache_values((slots, H, ctx, D), 8, fmt),
-                name=f"append H {H} fmt {fmt}")
+                llama_table(ctx, st=st) if table is None else table(ctx, st), qkv, cache_values((slots, H, ctx, D), 7, fmt, st),
+                cache_values((slots, H, ctx, D), 8, fmt, st), name=f"append H {H} fmt {fmt}", st=st)
 
 
-def embed_case(C, seed=0):
+def embed_case(C, seed=0, st=None):
     """Distinct codes; sources: token ids, feature rows, INT32_MIN, an id >= vocab, a feature index >= n_feat_rows."""
     vocab, nf = 37, 9
-    pool = f16_codes((vocab + nf) * C, 60 + seed)
+    pool = (st or FP16).codes((vocab + nf) * C, 60 + seed)
     table, feats = pool[: vocab * C].reshape(vocab, C), pool[vocab * C:].reshape(nf, C)
     src = np.array([0, vocab - 1, -1, -nf, INT32_MIN, vocab, vocab + 1000, -(nf + 1), -(nf + 500), 5, -3, 2 ** 31 - 1, INT32_MIN + 1, 17, 5],
                    np.int32)
@@ -684,12 +721,13 @@ def embed_case(C, seed=0):
 ARGMAX_COLS = [1, 255, 257, 1000]
 
 
-def argmax_case(cols, seed=0):
+def argmax_case(cols, seed=0, st=None):
     """Rows [9, ld] with ld = cols + 9: random values; the padding columns hold the largest value of all; rows with ties (the
     first wins), NaN (never wins), only NaN, only -inf, NaN and -inf."""
     rng = np.random.default_rng(70 + seed)
     ld = cols + 9
-    x = h(rng.standard_normal((9, ld)))
+    st = st or FP16
+    x = st.r(rng.standard_normal((9, ld)))
     x[:, cols:] = 1000.0
     x[1, rng.integers(0, cols, 3)] = 7.0                            # a tie of up to three columns
     x[2, :] = 3.0                                                    # every column ties: 0
@@ -704,4 +742,4 @@ def argmax_case(cols, seed=0):
     x[8, cols - 1] = 9.0
     if cols > 1:
         x[8, cols - 2] = 9.0                                         # a tie in the last two columns
-    return x, ld
+    return st.r(x), ld

@@ -41,11 +41,11 @@ def ulp16(t):
     return np.exp2(e - 10)
 
 
-def tie_slack(t, err):
-    """One fp16 step of t where t lies within err of a rounding tie of h() (a kernel whose value of t is off by up to err may round
-    to the other neighbour), 0 elsewhere."""
+def tie_slack(t, err, spacing=ulp16):
+    """One step of the storage type (default fp16; `spacing` gives another format's) at t where t lies within err of a rounding tie
+    (a kernel whose value of t is off by up to err may round to the other neighbour), 0 elsewhere."""
     t, err = np.asarray(t, F64), np.asarray(err, F64)
-    sp = ulp16(t)
+    sp = spacing(t)
     frac = np.abs(t) / sp
     dist = np.abs(frac - np.floor(frac) - 0.5) * sp
     return np.where(dist <= err, sp, 0.0)

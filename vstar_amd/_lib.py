@@ -34,6 +34,8 @@ EXPORTS = [
     "vstar_op_gemm_ex", "vstar_op_rope", "vstar_op_attention_grouped", "vstar_op_attention_mx_grouped",
     # the batched contextual-cue decode
     "vstar_vsm_generate_batch",
+    # doors of the bf16 decode kernels (tests/test_bf16_decode_gpu.py)
+    "vstar_op_rope_kv_append", "vstar_op_cached_attention", "vstar_op_embed_rows", "vstar_op_argmax_rows_lp", "vstar_op_gemm_skinny",
 ]
 
 # every symbol include/vstar_vqa.h declares
@@ -313,6 +315,19 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, "vstar_op_" + name)
         fn.argtypes = [c_void_p] + args
         fn.restype = c_int
+    # doors of the bf16 decode kernels: the argument lists of their vstar_vqa_op_* twins
+    lib.vstar_op_rope_kv_append.argtypes = [c_void_p, c_void_p, c_int, POINTER(VqaKvView), POINTER(VqaKvRows)]
+    lib.vstar_op_rope_kv_append.restype = c_int
+    lib.vstar_op_cached_attention.argtypes = [c_void_p, c_void_p, c_int, POINTER(VqaKvView), POINTER(VqaKvRows), c_int, c_int, c_int,
+                                              c_void_p, POINTER(c_int)]
+    lib.vstar_op_cached_attention.restype = c_int
+    lib.vstar_op_embed_rows.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int]
+    lib.vstar_op_embed_rows.restype = c_int
+    lib.vstar_op_argmax_rows_lp.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p]
+    lib.vstar_op_argmax_rows_lp.restype = c_int
+    lib.vstar_op_gemm_skinny.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_float, c_int, POINTER(c_int)]
+    lib.vstar_op_gemm_skinny.restype = c_int
     # ---- VQA-LLM engine (include/vstar_vqa.h) ----
     lib.vstar_vqa_create.argtypes = [POINTER(CVqaConfig), c_int, POINTER(H)]
     lib.vstar_vqa_create.restype = c_int

@@ -13,7 +13,7 @@ wanted() { [ -z "$ONLY" ] || [[ "$ONLY" == *" $1 "* ]]; }
 mkdir -p build
 rm -f build/gemm256a.o build/f16_gemm256a.o     # (round-3 experiment, moved to tools/experiments/gemm256a)
 pids=()
-HDRS="common.hpp kernels.hpp gemm_epilogue.hpp gemm256_direct_epilogue.hpp mx.hpp gemm4w_loop.inc engine_base.hpp llm_cached.hpp sample.hpp sample_core.hpp beam.hpp score.hpp spec.hpp edit.hpp logprob.hpp contrast.hpp tails_lp.hpp row_lse.hpp row_select.hpp ../../include/vstar_hip.h ../../include/vstar_vqa.h"
+HDRS="common.hpp kernels.hpp gemm_epilogue.hpp gemm256_direct_epilogue.hpp mx.hpp gemm4w_loop.inc engine_base.hpp llm_cached.hpp sample.hpp sample_core.hpp beam.hpp score.hpp spec.hpp edit.hpp logprob.hpp contrast.hpp tails_lp.hpp op_doors.hpp row_lse.hpp row_select.hpp ../../include/vstar_hip.h ../../include/vstar_vqa.h"
 stale() {  # stale <object> <source>
   [ ! -f "$1" ] && return 0
   [ "$2" -nt "$1" ] && return 0

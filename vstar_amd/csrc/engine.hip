@@ -5,6 +5,7 @@
 #include "llm_cached.hpp"
 #include "mx.hpp"
 #include "gemm_epilogue.hpp"      // gemm_map_row: the op-level doors check extents with the kernels' own row map
+#include "op_doors.hpp"           // the decode-side door bodies (shared with vqa_engine.hip)
 #include <algorithm>
 #include <atomic>
 #include <tuple>
@@ -2055,6 +2056,53 @@ int vstar_op_rmsnorm_quant_fp8(void* stream, const uint16_t* x, const uint16_t* 
 int vstar_op_small_attention(void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int Nq,
                              int Nk, int H, int D) {
   return op_done(small_attention(q, k, v, out, B, Nq, Nk, H, D, (hipStream_t)stream), stream);
+}
+
+// ---- op-level doors of the bf16 DECODE kernels (decode.hip / skinny.hip as this library's VSM engine runs them;
+// tests/test_bf16_decode_gpu.py): the checks and bodies are op_doors.hpp's, the ones the fp16 doors of vqa_engine.hip instantiate ----
+int vstar_op_rope_kv_append(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                            const vstar_vqa_kv_rows* rows) {
+  return door_rope_kv_append("vstar_op_rope_kv_append", dev_qkv, dev_cos_sin, table_rows, kv, rows);
+}
+int vstar_op_cached_attention(void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
+                              const vstar_vqa_kv_rows* rows, int max_keys, int path, int repeat, void* dev_out, int* path_ran) {
+  return door_cached_attention("vstar_op_cached_attention", dev_qkv, dev_cos_sin, table_rows, kv, rows, max_keys, path, repeat, dev_out, path_ran);
+}
+int vstar_op_embed_rows(const int32_t* host_src, int R, const void* dev_table, int vocab, const void* dev_feats, int64_t n_feat_rows,
+                        void* dev_x, int C) {
+  return door_embed_rows("vstar_op_embed_rows", host_src, R, dev_table, vocab, dev_feats, n_feat_rows, dev_x, C);
+}
+int vstar_op_argmax_rows_lp(const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out) {
+  return door_argmax_rows("vstar_op_argmax_rows_lp", dev_x, rows, cols, ld, host_out);
+}
+int vstar_op_gemm_skinny(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int epilogue,
+                         int kernel, int out_f32, const void* norm_w, float norm_eps, int layout, int* kernel_ran) {
+  const char* door = "vstar_op_gemm_skinny";
+  const bool silu = epilogue == VSTAR_EPI_SILU_MUL;
+  const int nt = silu ? 2 : 1;
+  if (!A || !W || !C || !kernel_ran) return op_refuse(door, "A, W, C and kernel_ran are required");
+  if (M < 1 || M > 64) return op_refuse(door, "M must lie in [1, 64]: the weight-streaming kernels' domain");
+  if (N < 1 || K < 64 || K % 64) return op_refuse(door, "N >= 1, K >= 64 and K % 64 == 0");
+  if (epilogue < VSTAR_EPI_NONE || epilogue > VSTAR_EPI_SILU_MUL) return op_refuse(door, "epilogue must be one of the five VSTAR_EPI_* values");
+  if (silu && N % 2) return op_refuse(door, "VSTAR_EPI_SILU_MUL needs an even N (gate | up)");
+  if (kernel != 1 && kernel != 3) return op_refuse(door, "kernel must be 1 (dispatch) or 3 (register kernel)");
+  if ((out_f32 != 0 && out_f32 != 1) || (layout != 0 && layout != 1)) return op_refuse(door, "out_f32 and layout must be 0 or 1");
+  if (layout == 1 && N % (16 * nt)) return op_refuse(door, "the tile-major layout needs whole 16-row (SiLU-mul: 32-row) tiles");
+  *kernel_ran = 0;
+  GemmParams p{};
+  const int n_out = silu ? N / 2 : N;
+  p.A = (const lp_t*)A; p.lda = K; p.W = (const lp_t*)W; p.bias = (const lp_t*)bias; p.res = (const lp_t*)res; p.ldr = n_out;
+  p.C = C; p.ldc = n_out; p.M = M; p.N = N; p.K = K;
+  p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
+  if (kernel == 3) p.tile_force = -1;      // the register-streaming kernel even where the LDS-ring variant would run
+  hipError_t e = hipSuccess;
+  OpBuf<lp_t> tiles(e, (size_t)N * K, layout == 1);
+  if (layout == 1 && e == hipSuccess) e = skinny_pack_tiles((const lp_t*)W, tiles.p, N, K, nt, nullptr);
+  p.dw = SkinnyWeights{SKINNY_W_F16, nullptr, nullptr, tiles.p};
+  if (e == hipSuccess) e = gemm_skinny_lp(p, epilogue, out_f32 != 0, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) *kernel_ran = gemm_skinny_last_kernel();
+  return op_result(e, door);
 }
 
 }  // extern "C"

@@ -127,6 +127,9 @@ bool gemm256_eligible(const GemmParams& p);   // true: gemm_lp runs the 256^2 ke
 // decode-sized GEMM (skinny.hip): M <= 64, identity row maps; same operands/epilogues as gemm_lp
 bool gemm_skinny_eligible(const GemmParams& p);
 hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s);
+// which kernel the last gemm_skinny_lp call of THIS thread launched: 1 = gemm_skinny_kernel (registers), 2 = gemm_skinny_ring_kernel,
+// 0 = it refused the call (observability for the op-level tests, like gemm_last_tile())
+int gemm_skinny_last_kernel();
 // Wt <- tile-major image of the packed row-major W [n_rows][K] for gemm_skinny_ring_kernel (nt = 2 for SiLU(gate)*up weights whose
 // rows interleave gate / up in blocks of 16, else 1); n_rows % (16 nt) == 0, K % 64 == 0; Wt holds n_rows * K elements
 hipError_t skinny_pack_tiles(const lp_t* W, lp_t* Wt, int n_rows, int K, int nt, hipStream_t s);

@@ -637,6 +637,8 @@ __global__ void skinny_tile_pack_w4_kernel(const uint32_t* __restrict__ q, const
 }
 #endif
 
+thread_local int t_last_kernel = 0;          // gemm_skinny_last_kernel()
+
 template <int EPI, bool OUT_F32, bool W8 = false>
 hipError_t launch_skinny_ring(const GemmParams& p0, hipStream_t s) {
   constexpr int NT = (EPI == VSTAR_EPI_SILU_MUL) ? 2 : 1;
@@ -652,6 +654,7 @@ hipError_t launch_skinny_ring(const GemmParams& p0, hipStream_t s) {
     if (e != hipSuccess) return e;
     attr_done[nm] = true;
   }
+  t_last_kernel = 2;
   if (nm) hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, true, W8>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
   else hipLaunchKernelGGL((gemm_skinny_ring_kernel<EPI, OUT_F32, false, W8>), dim3(blocks), dim3(SK_WAVES * 64), lds, s, p);
   return hipGetLastError();
@@ -670,6 +673,7 @@ hipError_t launch_skinny(const GemmParams& p0, hipStream_t s) {
   // (WQ == 4: there is no W4 ring, the register kernel below serves every M <= 64 — bit-identical)
   if constexpr (WQ != 4)
     if (ring && p.M <= (p.norm_w ? 7 : 8) && p.K >= 512 && p.tile_force != -1) return launch_skinny_ring<EPI, OUT_F32, WQ == 8>(p, s);   // tile_force -1: tests
+  if (mt >= 1 && mt <= 4) t_last_kernel = 1;
   switch (mt) {
     case 1: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 1, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
     case 2: hipLaunchKernelGGL((gemm_skinny_kernel<EPI, OUT_F32, 2, WQ>), dim3(blocks), dim3(SK_WAVES * 64), 0, s, p); break;
@@ -744,7 +748,10 @@ static hipError_t skinny_dispatch(const GemmParams& p, int epilogue, bool out_f3
   return hipErrorInvalidValue;
 }
 
+int gemm_skinny_last_kernel() { return t_last_kernel; }
+
 hipError_t gemm_skinny_lp(const GemmParams& p, int epilogue, bool out_f32, hipStream_t s) {
+  t_last_kernel = 0;
   if (!gemm_skinny_eligible(p)) return hipErrorInvalidValue;
   const SkinnyWeights& dw = p.dw;
   if (dw.fmt == SKINNY_W_F16) return skinny_dispatch<0>(p, epilogue, out_f32, s);
