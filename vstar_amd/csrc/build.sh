@@ -20,19 +20,19 @@ stale() {  # stale <object> <source>
   for h in $HDRS; do [ -f "$h" ] && [ "$h" -nt "$1" ] && return 0; done
   return 1
 }
-# bf16 instantiation: every kernel file + the VSM engine (sample.hip / beam.hip / score.hip / spec.hip / edit.hip / logprob.hip / contrast.hip are dtype-explicit — one launcher per storage type — and
+# bf16 instantiation: every kernel file + the VSM engine and its op-level doors (ops.hip) (sample.hip / beam.hip / score.hip / spec.hip / edit.hip / logprob.hip / contrast.hip are dtype-explicit — one launcher per storage type — and
 # built once)
 # gemm4w keeps its 256 accumulators in AGPRs BEHIND the compiler's back (they are clobbers of the K-loop asm statement, read back by
 # v_accvgpr_read statements in the epilogue): the compiler must never use AGPRs as VGPR spill space there — it did (a2..a9, round 6)
 extra() { [[ "$1" == gemm4w* ]] && echo "-mllvm -amdgpu-spill-vgpr-to-agpr=0"; }
 # (gemm4w_vit8.hip is gemm4w.hip compiled again for the W8A8 quick-GELU kernels: stale with either file)
-for f in gemm gemm256 gemm4w gemm4w_vit8 norm attention elementwise decode skinny quant heads preprocess engine comm sample beam score spec edit logprob contrast; do
+for f in gemm gemm256 gemm4w gemm4w_vit8 norm attention elementwise decode skinny quant heads preprocess engine ops comm sample beam score spec edit logprob contrast; do
   if wanted $f && { stale build/$f.o $f.hip || { [ $f = gemm4w_vit8 ] && [ gemm4w.hip -nt build/$f.o ]; }; }; then
     $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!)
   fi
 done
-# fp16 instantiation (-DVSTAR_LP_F16): the dtype-generic kernel files + the VQA-LLM engine
-for f in gemm gemm256 gemm4w norm attention elementwise decode skinny vqa_engine; do
+# fp16 instantiation (-DVSTAR_LP_F16): the dtype-generic kernel files + the VQA-LLM engine and its op-level doors (vqa_ops.hip)
+for f in gemm gemm256 gemm4w norm attention elementwise decode skinny vqa_engine vqa_ops; do
   [ -f $f.hip ] || continue
   if wanted $f && stale build/f16_$f.o $f.hip; then $HIPCC $FLAGS $(extra $f) -DVSTAR_LP_F16 -c $f.hip -o build/f16_$f.o & pids+=($!); fi
 done

@@ -1,7 +1,8 @@
-// op_doors.hpp — the dtype-generic parts of the op-level doors of the decode-side kernels (decode.hip): the checks of the host index
-// arrays, their upload, and the door bodies.  Lives in VS_NS like the kernels it drives, so engine.hip (bf16: vstar_op_*) and
-// vqa_engine.hip (fp16, -DVSTAR_LP_F16: vstar_vqa_op_*) instantiate the SAME rules; `fn` is the door's exported name, the prefix of
-// every message.  The structs vstar_vqa_kv_view / vstar_vqa_kv_rows are declared in include/vstar_hip.h.
+// op_doors.hpp — what the op-level doors share: the helpers every door reports through (op_refuse, op_result, the two
+// synchronise-then-report forms), device scratch (OpBuf), the dense GemmParams fill of the skinny / fp16 GEMM doors, and the
+// dtype-generic checks and bodies of the decode-side doors (decode.hip).  Lives in VS_NS like the kernels it drives, so ops.hip (bf16:
+// vstar_op_*) and vqa_ops.hip (fp16, -DVSTAR_LP_F16: vstar_vqa_op_*) instantiate the SAME text; `fn` is the door's exported name, the
+// prefix of every message.  The structs vstar_vqa_kv_view / vstar_vqa_kv_rows are declared in include/vstar_hip.h.
 #pragma once
 #include <string>
 #include <vector>
@@ -27,10 +28,38 @@ struct OpBuf {
   operator T*() const { return p; }
 };
 
-inline int op_result(hipError_t e, const char* op) {
+// a refused call: VSTAR_ERR_INVALID, message "<fn>: <why>"
+inline int op_refuse(const char* fn, const std::string& why) {
+  tls_error() = std::string(fn) + ": " + why;
+  return VSTAR_ERR_INVALID;
+}
+
+// the return code of a door whose device work ended in `e`; a failure's message is "<prefix>: <HIP's text>", prefix being the door's
+// name or, at the doors that predate the names, the fixed "HIP"
+inline int op_result(hipError_t e, const char* prefix) {
   if (e == hipSuccess) return VSTAR_OK;
-  tls_error() = std::string(op) + ": " + hipGetErrorString(e);
+  tls_error() = std::string(prefix) + ": " + hipGetErrorString(e);
   return VSTAR_ERR_HIP;
+}
+// synchronise, then report: the caller's stream (the doors that take one) / the device (the doors that launch on the null stream)
+inline int op_sync_stream(hipError_t e, void* stream, const char* prefix = "HIP") {
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  return op_result(e, prefix);
+}
+inline int op_sync_device(hipError_t e, const char* fn) {
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return op_result(e, fn);
+}
+
+// the dense A[M,K] · W[N,K]^T -> C[M,n_out] call of the skinny / fp16 GEMM doors: n_out = N / 2 under VSTAR_EPI_SILU_MUL, else N
+inline GemmParams op_dense_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int epilogue,
+                                const void* norm_w, float norm_eps) {
+  GemmParams p{};
+  const int n_out = epilogue == VSTAR_EPI_SILU_MUL ? N / 2 : N;
+  p.A = (const lp_t*)A; p.lda = K; p.W = (const lp_t*)W; p.bias = (const lp_t*)bias; p.res = (const lp_t*)res; p.ldr = n_out;
+  p.C = C; p.ldc = n_out; p.M = M; p.N = N; p.K = K;
+  p.norm_w = (const lp_t*)norm_w; p.norm_eps = norm_eps;
+  return p;
 }
 
 // ---- op-level doors of the decode-side kernels: every index array is a HOST array, checked here against the extents before
@@ -111,12 +140,11 @@ struct KvOpArgs {
 inline int door_rope_kv_append(const char* fn, void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
                                const vstar_vqa_kv_rows* rows) {
   const char* bad = !dev_qkv || !dev_cos_sin ? "qkv and cos_sin are required" : kv_op_check(kv, rows, table_rows, 0, -1);
-  if (bad) { tls_error() = std::string(fn) + ": " + bad; return VSTAR_ERR_INVALID; }
+  if (bad) return op_refuse(fn, bad);
   hipError_t e = hipSuccess;
   KvOpArgs a(e, *kv, *rows);
   if (e == hipSuccess) e = rope_kv_append((lp_t*)dev_qkv, (const lp_t*)dev_cos_sin, a.layer, a.rows, rows->R, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  return op_result(e, fn);
+  return op_sync_device(e, fn);
 }
 
 inline int door_cached_attention(const char* fn, void* dev_qkv, const void* dev_cos_sin, int table_rows, const vstar_vqa_kv_view* kv,
@@ -126,7 +154,7 @@ inline int door_cached_attention(const char* fn, void* dev_qkv, const void* dev_
                     : path >= 1 && !dev_cos_sin       ? "the fused paths need cos_sin"
                     : repeat < 1 || repeat > 16       ? "repeat must lie in [1, 16]"
                                                       : kv_op_check(kv, rows, table_rows, max_keys, path);
-  if (bad) { tls_error() = std::string(fn) + ": " + bad; return VSTAR_ERR_INVALID; }
+  if (bad) return op_refuse(fn, bad);
   *path_ran = -1;
   hipError_t e = hipSuccess;
   KvOpArgs a(e, *kv, *rows);
@@ -158,8 +186,7 @@ inline int door_embed_rows(const char* fn, const int32_t* host_src, int R, const
   OpBuf<int32_t> d_src(e, R);
   d_src.upload(host_src);
   if (e == hipSuccess) e = embed_rows(d_src, (const lp_t*)dev_table, vocab, (const lp_t*)dev_feats, n_feat_rows, (lp_t*)dev_x, R, C, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  return op_result(e, fn);
+  return op_sync_device(e, fn);
 }
 
 inline int door_argmax_rows(const char* fn, const void* dev_x, int rows, int cols, int64_t ld, int32_t* host_out) {
