@@ -390,6 +390,53 @@ int vstar_vqa_op_contrast(const void* dev_logits, int dtype, int rows, int vocab
                           const float* cand_prob, float alpha, int k_next, int32_t* sel_out, int32_t* next_tok, float* next_prob,
                           float* penalty_out);
 
+/* Guided decoding against a negative sequence: HF generate(guidance_scale = gamma, negative_prompt_ids = ...) —
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor, "visual contrastive decoding" when the negative sequence is the same question without
+ * (or with a degraded) image — with the combination of the two logits rows on the device, ahead of the logits edits (HF puts the
+ * guidance processor first in its list): lm_head -> guide -> edits -> tail -> log-probabilities.  The wanted rows of a guided call are
+ * the n_out OUTPUT rows want[0 .. n_out) followed by the NEGATIVE rows want[n_out .. n_want); every array of the tail, the edits and the
+ * log-probabilities (params, warpers, tokens, argmax, logits_f16, off / penalty, token_logprob ...) has n_out entries and describes the
+ * output rows.  All arrays HOST, n_out entries:
+ *   neg[j]       index into `want` (>= n_out) of output row j's negative row, each negative row belonging to exactly one output row;
+ *                -1: row j is unguided (its logits pass through untouched)
+ *   scale[j]     gamma, finite and >= 0 (1 gives log_softmax of the row itself, 0 that of the negative row); read where neg[j] >= 0
+ *   log_beta[j]  <= 0: the adaptive plausibility cut of Li et al. — token i stays iff x_c[i] - max x_c >= log_beta (an exact fp32
+ *                difference of fp16 values), every other token becomes -inf; -inf = off; the caller passes float32(log(beta))
+ * With x_c / x_u the two logits rows: lse = max + log(sum exp(x_i - max)) in double in vstar_vqa_forward_score's fixed order, c_i =
+ * x_c[i] - lse_c, u_i = x_u[i] - lse_u, g_i = gamma * (c_i - u_i) + u_i in double (every operation rounded on its own), rounded ONCE to
+ * fp16; a finite g_i beyond the fp16 range becomes +-65504.  x_c[i] = -inf or NaN gives -inf; x_u[i] non-finite with x_c[i] finite gives
+ * c_i rounded once; a non-finite lse_c or lse_u gives a row of -inf.  The guided row replaces the output row's logits: the edits, the
+ * tail and the log-probabilities see it, and logits_f16 returns it (HF's `scores`).  HF computes both log_softmax in the scores' dtype
+ * and rounds after every operation; here the value is exact and rounded once (a stated deviation).  Negative rows only write their K/V. */
+typedef struct vstar_vqa_guidance {   /* all HOST arrays */
+  int32_t        n_out;       /* output rows: the first n_out wanted rows */
+  const int32_t* neg;         /* [n_out] */
+  const float*   scale;       /* [n_out] */
+  const float*   log_beta;    /* [n_out] */
+} vstar_vqa_guidance;
+
+/* vstar_vqa_forward_logprobs / vstar_vqa_forward_sample_warp with the guidance stage; warpers, edits and lp stay nullable, guidance ==
+ * NULL is that call, bit for bit and launch for launch.  Errors (VSTAR_ERR_INVALID, before any device work, the engine stays usable):
+ * n_out outside [1, n_want], a neg entry that is neither -1 nor in [n_out, n_want), a negative row with no or with two output rows, a
+ * scale or log_beta out of range.  The device arrays for the records are allocated by the first call that carries guidance (a failed
+ * allocation is VSTAR_ERR_NOMEM and leaves the engine usable); an engine that never sees guidance allocates, launches and copies nothing
+ * for it.  The beam, scoring, verify and contrast tails have no such entry. */
+int vstar_vqa_forward_guided(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_guidance* guidance,
+                             const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp);
+int vstar_vqa_forward_sample_guided(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src,
+                                    const int32_t* kv_slot, const int32_t* prefix_slot, const int32_t* past_len,
+                                    int n_want, const int32_t* want, const vstar_vqa_sampling* params, int32_t* tokens,
+                                    const vstar_vqa_warpers* warpers, const vstar_vqa_guidance* guidance,
+                                    const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp);
+/* Kernel-level door (tests, micro-benchmarks): DEVICE logits [rows, ld] of dtype F16/BF16 (1 <= vocab <= 2^22, any ld >= vocab); host
+ * records of n_pairs (<= 65535) pairs: cond_row / neg_row (two different rows in [0, rows), no row in two records), scale (finite, >= 0),
+ * log_beta (<= 0, -inf = off), checked before any device work.  Row cond_row[p] is overwritten in place, columns [0, vocab) only; no other
+ * element is written.  Null stream, synchronises. */
+int vstar_vqa_guide_rows(void* dev_logits, int dtype, int rows, int vocab, int64_t ld, int n_pairs, const int32_t* cond_row,
+                         const int32_t* neg_row, const float* scale, const float* log_beta);
+
 /* Op-level entry for tests and micro-benchmarks, fp16, all pointers DEVICE pointers: C[M,N] = epilogue(A[M,K] · W[N,K]^T
  * + bias) (+ residual), epilogue codes and operand rules as vstar_op_gemm (W rows padded to a multiple of 256, K % 64 == 0).
  * kernel: 0 = the engine's dispatch (weight-streaming kernel for M <= 64, MFMA tile kernels otherwise), 1 = force the

@@ -8,6 +8,9 @@ logprobs=5), alternated in blocks of --steps at the --batches siz
 one-row sequences, the penalty / select / adopt kernels) alternated in blocks of --steps with greedy one-row steps of
 the same prompt in the same process; tokens/s of both (one token per step either way) and their ratio.  Written to
 profiles/vqa_contrast_bench.json unless --out says otherwise.
+--guidance (alone): `decode_guidance` — guided decode steps against greedy steps at the same and at twice the batch.
+--guide-kernels P (alone, under `rocprofv3 --kernel-trace --stats -- python tools/vqa_bench.py --guide-kernels P`): the guidance kernel
+on P pairs next to the beam select on P rows.
 --sample adds `decode_sample`: greedy and sampled decode steps (temperature 0.7, top_k 50, top_p 0.9: every pass of the
 sampling kernel) alternated in blocks of --steps at the same batch sizes, and the sampled / greedy tokens/s ratio; with --warp a
 third kind of block, the sampled step with min_p 0.05 and typical_p 0.9, and its cost over the plain sampled step.
@@ -83,12 +86,20 @@ def main():
                     "log-probability stage asking for n alternatives, alternated blocks (DESIGN.md 8.9; runs alone)")
     ap.add_argument("--contrast", default="", help="comma-separated candidate counts (e.g. '4,8'): contrastive-search steps against greedy "
                     "steps of the same process, alternated blocks (DESIGN.md 8.11; runs alone; default --out profiles/vqa_contrast_bench.json)")
+    ap.add_argument("--guidance", action="store_true", help="guided decode steps (guidance_scale 1.5 against the image-free prompt, DESIGN.md "
+                    "8.12) against greedy steps at the same batch and at twice the batch, alternated blocks (runs alone; default --out "
+                    "profiles/vqa_guide_bench.json)")
+    ap.add_argument("--guide-kernels", type=int, default=0, help="pairs: the guidance kernel on that many pairs of vocab-32001 rows and the "
+                    "beam select on as many rows, 20 launches each, for a kernel trace (no engine is built)")
     ap.add_argument("--spec-kernels", type=int, default=0, help="rows: the arg-max and verify tails alone, for a kernel trace")
     ap.add_argument("--score-kernels", type=int, default=0, help="rows: the arg-max and scoring tails alone, for a kernel trace")
     a = ap.parse_args()
     score_b = [int(x) for x in a.score.split(",")] if a.score else []
     if a.only_score and not score_b:
         ap.error("--only-score needs --score B[,B...]")
+    if a.guide_kernels:
+        print(json.dumps({"guide_kernels": guide_kernels(a.guide_kernels)}))
+        return
     if a.rules:
         out = {"decode_rules": decode_rules(a.layers, [int(x) for x in a.batches.split(",")], a.steps, a.rounds, a.ctx)}
         return finish(out, a)
@@ -141,6 +152,12 @@ def main():
     if a.logprobs:
         out["decode_logprobs"] = decode_logprobs(eng, plain_rows, [int(x) for x in a.batches.split(",")], a.steps, a.rounds,
                                                  [int(x) for x in a.logprobs.split(",")])
+        return finish(out, a)
+    if a.guidance:
+        neg_rows = text[:10] + text[10:]             # the same prompt without its image rows: the language prior
+        out["decode_guidance"] = decode_guidance(eng, plain_rows, neg_rows, [b for b in (int(x) for x in a.batches.split(",")) if 2 * b <= cfg.max_slots],
+                                                 a.steps, a.rounds)
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vqa_guide_bench.json")
         return finish(out, a)
     if a.contrast:
         out["decode_contrast"] = decode_contrast(eng, plain_rows, [int(x) for x in a.contrast.split(",")], a.steps, a.rounds)
@@ -572,6 +589,79 @@ def decode_logprobs(eng, rows, batches, steps, rounds, ns):
         for m in modes[1:]:
             leg[m]["over_off_tokens_per_s"] = round(leg[m]["tokens_per_s"] / leg["off"]["tokens_per_s"], 4)
             leg[m]["minus_off_device_ms"] = round(leg[m]["device_ms_per_step"] - leg["off"]["device_ms_per_step"], 4)
+        res[f"B{B}"] = leg
+    return res
+
+
+def guide_kernels(pairs, vocab=32001, reps=20):
+    """The guidance kernel through its door on `pairs` pairs of random fp16 rows (gamma 1.5, every other pair with the plausibility cut at
+    beta 0.1) and the beam select on `pairs` rows of the same matrix, `reps` launches each: the rows of a `rocprofv3 --kernel-trace
+    --stats` run of their own (guide_rows_kernel next to beam_rows_kernel, the same row pass over one row)."""
+    import ctypes
+    from vstar_amd import _lib
+    lib = _lib.load()
+    ld = (vocab + 255) // 256 * 256
+    x0 = (torch.randn(2 * pairs, ld, generator=torch.Generator().manual_seed(0)) * 3).half().cuda()
+    cond, neg = np.arange(pairs, dtype=np.int32), np.arange(pairs, 2 * pairs, dtype=np.int32)
+    sc = np.full(pairs, 1.5, np.float32)
+    lb = np.where(np.arange(pairs) % 2 == 1, np.float32(np.log(0.1)), np.float32(-np.inf)).astype(np.float32)
+    p = lambda arr: ctypes.c_void_p(arr.ctypes.data)      # noqa: E731
+    for _ in range(reps):
+        x = x0.clone()
+        _lib.check_vqa(lib.vstar_vqa_guide_rows(ctypes.c_void_p(x.data_ptr()), _lib.F16, 2 * pairs, vocab, ld, pairs, p(cond), p(neg), p(sc), p(lb)))
+    scores, goff = np.zeros(pairs, np.float32), np.arange(pairs + 1, dtype=np.int32)
+    cs, ct, cr = np.empty((pairs, 2), np.float32), np.empty((pairs, 2), np.int32), np.empty((pairs, 2), np.int32)
+    for _ in range(reps):
+        _lib.check_vqa(lib.vstar_vqa_op_beam_select(ctypes.c_void_p(x0.data_ptr()), _lib.F16, pairs, vocab, ld, p(scores), pairs, p(goff), 2,
+                                                    p(cs), p(ct), p(cr), None))
+    return {"pairs": pairs, "vocab": vocab, "launches_each": reps}
+
+
+def decode_guidance(eng, rows, neg_rows, batches, steps, rounds, gamma=1.5):
+    """Guided decode steps of B samples (B output rows + B negative rows in one call, then the guidance kernel) against two yardsticks of
+    the same process: greedy steps of B sequences, and greedy steps of 2 B sequences — the floor, as a guided step is a 2 B-row step plus
+    one kernel.  Slots 0 .. B-1 hold the prompt, slots B .. 2B-1 the image-free prompt; blocks of `steps` alternated `rounds` times,
+    every slot advancing from its own position.  tokens/s counts emitted tokens: B per guided and greedy step, 2 B per greedy2 step."""
+    modes = ("greedy", "greedy2", "guided")
+    res = {}
+    for B in batches:
+        seqs = [Seq(rows, kv_slot=i) for i in range(B)] + [Seq(neg_rows, kv_slot=B + i) for i in range(B)]
+        want2 = [(i, 0) for i in range(2 * B)]
+        g = (np.arange(B, 2 * B, dtype=np.int32), np.float32(gamma), np.float32(-np.inf))
+        _, nxt = eng.forward(seqs, [(i, -1) for i in range(2 * B)], logits=False)
+        eng.forward(seqs, [(i, -1) for i in range(2 * B)], logits=False, guidance=g)      # (the stage's buffers exist before the timing)
+        nxt = [int(t) for t in nxt]
+        pos = [len(rows)] * B + [len(neg_rows)] * B
+        dev = {m: [] for m in modes}
+        wall = {m: 0.0 for m in modes}
+        for r in range(rounds + 1):                  # (round 0 warms up and is dropped)
+            for m in modes:
+                t0 = time.time()
+                for s in range(steps):
+                    idx = range(B) if m == "greedy" else range(2 * B)
+                    step = [Seq([nxt[i if m != "guided" else i % B]], kv_slot=i, past_len=pos[i]) for i in idx]
+                    if m == "guided":
+                        tok = eng.forward(step, want2, logits=False, guidance=g)[1]
+                        for i in range(B):
+                            nxt[i] = int(tok[i])
+                    else:
+                        tok = eng.forward(step, want2[:len(step)], logits=False)[1]
+                        for j, i in enumerate(idx):
+                            nxt[i] = int(tok[j])
+                    for i in idx:
+                        pos[i] += 1
+                    if r:
+                        dev[m].append(eng.last_forward_ms())
+                if r:
+                    wall[m] += time.time() - t0
+        leg = {"gamma": gamma, "prompt_rows": len(rows), "negative_rows": len(neg_rows), "steps_per_block": steps, "blocks": rounds}
+        for m in modes:
+            w = wall[m] / (rounds * steps) * 1e3
+            leg[m] = {"device_ms_per_step": round(float(np.median(dev[m])), 3), "wall_ms_per_step": round(w, 3),
+                      "tokens_per_s": round((2 * B if m == "greedy2" else B) / w * 1e3, 1)}
+        leg["guided_over_greedy_tokens_per_s"] = round(leg["guided"]["tokens_per_s"] / leg["greedy"]["tokens_per_s"], 4)
+        leg["guided_minus_greedy2_device_ms"] = round(leg["guided"]["device_ms_per_step"] - leg["greedy2"]["device_ms_per_step"], 4)
+        leg["guided_minus_greedy2_wall_ms"] = round(leg["guided"]["wall_ms_per_step"] - leg["greedy2"]["wall_ms_per_step"], 4)
         res[f"B{B}"] = leg
     return res
 

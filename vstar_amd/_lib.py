@@ -60,6 +60,8 @@ EXPORTS_VQA = [
     "vstar_vqa_op_vit_assemble_tokens",
     # contrastive search
     "vstar_vqa_forward_contrast_begin", "vstar_vqa_forward_contrast_step", "vstar_vqa_op_contrast",
+    # guided decoding against a negative sequence
+    "vstar_vqa_forward_guided", "vstar_vqa_forward_sample_guided", "vstar_vqa_guide_rows",
 ]
 
 F32, F16, BF16 = 0, 1, 2
@@ -133,6 +135,16 @@ class VqaLogprobs(ctypes.Structure):
         ("token_rank", c_void_p),
         ("top_logprob", c_void_p),
         ("top_token", c_void_p),
+    ]
+
+
+class VqaGuidance(ctypes.Structure):
+    """vstar_vqa_guidance (include/vstar_vqa.h): n_out and the three host arrays of one call's guidance."""
+    _fields_ = [
+        ("n_out", c_int32),
+        ("neg", c_void_p),
+        ("scale", c_void_p),
+        ("log_beta", c_void_p),
     ]
 
 
@@ -450,6 +462,13 @@ def load() -> ctypes.CDLL:
     lib.vstar_vqa_op_contrast.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vstar_vqa_op_contrast.restype = c_int
+    #  logits / argmax, then guidance, edits, lp; the sampled form: params / tokens, then warpers, guidance, edits, lp
+    lib.vstar_vqa_forward_guided.argtypes = lib.vstar_vqa_forward.argtypes + [c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_guided.restype = c_int
+    lib.vstar_vqa_forward_sample_guided.argtypes = lib.vstar_vqa_forward_sample.argtypes + [c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_forward_sample_guided.restype = c_int
+    lib.vstar_vqa_guide_rows.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.vstar_vqa_guide_rows.restype = c_int
     lib.vstar_vqa_debug_read.argtypes = [H, c_char_p, c_void_p, c_int64]
     lib.vstar_vqa_debug_read.restype = c_int64
     lib.vstar_vqa_last_forward_ms.argtypes = [H]

@@ -246,7 +246,8 @@ class LlavaSearchModel:
                  num_return_sequences: int = 1, prompt_lookup_num_tokens=None, draft_fn=None, repetition_penalty=1.0,
                  no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None, allowed_tokens_fn=None,
                  prefix_allowed_tokens_fn=None, return_dict_in_generate: bool = False, output_scores: bool = False, top_logprobs=None,
-                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None, **unused):
+                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None, guidance_scale=None,
+                 negative_prompt_ids=None, plausibility_beta=0, **unused):
         """do_sample=False: greedy (num_beams 1) or HF 4.31 beam search (num_beams > 1, DESIGN.md §8.2: length_penalty,
         early_stopping, num_return_sequences; returns [num_return_sequences, len], rows EOS-padded).  do_sample=True: HF 4.31
         sampling (temperature > 0, top_k, top_p) on the device, keyed by `seed` (None: drawn from torch's default CPU generator)
@@ -274,9 +275,17 @@ class LlavaSearchModel:
         penalty_alpha in (0, 1] with top_k in [2, 32] (do_sample=False, num_beams 1): HF 4.31 contrastive search, the penalty and the
         pick on the device — the same ids as VQA_LLM.free_form_inference(penalty_alpha=, top_k=); it needs top_k KV
         slots.  Out-of-range values and prompt_lookup_num_tokens > 0 raise ValueError; do_sample, num_beams > 1, an active logits
-        rule or output_scores with it raise NotImplementedError (follow-ups).  None / 0: off."""
+        rule or output_scores with it raise NotImplementedError (follow-ups).  None / 0: off.
+        guidance_scale = gamma, negative_prompt_ids (HF's names and meaning: classifier-free guidance,
+        UnbatchedClassifierFreeGuidanceLogitsProcessor first in the processor list), greedy or sampled: a negative
+        sequence — negative_prompt_ids [1, L] (text ids), or (None) the prompt's last token alone, as the HF processor starts it — is
+        decoded in lock-step in KV slot 1 and every step's scores become gamma * (log_softmax(scores) - log_softmax(negative)) +
+        log_softmax(negative) on the device, exact in double and rounded once where HF rounds every operation to fp16.  None / 1: off.
+        plausibility_beta in [0, 1] (not an HF argument; 0: off): the adaptive plausibility cut of free_form_inference.  A negative
+        or non-finite guidance_scale raises ValueError; num_beams > 1, prompt_lookup_num_tokens > 0 or penalty_alpha with it raise
+        NotImplementedError."""
         from .logits import BEAM_RULES_MESSAGE, rules_from_kwargs
-        from .vqa import check_contrast, check_spec_tokens, resolve_seed, sampling_params, warper_params
+        from .vqa import check_contrast, check_guidance, check_spec_tokens, resolve_seed, sampling_params, warper_params
         from .vqa_engine import Seq, check_logprobs
         if allowed_tokens_fn is not None and prefix_allowed_tokens_fn is not None:
             raise ValueError("pass allowed_tokens_fn or prefix_allowed_tokens_fn, not both")
@@ -308,8 +317,19 @@ class LlavaSearchModel:
             raise ValueError(f"top_k={top_k} candidates need {top_k} KV slots; the engine has max_slots={self.cfg.max_slots}")
         warp = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff) if do_sample else {}
         warper_params(**warp)                          # (validated before any engine work)
+        guide = check_guidance(guidance_scale, plausibility_beta, negative_given=negative_prompt_ids is not None, num_beams=num_beams,
+                               speculative=spec, penalty_alpha=penalty_alpha)
+        if guide is not None and self.cfg.max_slots < 2:
+            raise ValueError("guided decoding needs 2 KV slots (one for the negative sequence); the engine has max_slots=1")
         ids, rows = self._rows(input_ids, images, object_features, images_long, objects_long)
         text = [[t for t in ids if t >= 0]]
+        if guide is not None:       # HF's negative context: negative_prompt_ids, or the prompt's last token alone
+            neg = [ids[-1]] if negative_prompt_ids is None else [int(v) for v in torch.as_tensor(negative_prompt_ids).reshape(-1).tolist()]
+            if not neg or any(not 0 <= t < self.cfg.llm_vocab for t in neg):
+                raise ValueError("negative_prompt_ids must be a non-empty list of vocabulary ids")
+            if len(neg) > len(rows) and len(neg) + max_new_tokens > self.cfg.max_ctx:
+                raise ValueError(f"negative_prompt_ids ({len(neg)} ids) plus max_new_tokens exceeds max_ctx={self.cfg.max_ctx}")
+            guide = ([Seq(neg, kv_slot=1)],) + guide
 
         def result(news, rec=None):
             seqs = torch.tensor([ids + o for o in news], dtype=torch.long)
@@ -338,8 +358,9 @@ class LlavaSearchModel:
                                                 early_stopping, num_return_sequences)[0])
         if do_sample:
             p = sampling_params(temperature, top_k, top_p, resolve_seed(seed))
-            return result(*one(self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text, logprobs=lp, **warp)))
-        return result(*one(self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text, logprobs=lp)))
+            return result(*one(self._llm.sample_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, [p], rules, text, logprobs=lp,
+                                                       guide=guide, **warp)))
+        return result(*one(self._llm.greedy_decode([Seq(rows, kv_slot=0)], [len(rows)], max_new_tokens, rules, text, logprobs=lp, guide=guide)))
 
 
 def load_pretrained_model(model_path, model_base=None, model_name: str = "", load_8bit: bool = False, load_4bit: bool = False,

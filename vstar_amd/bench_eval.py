@@ -164,6 +164,11 @@ def eval_model(args, vqa_llm, vsm=None, world: int = 1, rank: int = 0):
     if alpha is not None and float(alpha) != 0:
         spec_kw["penalty_alpha"], spec_kw["top_k"] = float(alpha), getattr(args, "vqa_top_k", None)
         slots_per_q = max(1, int(spec_kw["top_k"] or 1))            # (a missing / bad K is the decode's ValueError)
+    # `--vqa-guidance-scale G` [`--vqa-plausibility-beta B`]: the free-form pass decodes against the image-free prompt
+    gscale = getattr(args, "vqa_guidance_scale", None)
+    if gscale is not None and float(gscale) != 1:
+        spec_kw["guidance_scale"], spec_kw["plausibility_beta"] = float(gscale), float(getattr(args, "vqa_plausibility_beta", 0) or 0)
+        slots_per_q = max(slots_per_q, 2)                           # (with --vqa-penalty-alpha the decode refuses the combination)
 
     def confidence(i):      # sample i of the free-form call just made, as JSON values
         rec = vqa_llm.generated_logprobs[i]

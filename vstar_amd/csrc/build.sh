@@ -13,20 +13,20 @@ wanted() { [ -z "$ONLY" ] || [[ "$ONLY" == *" $1 "* ]]; }
 mkdir -p build
 rm -f build/gemm256a.o build/f16_gemm256a.o     # (round-3 experiment, moved to tools/experiments/gemm256a)
 pids=()
-HDRS="common.hpp kernels.hpp gemm_epilogue.hpp gemm256_direct_epilogue.hpp mx.hpp gemm4w_loop.inc engine_base.hpp llm_cached.hpp sample.hpp sample_core.hpp beam.hpp score.hpp spec.hpp edit.hpp logprob.hpp contrast.hpp tails_lp.hpp op_doors.hpp row_lse.hpp row_select.hpp ../../include/vstar_hip.h ../../include/vstar_vqa.h"
+HDRS="common.hpp kernels.hpp gemm_epilogue.hpp gemm256_direct_epilogue.hpp mx.hpp gemm4w_loop.inc engine_base.hpp llm_cached.hpp sample.hpp sample_core.hpp beam.hpp score.hpp spec.hpp edit.hpp logprob.hpp contrast.hpp guide.hpp tails_lp.hpp op_doors.hpp row_lse.hpp row_select.hpp ../../include/vstar_hip.h ../../include/vstar_vqa.h"
 stale() {  # stale <object> <source>
   [ ! -f "$1" ] && return 0
   [ "$2" -nt "$1" ] && return 0
   for h in $HDRS; do [ -f "$h" ] && [ "$h" -nt "$1" ] && return 0; done
   return 1
 }
-# bf16 instantiation: every kernel file + the VSM engine and its op-level doors (ops.hip) (sample.hip / beam.hip / score.hip / spec.hip / edit.hip / logprob.hip / contrast.hip are dtype-explicit — one launcher per storage type — and
+# bf16 instantiation: every kernel file + the VSM engine and its op-level doors (ops.hip) (sample.hip / beam.hip / score.hip / spec.hip / edit.hip / logprob.hip / contrast.hip / guide.hip are dtype-explicit — one launcher per storage type — and
 # built once)
 # gemm4w keeps its 256 accumulators in AGPRs BEHIND the compiler's back (they are clobbers of the K-loop asm statement, read back by
 # v_accvgpr_read statements in the epilogue): the compiler must never use AGPRs as VGPR spill space there — it did (a2..a9, round 6)
 extra() { [[ "$1" == gemm4w* ]] && echo "-mllvm -amdgpu-spill-vgpr-to-agpr=0"; }
 # (gemm4w_vit8.hip is gemm4w.hip compiled again for the W8A8 quick-GELU kernels: stale with either file)
-for f in gemm gemm256 gemm4w gemm4w_vit8 norm attention elementwise decode skinny quant heads preprocess engine ops comm sample beam score spec edit logprob contrast; do
+for f in gemm gemm256 gemm4w gemm4w_vit8 norm attention elementwise decode skinny quant heads preprocess engine ops comm sample beam score spec edit logprob contrast guide; do
   if wanted $f && { stale build/$f.o $f.hip || { [ $f = gemm4w_vit8 ] && [ gemm4w.hip -nt build/$f.o ]; }; }; then
     $HIPCC $FLAGS $(extra $f) -c $f.hip -o build/$f.o & pids+=($!)
   fi

@@ -82,6 +82,19 @@ struct LlmLogprobArgs {
   int32_t* top_tok_out = nullptr;
 };
 
+// The guidance stage of forward() (guide.hip): host arrays of n_out entries.  The first n_out wanted rows of the
+// call are its OUTPUT rows, wanted rows [n_out, n_want) its NEGATIVE rows; neg[j] = the wanted-row index (>= n_out) of output row j's
+// negative row (every negative row belongs to exactly one output row) or -1 (row j is unguided), scale[j] = gamma, log_beta[j] <= 0
+// (-inf: no plausibility cut).  Between lm_head and the edits the logits of output row j become the guided row; the tail, the edits,
+// the log-probabilities and all their arrays then have n_out entries and run on rows [0, n_out) of the logits buffer.  ARGMAX and
+// SAMPLE tails only.
+struct LlmGuide {
+  int n_out = 0;
+  const int32_t* neg = nullptr;
+  const float* scale = nullptr;
+  const float* log_beta = nullptr;
+};
+
 // The contrastive-search tail of forward() (contrast.hip): host arrays.  goff == null: the BEGIN call — a prefill
 // (prefix_slot == kv_slot, past_len == the slot's history length or 0) whose new rows' final-norm hidden rows fill the history of
 // their slot, and per wanted row the k best tokens and their probabilities come back, next_tok / next_prob [n_want, k].  goff given:
@@ -271,6 +284,11 @@ struct LlmCached {
   // ---- log-probabilities: allocated by the first forward() that asks for them, never by an engine that does not ----
   float *d_lp = nullptr, *d_lp_top = nullptr;    // [max_want], [max_want, 32] (row stride: the call's n_top)
   int32_t *d_lp_rank = nullptr, *d_lp_tok = nullptr;
+  // ---- guidance: allocated by the first forward() that carries guidance, never by an engine that sees none ----
+  // one device block [4][max_want] = cond row | neg row | scale | log_beta of the call's pairs, and its host image (guide_check fills it)
+  int32_t* d_guide = nullptr;
+  std::vector<int32_t> g_host;
+  int g_pairs = 0;
   // ---- contrastive search: allocated by the first forward() with the contrast tail, never by an engine without one ----
   // The hidden history [max_slots][max_ctx][hidden] and its fp32 reciprocal norms [max_slots][max_ctx]; hist_len[slot] (host) = the
   // rows of the slot's history that describe the slot's K/V rows.  Once the history exists every other forward() (and whatever else
@@ -367,9 +385,10 @@ struct LlmCached {
   // ---- forward(): the head and the tail's stages (one switch over the six tails each) ----
   struct TailCopy { void* dev = nullptr; const void* in = nullptr; void* out = nullptr; size_t bytes = 0; };
   size_t vpad() const { return (size_t)(cfg.vocab + 255) / 256 * 256; }      // row stride of the logits buffer
-  int forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits = nullptr);
+  int forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits = nullptr, const LlmGuide* guide = nullptr);
   int head(int w0, int m);
   int tail_check(const LlmRows& r, const LlmTail& t);
+  int guide_check(const LlmRows& r, const LlmTail& t, const LlmGuide& g);
   int edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed);
   int logprobs_check(const LlmRows& r, const LlmTail& t);
   std::array<TailCopy, 6> tail_copies(const LlmTail& t, int n_want);
@@ -849,6 +868,44 @@ inline void LlmCached::contrast_meta(const LlmRows& r, const LlmTail& t, const s
   goff[a.n_groups] = a.goff[a.n_groups];
 }
 
+// The guidance of a call, validated ahead of its tail (r: ALL wanted rows of the call) and before any device work; the pairs are
+// compacted into g_host (an unguided output row has no record) and the device block is allocated here, by the first call that
+// carries guidance.
+inline int LlmCached::guide_check(const LlmRows& r, const LlmTail& t, const LlmGuide& g) {
+  auto bad = [&](const std::string& m) { e->set_error(m); return VSTAR_ERR_INVALID; };
+  if (t.kind != LlmTail::ARGMAX && t.kind != LlmTail::SAMPLE) {
+    static const char* const names[] = {"arg-max", "sampling", "beam", "scoring", "verify", "contrast"};
+    return bad(std::string("guidance with the ") + names[t.kind] + " tail is not supported (the arg-max and sampling tails take it)");
+  }
+  const int n_want = r.n_want, n_out = g.n_out;
+  if (n_out < 1 || n_out > n_want || !g.neg || !g.scale || !g.log_beta)
+    return bad("guidance: n_out must be in [1, n_want] and neg, scale and log_beta are required");
+  const size_t W = (size_t)max_want;
+  g_host.assign(4 * W, 0);
+  int32_t *cond = g_host.data(), *neg = cond + W;
+  float *scale = (float*)(cond + 2 * W), *beta = (float*)(cond + 3 * W);
+  std::vector<char> owned((size_t)n_want, 0);
+  g_pairs = 0;
+  for (int j = 0; j < n_out; ++j) {
+    if (g.neg[j] == -1) continue;
+    if (g.neg[j] < n_out || g.neg[j] >= n_want) return bad("guidance: neg must be -1 (unguided) or an index into want in [n_out, n_want)");
+    if (owned[(size_t)g.neg[j]]++) return bad("guidance: a negative row belongs to two output rows");
+    cond[g_pairs] = j; neg[g_pairs] = g.neg[j]; scale[g_pairs] = g.scale[j]; beta[g_pairs] = g.log_beta[j];
+    ++g_pairs;
+  }
+  for (int k = n_out; k < n_want; ++k)
+    if (!owned[(size_t)k]) return bad("guidance: a negative row (want[n_out ..]) belongs to no output row");
+  if (g_pairs)
+    if (const char* m = vstar_guide_check(n_want, cfg.vocab, g_pairs, cond, neg, scale, beta)) return bad(std::string("guidance: ") + m);
+  if (!d_guide) {     // one block: a failed allocation leaves nothing behind and the engine as it was
+    int32_t* blk = nullptr;
+    const int rc = e->dalloc(&blk, 4 * W);
+    if (rc) { (void)hipGetLastError(); return rc; }
+    d_guide = blk;
+  }
+  return 0;
+}
+
 // The edits of a call, validated next to its tail (after the rows: the row fault is the one reported) and before any device work;
 // the device arrays for the lists are allocated here, by the first call that carries edits.
 inline int LlmCached::edits_check(const LlmRows& r, const LlmTail& t, const LlmEdits& ed) {
@@ -988,7 +1045,7 @@ inline int LlmCached::tail_launch(const LlmTail& t, int w0, int m) {
   return 0;
 }
 
-inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits) {
+inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmEdits* edits, const LlmGuide* guide) {
   if (!ready) { e->set_error("language-model runner not initialised"); return VSTAR_ERR_STATE; }
   const LlmCachedCfg& c = cfg;
   const int nseq = rw.nseq, n_want = rw.n_want;
@@ -1016,9 +1073,14 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   }
   for (int j = 0; j < n_want; ++j)
     if (want[j] < 0 || want[j] >= R) { e->set_error("want row out of range"); return VSTAR_ERR_INVALID; }
-  RC(tail_check(rw, tail));
-  if (edits) RC(edits_check(rw, tail, *edits));
-  if (tail.has_lp) RC(logprobs_check(rw, tail));
+  // with guidance the tail, the edits and the log-probabilities describe the OUTPUT rows, the first n_out wanted rows (LlmGuide)
+  if (guide) RC(guide_check(rw, tail, *guide));
+  const int n_out = guide ? guide->n_out : n_want;
+  LlmRows rt = rw;
+  rt.n_want = n_out;
+  RC(tail_check(rt, tail));
+  if (edits) RC(edits_check(rt, tail, *edits));
+  if (tail.has_lp) RC(logprobs_check(rt, tail));
   // ---- KV ancestry: a continued sequence in an ancestral slot attends through the table ----
   bool use_anc = false;
   for (int i = 0; i < nseq; ++i) {
@@ -1080,15 +1142,16 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   } else if (c_hist) {         // host arithmetic only: the history of a slot ends where this call starts writing its K/V rows
     for (int i = 0; i < nseq; ++i) hist_lower(kv_slot[i], past_len[i]);
   }
-  const std::array<TailCopy, 6> copies = tail_copies(tail, n_want);
+  const std::array<TailCopy, 6> copies = tail_copies(tail, n_out);
   for (const TailCopy& x : copies)
     if (x.in && x.bytes) LCHK(hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, e->stream));
   if (edits) {
-    const size_t n_tok = (size_t)edits->off[3 * n_want];
-    LCHK(hipMemcpyAsync(d_eoff, edits->off, ((size_t)3 * n_want + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    const size_t n_tok = (size_t)edits->off[3 * n_out];
+    LCHK(hipMemcpyAsync(d_eoff, edits->off, ((size_t)3 * n_out + 1) * 4, hipMemcpyHostToDevice, e->stream));
     if (n_tok) LCHK(hipMemcpyAsync(d_etok, edits->tok, n_tok * 4, hipMemcpyHostToDevice, e->stream));
-    if (edits->penalty) LCHK(hipMemcpyAsync(d_epen, edits->penalty, (size_t)n_want * 4, hipMemcpyHostToDevice, e->stream));
+    if (edits->penalty) LCHK(hipMemcpyAsync(d_epen, edits->penalty, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
   }
+  if (guide && g_pairs) LCHK(hipMemcpyAsync(d_guide, g_host.data(), g_host.size() * 4, hipMemcpyHostToDevice, e->stream));
   LCHK(hipStreamSynchronize(e->stream));       // the host vectors above go out of scope at return; keep it simple
   LCHK(hipEventRecord(ev0, e->stream));
   // ---- inputs_embeds (prepare_inputs_labels_for_multimodal, llava_search_arch.py:96-266) ----
@@ -1098,8 +1161,14 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
   else RC(llm_layers_cached(rows, max_keys, maxT == 1, use_anc ? d_anc : nullptr));
   // ---- head + tail, max_want wanted rows at a time: one pass, except for the scoring tail (CHUNKING RULE, LlmScoreArgs) ----
   for (int w0 = 0; w0 < n_want; w0 += max_want) {
-    const int m = n_want - w0 < max_want ? n_want - w0 : max_want;
+    int m = n_want - w0 < max_want ? n_want - w0 : max_want;
     RC(head(w0, m));
+    if (guide) {          // (one chunk: w0 == 0) output row j <- guided(row j, its negative row); the stages behind see rows [0, n_out)
+      if (g_pairs)
+        LCHK(vstar_guide_rows_lp(logits, c.vocab, (int64_t)vpad(), g_pairs, d_guide, d_guide + max_want, (const float*)(d_guide + 2 * max_want),
+                                 (const float*)(d_guide + 3 * max_want), e->stream));
+      m = n_out;
+    }
     if (edits) LCHK(vstar_edit_rows_lp(logits, m, c.vocab, (int64_t)vpad(), d_eoff + 3 * w0, d_etok, d_epen + w0, e->stream));
     RC(tail_launch(tail, w0, m));
     if (tail.has_lp)      // (one chunk: w0 == 0) the row the tail just read, the token it just chose
@@ -1107,16 +1176,16 @@ inline int LlmCached::forward(const LlmRows& rw, const LlmTail& tail, const LlmE
                                  tail.lp.rank_out ? d_lp_rank : nullptr, d_lp_top, d_lp_tok, e->stream));
   }
   LCHK(hipEventRecord(ev1, e->stream));
-  if (n_want && tail.logits_out)
-    LCHK(hipMemcpy2DAsync(tail.logits_out, (size_t)c.vocab * 2, logits, vpad() * 2, (size_t)c.vocab * 2, n_want,
+  if (n_out && tail.logits_out)
+    LCHK(hipMemcpy2DAsync(tail.logits_out, (size_t)c.vocab * 2, logits, vpad() * 2, (size_t)c.vocab * 2, n_out,
                             hipMemcpyDeviceToHost, e->stream));
   for (const TailCopy& x : copies)
     if (x.out && x.bytes) LCHK(hipMemcpyAsync(x.out, x.dev, x.bytes, hipMemcpyDeviceToHost, e->stream));
   if (tail.has_lp) {
     const LlmLogprobArgs& a = tail.lp;
-    const size_t nt4 = (size_t)n_want * a.n_top * 4;
-    LCHK(hipMemcpyAsync(a.lp_out, d_lp, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
-    if (a.rank_out) LCHK(hipMemcpyAsync(a.rank_out, d_lp_rank, (size_t)n_want * 4, hipMemcpyDeviceToHost, e->stream));
+    const size_t nt4 = (size_t)n_out * a.n_top * 4;
+    LCHK(hipMemcpyAsync(a.lp_out, d_lp, (size_t)n_out * 4, hipMemcpyDeviceToHost, e->stream));
+    if (a.rank_out) LCHK(hipMemcpyAsync(a.rank_out, d_lp_rank, (size_t)n_out * 4, hipMemcpyDeviceToHost, e->stream));
     if (nt4) {
       LCHK(hipMemcpyAsync(a.top_lp_out, d_lp_top, nt4, hipMemcpyDeviceToHost, e->stream));
       LCHK(hipMemcpyAsync(a.top_tok_out, d_lp_tok, nt4, hipMemcpyDeviceToHost, e->stream));

@@ -1,6 +1,6 @@
-// tails_lp.hpp — the four decode tails (sample / beam / score / spec .hip), the logits-edit stage (edit.hip), the log-probability stage (logprob.hip) and the contrastive-search kernels (contrast.hip) under `_lp` names, as argmax_rows_lp has one: each
+// tails_lp.hpp — the four decode tails (sample / beam / score / spec .hip), the logits-edit stage (edit.hip), the log-probability stage (logprob.hip), the guidance stage (guide.hip) and the contrastive-search kernels (contrast.hip) under `_lp` names, as argmax_rows_lp has one: each
 // forwards to the launcher of the including instantiation's storage type (VSTAR_LP_F16: fp16, else bf16).  The .hip files stay
-// compiled once, dtype-explicit; the arguments are documented at the launchers (sample.hpp, beam.hpp, score.hpp, spec.hpp, edit.hpp, logprob.hpp, contrast.hpp).
+// compiled once, dtype-explicit; the arguments are documented at the launchers (sample.hpp, beam.hpp, score.hpp, spec.hpp, edit.hpp, logprob.hpp, contrast.hpp, guide.hpp).
 #pragma once
 #include "common.hpp"
 #include "sample.hpp"
@@ -10,6 +10,7 @@
 #include "edit.hpp"
 #include "logprob.hpp"
 #include "contrast.hpp"
+#include "guide.hpp"
 
 #ifdef VSTAR_LP_F16
 #define VSTAR_TAIL_LP(name) name##_f16
@@ -37,6 +38,10 @@ inline hipError_t vstar_verify_rows_lp(const lp_t* x, int rows, int vocab, int64
 inline hipError_t vstar_edit_rows_lp(lp_t* x, int rows, int vocab, int64_t ld, const int32_t* off, const int32_t* tok, const float* penalty,
                                      hipStream_t s) {
   return VSTAR_TAIL_LP(vstar_edit_rows)(x, rows, vocab, ld, off, tok, penalty, s);
+}
+inline hipError_t vstar_guide_rows_lp(lp_t* x, int vocab, int64_t ld, int n_pairs, const int32_t* cond_row, const int32_t* neg_row,
+                                      const float* scale, const float* log_beta, hipStream_t s) {
+  return VSTAR_TAIL_LP(vstar_guide_rows)(x, vocab, ld, n_pairs, cond_row, neg_row, scale, log_beta, s);
 }
 inline hipError_t vstar_logprob_rows_lp(const lp_t* x, int rows, int vocab, int64_t ld, const int32_t* d_tokens, int n_top, float* lp_tok,
                                         int32_t* rank, float* top_lp, int32_t* top_tok, hipStream_t s) {

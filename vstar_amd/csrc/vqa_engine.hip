@@ -318,11 +318,26 @@ static const LlmLogprobArgs* logprobs_of(const vstar_vqa_logprobs* lp, LlmLogpro
 int vstar_vqa_forward_logprobs(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
                                const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                                uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
+  return vstar_vqa_forward_guided(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, logits_f16, argmax, nullptr, edits, lp);
+}
+
+// the two forms with the guidance stage between lm_head and the edits; the _logprobs / _warp entries pass NULL
+static const LlmGuide* guide_of(const vstar_vqa_guidance* g, LlmGuide* out) {
+  if (!g) return nullptr;
+  *out = LlmGuide{g->n_out, g->neg, g->scale, g->log_beta};
+  return out;
+}
+
+int vstar_vqa_forward_guided(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                             const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                             uint16_t* logits_f16, int32_t* argmax, const vstar_vqa_guidance* guidance,
+                             const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   LlmEdits ed;
   LlmLogprobArgs la;
+  LlmGuide gd;
   return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
-                        LlmTail::argmax(logits_f16, argmax).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
+                        LlmTail::argmax(logits_f16, argmax).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed), guide_of(guidance, &gd));
 }
 
 int vstar_vqa_forward_sample(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
@@ -349,12 +364,22 @@ int vstar_vqa_forward_sample_warp(vstar_vqa_handle* h, int nseq, const int32_t* 
                                   const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
                                   const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_warpers* warpers,
                                   const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
+  return vstar_vqa_forward_sample_guided(h, nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want, params, tokens, warpers, nullptr,
+                                         edits, lp);
+}
+
+int vstar_vqa_forward_sample_guided(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,
+                                    const int32_t* prefix_slot, const int32_t* past_len, int n_want, const int32_t* want,
+                                    const vstar_vqa_sampling* params, int32_t* tokens, const vstar_vqa_warpers* warpers,
+                                    const vstar_vqa_guidance* guidance, const vstar_vqa_logit_edits* edits, const vstar_vqa_logprobs* lp) {
   if (int rc = vqa_ready(h)) return rc;
   if (n_want > 0 && (!params || !tokens)) { h->set_error("forward_sample: params and tokens are required"); return VSTAR_ERR_INVALID; }
   LlmEdits ed;
   LlmLogprobArgs la;
+  LlmGuide gd;
   return h->run.forward(LlmRows{nseq, row_off, src, kv_slot, prefix_slot, past_len, n_want, want},
-                        LlmTail::sample(params, tokens, warpers).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed));
+                        LlmTail::sample(params, tokens, warpers).with_logprobs(logprobs_of(lp, &la)), edits_of(edits, &ed),
+                        guide_of(guidance, &gd));
 }
 
 int vstar_vqa_forward_beam(vstar_vqa_handle* h, int nseq, const int32_t* row_off, const int32_t* src, const int32_t* kv_slot,

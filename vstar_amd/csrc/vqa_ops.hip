@@ -246,6 +246,25 @@ int vstar_vqa_op_logprobs(const void* dev_logits, int dtype, int rows, int vocab
   return op_result(e, fn);
 }
 
+// the guidance kernel (guide.hip) on device logits: the records are checked, uploaded, one launch
+int vstar_vqa_guide_rows(void* dev_logits, int dtype, int rows, int vocab, int64_t ld, int n_pairs, const int32_t* cond_row,
+                         const int32_t* neg_row, const float* scale, const float* log_beta) {
+  const char* fn = "vstar_vqa_guide_rows";
+  if (!dev_logits || !cond_row || !neg_row || !scale || !log_beta) return op_refuse(fn, "a NULL pointer");
+  if (dtype != VSTAR_F16 && dtype != VSTAR_BF16) return op_refuse(fn, "dtype must be F16 or BF16");
+  if (ld < vocab) return op_refuse(fn, "ld must be >= vocab");
+  if (const char* m = vstar_guide_check(rows, vocab, n_pairs, cond_row, neg_row, scale, log_beta)) return op_refuse(fn, m);
+  hipError_t e = hipSuccess;
+  OpBuf<int32_t> d_c(e, n_pairs), d_n(e, n_pairs);
+  OpBuf<float> d_s(e, n_pairs), d_b(e, n_pairs);
+  d_c.upload(cond_row);
+  d_n.upload(neg_row);
+  d_s.upload(scale);
+  d_b.upload(log_beta);
+  op_launch(e, dtype, vstar_guide_rows_f16, vstar_guide_rows_bf16, (uint16_t*)dev_logits, vocab, ld, n_pairs, d_c, d_n, d_s, d_b, nullptr);
+  return op_result(e, fn);
+}
+
 // ---- GEMM, the weight-only quantisers and their GEMVs, the KV quantiser ----
 int vstar_vqa_op_gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,
                       int epilogue, int kernel, const void* norm_w, float norm_eps) {

@@ -151,6 +151,38 @@ def check_contrast(penalty_alpha, top_k, *, sampled: bool, num_beams: int, specu
     return alpha
 
 
+def check_guidance(guidance_scale, plausibility_beta=0, *, negative_given: bool = False, num_beams: int = 1, speculative: int = 0,
+                   penalty_alpha=None):
+    """The guidance arguments of free_form_batch / generate (HF: guidance_scale, negative_prompt_ids): None when the
+    mode is off (guidance_scale None or 1, as in HF), else (gamma, log_beta) — the fp32 pair every guided engine call carries, log_beta
+    = float32(log(plausibility_beta)), -inf for beta 0 (no plausibility cut).  ValueError for a value out of range (gamma negative or
+    not finite, beta outside [0, 1]) and for a negative prompt or a plausibility_beta > 0 without a guidance_scale (negative_given:
+    the caller got a negative_question / negative_image / negative_prompt_ids); NotImplementedError for the combinations that are
+    out of scope: beam search, speculative decoding, contrastive search."""
+    beta = float(plausibility_beta)
+    if not 0 <= beta <= 1:
+        raise ValueError(f"plausibility_beta must be in [0, 1] (0 = off), got {plausibility_beta!r}")
+    if guidance_scale is None:
+        if negative_given:
+            raise ValueError("a negative prompt (negative_question / negative_image / negative_prompt_ids) needs a guidance_scale")
+        if beta > 0:
+            raise ValueError("plausibility_beta > 0 needs a guidance_scale")
+        return None
+    gamma = float(guidance_scale)
+    if not 0 <= gamma <= float(np.finfo(np.float32).max):
+        raise ValueError(f"guidance_scale must be finite and >= 0 (None / 1 = off), got {guidance_scale!r}")
+    if gamma == 1:
+        return None
+    if num_beams > 1:
+        raise NotImplementedError("guided decoding (guidance_scale) with num_beams > 1 is not implemented")
+    if speculative:
+        raise NotImplementedError("guided decoding (guidance_scale) with speculative decoding is not implemented")
+    if penalty_alpha is not None and float(penalty_alpha) != 0:
+        raise NotImplementedError("guided decoding (guidance_scale) with contrastive search (penalty_alpha > 0) is not implemented")
+    with np.errstate(divide="ignore"):
+        return gamma, float(np.float32(np.log(np.float64(beta))))
+
+
 def _warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff) -> dict:
     """The `warpers=` keyword of the engine's sampled calls; empty when all four are off (the plain call)."""
     w = warper_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
@@ -272,7 +304,8 @@ class VQA_LLM:
                             object_crops=None, images_long=None, objects_long=None, *, top_k=50, seed=None, speculative=0,
                             draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
                             suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
-                            epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None) -> str:
+                            epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None, guidance_scale=None, negative_question=None,
+                            negative_image=None, plausibility_beta=0) -> str:
         """temperature 0: greedy (the evaluation's setting).  temperature > 0: model.generate(do_sample=True, temperature,
         top_k, top_p) as in HF 4.31, drawn on the device; `seed` (None: drawn from torch's default CPU generator,
         so torch.manual_seed makes runs reproducible) keys the Philox stream of the draws.  num_beams > 1 (temperature 0): HF
@@ -287,20 +320,30 @@ class VQA_LLM:
         logprobs = n in [0, 32]: self.generated_logprobs[0] then holds, per generated token, its log-probability and rank and the n
         best alternatives (`TokenLogprobs`), aligned with self.generated_ids[0]; the returned text is unchanged.
         penalty_alpha in (0, 1] (temperature 0, num_beams 1): HF 4.31 contrastive search with top_k (2 .. 32, to be given) candidates
-        per step, the degeneration penalty and the pick on the device (`contrastive_decode`); None / 0: off."""
+        per step, the degeneration penalty and the pick on the device (`contrastive_decode`); None / 0: off.
+        guidance_scale = gamma (None / 1: off, as in HF): guided decoding against a negative prompt (classifier-free guidance / visual
+        contrastive decoding), greedy or sampled: a second sequence is decoded in lock-step in a KV slot of its own
+        and every step's logits become gamma * (log_softmax(row) - log_softmax(negative row)) + log_softmax(negative row) on the device,
+        ahead of the logits rules.  The negative prompt is the same v1 prompt of negative_question (None: the question) with every
+        <image> / <object> placeholder left out (negative_image None: the language prior), or with negative_image (a PIL image) in
+        place of the image, the object crops kept.  plausibility_beta in [0, 1] (0: off): tokens whose probability under the
+        un-guided row is below beta times its maximum are dropped (-inf)."""
         return self.free_form_batch([dict(image=image, question=question, object_crops=object_crops, images_long=images_long,
                                           objects_long=objects_long)], max_new_tokens, temperature=temperature, top_p=top_p,
                                     top_k=top_k, seed=seed, num_beams=num_beams, speculative=speculative, draft_fn=draft_fn,
                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                     bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                                     allowed_tokens_fn=allowed_tokens_fn, logprobs=logprobs, min_p=min_p, typical_p=typical_p,
-                                    epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, penalty_alpha=penalty_alpha)[0]
+                                    epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, penalty_alpha=penalty_alpha,
+                                    guidance_scale=guidance_scale, negative_question=negative_question, negative_image=negative_image,
+                                    plausibility_beta=plausibility_beta)[0]
 
     def free_form_batch(self, samples: Sequence[dict], max_new_tokens: int = 200, *, temperature=0, top_p=None, top_k=50,
                         seed=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, speculative: int = 0,
                         draft_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
                         suppress_tokens=None, allowed_tokens_fn=None, logprobs=None, min_p=None, typical_p=None,
-                        epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None) -> List[str]:
+                        epsilon_cutoff=None, eta_cutoff=None, penalty_alpha=None, guidance_scale=None, negative_question=None,
+                        negative_image=None, plausibility_beta=0) -> List[str]:
         """Decode of several samples at once: one prefill call, then one engine call per generated position.  temperature 0:
         greedy; temperature > 0: sampled, sample i with seed samples[i].get("seed", seed + i) (stream 0), so element i equals a
         single free_form_inference call with that seed.  num_beams = k > 1: beam search, the k beams of sample i in KV slots
@@ -316,7 +359,12 @@ class VQA_LLM:
         DESIGN.md §8.10 for every sample; all off (the default): the engine calls are the plain ones.
         penalty_alpha in (0, 1] (temperature 0, num_beams 1, no rules, no logprobs, not speculative): contrastive search with
         top_k (2 .. 32) candidates, the k candidate slots of sample i in KV slots i*k .. i*k+k-1 (n*k <= max_slots), one group per
-        sample in every step's forward (`contrastive_decode`); None / 0 (default): off, every call is as before."""
+        sample in every step's forward (`contrastive_decode`); None / 0 (default): off, every call is as before.
+        guidance_scale, negative_question, negative_image, plausibility_beta (see free_form_inference; num_beams 1, not speculative, no
+        penalty_alpha; DESIGN.md §8.12): sample i decodes in KV slot 2 i and its negative sequence in slot 2 i + 1 (2 n <= max_slots);
+        both are prefilled in the one prefill call and take the chosen token at every step, in one engine call; a sample's dict may
+        carry its own negative_question / negative_image.  A negative_image takes one more feature slot per sample.  None / 1
+        (default): off, every call is as before."""
         cfg, eng = self.cfg, self.engine
         n = len(samples)
         if num_beams < 1:
@@ -326,6 +374,13 @@ class VQA_LLM:
         if rules is not None and num_beams > 1:
             raise NotImplementedError(BEAM_RULES_MESSAGE)
         speculative = check_spec_tokens(speculative)
+        neg_given = negative_question is not None or negative_image is not None or \
+            any(s.get("negative_question") is not None or s.get("negative_image") is not None for s in samples)
+        guide = check_guidance(guidance_scale, plausibility_beta, negative_given=neg_given, num_beams=num_beams, speculative=speculative,
+                               penalty_alpha=penalty_alpha)
+        if guide is not None and 2 * n > cfg.max_slots:
+            raise ValueError(f"{n} guided samples need {2 * n} KV slots (one more per sample for its negative sequence); the engine "
+                             f"has max_slots={cfg.max_slots} (build it with a larger VQAConfig.max_slots)")
         if speculative and num_beams > 1:
             raise ValueError("speculative decoding (speculative > 0) cannot be combined with beam search (num_beams > 1)")
         if num_beams > 1 and temperature > 0:
@@ -341,7 +396,7 @@ class VQA_LLM:
                                       "own scores, and exposing those is a follow-up")
         alpha = check_contrast(penalty_alpha, top_k, sampled=temperature > 0, num_beams=num_beams, speculative=speculative,
                                rules=rules, logprobs=logprobs)
-        k_slots = int(top_k) if alpha is not None else num_beams      # KV slots per sample
+        k_slots = int(top_k) if alpha is not None else 2 if guide is not None else num_beams      # KV slots per sample
         if alpha is not None and n * k_slots > cfg.max_slots:
             raise ValueError(f"{n} samples x {k_slots} candidates need {n * k_slots} KV slots; the engine has max_slots="
                              f"{cfg.max_slots} (build it with a larger VQAConfig.max_slots)")
@@ -350,7 +405,7 @@ class VQA_LLM:
             warper_params(**warp)                      # (validated before any engine work)
             base = resolve_seed(seed)
             params = [sampling_params(temperature, top_k, top_p, s.get("seed", base + i)) for i, s in enumerate(samples)]
-        seqs, lens, id_lens, text_ids = [], [], [], []
+        seqs, lens, id_lens, text_ids, neg_seqs = [], [], [], [], []
         fslot = 0
         for i, s in enumerate(samples):
             crops = s.get("object_crops")
@@ -361,6 +416,21 @@ class VQA_LLM:
             lens.append(len(rows))
             id_lens.append(len(ids))
             text_ids.append([t for t in ids if t >= 0])
+            if guide is not None:
+                neg_q, neg_img = s.get("negative_question", negative_question), s.get("negative_image", negative_image)
+                nids = ids if neg_q is None else self._question_rows(neg_q, img_slots, obj_slots, s.get("images_long"), s.get("objects_long"))[0]
+                if neg_img is None:       # the language prior: no image, no object crops
+                    nrows = [t for t in nids if t >= 0]
+                else:                     # the caller's degraded image in a feature slot of its own, the same crops
+                    if fslot + 1 > cfg.max_images:
+                        raise ValueError(f"the negative image needs one more feature slot than max_images={cfg.max_images}")
+                    eng.encode_images(self.image_processor.preprocess(neg_img, return_tensors="pt")["pixel_values"][0][None], fslot)
+                    nrows = eng.expand_ids(nids, [fslot], obj_slots, s.get("images_long"), s.get("objects_long"))
+                    fslot += 1
+                if len(nrows) > len(rows) and len(nrows) + max_new_tokens > cfg.max_ctx:
+                    raise ValueError(f"the negative prompt ({len(nrows)} rows) plus max_new_tokens exceeds max_ctx={cfg.max_ctx}")
+                neg_seqs.append(Seq(nrows, kv_slot=i * k_slots + 1))
+        guide = None if guide is None else (neg_seqs,) + guide
         if alpha is not None:
             res = self.contrastive_decode(seqs, lens, max_new_tokens, alpha, k_slots)
         elif speculative:
@@ -371,9 +441,9 @@ class VQA_LLM:
             outs = self.beam_decode(seqs, lens, id_lens, max_new_tokens, num_beams, length_penalty, early_stopping)
             res = [o[0] for o in outs]
         elif temperature > 0:
-            res = self.sample_decode(seqs, lens, max_new_tokens, params, rules, text_ids, logprobs=logprobs, **warp)
+            res = self.sample_decode(seqs, lens, max_new_tokens, params, rules, text_ids, logprobs=logprobs, guide=guide, **warp)
         else:
-            res = self.greedy_decode(seqs, lens, max_new_tokens, rules, text_ids, logprobs=logprobs)
+            res = self.greedy_decode(seqs, lens, max_new_tokens, rules, text_ids, logprobs=logprobs, guide=guide)
         self.generated_ids, self.generated_logprobs = res if logprobs is not None else (res, None)
         texts = []
         for ids in self.generated_ids:
@@ -390,27 +460,50 @@ class VQA_LLM:
             return None
         return LogitRules.pack([rules.plan(h, g, self.eos_token_id, b) for h, g, b in rows])
 
+    def _with_negatives(self, guide, call):
+        """The chooser of `_decode` for `call(step, want, idx, t, edits, **kw)`.  guide None: `call` itself.  guide = (neg_seqs, gamma,
+        log_beta): every engine call also carries the negative sequence of each of its sequences — neg_seqs[i], the
+        negative prompt of sequence i in a KV slot of its own, at the prefill; afterwards the same new token at the negative
+        sequence's own position — with its last row wanted behind the output rows, and `guidance=` pairs output row j with it."""
+        if guide is None:
+            return call
+        neg_seqs, gamma, log_beta = guide
+        neg_pos = [s.past_len + len(s.rows) for s in neg_seqs]
+
+        def choose(step, want, idx, t, edits):
+            m = len(step)
+            if t == 0:
+                negs = [neg_seqs[i] for i in idx]
+            else:
+                negs = [Seq(list(step[j].rows), kv_slot=neg_seqs[i].kv_slot, past_len=neg_pos[i]) for j, i in enumerate(idx)]
+                for i in idx:
+                    neg_pos[i] += 1
+            g = (np.arange(m, 2 * m, dtype=np.int32), np.float32(gamma), np.float32(log_beta))
+            return call(list(step) + negs, list(want) + [(m + j, -1) for j in range(m)], idx, t, edits, guidance=g)
+        return choose
+
     def greedy_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, rules: Optional[LogitRules] = None,
-                      histories=None, logprobs=None):
-        """model.generate(do_sample=False, use_cache=True) for every sequence.  rules + histories, logprobs: see `_decode`."""
+                      histories=None, logprobs=None, guide=None):
+        """model.generate(do_sample=False, use_cache=True) for every sequence.  rules + histories, logprobs: see `_decode`; guide: see
+        `_with_negatives` (None: the plain engine calls)."""
         if logprobs is None:
-            return self._decode(seqs, lens, max_new_tokens,
-                                lambda step, want, idx, t, edits: self.engine.forward(step, want, logits=False, edits=edits)[1], rules, histories)
-        return self._decode(seqs, lens, max_new_tokens,
-                            lambda step, want, idx, t, edits: self.engine.forward(step, want, logits=False, edits=edits, logprobs=logprobs)[1:],
-                            rules, histories, logprobs)
+            return self._decode(seqs, lens, max_new_tokens, self._with_negatives(
+                guide, lambda step, want, idx, t, edits, **kw: self.engine.forward(step, want, logits=False, edits=edits, **kw)[1]), rules, histories)
+        return self._decode(seqs, lens, max_new_tokens, self._with_negatives(
+            guide, lambda step, want, idx, t, edits, **kw: self.engine.forward(step, want, logits=False, edits=edits, logprobs=logprobs, **kw)[1:]),
+            rules, histories, logprobs)
 
     def sample_decode(self, seqs: Sequence[Seq], lens: Sequence[int], max_new_tokens: int, params, rules: Optional[LogitRules] = None,
-                      histories=None, logprobs=None, *, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+                      histories=None, logprobs=None, *, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, guide=None):
         """model.generate(do_sample=True, use_cache=True): params[i] (`_lib.VqaSampling`) drives sequence i; the Philox step
         of a draw is the index of the token it generates (0 = the token drawn from the prefill's last row).  rules + histories,
         logprobs: see `_decode`.  min_p .. eta_cutoff: `warper_params` (DESIGN.md §8.10), the same record for every sequence;
-        all off: the engine calls are the plain ones."""
+        all off: the engine calls are the plain ones.  guide: see `_with_negatives` (None: the plain engine calls)."""
         wkw = _warp_kw(min_p, typical_p, epsilon_cutoff, eta_cutoff)
 
-        def choose(step, want, idx, t, edits):
-            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx], edits=edits, logprobs=logprobs, **wkw)
-        return self._decode(seqs, lens, max_new_tokens, choose, rules, histories, logprobs)
+        def choose(step, want, idx, t, edits, **kw):
+            return self.engine.forward_sample(step, want, [_with_step(params[i], t) for i in idx], edits=edits, logprobs=logprobs, **wkw, **kw)
+        return self._decode(seqs, lens, max_new_tokens, self._with_negatives(guide, choose), rules, histories, logprobs)
 
     def speculative_decode(self, seqs: Sequence[Seq], lens: Sequence[int], ids: Sequence[Sequence[int]], max_new_tokens: int,
                            d: int, params=None, draft_fn=None, rules: Optional[LogitRules] = None, logprobs=None, *, min_p=None,

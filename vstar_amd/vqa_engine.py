@@ -195,20 +195,63 @@ class VqaEngine:
         st = _lib.VqaLogprobs(n, lp.ctypes.data, rk.ctypes.data, tl.ctypes.data if n else None, tt.ctypes.data if n else None)
         return st, TokenLogprobs(lp[:nw], rk[:nw], tt[:nw], tl[:nw])
 
+    @staticmethod
+    def _guidance_struct(guidance, nw: int):
+        """`guidance` = (neg, scale, log_beta), one entry per OUTPUT row (the first len(neg) wanted rows; the rest of the nw wanted
+        rows are the negative rows neg points at, -1 = unguided) -> the vstar_vqa_guidance record behind the C pointer, the arrays to
+        keep alive while the call runs, and n_out."""
+        neg, scale, lb = guidance
+        neg = np.ascontiguousarray(neg, np.int32)
+        n_out = int(neg.size)
+        scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float32), neg.shape))
+        lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lb, np.float32), neg.shape))
+        if neg.ndim != 1 or not 1 <= n_out <= nw:
+            raise ValueError(f"guidance for {n_out} output rows given for {nw} wanted rows")
+        return _lib.VqaGuidance(n_out, neg.ctypes.data, scale.ctypes.data, lb.ctypes.data), (neg, scale, lb), n_out
+
+    def guide_rows(self, dev_logits: torch.Tensor, cond_row, neg_row, scale, log_beta, vocab: Optional[int] = None) -> None:
+        """The guidance kernel alone (csrc/guide.hip) on a DEVICE tensor [rows, ld] of float16 / bfloat16: row
+        cond_row[p] becomes the guided combination of itself and row neg_row[p], in place, for its first `vocab` (default ld)
+        columns; scale[p] = gamma, log_beta[p] <= 0 (-inf: no plausibility cut).  Nothing else is written."""
+        if dev_logits.dim() != 2 or not dev_logits.is_contiguous() or dev_logits.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("guide_rows needs a contiguous 2-d float16 / bfloat16 device tensor")
+        rows, ld = dev_logits.shape
+        c, u = np.ascontiguousarray(cond_row, np.int32), np.ascontiguousarray(neg_row, np.int32)
+        sc, lb = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(log_beta, np.float32)
+        if not (c.shape == u.shape == sc.shape == lb.shape and c.ndim == 1):
+            raise ValueError("guide_rows: cond_row, neg_row, scale and log_beta must be 1-d arrays of one length")
+        _lib.check_vqa(self.lib.vstar_vqa_guide_rows(ctypes.c_void_p(dev_logits.data_ptr()), _DT[dev_logits.dtype], rows,
+                                                     ld if vocab is None else int(vocab), ld, int(c.size), _ptr(c), _ptr(u), _ptr(sc), _ptr(lb)))
+
     def logit_edit_capacity(self) -> int:
         """The most token ids (the three lists of all wanted rows together) one call with edits may carry."""
         return int(self.lib.vstar_vqa_logit_edit_capacity(self.handle))
 
-    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True, edits=None, logprobs=None):
+    def forward(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], logits: bool = True, edits=None, logprobs=None, guidance=None):
         """want: (sequence index, row index inside that sequence's new rows; negative counts from the end).
         edits: None, or the packed arrays of `LogitRules.pack` (one plan per wanted row): the logits are edited on the device
         ahead of the arg-max (csrc/edit.hip) and the returned logits are the edited ones (HF's `scores`).
         logprobs: None, or n in [0, 32]: the arg-max's log-probability and rank and the n best alternatives of every wanted row,
         computed on the device from the (edited) row the arg-max was taken from (csrc/logprob.hip).
+        guidance: None, or (neg, scale, log_beta) with one entry per OUTPUT row (csrc/guide.hip): the first
+        len(neg) wanted rows are the output rows, the rest the negative rows; neg[j] = the index into `want` of output row j's
+        negative row (-1: unguided), scale[j] = gamma, log_beta[j] = float32(log beta) <= 0 (-inf: no plausibility cut).  The
+        output row's logits become gamma * (log_softmax(row) - log_softmax(negative)) + log_softmax(negative) ahead of the edits;
+        edits, logprobs and everything returned then have one entry per OUTPUT row.  None takes the call without it.
         Returns (logits float16 [n_want, vocab] or None, argmax int32 [n_want]), with logprobs one more value, a `TokenLogprobs`."""
         n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
+        if guidance is not None:
+            gd, _keep3, nw = self._guidance_struct(guidance, nw)
+            out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if logits else None
+            out_arg = np.empty((nw,), np.int32)
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw) if n_lp is not None else (None, None)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_guided(self.handle, *args, _ptr(out_logits), _ptr(out_arg), ctypes.byref(gd),
+                                                             ctypes.byref(st) if st is not None else None,
+                                                             ctypes.byref(lp) if lp is not None else None), self.handle)
+            return (out_logits, out_arg, rec) if n_lp is not None else (out_logits, out_arg)
         out_logits = np.empty((nw, self.cfg.llm_vocab), np.float16) if (logits and nw) else None
         out_arg = np.empty((max(nw, 1),), np.int32)
         if n_lp is not None:
@@ -225,16 +268,31 @@ class VqaEngine:
                            self.handle)
         return out_logits, out_arg[:nw]
 
-    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None, logprobs=None, warpers=None):
+    def forward_sample(self, seqs: Sequence[Seq], want: Sequence[Tuple[int, int]], params, edits=None, logprobs=None, warpers=None,
+                       guidance=None):
         """`forward` with the arg-max replaced by the on-device sampling tail (csrc/sample.hip): `params` holds one
         `_lib.VqaSampling` per wanted row (or one record for all of them); edits as in `forward` (the draw sees the edited
         logits).  logprobs as in `forward`, of the drawn token — under the edited, UN-WARPED, temperature-1 distribution (DESIGN.md
         §8.9).  warpers: None, or one `_lib.VqaWarpers` per wanted row (or one record for all): min-p, typical-p and the epsilon /
         eta cutoffs between top-p and the draw (`vqa.warper_params`); None is the call without them, launch for
-        launch.  Returns the drawn tokens, int32 [n_want], with logprobs (tokens, `TokenLogprobs`); the logits never leave the device."""
+        launch.  guidance as in `forward`: the draw is made from the guided (then edited) row, and params, warpers, edits, logprobs and
+        the result have one entry per OUTPUT row.
+        Returns the drawn tokens, int32 [n_want], with logprobs (tokens, `TokenLogprobs`); the logits never leave the device."""
         n_lp = check_logprobs(logprobs)
         args, _keep = self._rows_args(seqs, want)
         nw = args[6]
+        if guidance is not None:
+            gd, _keep3, nw = self._guidance_struct(guidance, nw)
+            prm = self._sampling_array(params, nw)
+            out = np.empty((nw,), np.int32)
+            wrp = self._warpers_array(warpers, nw) if warpers is not None else None
+            st, _keep2 = self._edits_struct(edits, nw) if edits is not None else (None, None)
+            lp, rec = self._logprobs_struct(n_lp, nw) if n_lp is not None else (None, None)
+            _lib.check_vqa(self.lib.vstar_vqa_forward_sample_guided(self.handle, *args, ctypes.cast(prm, ctypes.c_void_p), _ptr(out),
+                                                                    ctypes.cast(wrp, ctypes.c_void_p) if wrp is not None else None,
+                                                                    ctypes.byref(gd), ctypes.byref(st) if st is not None else None,
+                                                                    ctypes.byref(lp) if lp is not None else None), self.handle)
+            return (out, rec) if n_lp is not None else out
         prm = self._sampling_array(params, nw)
         out = np.empty((max(nw, 1),), np.int32)
         if warpers is not None:

@@ -53,6 +53,13 @@ def parse_args(argv):
                    "the pick on the device (DESIGN.md 8.11); off (default) is the greedy decode")
     p.add_argument("--vqa-top-k", dest="vqa_top_k", default=None, type=int, help="K in [2, 32]: the candidates per step of "
                    "--vqa-penalty-alpha (each question then takes K KV slots); required with it, ignored without")
+    p.add_argument("--vqa-guidance-scale", dest="vqa_guidance_scale", default=None, type=float, help="G >= 0: the free-form pass decodes "
+                   "every question against the same prompt without the image (classifier-free guidance / visual contrastive decoding, "
+                   "HF's guidance_scale), the two logits rows combined on the device (DESIGN.md 8.12); each question then takes 2 KV "
+                   "slots; off (default) or 1 is the plain decode")
+    p.add_argument("--vqa-plausibility-beta", dest="vqa_plausibility_beta", default=0.0, type=float, help="B in [0, 1]: with "
+                   "--vqa-guidance-scale, tokens whose probability under the un-guided row is below B times its maximum are dropped "
+                   "(the adaptive plausibility constraint); 0 = off")
     p.add_argument("--engine-comm", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="world > 1 on GPUs: gather the per-step records with the C-ABI's own RCCL communicator on the engine stream "
                    "(vstar_allgather_results) instead of torch.distributed.  auto (default, round 6): used when the communicator comes up "
